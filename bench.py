@@ -8,7 +8,7 @@ all-gather that re-assembles the consumed outputs (con_rgb + dif) on every rank,
 step's compute.  Rank 0 prints ONE JSON line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--dtype f32|f16] [--workload gsc256|tsm512]
-                    [--no-cpu-baseline] [--loop ffhq|ucb]
+                    [--no-cpu-baseline] [--loop ffhq|ucb] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this process a LAUNCHER: it starts N rank
 processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set) before anything touches
@@ -326,9 +326,13 @@ class _StubGenerator:
     """Stand-in for the HIP generator so the rank logic (launcher, sharding, double-buffered all-gather, JSON contract)
     runs on a CPU box over gloo.  NOT a fallback of the product path: bench lines produced with it carry "stub": true."""
 
+    def __init__(self):
+        self.calls = 0          # forwards so far: gs carries it, so a test can tell which step an output came from
+
     def __call__(self, inputs, uv, out=None, packed_out=None):
         import torch
-        g0 = inputs.mean(dim=3, keepdim=True)
+        self.calls += 1
+        g0 = inputs.mean(dim=3, keepdim=True) + self.calls
         res = (g0, inputs * 0.5 + uv * 0.5, torch.cat([g0, g0 * 0, -g0], 3), g0 - uv[..., :1])
         if packed_out is not None:
             packed_out[..., :3].copy_(res[1])
@@ -739,6 +743,40 @@ def secondary_batch16(gen, dev, rate_b32):
     return res
 
 
+# ----------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 64 * 10 ** 6                   # all .npy files of one dump together (headers included) stay under this
+OUTPUT_NAMES = ("gs", "con_rgb", "mask22", "dif")       # what Generator / GeneratorTSM return, in that order
+
+
+def dump_rows(outputs, budget=DUMP_BYTES):
+    """Batch rows --dump-outputs keeps: every row when the four outputs fit in `budget`, else a fixed seeded sample of as many
+    rows as fit (sorted), the same for every run of the same shape."""
+    import numpy as np
+    B = int(outputs[0].shape[0])
+    per_row = sum(int(t[0].numel()) * 4 for t in outputs)
+    k = min(B, (budget - 1024 * len(outputs)) // per_row)
+    if k >= B:
+        return list(range(B))
+    return sorted(int(i) for i in np.random.default_rng(0).choice(B, k, replace=False))
+
+
+def snapshot_outputs(outputs):
+    """Host float32 copies of the dumped rows of one step's outputs (call after the device is synchronised)."""
+    import torch
+    rows = dump_rows(outputs)
+    idx = torch.tensor(rows, dtype=torch.long, device=outputs[0].device)
+    return rows, [t.index_select(0, idx).float().cpu().numpy() for t in outputs]
+
+
+def write_outputs(out_dir, rows, arrays):
+    import numpy as np
+    for name, a in zip(OUTPUT_NAMES, arrays):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "files": [n + ".npy" for n in OUTPUT_NAMES], "shapes": [list(a.shape) for a in arrays], "batch_rows": rows,
+            "note": "outputs of the last timed step of the first timed region (rank 0's own forward), float32; batch_rows = the rows "
+                    "of the batch kept (all of them, or a fixed seeded sample when the whole batch exceeds %d bytes)" % DUMP_BYTES}
+
+
 # ----------------------------------------------------------------------------------------------- one rank
 def run_rank(args):
     import torch
@@ -905,6 +943,7 @@ def run_rank(args):
         serial(i)
     drain()
     elapsed, own = timed(args.steps, serial)                # THE timed region: exactly K steps
+    dumped = snapshot_outputs(last[(args.steps - 1) & 1]) if args.dump_outputs and rank == 0 else None     # its last step, outside the timing
     reps = [elapsed] + [timed(args.steps, serial)[0] for _ in range(max(0, args.repeats - 1))]
     extra = {}
     sustained = None
@@ -1045,6 +1084,8 @@ def run_rank(args):
             if args.loop and world == 1:
                 from blindshadowremoval_amd.loop_bench import loop_bench
                 result["loop"] = loop_bench(args.loop, os.path.join(ROOT, "tests", "golden"), gen)
+        if dumped is not None:
+            result["dump_outputs"] = write_outputs(args.dump_outputs, *dumped)
         line = json.dumps(result) + "\n"
         if real_stdout is not None:
             sys.stdout.flush()
@@ -1095,7 +1136,18 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true", help="CPU stand-in generator: tests the launcher / sharding / JSON contract, measures nothing")
     ap.add_argument("--loop", choices=("ffhq", "ucb"), default=None,
                     help="also time the end-to-end FSRNet.testFFHQ / FSRNet.test loop (host prep + H2D + forward + post + PNG) on the shipped fixtures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (gs, con_rgb, mask22, dif) as DIR/<name>.npy, float32, at most %d bytes in all; "
+                         "when the whole batch is larger a fixed seeded sample of its rows is kept, listed as batch_rows in the result line (the default "
+                         "gsc256 batch of 32 comes to 67.1e6 bytes, so 30 of its 32 rows are kept).  With --gpus N > 1 these are rank 0's own outputs, "
+                         "not the all-gathered con_rgb | dif; every rank runs the same code on seeded inputs.  The inputs are seeded, so two builds can "
+                         "be compared output for output" % DUMP_BYTES)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.batch is None:
         args.batch = 8 if args.workload == "tsm512" else 32
     if args.device is not None:

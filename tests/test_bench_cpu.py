@@ -36,6 +36,45 @@ def test_gpus2_launches_two_ranks_over_gloo():
     assert j["value_mode"] == "one forward at a time" and j["single_stream_value"] == j["value"] and "roofline_in_flight" not in j
 
 
+def test_dump_outputs_writes_the_last_step_reproducibly(tmp_path):
+    """--dump-outputs DIR: the last timed step's four outputs as float32 .npy files, identical from run to run (seeded inputs), at most
+    bench.DUMP_BYTES in all — a fixed seeded sample of the batch rows once the whole batch is larger.  --steps K sets the timed steps.
+    The stand-in's gs is the channel mean of the inputs plus the number of forwards so far, so the dump shows which step it holds:
+    with W warm-up steps and K timed ones, the last timed step is forward W + K."""
+    import numpy as np
+    import torch
+    names = ("gs", "con_rgb", "mask22", "dif")
+
+    def run(tag, batch, steps, warmup):
+        out = tmp_path / tag
+        r = _run(["--backend", "gloo", "--stub", "--batch", str(batch), "--steps", str(steps), "--warmup", str(warmup), "--repeats", "2",
+                  "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names) and j["dump_outputs"]["files"] == [n + ".npy" for n in names]
+        assert sum(os.path.getsize(os.path.join(out, n + ".npy")) for n in names) <= 64 * 10 ** 6
+        arrays = [np.load(os.path.join(out, n + ".npy")) for n in names]
+        assert all(a.dtype == np.float32 for a in arrays)
+        rows = j["dump_outputs"]["batch_rows"]
+        assert [a.shape for a in arrays] == [(len(rows), 256, 256, c) for c in (1, 3, 3, 1)]
+        g = torch.Generator(device="cpu").manual_seed(1234)
+        inp = torch.rand(batch, 256, 256, 3, generator=g)
+        want_gs = (inp.mean(dim=3, keepdim=True) + (warmup + steps))[rows].numpy()
+        assert np.array_equal(arrays[0], want_gs)                   # forward W + K: the last step of the FIRST timed region
+        return rows, arrays
+
+    for tag, batch, steps, warmup in (("odd", 2, 3, 1), ("even", 40, 2, 1)):      # last step in slot 0 / slot 1
+        rows, arrays = run(tag, batch, steps, warmup)
+        rows2, arrays2 = run(tag + "_again", batch, steps, warmup)
+        assert rows == rows2 and all(np.array_equal(a, b) for a, b in zip(arrays, arrays2))       # same arguments, same dump
+        if batch == 2:
+            assert rows == [0, 1]
+        else:                                                       # 40 rows exceed the cap: a seeded sample, sorted, no repeats
+            assert 0 < len(rows) < 40 and rows == sorted(set(rows))
+    assert _run(["--backend", "gloo", "--stub", "--steps", "0"]).returncode != 0
+
+
 def test_gpus_without_devices_fails_loudly():
     """No silent fall-back to one GPU: on this CPU box `--gpus 2` on the real path must exit non-zero before starting ranks."""
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])

@@ -1,6 +1,6 @@
 """Input-preparation counterpart (blindshadowremoval_amd/dataset.py) against the fixture produced by the REFERENCE's own
-functions on sample_imgs/02165 (tests/golden/sample_02165.npz, tools/make_sample_fixture.py).  The sample image and
-landmarks live under /root/reference, so the end-to-end comparison runs in the build container only."""
+functions on sample_imgs/02165 (tests/golden/sample_02165.npz, tools/make_sample_fixture.py).  The sample image, its
+landmarks and the UCB items are committed under tests/golden."""
 import os
 
 import numpy as np
@@ -49,7 +49,7 @@ def test_row_matches_reference_prepared_fixture(golden_dir):
         np.testing.assert_allclose(row[..., sl], z["row"][..., sl], atol=tol, err_msg=name)
 
 
-def test_dataset_feed_layout():
+def test_dataset_feed_layout(golden_dir):
     from blindshadowremoval_amd.fsrnet import Config
     cfg = Config()
     cfg.DATA_DIR_TEST = [os.path.join(os.path.dirname(REF_SAMPLE), "..", "*")]
@@ -60,9 +60,7 @@ def test_dataset_feed_layout():
     np.testing.assert_array_equal(img[0, 0], img[0, 9])          # single-image folder: every sibling is the image itself
     with pytest.raises(StopIteration):
         next(ds.feed)
-    if not os.path.isdir("/root/reference/UCB/train/input"):
-        return
-    ucb = D.Dataset(type("C", (), {"DATA_DIR_TEST": ["/root/reference/UCB/train/input/*"], "IMG_SIZE": 256})(), "test", ucb=True)
+    ucb = D.Dataset(type("C", (), {"DATA_DIR_TEST": [os.path.join(golden_dir, "UCB", "train", "input", "*")], "IMG_SIZE": 256})(), "test", ucb=True)
     assert len(ucb.name_list) == 100                              # 100 items, not 99
     assert ucb._gt_path(ucb.name_list[0]).replace("/gt/", "/input/") == os.path.splitext(ucb.name_list[0])[0] + ".png"
     im, bx, nm = next(ucb.feed)
