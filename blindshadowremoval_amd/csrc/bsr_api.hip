@@ -734,9 +734,10 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     // z = y3 + BN(w(att)); out = LeakyReLU(pad(x) + pad(z))  (model.py:56-59, 105-113) = LeakyReLU(y3x + BN(w(att))).
     // ONE launch — the `w` GEMM runs as the tail of the attention kernel on the workgroup's own 128 pixels (attention.h /
     // attention_h16.h, FUSEW; the attention output never goes to HBM).  fp32 small batches (the 4- / 2-wave attention shapes) keep the
-    // two launches; both forms give the same bits (tests/test_gpu_parity.py).
+    // two launches; on the fp32 path both forms give the same bits (tests/test_gpu_parity.py).
     // 16-bit modes: the one-wave-per-SIMD kernel of attention_h16.h (round 6), whose normalised O^T accumulators are the tail's A operand, at
-    // every batch (that kernel has one workgroup shape).
+    // every batch (that kernel has one workgroup shape).  There the two forms sum in different orders and agree to a tolerance, not to the
+    // bit, and f16 runs P.V on the hi planes only (att_pv1); tests/test_stage_parity_gpu.py holds both forms to per-stage fp64 budgets.
     const bool h16 = h->dtype != BSR_DTYPE_F32;
     const bool fuse_w = h->fuse_attw && (h16 || bsr::attention_auto_qw(B, H8 * W8) == 4);
     h->att_in_lds = fuse_w;

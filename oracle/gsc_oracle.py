@@ -12,7 +12,9 @@ its trained weights are absent (/root/reference/.MISSING_LARGE_BLOBS).  This fil
 (oracle/np_loops.py) on small shapes, and (3) the variable inventory parsed from the reference's own
 ``ckpt-94.index`` (tests/golden/gsc_ckpt94_inventory.json) chaining shape-correctly through it.
 
-Tensors are NHWC float32 torch CPU tensors, exactly as the reference passes them.
+Tensors are NHWC float32 torch CPU tensors, exactly as the reference passes them.  ``dtype=torch.float64`` runs the same
+statements in double precision (every weight, constant and intermediate in fp64): the reference the per-stage parity tests
+(tests/stage_parity.py) hold the kernels to, whose own error is far below the fp32 kernels' and the fp32 oracle's.
 """
 from __future__ import annotations
 
@@ -28,10 +30,10 @@ GRAY = (0.2989, 0.5870, 0.1140)   # tf.image.rgb_to_grayscale weights (model.py:
 BMASK_THRESHOLD = 0.1             # model.py:256
 
 
-def _t(a) -> torch.Tensor:
+def _t(a, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     if isinstance(a, torch.Tensor):
-        return a.detach().to(torch.float32).cpu()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        return a.detach().to(dtype).cpu()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if dtype == torch.float64 else np.float32))
 
 
 def same_pad(size: int, k: int, s: int) -> Tuple[int, int]:
@@ -43,13 +45,13 @@ def same_pad(size: int, k: int, s: int) -> Tuple[int, int]:
 
 def conv2d_same(x: torch.Tensor, kernel_hwio, bias, stride: int = 1) -> torch.Tensor:
     """``layers.Conv2D(padding='same')`` (model.py:10-13,84-86,119): cross-correlation, HWIO kernel."""
-    w = _t(kernel_hwio)
+    w = _t(kernel_hwio, x.dtype)
     kh, kw = w.shape[0], w.shape[1]
     xt = x.permute(0, 3, 1, 2)
     pt, pb = same_pad(x.shape[1], kh, stride)
     pl, pr = same_pad(x.shape[2], kw, stride)
     xt = F.pad(xt, (pl, pr, pt, pb))
-    y = F.conv2d(xt, w.permute(3, 2, 0, 1).contiguous(), _t(bias), stride=stride)
+    y = F.conv2d(xt, w.permute(3, 2, 0, 1).contiguous(), _t(bias, x.dtype), stride=stride)
     return y.permute(0, 2, 3, 1).contiguous()
 
 
@@ -59,18 +61,18 @@ def conv2d_transpose_same(x: torch.Tensor, kernel_hwoi, bias, stride: int = 2) -
 
     For k=3, s=2 TF's SAME deconv pads (k-s)=1 in total, 0 before / 1 after, i.e. the full
     (2H+1)-long scatter result is cropped at the end."""
-    w = _t(kernel_hwoi)
+    w = _t(kernel_hwoi, x.dtype)
     kh = w.shape[0]
     assert stride == 2 and kh == 3, "only the reference's ConvT(3, stride 2) is restated"
     xt = x.permute(0, 3, 1, 2)
-    y = F.conv_transpose2d(xt, w.permute(3, 2, 0, 1).contiguous(), _t(bias), stride=stride, padding=0)
+    y = F.conv_transpose2d(xt, w.permute(3, 2, 0, 1).contiguous(), _t(bias, x.dtype), stride=stride, padding=0)
     H, W = x.shape[1] * stride, x.shape[2] * stride
     return y[:, :, :H, :W].permute(0, 2, 3, 1).contiguous()
 
 
 def batchnorm_infer(x: torch.Tensor, gamma, beta, mean, var) -> torch.Tensor:
     """``BatchNormalization()(x, training=False)`` (A.3)."""
-    g, b, m, v = _t(gamma), _t(beta), _t(mean), _t(var)
+    g, b, m, v = (_t(a, x.dtype) for a in (gamma, beta, mean, var))
     return (x - m) * torch.rsqrt(v + BN_EPS) * g + b
 
 
@@ -80,7 +82,7 @@ def leaky_relu(x: torch.Tensor) -> torch.Tensor:
 
 def rgb_to_grayscale(x: torch.Tensor) -> torch.Tensor:
     """``tf.image.rgb_to_grayscale`` (A.6): tensordot with [0.2989, 0.5870, 0.1140], keeps a size-1 channel."""
-    w = torch.tensor(GRAY, dtype=torch.float32)
+    w = torch.tensor(GRAY, dtype=x.dtype)
     return (x * w).sum(-1, keepdim=True)
 
 
@@ -93,9 +95,11 @@ def resize_bilinear(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 class GeneratorOracle:
     """Restatement of ``Generator`` (/root/reference/model.py:198-290) at ``training=False``."""
 
-    def __init__(self, weights: Dict[str, np.ndarray], n_res: int = 6):
+    def __init__(self, weights: Dict[str, np.ndarray], n_res: int = 6, dtype: torch.dtype = torch.float32):
+        assert dtype in (torch.float32, torch.float64)
         self.w = weights
         self.n_res = n_res
+        self.dtype = dtype
 
     # -- blocks -----------------------------------------------------------------------------
     def conv_block(self, x, stem: str, stride: int = 1, bn: bool = True, act: bool = True):
@@ -142,9 +146,9 @@ class GeneratorOracle:
         y = self.non_local(y, st + "non_local/", probes)
         cx, cy = x.shape[-1], y.shape[-1]
         if cx < cy:                                               # :105-108
-            x = torch.cat([x, torch.zeros(*x.shape[:3], cy - cx)], dim=3)
+            x = torch.cat([x, x.new_zeros(*x.shape[:3], cy - cx)], dim=3)
         elif cy < cx:                                             # :109-112
-            y = torch.cat([y, torch.zeros(*y.shape[:3], cx - cy)], dim=3)
+            y = torch.cat([y, y.new_zeros(*y.shape[:3], cx - cy)], dim=3)
         return leaky_relu(x + y)                                  # :113
 
     # -- forward ----------------------------------------------------------------------------
@@ -154,7 +158,7 @@ class GeneratorOracle:
         the reference.  ``probes`` (dict) receives intermediates; ``bmask_override`` substitutes the
         thresholded mask (used by parity tests to separate threshold flips from arithmetic error)."""
         assert not training, "the oracle restates the inference path only"
-        inputs, uv = _t(inputs), _t(uv)
+        inputs, uv = _t(inputs, self.dtype), _t(uv, self.dtype)
         x1 = self.conv_block(inputs, "conv1")                     # :230
         x2 = self.conv_block(x1, "down1", 2)                      # :231
         x3 = self.conv_block(x2, "down2", 2)                      # :232
@@ -175,34 +179,56 @@ class GeneratorOracle:
         if probes is not None:
             probes["up2"] = y
         y = self.convt_block(torch.cat([y, x2], dim=3), "up3")    # :245
+        if probes is not None:
+            probes["y"] = y
+        gs, mask22, dif, d32 = self.heads(y, inputs, probes)      # :246-252
+        bmask = (d32 > BMASK_THRESHOLD).to(self.dtype)            # :256 (strict >)
+        if probes is not None:
+            probes.update(d32=d32, bmask=bmask)
+        if bmask_override is not None:
+            bmask = _t(bmask_override, self.dtype).reshape(bmask.shape)
+        x_hole = x * (1 - bmask)                                  # :258
+        x = torch.cat([x_hole, bmask, uv_s], dim=3)               # :259
+        if probes is not None:
+            probes["xh"] = x
+        for i in range(self.n_res // 2, self.n_res):              # :261-262
+            x = self.res_bottleneck(x, i, probes)
+            if probes is not None:
+                probes["res%d" % i] = x
+        f = self.colour_decoder(x, probes)                        # :264-266
+        con_rgb, dif2 = self.colour_tail(gs, f, inputs)           # :267-269,288
+        return gs, con_rgb, mask22, dif2                          # :290
+
+    # -- the stages that follow the decoders (also run on their own by tests/stage_parity.py) --------------------
+    def heads(self, y, inputs, probes: Optional[dict] = None):
+        """model.py:246-252 and the resize of :256: ``y, inputs -> gs, mask22, dif, d32``."""
         mask = torch.tanh(self.conv_block(y, "conv2", 1, bn=False, act=False))   # :246
         con = self.conv_block(y, "conv3", 1, bn=False, act=False)                # :247
         g0 = rgb_to_grayscale(inputs)
         gs = g0 * (1 + mask) + con                                # :250
         dif = gs - g0                                             # :251
         mask22 = torch.cat([torch.relu(mask), mask * 0, torch.relu(-mask)], dim=3)   # :252
-        d32 = resize_bilinear(dif, (h, w))
-        bmask = (d32 > BMASK_THRESHOLD).to(torch.float32)         # :256 (strict >)
+        d32 = resize_bilinear(dif, (-(-y.shape[1] // 8), -(-y.shape[2] // 8)))   # the trunk's size: three SAME stride-2 convs
         if probes is not None:
-            probes.update(y=y, mask=mask, con=con, d32=d32, bmask=bmask)
-        if bmask_override is not None:
-            bmask = _t(bmask_override).reshape(bmask.shape)
-        x_hole = x * (1 - bmask)                                  # :258
-        x = torch.cat([x_hole, bmask, uv_s], dim=3)               # :259
-        for i in range(self.n_res // 2, self.n_res):              # :261-262
-            x = self.res_bottleneck(x, i, probes)
-            if probes is not None:
-                probes["res%d" % i] = x
-        f = self.convt_block(x, "clr_up1")                        # :264
-        f = self.convt_block(f, "clr_up2")                        # :265
-        f = self.convt_block(f, "clr_up3")                        # :266
+            probes.update(mask=mask, con=con)
+        return gs, mask22, dif, d32
+
+    def colour_decoder(self, x, probes: Optional[dict] = None):
+        """model.py:264-266: clr_up1..3."""
+        f1 = self.convt_block(x, "clr_up1")
+        f2 = self.convt_block(f1, "clr_up2")
+        f = self.convt_block(f2, "clr_up3")
         if probes is not None:
-            probes["f"] = f
+            probes.update(f1=f1, f2=f2, f=f)
+        return f
+
+    def colour_tail(self, gs, f, inputs):
+        """model.py:267-269,288: ``gs, f, inputs -> con_rgb, dif2``."""
         c = self.conv_block(torch.cat([gs, f], dim=3), "clr_conv1")              # :267
         c = self.conv_block(c, "clr_conv2")                       # :268
         con_rgb = self.conv_block(c, "clr_conv3", bn=False, act=False)           # :269
         dif2 = rgb_to_grayscale(con_rgb) - rgb_to_grayscale(inputs)              # :288
-        return gs, con_rgb, mask22, dif2                          # :290
+        return con_rgb, dif2
 
     __call__ = forward
 
@@ -237,7 +263,7 @@ def batch_map_offsets(x: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     off = resize_bilinear(offsets, (S, S)) * S
     off = off[..., 0:2].reshape(B, -1, 2)
     ii, jj = torch.meshgrid(torch.arange(S), torch.arange(S), indexing="ij")
-    grid = torch.stack([ii, jj], dim=-1).to(torch.float32).reshape(1, -1, 2)
+    grid = torch.stack([ii, jj], dim=-1).to(x.dtype).reshape(1, -1, 2)
     return batch_map_coordinates(x, off + grid).reshape(B, S, S, -1)
 
 
@@ -261,7 +287,7 @@ class GeneratorTSMOracle(GeneratorOracle):
     def forward(self, inputs, uv, reg, frame, share=True, chuck=1, training=False, probes: Optional[dict] = None,
                 bmask_override: Optional[torch.Tensor] = None):
         assert not training
-        inputs, uv, reg = _t(inputs), _t(uv), _t(reg)
+        inputs, uv, reg = _t(inputs, self.dtype), _t(uv, self.dtype), _t(reg, self.dtype)
         x1 = self.conv_block(inputs, "conv1")
         x2 = self.conv_block(x1, "down1", 2)
         x3 = self.conv_block(x2, "down2", 2)
@@ -271,7 +297,7 @@ class GeneratorTSMOracle(GeneratorOracle):
         x_share = share_layer(x, reg, frame, share)                           # :271
         x = torch.cat([x, x_share, uv_s], dim=3)                              # :272
         if probes is not None:
-            probes.update(x_share1=x_share, x0=x)
+            probes.update(x1=x1, x2=x2, x3=x3, x_share1=x_share, x0=x)
         for i in range(self.n_res // 2):
             x = self.res_bottleneck(x, i, probes)
         if probes is not None:
@@ -279,18 +305,12 @@ class GeneratorTSMOracle(GeneratorOracle):
         y = self.convt_block(x, "up1")
         y = self.convt_block(torch.cat([y, x3], dim=3), "up2")
         y = self.convt_block(torch.cat([y, x2], dim=3), "up3")
-        mask = torch.tanh(self.conv_block(y, "conv2", 1, bn=False, act=False))
-        con = self.conv_block(y, "conv3", 1, bn=False, act=False)
-        g0 = rgb_to_grayscale(inputs)
-        gs = g0 * (1 + mask) + con
-        dif = gs - g0
-        mask22 = torch.cat([torch.relu(mask), mask * 0, torch.relu(-mask)], dim=3)
-        d32 = resize_bilinear(dif, (h, w))
-        bmask = (d32 > BMASK_THRESHOLD).to(torch.float32)                     # :289
+        gs, mask22, dif, d32 = self.heads(y, inputs)
+        bmask = (d32 > BMASK_THRESHOLD).to(self.dtype)                        # :289
         if probes is not None:
             probes.update(d32=d32, bmask=bmask)
         if bmask_override is not None:
-            bmask = _t(bmask_override).reshape(bmask.shape)
+            bmask = _t(bmask_override, self.dtype).reshape(bmask.shape)
         x_hole = x * (1 - bmask)                                              # :291
         x_share = share_layer(x_hole, reg, frame, share)                      # :292
         x = torch.cat([x_hole, bmask, x_share, uv_s], dim=3)                  # :293
@@ -300,13 +320,8 @@ class GeneratorTSMOracle(GeneratorOracle):
             x = self.res_bottleneck(x, i, probes)
         if probes is not None:
             probes["res5"] = x
-        f = self.convt_block(x, "clr_up1")
-        f = self.convt_block(f, "clr_up2")
-        f = self.convt_block(f, "clr_up3")
-        c = self.conv_block(torch.cat([gs, f], dim=3), "clr_conv1")
-        c = self.conv_block(c, "clr_conv2")
-        con_rgb = self.conv_block(c, "clr_conv3", bn=False, act=False)
-        dif2 = rgb_to_grayscale(con_rgb) - rgb_to_grayscale(inputs)
+        f = self.colour_decoder(x)
+        con_rgb, dif2 = self.colour_tail(gs, f, inputs)
         return gs, con_rgb, mask22, dif2
 
     __call__ = forward
