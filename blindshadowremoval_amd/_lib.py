@@ -17,7 +17,8 @@ _lib: Optional[ctypes.CDLL] = None
 
 # every symbol include/bsr_hip.h declares
 EXPORTS = ("bsr_create", "bsr_forward", "bsr_forward_tsm", "bsr_workspace_bytes", "bsr_reserve", "bsr_probe", "bsr_set_timing",
-           "bsr_get_timing", "bsr_timing_launches", "bsr_timing_entry", "bsr_handle_workspace_bytes", "bsr_debug_attention", "bsr_debug_attention_dtype", "bsr_debug_attention_qw", "bsr_debug_split_qkv", "bsr_clock_trace", "bsr_debug_attention_split", "bsr_destroy", "bsr_last_error", "bsr_abi_version", "bsr_check_range", "bsr_prep_rows", "bsr_png_unfilter", "bsr_forward_packed", "bsr_source_sha", "bsr_peek_range", "bsr_png_file_bytes", "bsr_png_scratch_bytes", "bsr_png_encode", "bsr_png_encode_figs", "bsr_ucb_post_scratch_bytes", "bsr_ucb_post")
+           "bsr_get_timing", "bsr_timing_launches", "bsr_timing_entry", "bsr_handle_workspace_bytes", "bsr_debug_attention", "bsr_debug_attention_dtype", "bsr_debug_attention_qw", "bsr_debug_split_qkv", "bsr_clock_trace", "bsr_debug_attention_split", "bsr_destroy", "bsr_last_error", "bsr_abi_version", "bsr_check_range", "bsr_prep_rows", "bsr_png_unfilter", "bsr_forward_packed", "bsr_source_sha", "bsr_peek_range", "bsr_png_file_bytes", "bsr_png_scratch_bytes", "bsr_png_encode", "bsr_png_encode_figs", "bsr_ucb_post_scratch_bytes", "bsr_ucb_post",
+           "bsr_forward_rgb", "bsr_debug_attention_rgb")
 
 
 def load() -> ctypes.CDLL:
@@ -56,6 +57,10 @@ def load() -> ctypes.CDLL:
     lib.bsr_forward_packed.restype = c_i
     lib.bsr_forward_tsm.argtypes = [c_v, c_v, c_v, c_v, c_i, c_i, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_v]
     lib.bsr_forward_tsm.restype = c_i
+    lib.bsr_forward_rgb.argtypes = [c_v, c_v, c_v, c_i, c_i, c_i, c_v, c_v]
+    lib.bsr_forward_rgb.restype = c_i
+    lib.bsr_debug_attention_rgb.argtypes = [c_v, c_v, c_i, c_i, c_v]
+    lib.bsr_debug_attention_rgb.restype = c_i
     lib.bsr_workspace_bytes.argtypes = [c_i, c_i, c_i]
     lib.bsr_workspace_bytes.restype = c_sz
     lib.bsr_reserve.argtypes = [c_v, c_i, c_i, c_i]

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "attention256.h"
 #include "attention_h16.h"
 #include "conv3_f16.h"
 #include "conv_n16.h"
@@ -23,6 +24,7 @@
 #include "igemm_h16.h"
 #include "png_kernels.h"
 #include "prep_kernels.h"
+#include "rgb_head.h"
 #include "stem7.h"
 #include "ucb_kernels.h"
 
@@ -86,12 +88,16 @@ struct Variant {
   int c_a, cs_a, uv_a;        // res0 input: real channels, stride, uv slot
   int c_r, cs_r;              // blocks 0-2 output
   int c_h, cs_h, uv_h;        // blocks 3-5 input/output, uv slot
+  bool rgb = false;           // the single-stage RGB baseline (model_RGB.py): its own plan and forward (PlanRGB, forward_rgb)
 };
 constexpr Variant kGSC{false, 99, 120, 96, 257, 264, 261, 264, 258};
 // 16-bit matrix-core modes (BSR_DTYPE_F16 / BSR_DTYPE_F32X3): K chunks are 32 channels, so the 257 / 261-wide tensors get stride 288
 constexpr Variant kGSC16{false, 99, 128, 96, 257, 288, 261, 288, 258};
 constexpr Variant kTSM{true, 291, 312, 288, 291, 312, 877, 888, 874};
 constexpr Variant kTSM16{true, 291, 320, 288, 291, 320, 877, 896, 874};          // TSM widths at the 16-bit kernels' 32-channel granularity
+// RGB baseline (/root/reference/model_RGB.py:198-266): xa = cat[x 96 | uv 3] at stride 128, blocks 0-2 are 513 wide (stride 544); no
+// blocks 3-5, no xh (c_h / cs_h / uv_h unused)
+constexpr Variant kRGB{false, 99, 128, 96, 513, 544, 0, 0, 0, true};
 constexpr int CS_CF = 64;    // f = clr_up3 output; the gs channel of cat[gs, f] (model.py:267) is read from the gs output
 
 struct Plan {  // float offsets into the workspace for a (B,H,W) problem
@@ -130,6 +136,44 @@ Plan make_plan(size_t B, size_t H, size_t W, const Variant& v = kGSC) {
   return p;
 }
 
+// Workspace of the RGB forward.  Concatenations are channel slices: c3 = [up2 128 | x2 64] (model_RGB.py:252), c2 = [up1 192 | x3 64]
+// (:251); y3x<i> = [y3 513 | 0] + pad(x) at stride 544; qkv = theta | phi | g, 256 each; qh = the 7x1 head's (kx, co) partial sums.
+struct PlanRGB {
+  size_t x1, c3, c2, xa, t1, t2, y3[3], qkv, att[3], r[3], ybuf, qh, yh, con, total;
+};
+constexpr int RGB_CS_R = 544, RGB_CS_A = 128, RGB_D = 256, RGB_CS_C3 = 192, RGB_CS_C2 = 256, RGB_CS_QH = 32;
+
+PlanRGB make_plan_rgb(size_t B, size_t H, size_t W) {
+  PlanRGB p;
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    size_t o = off;
+    off += (floats + 63) & ~size_t(63);
+    return o;
+  };
+  const size_t px = B * H * W, cells = px / 64;
+  p.x1 = take(px * 32);
+  p.c3 = take(px / 4 * RGB_CS_C3);
+  p.c2 = take(px / 16 * RGB_CS_C2);
+  p.xa = take(cells * RGB_CS_A);
+  p.t1 = take(cells * RGB_D);
+  p.t2 = take(cells * RGB_D);
+  for (int i = 0; i < 3; ++i) p.y3[i] = take(cells * RGB_CS_R);
+  p.qkv = take(cells * 3 * RGB_D);
+  for (int i = 0; i < 3; ++i) p.att[i] = take(cells * RGB_D);
+  for (int i = 0; i < 3; ++i) p.r[i] = take(cells * RGB_CS_R);
+  p.ybuf = take(px * 128);
+  p.qh = take(px * RGB_CS_QH);
+  p.yh = take(px * 3);
+  p.con = take(px * 3);
+  p.total = off;
+  return p;
+}
+
+size_t plan_floats(const Variant& v, size_t B, size_t H, size_t W) {
+  return v.rgb ? make_plan_rgb(B, H, W).total : make_plan(B, H, W, v).total;
+}
+
 }  // namespace
 
 struct bsr_handle {
@@ -144,6 +188,9 @@ struct bsr_handle {
   float* ws = nullptr;
   size_t ws_floats = 0;
   Plan plan{};
+  PlanRGB plan_rgb{};            // RGB handles: the plan of the last forward
+  const float* rgb_tail_w = nullptr;   // RGB: conv3 (7x7, 3 -> 3) HWIO weights + bias, 444 floats
+  const float* rgb_head_b = nullptr;   // RGB: conv2 bias, 3 floats
   int B = 0, H = 0, W = 0;       // shape of the last forward
   bool ran = false;
   bool att_in_lds = false;       // the last forward ran attention + `w` as ONE launch: the attention output never reached the att<i> workspace slots
@@ -300,7 +347,8 @@ struct Launcher {
     end();
   }
   // 1x1 conv as a resident-activation GEMM (K = NCH*32) over all N
-  template <int NI, int NCH>
+  // MINW: waves per SIMD the kernel's register budget is sized for (gemm_nloop.h); 1 for the K = 256 GEMMs of the RGB bottleneck
+  template <int NI, int NCH, int MINW = 2>
   void gemm(int cls, const char* name, const float* in, int in_cs, size_t pixels, float* out, int out_cs, int n_store, int act,
             const float* res1 = nullptr, int res1_cs = 0, int res1_c = 0,
             float* out2 = nullptr, int out2_cs = 0, int n_split = 0, int n_store1 = 0) {
@@ -332,9 +380,28 @@ struct Launcher {
     a.out2_split = (h->dtype != BSR_DTYPE_F32 && out2 != nullptr) ? 1 : 0;      // conv3 | theta|phi|g of the 16-bit modes: qkv in the split layout of attention_h16.h
     begin(cls, name);
     if (h->dtype == BSR_DTYPE_F32)
-      check(bsr::launch_gemm_nloop<NI, NCH, 0>(a, pixels, kNSplit, s), name);
-    else
+      check(bsr::launch_gemm_nloop<NI, NCH, 0, MINW>(a, pixels, kNSplit, s), name);
+    else if constexpr (MINW == 2)
       check(bsr::launch_gemm_nloop<NI, NCH, 2>(a, pixels, kNSplit, s), name);      // split-precision in both 16-bit modes
+    else
+      rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': the RGB bottleneck GEMMs are fp32 only");
+    end();
+  }
+
+  // RGB head conv2 (7x7, 128 -> 3) as a 7x1 implicit GEMM over N = (kx, co): rgb_head.h
+  void conv71(const char* name, const float* in, int in_cs, int k_pad, int H, int W, float* out, int out_cs) {
+    if (rc != BSR_OK) return;
+    LayerW l;
+    rc = find_layer(h, name, k_pad / 32, 7, 36, 32, &l);
+    if (rc != BSR_OK) return;
+    if (H % 4 != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': image is not a multiple of the 4x32 tile"); return; }
+    bsr::ConvArgs a{};
+    a.in = in; a.in_cs = in_cs; a.in_coff = 0; a.H = H; a.W = W;
+    a.out = out; a.out_cs = out_cs; a.out_coff = 0; a.Ho = H; a.Wo = W;
+    a.w = l.w; a.bias = l.b; a.nchunk = l.nchunk; a.n_pad = l.n_pad; a.n_store = 32;
+    a.pad_t = 3; a.pad_l = 0; a.act = 0;
+    begin(K_CONV7, name);
+    check(bsr::launch_igemm_conv<7, 1, 1, false, 4, 32, 4, 1, 1, 1, 32, 1>(a, h->B, s), name);
     end();
   }
 
@@ -398,7 +465,35 @@ struct Launcher {
   }
 };
 
+// RGB: as ensure_workspace below.  On a new shape only the pad lanes of xa (channels 99-127, the K pad of res0.conv1 and the residual
+// of res0) need clearing; every other buffer is fully rewritten by its producers each forward, pad channels included.
+int ensure_workspace_rgb(bsr_handle* h, int B, int H, int W, hipStream_t s) {
+  const PlanRGB p = make_plan_rgb(B, H, W);
+  bool fresh = false;
+  if (p.total > h->ws_floats) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h->ws) HIP_TRY(hipFree(h->ws));
+    h->ws = nullptr;
+    h->ws_floats = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), p.total * sizeof(float)));
+    h->ws_floats = p.total;
+    h->B = 0;
+    fresh = true;
+  }
+  if (fresh) {
+    HIP_TRY(hipMemsetAsync(h->ws, 0, p.total * sizeof(float), s));
+    h->ran = false;
+  } else if (B != h->B || H != h->H || W != h->W) {
+    HIP_TRY(hipMemsetAsync(h->ws + p.xa, 0, (size_t)B * H * W / 64 * RGB_CS_A * sizeof(float), s));
+    h->ran = false;
+  }
+  h->plan_rgb = p;
+  h->B = B; h->H = H; h->W = W;
+  return BSR_OK;
+}
+
 int ensure_workspace(bsr_handle* h, int B, int H, int W, hipStream_t s) {
+  if (h->var.rgb) return ensure_workspace_rgb(h, B, H, W, s);
   Plan p = make_plan(B, H, W, h->var);
   bool fresh = false;
   if (p.total > h->ws_floats) {
@@ -497,6 +592,12 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     } else if (nm == "clr_conv1.gs") {
       if (en.nfloats != 256) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: clr_conv1.gs must hold 16x16 floats"); }
       h->clr_gs_w = dptr;
+    } else if (nm == "rgb.tail") {
+      if (en.nfloats != 7 * 7 * 3 * 3 + 3) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: rgb.tail must hold 7x7x3x3 + 3 floats"); }
+      h->rgb_tail_w = dptr;
+    } else if (nm == "rgb.head_bias") {
+      if (en.nfloats != 3) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: rgb.head_bias must hold 3 floats"); }
+      h->rgb_head_b = dptr;
     } else if (nm == "tail.w") {
       if (en.nfloats != 16 * 16 + 16 + 48 + 3) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: tail.w has the wrong size"); }
       h->tail_w = dptr;
@@ -511,6 +612,16 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     } else if (nm.size() > 2 && nm.compare(nm.size() - 2, 2, ".b") == 0) {
       h->layers[nm.substr(0, nm.size() - 2)].b = dptr;
     }
+  }
+  if (h->layers.count("rgb_head") != 0) {      // the RGB baseline (model_RGB.py): its 7x1 head layer exists in no other variant's blob
+    if (dtype != BSR_DTYPE_F32) {
+      bsr_destroy(h);
+      return fail(BSR_ERR_ARG, "bsr_create: these are RGB-baseline weights (model_RGB.py), which run in BSR_DTYPE_F32 only: BSR_DTYPE_F32X3 and BSR_DTYPE_F16 are not provided for them");
+    }
+    if (h->rgb_tail_w == nullptr || h->rgb_head_b == nullptr) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: RGB blob lacks 'rgb.tail' / 'rgb.head_bias'"); }
+    h->var = kRGB;
+    *out = h;
+    return BSR_OK;
   }
   if (h->tail_w == nullptr || h->clr_gs_w == nullptr) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: blob lacks 'tail.w' / 'clr_conv1.gs'"); }
   if (dtype != BSR_DTYPE_F32) {
@@ -544,15 +655,15 @@ int bsr_reserve(bsr_handle* h, int B, int H, int W) {
   if (h == nullptr || B <= 0 || H <= 0 || W <= 0) return fail(BSR_ERR_ARG, "bsr_reserve: bad argument");
   DeviceGuard guard(h->device);
   HIP_TRY(guard.err);
-  Plan p = make_plan(B, H, W, h->var);
-  if (p.total > h->ws_floats) {
+  const size_t total = plan_floats(h->var, B, H, W);
+  if (total > h->ws_floats) {
     HIP_TRY(hipDeviceSynchronize());
     if (h->ws) HIP_TRY(hipFree(h->ws));
     h->ws = nullptr;
     h->ws_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), p.total * sizeof(float)));
-    HIP_TRY(hipMemset(h->ws, 0, p.total * sizeof(float)));
-    h->ws_floats = p.total;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), total * sizeof(float)));
+    HIP_TRY(hipMemset(h->ws, 0, total * sizeof(float)));
+    h->ws_floats = total;
     h->B = 0;
     h->ran = false;
   }
@@ -615,7 +726,7 @@ int bsr_timing_entry(bsr_handle* h, int i, char* name, size_t name_cap, float* m
 
 size_t bsr_handle_workspace_bytes(const bsr_handle* h, int B, int H, int W) {
   if (h == nullptr || B <= 0 || H <= 0 || W <= 0) return 0;
-  return make_plan(B, H, W, h->var).total * sizeof(float);
+  return plan_floats(h->var, B, H, W) * sizeof(float);
 }
 
 static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, const float* reg, int frame, int share, int B, int H, int W,
@@ -624,6 +735,9 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     return fail(BSR_ERR_ARG, "bsr_forward: null argument");
   if (B <= 0) return fail(BSR_ERR_ARG, "bsr_forward: B must be positive");
   const Variant& V = h->var;
+  if (V.rgb)
+    return fail(BSR_ERR_ARG, reg != nullptr ? "bsr_forward_tsm: this handle holds RGB-baseline weights: call bsr_forward_rgb"
+                                            : "bsr_forward: this handle holds RGB-baseline weights: call bsr_forward_rgb");
   if (V.tsm != (reg != nullptr))
     return fail(BSR_ERR_ARG, V.tsm ? "bsr_forward: this handle holds TSM weights: call bsr_forward_tsm" : "bsr_forward_tsm: this handle holds GSC weights: call bsr_forward");
   if (V.tsm && (frame <= 0 || B % frame != 0 || H != W))
@@ -813,6 +927,101 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
   return L.rc;
 }
 
+// The RGB baseline's Generator.call (/root/reference/model_RGB.py:228-266): stem, down1-3, uv concat, three 513-wide ResBottlenecks,
+// up1-3, conv2 (7x7 -> 3), conv3 (7x7 -> 3).  fp32 only (bsr_create refuses other dtypes for these weights).
+int bsr_forward_rgb(bsr_handle* h, const float* inputs, const float* uv, int B, int H, int W, float* con, void* stream) {
+  if (h == nullptr || inputs == nullptr || uv == nullptr || con == nullptr) return fail(BSR_ERR_ARG, "bsr_forward_rgb: null argument");
+  if (!h->var.rgb)
+    return fail(BSR_ERR_ARG, h->var.tsm ? "bsr_forward_rgb: this handle holds TSM weights: call bsr_forward_tsm"
+                                        : "bsr_forward_rgb: this handle holds GSC weights: call bsr_forward");
+  if (B <= 0) return fail(BSR_ERR_ARG, "bsr_forward_rgb: B must be positive");
+  if (H <= 0 || W <= 0 || H % 32 != 0 || W % 256 != 0)
+    return fail(BSR_ERR_ARG, "bsr_forward_rgb: H must be a multiple of 32 and W a multiple of 256 (reference: 256x256)");
+  const int H8 = H / 8, W8 = W / 8;
+  if ((H8 * W8) % 128 != 0) return fail(BSR_ERR_ARG, "bsr_forward_rgb: (H/8)*(W/8) must be a multiple of 128");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  HIP_TRY(guard.err);
+  int rc = ensure_workspace(h, B, H, W, s);
+  if (rc != BSR_OK) return rc;
+  h->ev_used = 0;
+  h->att_in_lds = false;
+  const PlanRGB& p = h->plan_rgb;
+  float* ws = h->ws;
+  const size_t npix = (size_t)B * H * W, ncell = npix / 64;
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+  Launcher L{h, s};
+  auto glue_begin = [&](const char* what) { L.begin(K_GLUE, what); };
+  auto glue_end = [&](const char* what) { L.check(hipGetLastError(), what); L.end(); };
+
+  // conv1 (model_RGB.py:230): the GSC stem kernel
+  {
+    LayerW l;
+    L.rc = find_layer(h, "conv1", 1, 7, 28, 32, &l);
+    if (L.rc == BSR_OK) {
+      bsr::StemArgs a{inputs, ws + p.x1, l.w, l.b, H, W, 0, 0, 0, nullptr};
+      L.begin(K_CONV7, "conv1");
+      L.check(bsr::launch_stem7<4, 0>(a, B, s), "conv1");
+      L.end();
+    }
+  }
+  // down1..3 (:231-233); x2 / x3 land in their skip-concat slots (:251-252)
+  L.conv<3, 3, 2, false, 2, 16, 1>(K_CONV3, "down1", ws + p.x1, 32, 0, 32, H, W, ws + p.c3, RGB_CS_C3, 128, 64, 1);
+  L.conv<3, 3, 2, false, 2, 16, 1>(K_CONV3, "down2", ws + p.c3, RGB_CS_C3, 128, 64, H2, W2, ws + p.c2, RGB_CS_C2, 192, 64, 1);
+  L.conv<3, 3, 2, false, 3, 16, 1>(K_CONV3, "down3", ws + p.c2, RGB_CS_C2, 192, 64, H4, W4, ws + p.xa, RGB_CS_A, 0, 96, 1);
+  // uv = resize(uv, [h, w]); x = cat[x, uv] (:237-238)
+  glue_begin("uv_resize8");
+  hipLaunchKernelGGL(bsr::uv_resize8_kernel, dim3((unsigned)((ncell * 3 + 255) / 256)), dim3(256), 0, s, uv, H, W, ws + p.xa, RGB_CS_A, 96,
+                     ws + p.xa, RGB_CS_A, 96, ncell);
+  glue_end("uv_resize8");
+
+  // ResBottleneck(513) + NonLocalBlock(513) (model.py:81-113, 6-61), blocks 0-2 only (:239-240)
+  auto res_block = [&](int i, const float* x, int x_cs) {
+    char nm[32];
+    float* y3 = ws + p.y3[i];
+    snprintf(nm, sizeof nm, "res%d.conv1", i);
+    L.conv<1, 1, 1, false, 2, 32, 3>(K_CONV1, nm, x, x_cs, 0, x_cs, H8, W8, ws + p.t1, RGB_D, 0, RGB_D, 1);
+    snprintf(nm, sizeof nm, "res%d.conv2", i);
+    L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, RGB_D, 0, RGB_D, H8, W8, ws + p.t2, RGB_D, 0, RGB_D, 1);
+    // conv3 + BN (256 -> 513) and theta | phi | g (513 -> 3 x 256) composed offline into ONE K = 256 GEMM (pack.py), N = [y3 544 | qkv 768];
+    // y3x = y3 + pad(x) absorbs the block's skip, so that the `w` GEMM reads one residual
+    snprintf(nm, sizeof nm, "res%d.c3q", i);
+    L.gemm<3, 8, 1>(K_CONV1, nm, ws + p.t2, RGB_D, ncell, y3, RGB_CS_R, RGB_CS_R + 3 * RGB_D, 0, x, x_cs, x_cs, ws + p.qkv, 3 * RGB_D, RGB_CS_R,
+                    RGB_CS_R);
+    if (L.rc == BSR_OK) {
+      snprintf(nm, sizeof nm, "res%d.attention", i);
+      L.begin(K_ATT, nm);
+      L.check(bsr::launch_nonlocal_attention256(ws + p.qkv, ws + p.att[i], B, H8 * W8, s), "attention256");
+      L.end();
+    }
+    // out = LeakyReLU(y3x + BN(w(att)))  (model.py:56-59, 105-113); pad channels 513-543 come out 0 (zero weights, bias, residual)
+    snprintf(nm, sizeof nm, "res%d.w", i);
+    L.gemm<3, 8, 1>(K_CONV1, nm, ws + p.att[i], RGB_D, ncell, ws + p.r[i], RGB_CS_R, RGB_CS_R, 1, y3, RGB_CS_R, RGB_CS_R);
+  };
+  res_block(0, ws + p.xa, RGB_CS_A);
+  res_block(1, ws + p.r[0], RGB_CS_R);
+  res_block(2, ws + p.r[1], RGB_CS_R);
+
+  // up1..3 = ConvT (:250-252)
+  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT, "up1", ws + p.r[2], RGB_CS_R, 0, RGB_CS_R, H8, W8, ws + p.c2, RGB_CS_C2, 0, 192, 1);
+  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up2", ws + p.c2, RGB_CS_C2, 0, RGB_CS_C2, H4, W4, ws + p.c3, RGB_CS_C3, 0, 128, 1);
+  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up3", ws + p.c3, RGB_CS_C3, 0, RGB_CS_C3, H2, W2, ws + p.ybuf, 128, 0, 128, 1);
+  // conv2 (:253): 7x1 matrix-core pass, then the seven horizontal taps + bias
+  L.conv71("rgb_head", ws + p.ybuf, 128, 128, H, W, ws + p.qh, RGB_CS_QH);
+  if (L.rc == BSR_OK) {
+    glue_begin("rgb_hsum");
+    hipLaunchKernelGGL(bsr::rgb_hsum_kernel, dim3((unsigned)((npix * 3 + 255) / 256)), dim3(256), 0, s, ws + p.qh, RGB_CS_QH, h->rgb_head_b, W,
+                       ws + p.yh, npix);
+    glue_end("rgb_hsum");
+    // conv3 (:254) -> con, and the workspace copy bsr_probe("con") reads
+    L.begin(K_CONV7, "rgb_tail");
+    L.check(bsr::launch_rgb_conv7(ws + p.yh, h->rgb_tail_w, B, H, W, con, ws + p.con, s), "rgb_tail");
+    L.end();
+  }
+  if (L.rc == BSR_OK) h->ran = true;
+  return L.rc;
+}
+
 int bsr_forward(bsr_handle* h, const float* inputs, const float* uv, int B, int H, int W, float* gs, float* con_rgb, float* mask22,
                 float* dif, void* stream) {
   return forward_impl(h, inputs, uv, nullptr, 1, 0, B, H, W, gs, con_rgb, mask22, dif, stream);
@@ -992,6 +1201,13 @@ int bsr_debug_attention_qw(const float* qkv, float* y, int B, int tokens, int qw
   return BSR_OK;
 }
 
+int bsr_debug_attention_rgb(const float* qkv, float* y, int B, int tokens, void* stream) {
+  if (qkv == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: null argument");
+  if (B <= 0 || tokens <= 0 || tokens % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: tokens must be a positive multiple of 32");
+  HIP_TRY(bsr::launch_nonlocal_attention256(qkv, y, B, tokens, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream) {
   return bsr_debug_attention_dtype(qkv, y, B, tokens, BSR_DTYPE_F32, stream);
 }
@@ -1005,6 +1221,34 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
   const Plan& p = h->plan;
   const int B = h->B, H = h->H, W = h->W;
   struct Src { size_t off; int hh, ww, cs, coff, c; bool half; };
+  if (h->var.rgb) {      // the RGB forward's probes (its workspace plan: PlanRGB)
+    const PlanRGB& q = h->plan_rgb;
+    std::string nm(name);
+    Src src{};
+    int i = -1;
+    if (nm.size() >= 4 && nm[nm.size() - 1] >= '0' && nm[nm.size() - 1] <= '2') i = nm[nm.size() - 1] - '0';
+    const std::string stem = i >= 0 ? nm.substr(0, nm.size() - 1) : nm;
+    if (nm == "x1") src = {q.x1, H, W, 32, 0, 32, false};
+    else if (nm == "x2") src = {q.c3, H / 2, W / 2, RGB_CS_C3, 128, 64, false};
+    else if (nm == "x3") src = {q.c2, H / 4, W / 4, RGB_CS_C2, 192, 64, false};
+    else if (nm == "x0") src = {q.xa, H / 8, W / 8, RGB_CS_A, 0, 99, false};
+    else if (i >= 0 && stem == "res") src = {q.r[i], H / 8, W / 8, RGB_CS_R, 0, 513, false};
+    else if (i >= 0 && stem == "att") src = {q.att[i], H / 8, W / 8, RGB_D, 0, RGB_D, false};
+    else if (i >= 0 && stem == "y3x") src = {q.y3[i], H / 8, W / 8, RGB_CS_R, 0, 513, false};
+    else if (nm == "up1") src = {q.c2, H / 4, W / 4, RGB_CS_C2, 0, 192, false};
+    else if (nm == "up2") src = {q.c3, H / 2, W / 2, RGB_CS_C3, 0, 128, false};
+    else if (nm == "up3") src = {q.ybuf, H, W, 128, 0, 128, false};
+    else if (nm == "y") src = {q.yh, H, W, 3, 0, 3, false};
+    else if (nm == "con") src = {q.con, H, W, 3, 0, 3, false};
+    else return fail(BSR_ERR_STATE, std::string("bsr_probe: unknown probe '") + name + "' for an RGB handle");
+    const size_t npix = (size_t)B * src.hh * src.ww;
+    shape4[0] = B; shape4[1] = src.hh; shape4[2] = src.ww; shape4[3] = src.c;
+    if (npix * src.c > cap_floats) return fail(BSR_ERR_ARG, "bsr_probe: destination too small");
+    hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, s, h->ws + src.off, src.cs, src.coff,
+                       src.c, dst, npix, 0);
+    HIP_TRY(hipGetLastError());
+    return BSR_OK;
+  }
   const bool p16 = h->dtype == BSR_DTYPE_F16;          // the tensors the f16 mode keeps as fp16 (forward_impl)
   Src src{};
   std::string nm(name);

@@ -242,3 +242,66 @@ class GeneratorTSM(Generator):
 
     def __call__(self, inputs, uv, reg, frame, share=True, chuck: int = 1, training: bool = False):
         return self.call_tsm(inputs, uv, reg, frame, share, chuck, training)
+
+
+class GeneratorRGB(Generator):
+    """Drop-in for ``Generator`` of /root/reference/model_RGB.py:198-266, the paper's single-stage RGB baseline (call site
+    /root/reference/train_RGB_test.py:414): one decoder predicts the shadow-free RGB image directly.
+
+        gen = GeneratorRGB()
+        gen.load_weights(weights)                    # model_RGB.py variables (generator_variable_shapes("rgb"))
+        con = gen(inputs, uv, reg, chuck=4, training=False)
+
+    ``reg`` and ``chuck`` are accepted and unused, as in the reference's ``call``.  fp32 only (``dtype="f32"``)."""
+
+    def __init__(self, downsize: int = 1, n_res: int = 6, device: Optional[int] = None, dtype: str = "f32"):
+        if dtype != "f32":
+            raise ValueError("GeneratorRGB is provided in dtype 'f32' only (the RGB baseline has no 'f32x3' / 'f16' path), got %r" % (dtype,))
+        super().__init__(downsize, n_res, device, dtype)
+
+    def load_weights(self, weights: Dict[str, np.ndarray]) -> "GeneratorRGB":
+        from .weights import detect_variant
+        if detect_variant(weights) != "rgb":
+            raise ValueError("GeneratorRGB needs the RGB baseline's weights (model_RGB.py: 256-wide res_stack/0/conv1), got %s weights"
+                             % detect_variant(weights))
+        return super().load_weights(weights)
+
+    def __call__(self, inputs, uv, reg=None, chuck: int = 1, training: bool = False, out: Optional[torch.Tensor] = None):
+        """``out``: optional caller-supplied [B,H,W,3] float32 CUDA tensor for ``con``.  Returns ``con`` [B,H,W,3]."""
+        if training:
+            raise NotImplementedError("only the inference path (training=False) is implemented (/root/reference/train_RGB_test.py:414)")
+        if self._handle is None:
+            raise RuntimeError("GeneratorRGB has no weights: call load_weights() or restore() first")
+        dev = self._device
+        inputs = self._check_input(inputs, "inputs", dev)
+        uv = self._check_input(uv, "uv", dev)
+        if uv.shape != inputs.shape:
+            raise ValueError("inputs %s and uv %s must have the same shape" % (tuple(inputs.shape), tuple(uv.shape)))
+        B, H, W, _ = inputs.shape
+        if H % 32 or W % 256:
+            raise ValueError("H must be a multiple of 32 and W of 256 (reference IMG_SIZE = 256), got %dx%d" % (H, W))
+        with torch.cuda.device(dev):
+            if out is None:
+                con = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
+            else:
+                if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.float32
+                        or out.device.type != "cuda" or out.device.index != dev or not out.is_contiguous()):
+                    raise ValueError("out must be a contiguous float32 [B,H,W,3] tensor on cuda:%d" % dev)
+                con = out
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = self._lib.bsr_forward_rgb(self._handle, inputs.data_ptr(), uv.data_ptr(), B, H, W, con.data_ptr(), stream)
+        _lib.check(rc, "bsr_forward_rgb")
+        self._shape = (B, H, W)
+        return con
+
+    def reserve(self, B: int, H: int, W: int) -> None:
+        """Allocate the workspace for forwards up to [B,H,W] now: later forwards of that size allocate nothing (bsr_reserve)."""
+        if self._handle is None:
+            raise RuntimeError("GeneratorRGB has no weights: call load_weights() or restore() first")
+        _lib.check(self._lib.bsr_reserve(self._handle, int(B), int(H), int(W)), "bsr_reserve")
+
+    def workspace_bytes(self, B: int, H: int, W: int) -> int:
+        return int(self._lib.bsr_handle_workspace_bytes(self._handle, int(B), int(H), int(W)))
+
+    def call_tsm(self, *a, **k):
+        raise TypeError("GeneratorRGB has no TSM forward")

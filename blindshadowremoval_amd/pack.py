@@ -40,6 +40,8 @@ def geometry(variant: str = "gsc", dtype: str = "f32") -> Dict[str, Tuple[int, i
     (/root/reference/model_with_TSM.py) only widens the K of the layers fed by the ShareLayer concats: 291 -> 312, 877 -> 888
     (320 / 896 in the 16-bit modes).
     The 16-bit modes use 32-channel K chunks, so the 257 / 261-wide trunk tensors get stride 288 instead of 264 (kGSC16)."""
+    if variant == "rgb":
+        return geometry_rgb(dtype)
     tsm = variant == "tsm"
     h16 = dtype != "f32"
     if tsm:
@@ -57,6 +59,25 @@ def geometry(variant: str = "gsc", dtype: str = "f32") -> Dict[str, Tuple[int, i
         g["res%d.conv2" % i] = (32, 128, 128)
         g["res%d.c3q" % i] = (32, 128, 768)       # [y3: 257 real of 288 | theta|phi|g: 384 | 3 zero tiles of slack]
         g["res%d.w" % i] = (32, 128, 384)         # 257 real of 288 + 3 zero tiles of slack (gemm_nloop group reads)
+    return g
+
+
+def geometry_rgb(dtype: str = "f32") -> Dict[str, Tuple[int, int, int]]:
+    """The RGB baseline (/root/reference/model_RGB.py; fp32 only): name -> (CC, k_pad, n_pad), matching bsr_forward_rgb in csrc/bsr_api.hip.
+    The 513-wide block outputs and y3x live at stride 544 (17 tiles of 32); xa = cat[x, uv] (99) at stride 128.
+    c3q: N = [y3 513 of 544 | theta|phi|g 768] + 2 zero tiles of slack (gemm_nloop group reads, NI = 3); w: 513 of 544 + 3 zero tiles.
+    rgb_head: conv2 as a 7x1 conv, taps = ky, K = 128 channels, N = (kx, co) = 21 of 32."""
+    if dtype != "f32":
+        raise ValueError("the RGB baseline is provided in f32 only (dtype 'f32x3' / 'f16' are not)")
+    g: Dict[str, Tuple[int, int, int]] = {
+        "conv1": (24, 24, 32), "down1": (16, 32, 64), "down2": (16, 64, 64), "down3": (16, 64, 96),
+        "up1": (32, 544, 192), "up2": (32, 256, 128), "up3": (32, 192, 128), "rgb_head": (32, 128, 32),
+    }
+    for i in range(N_RES // 2):
+        g["res%d.conv1" % i] = (32, 128 if i == 0 else 544, 256)
+        g["res%d.conv2" % i] = (32, 256, 256)
+        g["res%d.c3q" % i] = (32, 256, 544 + 768 + 64)
+        g["res%d.w" % i] = (32, 256, 544 + 96)
     return g
 
 
@@ -223,6 +244,48 @@ def layer_matrices(w: Dict[str, np.ndarray]) -> "Dict[str, Tuple[np.ndarray, np.
     return out
 
 
+def layer_matrices_rgb(w: Dict[str, np.ndarray]) -> "Dict[str, Tuple[np.ndarray, np.ndarray]]":
+    """layer_matrices() of the RGB baseline (/root/reference/model_RGB.py:198-266): folded [taps, K, N] kernels + biases (float64)."""
+    out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
+
+    def hwio(stem):
+        k = w[stem + "/kernel"]
+        return k.reshape(k.shape[0] * k.shape[1], k.shape[2], k.shape[3])
+
+    k = w["conv1/conv/kernel"]
+    out["conv1"] = fold_bn(k.reshape(7, 21, 32), w["conv1/conv/bias"], _bn(w, "conv1/bnorm"))
+    for nm in ("down1", "down2", "down3"):
+        out[nm] = fold_bn(hwio(nm + "/conv"), w[nm + "/conv/bias"], _bn(w, nm + "/bnorm"))
+    for nm in ("up1", "up2", "up3"):
+        k = w[nm + "/conv/kernel"]
+        out[nm] = fold_bn(k.reshape(9, k.shape[2], k.shape[3]).transpose(0, 2, 1), w[nm + "/conv/bias"], _bn(w, nm + "/bnorm"))
+    # conv2 'tconv3' (7x7, 128 -> 3, no BN): taps = ky, K = c, N = kx * 3 + co; its bias is added after the horizontal sum (rgb_head.h)
+    k2 = w["conv2/conv/kernel"].astype(np.float64)                             # [ky, kx, c, co]
+    out["rgb_head"] = (k2.transpose(0, 2, 1, 3).reshape(7, 128, 21), np.zeros(21))
+    for i in range(N_RES // 2):
+        st = "res_stack/%d/" % i
+        out["res%d.conv1" % i] = fold_bn(hwio(st + "conv1"), w[st + "conv1/bias"], _bn(w, st + "bnorm1"))
+        out["res%d.conv2" % i] = fold_bn(hwio(st + "conv2"), w[st + "conv2/bias"], _bn(w, st + "bnorm2"))
+        # conv3 + bnorm3 -> y3 (513), then theta | phi | g with no nonlinearity in between: one K = 256 GEMM, N = [y3 (513 of 544) | q k v]
+        k3, b3 = fold_bn(hwio(st + "conv3"), w[st + "conv3/bias"], _bn(w, st + "bnorm3"))            # [1,256,513], [513]
+        qkv = np.concatenate([hwio(st + "non_local/" + n) for n in ("theta", "phi", "g")], axis=2).astype(np.float64)   # [1,513,768]
+        qb = np.concatenate([w[st + "non_local/%s/bias" % n] for n in ("theta", "phi", "g")]).astype(np.float64)
+        kc = np.zeros((1, 256, 544 + 768))
+        bc = np.zeros(544 + 768)
+        kc[0, :, :513] = k3[0]
+        bc[:513] = b3
+        kc[0, :, 544:] = k3[0] @ qkv[0]
+        bc[544:] = b3 @ qkv[0] + qb
+        out["res%d.c3q" % i] = (kc, bc)
+        out["res%d.w" % i] = fold_bn(hwio(st + "non_local/w"), w[st + "non_local/w/bias"], _bn(w, st + "non_local/bnorm"))
+    return out
+
+
+def rgb_tail_weights(w: Dict[str, np.ndarray]) -> np.ndarray:
+    """conv3 'tconv4' (7x7, 3 -> 3, no BN) as HWIO [7][7][3][3] then its bias [3], for rgb_conv7_kernel (csrc/rgb_head.h)."""
+    return np.concatenate([w["conv3/conv/kernel"].reshape(-1), w["conv3/conv/bias"]]).astype(np.float32)
+
+
 def clr_gs_weights(w: Dict[str, np.ndarray]) -> np.ndarray:
     """[16 n][16 k] float32: BN-folded clr_conv1 weights of the gs input channel, k = 3x3 tap index (k >= 9 zero)."""
     k, _ = fold_bn(w["clr_conv1/conv/kernel"].reshape(9, 65, 16), w["clr_conv1/conv/bias"], _bn(w, "clr_conv1/bnorm"))
@@ -244,6 +307,8 @@ def pack_generator(weights: Dict[str, np.ndarray], dtype: str = "f32") -> bytes:
         raise ValueError("dtype must be one of %s" % sorted(DTYPES))
     variant = detect_variant(weights)
     check_weights(weights, variant)
+    if variant == "rgb":
+        return _pack_rgb(weights, dtype)
     geo = geometry(variant, dtype)
     entries: List[Tuple[str, np.ndarray, Tuple[int, int, int, int]]] = []
     for name, (k, b) in layer_matrices(weights).items():
@@ -267,7 +332,23 @@ def pack_generator(weights: Dict[str, np.ndarray], dtype: str = "f32") -> bytes:
     entries.append(("heads.bias", np.array([weights["conv2/conv/bias"][0], weights["conv3/conv/bias"][0]], np.float32), (2, 0, 0, 0)))
     entries.append(("clr_conv1.gs", clr_gs_weights(weights), (16, 16, 0, 0)))
     entries.append(("tail.w", tail_weights(weights), (323, 0, 0, 0)))
+    return _write_blob(entries, dtype)
 
+
+def _pack_rgb(weights: Dict[str, np.ndarray], dtype: str) -> bytes:
+    geo = geometry_rgb(dtype)
+    entries: List[Tuple[str, np.ndarray, Tuple[int, int, int, int]]] = []
+    for name, (k, b) in layer_matrices_rgb(weights).items():
+        cc, k_pad, n_pad = geo[name]
+        arr, bias = pack_taps(k, b, cc, k_pad, n_pad)
+        entries.append((name + ".w", arr, tuple(arr.shape)))
+        entries.append((name + ".b", bias, (n_pad, 0, 0, 0)))
+    entries.append(("rgb.head_bias", weights["conv2/conv/bias"].astype(np.float32), (3, 0, 0, 0)))
+    entries.append(("rgb.tail", rgb_tail_weights(weights), (444, 0, 0, 0)))
+    return _write_blob(entries, dtype)
+
+
+def _write_blob(entries, dtype: str) -> bytes:
     off = _HEADER.size + _ENTRY.size * len(entries)
     off = (off + 255) & ~255
     table = bytearray()

@@ -31,11 +31,53 @@ def _conv(spec, stem, kh, cin, cout, bn, transpose=False):
             spec[stem + "/bnorm/" + p] = (cout,)
 
 
+RGB_CH = 2 * N_CH[5] + 1        # 513: ResBottleneck(n_ch[5]*2+1) of /root/reference/model_RGB.py:226
+
+
+def rgb_variable_shapes() -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape for the variables of the single-stage RGB baseline (/root/reference/model_RGB.py:198-266).  Keras creates variables
+    only for layers that are called: ``call`` (:228-266) uses conv1-3, down1-3, up1-3 and res_stack[0:3]; clr_*, res_stack[3:6] and
+    info_share are constructed but never called, so the checkpoint holds none of their variables (tests/golden/model_py_rgb_64.npz records
+    the inventory the reference's own forward builds)."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c0 = N_CH[3] + 3                                        # cat[x, uv] = 99 (:237-238)
+    _conv(s, "conv1", 7, 3, N_CH[0], True)                  # :203 'tconv1'
+    _conv(s, "conv2", 7, N_CH[1] * 2, 3, False)             # :204 'tconv3': 7x7 on up3's 128 channels, no BN, no activation
+    _conv(s, "conv3", 7, 3, 3, False)                       # :205 'tconv4': 7x7 on conv2's output
+    _conv(s, "down1", 3, N_CH[0], N_CH[1], True)
+    _conv(s, "down2", 3, N_CH[1], N_CH[2], True)
+    _conv(s, "down3", 3, N_CH[2], N_CH[3], True)
+    _conv(s, "up1", 3, RGB_CH, N_CH[3] * 2, True, transpose=True)                  # 513 -> 192 (:210,250)
+    _conv(s, "up2", 3, N_CH[3] * 2 + N_CH[2], N_CH[2] * 2, True, transpose=True)   # cat[y, x3] = 256 -> 128 (:211,251)
+    _conv(s, "up3", 3, N_CH[2] * 2 + N_CH[1], N_CH[1] * 2, True, transpose=True)   # cat[y, x2] = 192 -> 128 (:212,252)
+    half = RGB_CH // 2                                      # 256
+    for i in range(N_RES // 2):                             # :239-240
+        cin = c0 if i == 0 else RGB_CH
+        st = "res_stack/%d/" % i
+        for name, shp in (("conv1", (1, 1, cin, half)), ("conv2", (3, 3, half, half)), ("conv3", (1, 1, half, RGB_CH))):
+            s[st + name + "/kernel"] = shp
+            s[st + name + "/bias"] = (shp[3],)
+        for j, c in ((1, half), (2, half), (3, RGB_CH)):
+            for p in ("gamma", "beta", "moving_mean", "moving_variance"):
+                s[st + "bnorm%d/%s" % (j, p)] = (c,)
+        for name in ("g", "phi", "theta"):
+            s[st + "non_local/%s/kernel" % name] = (1, 1, RGB_CH, half)
+            s[st + "non_local/%s/bias" % name] = (half,)
+        s[st + "non_local/w/kernel"] = (1, 1, half, RGB_CH)
+        s[st + "non_local/w/bias"] = (RGB_CH,)
+        for p in ("gamma", "beta", "moving_mean", "moving_variance"):
+            s[st + "non_local/bnorm/" + p] = (RGB_CH,)
+    return s
+
+
 def generator_variable_shapes(variant: str = "gsc") -> "OrderedDict[str, Tuple[int, ...]]":
-    """name -> shape for the 258 float32 variables of the generator.  ``variant``: "gsc" (/root/reference/model.py) or
-    "tsm" (/root/reference/model_with_TSM.py: ShareLayer widens the bottleneck inputs to 291 / 877 channels)."""
-    if variant not in ("gsc", "tsm"):
-        raise ValueError("variant must be 'gsc' or 'tsm'")
+    """name -> shape for the 258 float32 variables of the generator.  ``variant``: "gsc" (/root/reference/model.py),
+    "tsm" (/root/reference/model_with_TSM.py: ShareLayer widens the bottleneck inputs to 291 / 877 channels) or "rgb"
+    (/root/reference/model_RGB.py: the single-stage baseline, ``rgb_variable_shapes``)."""
+    if variant not in ("gsc", "tsm", "rgb"):
+        raise ValueError("variant must be 'gsc', 'tsm' or 'rgb'")
+    if variant == "rgb":
+        return rgb_variable_shapes()
     tsm = variant == "tsm"
     c0 = N_CH[3] + 3 + (2 * N_CH[3] if tsm else 0)            # cat[x, (x_share,) uv]: 99 | 291
     c12 = max(c0, RES_CH)                                       # output width of res blocks 0-2: 257 | 291
@@ -116,13 +158,16 @@ def init_weights(seed: int = 1, con_bias_shift: float = 0.25, variant: str = "gs
         else:                               # bias, beta, moving_mean
             w = rng.standard_normal(shp) * 0.05
         out[name] = w.astype(np.float32)
-    if con_bias_shift:
+    if con_bias_shift and variant != "rgb":          # the RGB baseline has no threshold: its conv3 is the output layer
         out["conv3/conv/bias"] = (out["conv3/conv/bias"] + np.float32(con_bias_shift)).astype(np.float32)
     return out
 
 
 def detect_variant(weights: Dict[str, np.ndarray]) -> str:
+    """"gsc", "tsm" (291-channel res0 input) or "rgb" (256-wide bottleneck convs of the 513-channel blocks)."""
     k = weights.get("res_stack/0/conv1/kernel")
+    if k is not None and k.shape[3] == RGB_CH // 2:
+        return "rgb"
     return "tsm" if k is not None and k.shape[2] == 291 else "gsc"
 
 

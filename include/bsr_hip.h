@@ -75,6 +75,14 @@ int bsr_forward_packed(bsr_handle* h, const float* inputs, const float* uv, int 
 int bsr_forward_tsm(bsr_handle* h, const float* inputs, const float* uv, const float* reg, int B, int H, int W, int frame, int share,
                     float* gs, float* con_rgb, float* mask22, float* dif, void* stream);
 
+/* The single-stage RGB baseline (added in ABI 8: additive, no existing signature changed): replaces Generator.call(inputs, uv, reg, chuck, training=False) of /root/reference/model_RGB.py:228-266
+ * (call site /root/reference/train_RGB_test.py:414).  The handle must have been created from RGB weights (pack_generator of the
+ * model_RGB.py variable set; bsr_create recognises them and accepts BSR_DTYPE_F32 only).  con [B,H,W,3]: caller-allocated output, the
+ * reference's only return value.  Same shape rules as bsr_forward; asynchronous and allocation-free after bsr_reserve.  bsr_forward /
+ * bsr_forward_tsm refuse an RGB handle and this entry refuses a GSC or TSM one (BSR_ERR_ARG).  Probes: x1 x2 x3 x0 y3x<i> att<i> res<i>
+ * (i < 3) up1 up2 up3 y (conv2's output) con.  bsr_workspace_bytes(B,H,W) describes GSC handles; use bsr_handle_workspace_bytes. */
+int bsr_forward_rgb(bsr_handle* h, const float* inputs, const float* uv, int B, int H, int W, float* con, void* stream);
+
 /* Range guard of BSR_DTYPE_F32X3 / BSR_DTYPE_F16.  Those modes convert fp32 activations to fp16 operands inside the kernels; a value of
  * magnitude >= 65520 would become inf (and its lo half NaN) where the fp32 path stays finite.  Every converting kernel checks what
  * it converts and sets a sticky, host-visible flag on the handle.  bsr_check_range synchronises `stream` (the stream the forwards
@@ -185,6 +193,9 @@ int bsr_ucb_post(int device, const float* rows10, const unsigned char* masks, co
 /* Test hook: the fused NonLocalBlock attention kernel alone (/root/reference/model.py:51-53).
  * qkv [B,tokens,384] (theta | phi | g, 128 channels each) -> y [B,tokens,128]; tokens % 128 == 0. */
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream);
+/* Test hook (added in ABI 8: additive, no existing signature changed): the d = 256 attention of the RGB baseline's 513-channel NonLocalBlock alone (csrc/attention256.h).
+ * qkv [B,tokens,768] (theta | phi | g, 256 channels each) -> y [B,tokens,256]; tokens % 32 == 0. */
+int bsr_debug_attention_rgb(const float* qkv, float* y, int B, int tokens, void* stream);
 /* The same with the kernel of a given BSR_DTYPE_*: F32 = fp32 matrix cores; F32X3 / F16 = the split-precision kernel (attention is
  * split-precision in both 16-bit modes). */
 int bsr_debug_attention_dtype(const float* qkv, float* y, int B, int tokens, int dtype, void* stream);
