@@ -56,6 +56,9 @@ def main() -> int:
             elif isinstance(job, tuple) and job and job[0] == "ucb_post":
                 from blindshadowremoval_amd.ucb_post import run_post_job
                 result = run_post_job(job[1])
+            elif isinstance(job, tuple) and job and job[0] == "ucb_post_rgb":                  # FSRNetRGB.test's host post-processing
+                from blindshadowremoval_amd.ucb_post_rgb import run_post_job_rgb
+                result = run_post_job_rgb(job[1])
             else:
                 result = build_element(job)
             payload = pickle.dumps(("ok", result), protocol=pickle.HIGHEST_PROTOCOL)

@@ -27,6 +27,7 @@
 #include "rgb_head.h"
 #include "stem7.h"
 #include "ucb_kernels.h"
+#include "ucb_rgb_kernels.h"
 
 namespace {
 
@@ -1143,6 +1144,24 @@ int bsr_ucb_post(int device, const float* rows10, const unsigned char* masks, co
   DeviceGuard guard(device);
   HIP_TRY(guard.err);
   HIP_TRY(bsr::launch_ucb_post(rows10, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+size_t bsr_ucb_post_rgb_scratch_bytes(int B, int S) {
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
+  return (size_t)B * bsr::ucb_rgb_item_scratch_bytes(S);
+}
+
+int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
+                     unsigned char* strips, float* figs, int* status, void* scratch, void* stream) {
+  if (rows9 == nullptr || masks == nullptr || boxes == nullptr || losses == nullptr || strips == nullptr || status == nullptr || scratch == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: null argument");
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
+    return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: scratch must be 256-byte aligned");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_ucb_post_rgb(rows9, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
   return BSR_OK;
 }
 

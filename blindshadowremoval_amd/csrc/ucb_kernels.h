@@ -21,7 +21,8 @@
 // scalars of the next stage).  Same arithmetic, same decisions, same bytes; what a stage reads of another workgroup's results crosses a
 // kernel boundary (union-find parents: agent-scope atomics, as before).
 // ucb_ssim_kernel: tf.image.ssim's 11x11 Gaussian window as two separable float32 passes through LDS + the squared error for PSNR,
-// one partial sum per workgroup, folded in a fixed order (deterministic).
+// one partial sum per workgroup, folded in a fixed order (deterministic).  Its tile routine (ucb_ssim_tile) and the fold
+// (ucb_ssim_finish) also serve the RGB baseline's post-processing (ucb_rgb_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -556,14 +557,17 @@ __global__ __launch_bounds__(256) void ucb_s7_kernel(int S, void* scratch, unsig
 // 'VALID', float32, vertical then horizontal pass over x, y, x^2, y^2, xy; one 16x16 tile of the (S-10)^2 map per workgroup.
 constexpr int kSsimTile = 16, kSsimWin = 11, kSsimIn = kSsimTile + kSsimWin - 1;
 
-__global__ __launch_bounds__(256) void ucb_ssim_kernel(int S, void* scratch) {
+// The tile routine is shared by the GSC chain (ucb_ssim_kernel) and the RGB baseline's post-processing (ucb_rgb_kernels.h): `src`
+// says where the two operands live — src.x(q, c) / src.y(q, c) = channel c of pixel q of the ground truth / the composite.  Tile
+// blockIdx.x of the image writes its two partial sums to part[blockIdx.x] and part[nblk + blockIdx.x].
+template <typename Src>
+__device__ __forceinline__ void ucb_ssim_tile(const Src& src, int S, double* part) {
   __shared__ float s_x[kSsimIn][kSsimIn + 1], s_y[kSsimIn][kSsimIn + 1];
   __shared__ float s_v[5][kSsimTile][kSsimIn + 1];
   __shared__ double s_red[2][256];
-  const int item = blockIdx.y, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const int tiles = (S + kSsimTile - 1) / kSsimTile;
   const int ty0 = (blockIdx.x / tiles) * kSsimTile, tx0 = (blockIdx.x % tiles) * kSsimTile;
-  const UcbScratch sc = ucb_scratch(scratch, item, S);
   const int M = S - kSsimWin + 1;                              // size of the SSIM map
   float g[kSsimWin];
   {
@@ -578,7 +582,7 @@ __global__ __launch_bounds__(256) void ucb_ssim_kernel(int S, void* scratch) {
       const int yy = i / kSsimIn, xx = i % kSsimIn;
       const int y = ty0 + yy, x = tx0 + xx;
       float a = 0.f, b = 0.f;
-      if (y < S && x < S) { a = sc.w[((size_t)y * S + x) * kUcbCh + c]; b = sc.out[((size_t)y * S + x) * 3 + c]; }
+      if (y < S && x < S) { a = src.x((size_t)y * S + x, c); b = src.y((size_t)y * S + x, c); }
       s_x[yy][xx] = a; s_y[yy][xx] = b;
     }
     __syncthreads();
@@ -621,23 +625,40 @@ __global__ __launch_bounds__(256) void ucb_ssim_kernel(int S, void* scratch) {
   }
   if (tid == 0) {
     const int nblk = tiles * tiles;
-    sc.ssim_part[blockIdx.x] = s_red[0][0];
-    sc.ssim_part[nblk + blockIdx.x] = s_red[1][0];
+    part[blockIdx.x] = s_red[0][0];
+    part[nblk + blockIdx.x] = s_red[1][0];
   }
 }
 
-__global__ __launch_bounds__(64) void ucb_ssim_finish_kernel(int S, void* scratch, const int* __restrict__ status, float* __restrict__ losses, int B) {   // grid (B), one wave
-  const int item = blockIdx.x, lane = threadIdx.x;
-  const UcbScratch sc = ucb_scratch(scratch, item, S);
+struct UcbGscSsimOperands {              // the GSC chain's operands: gt in channels 0-2 of the resized planes, the composite in `out`
+  const float* w;
+  const float* out;
+  __device__ float x(size_t q, int c) const { return w[q * kUcbCh + c]; }
+  __device__ float y(size_t q, int c) const { return out[q * 3 + c]; }
+};
+
+__global__ __launch_bounds__(256) void ucb_ssim_kernel(int S, void* scratch) {
+  const UcbScratch sc = ucb_scratch(scratch, blockIdx.y, S);
+  ucb_ssim_tile(UcbGscSsimOperands{sc.w, sc.out}, S, sc.ssim_part);
+}
+
+// The tiles' partial sums of one item -> loss2[0] = ssim, loss2[1] = psnr (NaN both when !ok).  One wave.
+__device__ __forceinline__ void ucb_ssim_finish(const double* part, int S, bool ok, float* loss2) {
+  const int lane = threadIdx.x;
   const int tiles = (S + kSsimTile - 1) / kSsimTile, nblk = tiles * tiles;
   double a = 0.0, e = 0.0;
-  for (int i = lane; i < nblk; i += 64) { a += sc.ssim_part[i]; e += sc.ssim_part[nblk + i]; }      // a fixed order: lane partials, then a butterfly
+  for (int i = lane; i < nblk; i += 64) { a += part[i]; e += part[nblk + i]; }      // a fixed order: lane partials, then a butterfly
   for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); e += __shfl_xor(e, o); }
   if (lane != 0) return;
   const int M = S - kSsimWin + 1;
-  if (status[item] != UCB_OK) { losses[2 * item] = __builtin_nanf(""); losses[2 * item + 1] = __builtin_nanf(""); return; }
-  losses[2 * item] = (float)(a / ((double)M * M * 3.0));
-  losses[2 * item + 1] = (float)(20.0 * log10(1.0) - 10.0 * log10(e / ((double)S * S * 3.0)));
+  if (!ok) { loss2[0] = __builtin_nanf(""); loss2[1] = __builtin_nanf(""); return; }
+  loss2[0] = (float)(a / ((double)M * M * 3.0));
+  loss2[1] = (float)(20.0 * log10(1.0) - 10.0 * log10(e / ((double)S * S * 3.0)));
+}
+
+__global__ __launch_bounds__(64) void ucb_ssim_finish_kernel(int S, void* scratch, const int* __restrict__ status, float* __restrict__ losses, int B) {   // grid (B), one wave
+  const int item = blockIdx.x;
+  ucb_ssim_finish(ucb_scratch(scratch, item, S).ssim_part, S, status[item] == UCB_OK, losses + 2 * item);
 }
 
 inline hipError_t launch_ucb_post(const float* rows10, const unsigned char* masks, const float* boxes, int B, int S, float* losses,

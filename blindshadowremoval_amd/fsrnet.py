@@ -440,6 +440,7 @@ class FSRNet(object):
         (the multi-process CPU tests pass a stand-in: the product path has no CPU generator)."""
         self.config = config
         self.group = group
+        self._check_gen(gen)
         if gen is not None:
             self.gen = gen
         else:
@@ -462,6 +463,59 @@ class FSRNet(object):
         self.return_figs = True                  # False: FSRNet.test returns (name, None, losses) — the figures are only written as PNG strips
         self._post_writes_png = False            # set by test(): the post-processing workers write the PNG strips themselves
         self._post_pool, self._post_pool_n = None, 0
+
+    # -- what is model-specific in the loops (FSRNetRGB overrides these) ----------------------
+    POST_FIGS = 7                                # figures per item of test()'s post-processing (train_test_GSC.py:744)
+    POST_JOB = "ucb_post"                        # the worker pool's job kind of the host post-processing (_row_worker.py)
+
+    @staticmethod
+    def _check_gen(gen) -> None:
+        from .model import GeneratorRGB
+        if isinstance(gen, GeneratorRGB):
+            raise TypeError("FSRNet drives the GSC generator; the RGB baseline (GeneratorRGB) is driven by fsrnet.FSRNetRGB")
+
+    def _generate(self, im_d: torch.Tensor, uv_d: torch.Tensor, ucb: bool):
+        """The loops' generator call (train_test_GSC.py:421, :868) -> the generator's outputs."""
+        return self.gen(im_d, uv_d, None, chuck=4 if ucb else 1, training=False)
+
+    @staticmethod
+    def _post_outputs(outs) -> Tuple[torch.Tensor, ...]:
+        """The generator outputs test()'s post-processing reads, in their channel order after input | gt: con_rgb 3 | dif 1."""
+        _, con_rgb, _, mask_pred = outs
+        return con_rgb, mask_pred
+
+    @staticmethod
+    def _post_device(device: int):
+        from .ucb_post_gpu import UcbPostDevice
+        return UcbPostDevice(device)
+
+    @staticmethod
+    def _run_post_device(post_dev, rows: torch.Tensor, masks: torch.Tensor, boxes: torch.Tensor, want_figs: bool):
+        """rows: [B,S,S,3+3+channels of _post_outputs], masks: [B,7,S,S] uint8 (MASK_ORDER) -> (losses, strips, figs | None, status)."""
+        return post_dev.run(rows, masks, boxes, want_figs=want_figs)
+
+    @staticmethod
+    def _host_post_arrays(host: np.ndarray, j: int) -> Dict[str, np.ndarray]:
+        """Item j's arrays of the host post-processing, from the [B,S,S,10] block copied off the device."""
+        return {"im": host[j, ..., 0:3], "gt": host[j, ..., 3:6], "con": host[j, ..., 6:9], "mp": host[j, ..., 9:10]}
+
+    @staticmethod
+    def _host_post_fn():
+        from .ucb_post import run_post_job
+        return run_post_job
+
+    def _warm_post_device(self, dev: int) -> None:
+        """Run the device post-processing and the PNG encoder once on a dummy item (warm_pools)."""
+        from .prep import unpack_masks
+        s = self.config.IMG_SIZE
+        d = torch.device("cuda", dev)
+        bits = np.zeros((7, s * s // 8), np.uint8)
+        bits[:, : s * s // 16] = 255
+        masks = unpack_masks([("bits", bits, s)], d)
+        rows = torch.rand((1, s, s, 10), device=d)
+        _, strips, _, status = self._post_device(dev).run(rows, masks, torch.tensor([[0, 0, s - 16, s - 16]], dtype=torch.float32, device=d))
+        self.log.encode_strips(strips)
+        torch.cat([strips.reshape(-1)[:8], status.view(torch.uint8)]).cpu()
 
     # -- worker pools ----------------------------------------------------------------------
     def _get_post_pool(self):
@@ -494,17 +548,7 @@ class FSRNet(object):
                 if self._pin_pool[k] is None:
                     self._pin_pool[k] = torch.empty(24 << 20, dtype=torch.uint8).pin_memory()
         if self.post_device and dev is not None and torch.cuda.is_available():
-            from .prep import unpack_masks
-            from .ucb_post_gpu import UcbPostDevice
-            s = self.config.IMG_SIZE
-            d = torch.device("cuda", dev)
-            bits = np.zeros((7, s * s // 8), np.uint8)
-            bits[:, : s * s // 16] = 255
-            masks = unpack_masks([("bits", bits, s)], d)
-            rows = torch.rand((1, s, s, 10), device=d)
-            _, strips, _, status = UcbPostDevice(dev).run(rows, masks, torch.tensor([[0, 0, s - 16, s - 16]], dtype=torch.float32, device=d))
-            self.log.encode_strips(strips)
-            torch.cat([strips.reshape(-1)[:8], status.view(torch.uint8)]).cpu()
+            self._warm_post_device(dev)
         elif self.post_workers > 0:
             self._get_post_pool().warm("post")
 
@@ -640,8 +684,7 @@ class FSRNet(object):
         post_dev = None
         pend_masks: Dict[int, object] = {}
         if ucb and postprocess and on_gpu and self.post_device:
-            from .ucb_post_gpu import UcbPostDevice
-            post_dev = UcbPostDevice(self.gen._device)
+            post_dev = self._post_device(self.gen._device)
             if hasattr(dataset, "ucb_mask_files") and getattr(dataset, "device_prep", None) is not None and not getattr(dataset, "_started", False):
                 dataset.ucb_mask_files = mask_files      # the loader's workers decode the masks next to the images (bit-packed through the pipe)
         post_pool = self._get_post_pool() if ucb and postprocess and self.post_workers > 0 and post_dev is None else None
@@ -749,7 +792,7 @@ class FSRNet(object):
                 rows = torch.cat([self._split_row0(p[2]) for p in pending], dim=0)
                 rows_d = rows.to(dev, non_blocking=True)            # ONE host-to-device copy of the packed rows (none when the loader prepared them on the device)
             im_d, gt_d, uv_d, _, face_d = torch.split(rows_d, list(SPLIT_FFHQ), dim=3)
-            gs, con_rgb, _, mask_pred = self.gen(im_d, uv_d, None, chuck=4 if ucb else 1, training=False)
+            outs = self._generate(im_d, uv_d, ucb)
             items = list(pending)
             pending.clear()
             if post_dev is not None:
@@ -763,14 +806,14 @@ class FSRNet(object):
                 if side:
                     fwd_done = torch.cuda.Event()
                     fwd_done.record()
-                    for t_ in (rows_d, con_rgb, mask_pred) + tuple(pk[1] for pk in packed if isinstance(pk[1], torch.Tensor)):
+                    for t_ in (rows_d,) + tuple(self._post_outputs(outs)) + tuple(pk[1] for pk in packed if isinstance(pk[1], torch.Tensor)):
                         t_.record_stream(post_stream)      # allocated on other streams, read by this one
                 with torch.cuda.stream(post_stream) if side else contextlib.nullcontext():
                     if side:
                         post_stream.wait_event(fwd_done)
                     boxes = torch.from_numpy(np.stack([np.asarray(it[3], np.float32).reshape(-1)[:4] for it in items])).to(dev, non_blocking=True)
-                    losses_d, strips_d, figs_d, status_d = post_dev.run(torch.cat([im_d, gt_d, con_rgb, mask_pred], dim=3), unpack_masks(packed, dev), boxes,
-                                                                        want_figs=self.return_figs)
+                    losses_d, strips_d, figs_d, status_d = self._run_post_device(post_dev, torch.cat([im_d, gt_d, *self._post_outputs(outs)], dim=3),
+                                                                                 unpack_masks(packed, dev), boxes, self.return_figs)
                     files_d = self.log.encode_strips(strips_d)
                     nfile = files_d.shape[1]
                     payload = torch.cat([losses_d.view(torch.uint8).reshape(-1), status_d.view(torch.uint8).reshape(-1), files_d.reshape(-1)])      # 12 bytes per item, then the files
@@ -778,11 +821,12 @@ class FSRNet(object):
                 figs_b = ("post_dev", nfile, figs_d)
             elif ucb and postprocess:
                 # train_test_GSC.py:424-748 runs on the host, one independent item per call: what it reads comes over in ONE copy
-                host, ev, slot = to_host_async(torch.cat([im_d, gt_d, con_rgb, mask_pred], dim=3), to_pool=post_pool is not None)      # [B,S,S,10]
+                host, ev, slot = to_host_async(torch.cat([im_d, gt_d, *self._post_outputs(outs)], dim=3), to_pool=post_pool is not None)      # [B,S,S,10]
                 figs_b = None
             else:
                 # FFHQ / raw-UCB: the figures stay on the device; the PNG strips of the whole batch are assembled there and come
                 # over as bytes in one copy (Logging.strips_on_device = get_imgs per item, same arithmetic)
+                gs, con_rgb, _, mask_pred = outs
                 lazy = gpu_png and not self.return_figs        # nobody gets the figures back: the encoder clips / multiplies while it reads them
                 if ucb:
                     figs_b = [im_d, gs, con_rgb, mask_pred, gt_d, face_d]
@@ -843,7 +887,7 @@ class FSRNet(object):
                     lo_ = {"ssim": float(losses[j, 0]), "psnr": float(losses[j, 1])}
                     self.log.display(lo_, 0, it[0], False, num_list)
                     tm["items"] += 1
-                    results.append((it[1], [figs_h[j, k][None] for k in range(7)] if figs_h is not None else None, lo_))
+                    results.append((it[1], [figs_h[j, k][None] for k in range(self.POST_FIGS)] if figs_h is not None else None, lo_))
                 tm["post_s"] += time.perf_counter() - t1
                 return
             if ucb and postprocess:
@@ -862,7 +906,7 @@ class FSRNet(object):
                                 "png": self.log._png_path(name) if self._post_writes_png else None, "return_figs": self.return_figs}
                     # worker PROCESSES (the post-processing is ~30 ms of small numpy / torch-CPU calls per item, GIL-bound in threads);
                     # results are collected up to post_inflight batches later
-                    inflight.append((items, [post_pool.submit(("ucb_post", job(j))) for j in range(len(items))], shm, slot))
+                    inflight.append((items, [post_pool.submit((self.POST_JOB, job(j))) for j in range(len(items))], shm, slot))
                     tm["post_s"] += time.perf_counter() - t1
                     drain(keep=self.post_inflight)
                     return
@@ -870,10 +914,9 @@ class FSRNet(object):
 
                 def job(j):                                         # noqa: F811
                     step, name, _, box = items[j]
-                    return {"im": host[j, ..., 0:3], "gt": host[j, ..., 3:6], "con": host[j, ..., 6:9], "mp": host[j, ..., 9:10],
-                            "box": np.asarray(box, np.float32).reshape(-1)[:4], "masks": mask_files[step],
-                            "png": self.log._png_path(name) if self._post_writes_png else None, "return_figs": self.return_figs}
-                from .ucb_post import run_post_job
+                    return dict(self._host_post_arrays(host, j), box=np.asarray(box, np.float32).reshape(-1)[:4], masks=mask_files[step],
+                                png=self.log._png_path(name) if self._post_writes_png else None, return_figs=self.return_figs)
+                run_post_job = self._host_post_fn()
                 if len(items) > 1 and self.post_threads > 1:
                     from concurrent.futures import ThreadPoolExecutor
                     with ThreadPoolExecutor(max_workers=min(self.post_threads, len(items))) as ex:
@@ -1005,6 +1048,94 @@ class FSRNet(object):
         # post_workers == 0) writes its PNG strip itself — the reference always writes the strip (utils.py:196-204)
         self._post_writes_png = bool(postprocess and not self.return_figs)
         return self._loop(dataset_val, batch, ucb=True, postprocess=postprocess, mask_files=mask_files)
+
+
+class FSRNetRGB(FSRNet):
+    """Inference harness of the paper's single-stage RGB baseline: ``FSRNet.test`` / ``test_step`` of /root/reference/train_RGB_test.py
+    (:357-505) driving ``GeneratorRGB`` (model_RGB.py).  The loop is FSRNet's — the same mask-file listing, dataset element, batching,
+    data-parallel sharding, pipelining and PNG names — with the RGB step's own post-processing: the composite of ``con`` over the input
+    inside the with-hair face mask, SSIM / PSNR and the three figures [input, composite, ground truth] (ucb_post_rgb.py on the host,
+    ucb_post_rgb_gpu.py on the device).  train_RGB_test.py has no ``testFFHQ``; its ``testsfw`` cannot run against model_RGB's
+    generator (it unpacks four outputs from ``con``) and is not mirrored.  fp32 only, as ``GeneratorRGB``."""
+    POST_FIGS = 3
+    POST_JOB = "ucb_post_rgb"
+
+    def __init__(self, config: Config, weights: Optional[Dict[str, np.ndarray]] = None, dtype: str = "f32", group=None, gen=None):
+        from .model import GeneratorRGB
+        if dtype != "f32":
+            raise ValueError("FSRNetRGB runs in dtype 'f32' only (GeneratorRGB has no 'f32x3' / 'f16' path), got %r" % (dtype,))
+        if gen is None:
+            gen = GeneratorRGB(device=config.GPU_INDEX if torch.cuda.is_available() else None, dtype=dtype)
+            if weights is not None:
+                gen.load_weights(weights)
+        super().__init__(config, None, dtype, group, gen=gen)
+
+    @staticmethod
+    def _check_gen(gen) -> None:
+        from .model import Generator, GeneratorRGB
+        if isinstance(gen, Generator) and not isinstance(gen, GeneratorRGB):
+            raise TypeError("FSRNetRGB drives the RGB baseline (GeneratorRGB); a %s is driven by fsrnet.FSRNet%s"
+                            % (type(gen).__name__, "TSM" if type(gen).__name__ == "GeneratorTSM" else ""))
+
+    def _generate(self, im_d: torch.Tensor, uv_d: torch.Tensor, ucb: bool):
+        return self.gen(im_d, uv_d, None, chuck=4, training=False)          # train_RGB_test.py:414 -> con [B,S,S,3]
+
+    @staticmethod
+    def _post_outputs(outs) -> Tuple[torch.Tensor, ...]:
+        return (outs,)
+
+    @staticmethod
+    def _post_device(device: int):
+        from .ucb_post_rgb_gpu import UcbPostRgbDevice
+        return UcbPostRgbDevice(device)
+
+    @staticmethod
+    def _run_post_device(post_dev, rows: torch.Tensor, masks: torch.Tensor, boxes: torch.Tensor, want_figs: bool):
+        return post_dev.run(rows, masks[:, 0], boxes, want_figs=want_figs)  # MASK_ORDER[0]: the with-hair face mask, the only one read
+
+    @staticmethod
+    def _host_post_arrays(host: np.ndarray, j: int) -> Dict[str, np.ndarray]:
+        return {"im": host[j, ..., 0:3], "gt": host[j, ..., 3:6], "con": host[j, ..., 6:9]}
+
+    @staticmethod
+    def _host_post_fn():
+        from .ucb_post_rgb import run_post_job_rgb
+        return run_post_job_rgb
+
+    def _warm_post_device(self, dev: int) -> None:
+        s = self.config.IMG_SIZE
+        d = torch.device("cuda", dev)
+        masks = torch.zeros((1, s, s), dtype=torch.uint8, device=d)
+        masks[:, : s // 2] = 255
+        rows = torch.rand((1, s, s, 9), device=d)
+        _, strips, _, status = self._post_device(dev).run(rows, masks, torch.tensor([[0, 0, s - 16, s - 16]], dtype=torch.float32, device=d))
+        self.log.encode_strips(strips)
+        torch.cat([strips.reshape(-1)[:8], status.view(torch.uint8)]).cpu()
+
+    def test_step_FFHQ(self, *a, **k):
+        raise NotImplementedError("train_RGB_test.py has no testFFHQ")
+
+    def testFFHQ(self, *a, **k):
+        raise NotImplementedError("train_RGB_test.py has no testFFHQ")
+
+    def test_step(self, img, box, curr_mask, *other_masks, training: bool = False, all_rows: bool = False):
+        """train_RGB_test.py:403-505 for one dataset element, post-processing on the host (ucb_post_rgb): ``curr_mask`` is the with-hair
+        face mask ([S,S,3] or [S,S,1] in [0, 1]); the six other masks the reference takes are accepted and not read (it never reads them
+        after resizing).  -> ({'ssim','psnr'}, [tmp, out, gt_sc]) as [1,S,S,3] float32 tensors."""
+        from .ucb_post_rgb import ucb_postprocess_rgb
+        im, gt, uv, reg, face = self._split(img, None if all_rows else 1)
+        dev = "cuda:%d" % self.gen._device if getattr(self.gen, "_device", None) is not None else "cpu"
+        con = self.gen(im.contiguous().to(dev), uv.contiguous().to(dev), reg, chuck=4, training=training)
+        con0 = con[0].detach().float().cpu().numpy()
+        losses, figs = ucb_postprocess_rgb(im[0].numpy(), gt[0].numpy(), con0, np.asarray(box, np.float32).reshape(-1)[:4], np.asarray(curr_mask))
+        return losses, [torch.from_numpy(f) for f in figs]
+
+    def test(self, dataset_val, batch: int = 16, mask_files=None):
+        """train_RGB_test.py:357-401 + test_step :403-505.  Returns [(name, figs[3] | None, {'ssim','psnr'})] in list order; the strips
+        go to <CHECKPOINT_DIR>/test/<dir>_<stem>-result.png.  ``mask_files``: optional explicit per-item list (as ``_ucb_masks()``
+        returns it) instead of the folder listing."""
+        self._post_writes_png = not self.return_figs
+        return self._loop(dataset_val, batch, ucb=True, postprocess=True, mask_files=mask_files)
 
 
 def roc_auc_score(labels: np.ndarray, scores: np.ndarray) -> float:

@@ -2,6 +2,7 @@
 fsr.testFFHQ / fsr.test) as a command, data-parallel when launched with one process per GPU:
 
     python -m blindshadowremoval_amd.run_loop --loop ffhq --data 'sample_imgs/*' --checkpoint-dir log/run
+    python -m blindshadowremoval_amd.run_loop --model rgb --loop ucb --data 'UCB/train/input/*' --mask-root . --checkpoint-dir log/rgb
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29611 \\
         -m blindshadowremoval_amd.run_loop --loop ucb --data 'UCB/train/input/*' --mask-root . --checkpoint-dir log/run
 
@@ -10,6 +11,7 @@ and `FSRNet` shards `dataset.name_list` contiguously over the ranks (fsrnet.py);
 into the same `<checkpoint-dir>/test/`, rank 0 prints the progress and the final running means over ALL items, and one JSON line
 with the loop's rate.  The process group is created by THIS process before it touches the GPU; nothing is re-exec'ed.
 Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random-weights SEED` (the reference ships no data shards).
+`--model rgb` runs the paper's single-stage RGB baseline instead (train_RGB_test.py's `main`: `FSRNetRGB.test`, `--loop ucb`, fp32 only).
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import time
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model", choices=("gsc", "rgb"), default="gsc", help="gsc = FSRNet (train_test_GSC.py), rgb = FSRNetRGB (train_RGB_test.py: --loop ucb, --dtype f32 only)")
     ap.add_argument("--loop", choices=("ffhq", "ucb"), required=True, help="ffhq = FSRNet.testFFHQ, ucb = FSRNet.test (post-processing + SSIM / PSNR)")
     ap.add_argument("--data", action="append", required=True, help="glob of item folders (Config.DATA_DIR_TEST entry); repeatable")
     ap.add_argument("--checkpoint-dir", required=True, help="Config.CHECKPOINT_DIR: weights are restored from it, PNG strips go to <dir>/test/")
@@ -36,6 +39,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=None, help="GPU index of this rank (default: LOCAL_RANK).  With --backend gloo several ranks may share one "
                                                               "GPU — how the world-2 loop is exercised on a one-GPU box (tests/test_fsrnet.py)")
     args = ap.parse_args(argv)
+    if args.model == "rgb" and (args.loop != "ucb" or args.dtype != "f32"):
+        sys.stderr.write("run_loop: --model rgb runs train_RGB_test.py's test loop only: --loop ucb --dtype f32 (it has no testFFHQ and no 16-bit path)\n")
+        return 2
 
     # Before ANYTHING initialises the HIP / HSA runtime (torch.cuda.is_available() below already does): the runtime reads this at
     # start-up — the host driver only supports dmabuf IPC, and RCCL's buffer registration fails without it.  Set here, not after the
@@ -68,7 +74,7 @@ def main(argv=None) -> int:
             dist.init_process_group("gloo", rank=rank, world_size=world)
 
     from .dataset import Dataset, cpu_share
-    from .fsrnet import Config, FSRNet
+    from .fsrnet import Config, FSRNet, FSRNetRGB
     from .weights import init_weights
     cfg = Config(local_rank)
     cfg.DATA_DIR_TEST = list(args.data)
@@ -83,7 +89,10 @@ def main(argv=None) -> int:
     if not args.host_prep:
         ds_kw.update(device_prep=local_rank, device_batch=args.batch)
     ds = Dataset(cfg, "test", ucb=ucb, **ds_kw)
-    fsr = FSRNet(cfg, weights=init_weights(args.random_weights) if args.random_weights is not None else None, dtype=args.dtype)
+    if args.model == "rgb":
+        fsr = FSRNetRGB(cfg, weights=init_weights(args.random_weights, variant="rgb") if args.random_weights is not None else None)
+    else:
+        fsr = FSRNet(cfg, weights=init_weights(args.random_weights) if args.random_weights is not None else None, dtype=args.dtype)
     fsr.post_device = fsr.log.gpu_png = not args.host_post
     fsr.post_workers = max(2, ncpu) if ucb and args.host_post else 0
     fsr.post_inflight = 3
@@ -106,7 +115,7 @@ def main(argv=None) -> int:
         if rank == 0:
             n = len(fsr.all_losses)
             means = {k: s / max(c, 1) for k, (s, c) in fsr.log.losses.items()}
-            print("\n" + json.dumps({"loop": "FSRNet.test" if ucb else "FSRNet.testFFHQ", "items": n, "ranks": world, "process_group": (args.backend if grouped else None), "items_this_rank": len(res),
+            print("\n" + json.dumps({"loop": ("FSRNetRGB.test" if args.model == "rgb" else "FSRNet.test") if ucb else "FSRNet.testFFHQ", "items": n, "ranks": world, "process_group": (args.backend if grouped else None), "items_this_rank": len(res),
                                      "images_per_sec": round(n / dt, 2), "seconds": round(dt, 3), "batch": args.batch, "dtype": args.dtype,
                                      "cpus_per_rank": ncpu, "post_and_png": "host" if args.host_post else "device", "means": means}))
     finally:

@@ -190,6 +190,19 @@ size_t bsr_ucb_post_scratch_bytes(int B, int S);
 int bsr_ucb_post(int device, const float* rows10, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
                  unsigned char* strips, float* figs, int* status, void* scratch, void* stream);
 
+/* The per-item post-processing of the RGB baseline's FSRNet.test_step on the device (added in ABI 8: additive, no existing signature
+ * changed): replaces /root/reference/train_RGB_test.py:427-502 (resize to the crop box + zero pad, the rounded with-hair face mask,
+ * composite + clip, SSIM / PSNR, the three figures input | composite | ground truth as one strip) for a batch of B items.
+ * rows9: [B,S,S,9] float32 = input 3 | ground truth 3 | con 3 (row 0 of each item's generator call); masks: [B,S,S] uint8 grey levels
+ * of the with-hair face mask (the only one of the seven the reference reads after resizing them); boxes: [B,4] float32.  All device
+ * pointers.  losses: [B,2] float32 = ssim, psnr; strips: [B,S,3*S,3] uint8 RGB; figs: optional [B,3,S,S,3] float32 (may be NULL);
+ * status: [B] int32 — 0 = done, 2 = the crop box is empty or does not fit S (black strip, NaN losses).
+ * scratch: bsr_ucb_post_rgb_scratch_bytes(B, S) bytes, 256-byte aligned (0 = unsupported S).  S in {32, 64, 128, 256}.  Every figure
+ * is bit-identical to blindshadowremoval_amd/ucb_post_rgb.py, the host statement. */
+size_t bsr_ucb_post_rgb_scratch_bytes(int B, int S);
+int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
+                     unsigned char* strips, float* figs, int* status, void* scratch, void* stream);
+
 /* Test hook: the fused NonLocalBlock attention kernel alone (/root/reference/model.py:51-53).
  * qkv [B,tokens,384] (theta | phi | g, 128 channels each) -> y [B,tokens,128]; tokens % 128 == 0. */
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream);
