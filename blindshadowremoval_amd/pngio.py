@@ -208,6 +208,9 @@ def read_rgb_raw(path: str):
     try:
         _host_lib()                                            # (its inflate, when there is one)
         w, h, c, raw = _parse_8bit(b)
+        # a filter type above 4 is undefined: the device kernel would take it for 0, PIL (below) refuses the file as read_rgb_u8 does
+        if raw[::1 + w * c].max() > 4:
+            raise ValueError
         return RawScanlines(h, w, c, raw)
     except (ValueError, TypeError, struct.error, zlib.error):
         import io

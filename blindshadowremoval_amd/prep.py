@@ -125,6 +125,8 @@ def _masks_raw(paths):
                 w, h, c, raw = pngio._parse_8bit(f.read())
             if c != 1 or w != h or h > UNFILTER_MAX_ROWS or w < 4 or (S is not None and h != S):
                 return None
+            if raw[::1 + w].max() > 4:             # an undefined filter type: the host readers refuse the file (PIL raises), so does this path
+                return None
             S = h
             raws.append(raw)
     except (ValueError, TypeError, KeyError, OSError, __import__("struct").error, __import__("zlib").error):
@@ -219,13 +221,12 @@ def host_part_ring(job, ring):
     use_raw = bool(ring[3]) if len(ring) > 3 else False       # dataset.Dataset.device_unfilter decides
     part = host_part(job, raw=use_raw)
     img, gt, box, tabs, name = part[:5]
-    # the device kernel takes images of at most UNFILTER_MAX_ROWS rows whose scanlines hold at least one dword; anything else is decoded here
+    masks = part[5] if len(part) > 5 else None
+    # the device kernel takes images of at most UNFILTER_MAX_ROWS rows whose scanlines hold at least one dword; anything else is decoded
+    # here.  "raw8" masks stay as they are: _masks_raw only made them for S x S grey files the kernel takes, whatever the images are
     fits = lambda a: not hasattr(a, "raw") or (a.h <= UNFILTER_MAX_ROWS and a.w * a.c >= 4)
     if not (fits(img) and (gt is None or fits(gt))):
         img, gt = (img.decode() if hasattr(img, "raw") else img), (gt.decode() if gt is not None and hasattr(gt, "raw") else gt)
-        if masks is not None and masks[0] == "raw8":
-            masks = masks_from_raw(masks)
-    masks = part[5] if len(part) > 5 else None
     rawc = tuple(int(getattr(a, "c", 0)) if hasattr(a, "raw") else 0 for a in ([img] + ([gt] if gt is not None else [])))
     arrays = [getattr(a, "raw", a) for a in ([img] + ([gt] if gt is not None else []))] + list(tabs) + ([masks[1]] if masks is not None else [])
     offs, off = [], 0

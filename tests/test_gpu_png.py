@@ -16,7 +16,9 @@ def _decode(data: bytes) -> np.ndarray:
     return np.asarray(im.convert("RGB"))
 
 
-@pytest.mark.parametrize("shape", [(256, 768), (256, 1792), (5, 7), (1, 1), (37, 5461), (300, 21844 // 4)])
+# (771, 28), (1542, 28), (6, 5461): H a multiple of the R = 65535 // (1 + 3 W) scanlines of a stored block — the last block exactly
+# full, at R = 771 as long as a stored block can be (65 535 bytes)
+@pytest.mark.parametrize("shape", [(256, 768), (256, 1792), (5, 7), (1, 1), (37, 5461), (300, 21844 // 4), (771, 28), (1542, 28), (6, 5461)])
 def test_host_statement_decodes_to_the_pixels(shape):
     h, w = shape
     rng = np.random.default_rng(h * 131 + w)
@@ -76,7 +78,8 @@ def test_crc_combination_identity():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(16, 256, 768), (3, 256, 1792), (2, 5, 7), (1, 1, 1), (2, 37, 5461), (5, 64, 250)])
+@pytest.mark.parametrize("shape", [(16, 256, 768), (3, 256, 1792), (2, 5, 7), (1, 1, 1), (2, 37, 5461), (5, 64, 250),
+                                   (2, 771, 28), (1, 1542, 28), (1, 6, 5461)])
 def test_device_encoder_matches_the_host_statement(shape):
     import torch
     from blindshadowremoval_amd.gpu_png import StripEncoder, file_bytes

@@ -1,0 +1,199 @@
+"""The loader's ring path with the PNG scanline reconstruction on the device (prep.host_part_ring + prep._layout_ex, round 6) against
+the pipe path (prep.host_part -> pngio.read_rgb_u8, itself pinned to PIL) on the inputs its fallback branches exist for: images the
+kernel cannot take (over 256 rows, scanlines under 4 bytes), items that overflow a slot, files the worker decodes (palette, 16-bit),
+a ground truth of another PNG kind than its input, masks in every form, and files with an undefined filter-type byte (tests/ring_corpus.py).
+For every item the two must carry byte-identical images and masks.  CPU only: the kernel's part is done by pngio.unfilter_host on the
+blob DevicePrep.rows_ex would upload; tests/test_ring_decode_edges_gpu.py runs the kernel."""
+import os
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import ring_corpus as RC
+from blindshadowremoval_amd import pngio, prep
+
+CAP = prep.RING_CAP
+SLACK = 16                     # csrc/prep_kernels.h kUnfilterSlack
+
+
+@pytest.fixture(scope="module")
+def corpus(tmp_path_factory):
+    return RC.make_corpus(str(tmp_path_factory.mktemp("ring_corpus")))
+
+
+@pytest.fixture(params=["c", "numpy"])
+def host(request, monkeypatch):
+    """The workers' PNG code with libbsr_host.so and with the numpy statement used where no C compiler exists."""
+    if request.param == "numpy":
+        monkeypatch.setattr(pngio, "_HOST", [None, True])
+    else:
+        assert pngio._host_lib() is not None, "libbsr_host.so did not build"
+    return request.param
+
+
+def _ring_file(tmp_path, nslots: int) -> str:
+    path = str(tmp_path / "ring")
+    with open(path, "wb") as f:
+        f.truncate(nslots * CAP)
+    return path
+
+
+def _levels(packed) -> np.ndarray:
+    """A host-form mask record (pack_masks) -> [7,S,S] uint8 grey levels."""
+    import torch
+    return prep.unpack_masks([packed], torch.device("cpu"))[0].numpy()
+
+
+def _rebuild(parts, ring_path: str):
+    """The blob DevicePrep.rows_ex would upload for `parts`, with bsr_png_unfilter's work done by pngio.unfilter_host, read back the
+    way bsr_prep_rows and rows_ex read it: -> per item (img, gt | None, box, [4 tables], name, mask levels [7,S,S] | None).  Checks the
+    unfilter table on the way: every filtered image has SLACK readable bytes of the blob in front of and behind it, and no output area
+    overlaps another or any filtered image."""
+    total, rows_off, grid_off, pieces, head, cells, (unf_off, n_unf, mask_out) = prep._layout_ex(parts, 256, CAP)
+    ring = np.fromfile(ring_path, np.uint8)
+    blob = np.zeros(total, np.uint8)
+    prep.pack_into(blob, pieces)
+    for i, slot, base in cells:
+        blob[base:base + CAP] = ring[slot * CAP:(slot + 1) * CAP]
+    unf = blob[unf_off:unf_off + n_unf * prep.UNFILTER_DTYPE.itemsize].view(prep.UNFILTER_DTYPE).copy()
+    assert n_unf == 0 or unf_off + n_unf * prep.UNFILTER_DTYPE.itemsize <= head
+    spans = []
+    for u in unf:
+        h, w, c, grey = (int(u[k]) for k in ("h", "w", "c", "grey_out"))
+        assert 1 <= h <= prep.UNFILTER_MAX_ROWS and w * c >= 4 and c in (1, 3, 4) and (grey == 0 or c == 1)
+        ro, n = int(u["raw_off"]), h * (1 + w * c)
+        assert ro >= SLACK and ro + n + SLACK <= total, (ro, n, total)
+        assert head <= ro and ro + n <= head + len(cells) * CAP                      # inside the cells: bytes of a slot
+        oo = int(u["out_off"])
+        assert head + len(cells) * CAP <= oo and oo + h * w * (1 if grey else 3) <= total
+        spans.append((ro, ro + n, False))
+        spans.append((oo, oo + h * w * (1 if grey else 3), True))
+    spans.sort()
+    for (a0, a1, out_a), (b0, b1, out_b) in zip(spans, spans[1:]):
+        assert a1 <= b0 or not (out_a or out_b), "an output area overlaps %s" % ("an output area" if out_a and out_b else "a filtered image")
+    for u in unf:
+        h, w, c, grey, ro, oo = (int(u[k]) for k in ("h", "w", "c", "grey_out", "raw_off", "out_off"))
+        a = pngio.unfilter_host(blob[ro:ro + h * (1 + w * c)], h, w, c)
+        blob[oo:oo + h * w * (1 if grey else 3)] = (a[:, :, 0] if grey else pngio._to_rgb(a)).reshape(-1)
+    rows = blob[rows_off:rows_off + len(parts) * prep.ROW_DTYPE.itemsize].view(prep.ROW_DTYPE)
+    out = []
+    for i, p in enumerate(parts):
+        r = rows[i]
+        h, w = int(r["h"]), int(r["w"])
+        img = blob[r["img_off"]:r["img_off"] + h * w * 3].reshape(h, w, 3)
+        has_gt = p[3] if prep._is_ring(p) else p[1] is not None
+        gt = blob[r["gt_off"]:r["gt_off"] + h * w * 3].reshape(h, w, 3) if has_gt else None
+        assert has_gt == (r["gt_off"] != r["img_off"])
+        tabs = [blob[r["tri_off"][m]:r["tri_off"][m] + int(r["ntri"][m]) * prep.TRI_DOUBLES * 8].view("<f8").reshape(-1, prep.TRI_DOUBLES)
+                for m in range(4)]
+        if prep._is_ring(p):
+            name, m = p[8], p[9]
+            if m is None:
+                lv = None
+            elif m[0] == "raw8":
+                o, S = mask_out[i]
+                lv = blob[o:o + 7 * S * S].reshape(7, S, S)
+            else:
+                base = [c[2] for c in cells if c[0] == i][0]
+                v = blob[base + m[2]:base + m[2] + m[3]]
+                lv = _levels((m[0], v.reshape(7, -1) if m[0] == "bits" else v.reshape(7, m[1], m[1]), m[1]))
+        else:
+            name, lv = p[4], (_levels(p[5]) if len(p) > 5 else None)
+        out.append((img, gt, r["box"].copy(), tabs, name, lv))
+    return out
+
+
+def _same_as_pipe(got, pipe) -> None:
+    img, gt, box, tabs, name, lv = got
+    assert np.array_equal(img, pipe[0]) and img.dtype == np.uint8
+    assert np.array_equal(gt, pipe[1]) if pipe[1] is not None else gt is None
+    assert np.array_equal(box, pipe[2]) and name == pipe[4]
+    assert len(tabs) == len(pipe[3]) == 4 and all(a.tobytes() == b.tobytes() for a, b in zip(tabs, pipe[3]))
+    assert np.array_equal(lv, _levels(pipe[5]))
+
+
+@pytest.mark.parametrize("name", RC.GOOD)
+def test_ring_record_carries_what_the_pipe_carries(corpus, name, host, tmp_path, monkeypatch):
+    """One item: host_part_ring with the device reconstruction on takes the branch the corpus names for it, and the slot (rebuilt as
+    the device sees it) holds the pipe's images, tables, box, name and masks; the pipe's images are PIL's."""
+    job = RC.job(corpus, name)
+    lm_path, gt_path, _ = corpus[name]
+    pipe = prep.host_part(job)
+    assert np.array_equal(pipe[0], np.asarray(Image.open(os.path.splitext(lm_path)[0] + ".png").convert("RGB")))
+    assert np.array_equal(pipe[1], np.asarray(Image.open(gt_path).convert("RGB")))
+    path = _ring_file(tmp_path, 2)
+    rec = prep.host_part_ring(job, (path, 1, CAP, True))
+    want = RC.BRANCH[name]
+    if want == "pipe":                                          # overflows its slot: host_part's tuple, every raw piece decoded
+        assert isinstance(rec, tuple) and not prep._is_ring(rec) and len(rec) == 6
+        assert not np.fromfile(path, np.uint8).any()
+        assert rec[5][0] == pipe[5][0] and np.array_equal(rec[5][1], pipe[5][1]) and rec[5][2] == pipe[5][2]
+    else:
+        assert rec[0] == "ring" and rec[1] == 1 and rec[10] <= CAP, rec[10]
+        assert (rec[11], rec[9][0]) == want[1:], (rec[11], rec[9][0])
+        if rec[9][0] != "raw8":
+            assert rec[9][0] == pipe[5][0]                      # a fallback kind is what the pipe sends
+    monkeypatch.undo()                                          # (the kernel's part, whatever the worker had)
+    _same_as_pipe(_rebuild([rec], path)[0], pipe)
+
+
+def test_one_batch_of_every_item_ring_and_mixed(corpus, tmp_path):
+    """All items in one blob — ring records in a ring that wraps, and ring records alternating with pipe tuples: per item the pipe's
+    bytes, SLACK bytes around every filtered image, no output area on another or on a filtered image."""
+    n = len(RC.GOOD)
+    path = _ring_file(tmp_path, n + 3)
+    slots = [(5 + k) % (n + 3) for k in range(n)]
+    pipes = [prep.host_part(RC.job(corpus, nm)) for nm in RC.GOOD]
+    recs = [prep.host_part_ring(RC.job(corpus, nm), (path, s, CAP, True)) for nm, s in zip(RC.GOOD, slots)]
+    assert sum(prep._is_ring(r) for r in recs) == sum(RC.BRANCH[nm] != "pipe" for nm in RC.GOOD) >= n - 2
+    mixed = [r if k % 2 else p for k, (r, p) in enumerate(zip(recs, pipes))]
+    for parts, ref in ((recs, pipes), (mixed, pipes), (mixed[::-1], pipes[::-1])):
+        for got, pipe in zip(_rebuild(parts, path), ref):
+            _same_as_pipe(got, pipe)
+
+
+@pytest.mark.parametrize("name", RC.BAD)
+def test_an_undefined_filter_type_fails_both_paths(corpus, name, host, tmp_path):
+    """A filter-type byte of 5 (one scanline of the photograph, of one mask): PIL refuses the file on the pipe path, and the ring path
+    refuses it the same way in the worker — nothing of the item reaches its slot, so no kernel ever reconstructs it as type 0."""
+    job = RC.job(corpus, name)
+    lm_path, _, mp = corpus[name]
+    with pytest.raises(OSError):
+        prep.host_part(job)
+    path = _ring_file(tmp_path, 1)
+    with pytest.raises(OSError):
+        prep.host_part_ring(job, (path, 0, CAP, True))
+    assert not np.fromfile(path, np.uint8).any()
+    if name == "bad_photo":
+        f = os.path.splitext(lm_path)[0] + ".png"
+        for read in (pngio.read_rgb_raw, pngio.read_rgb_u8):
+            with pytest.raises(OSError):
+                read(f)
+    else:
+        assert prep._masks_raw(mp) is None
+        with pytest.raises(OSError):
+            prep.pack_masks(mp, raw=True)
+
+
+def test_layout_refuses_what_the_kernel_cannot_take(corpus, tmp_path):
+    """Records the unfilter kernel must never see are refused by _layout_ex: a filtered image of 257 rows, scanlines of 3 bytes
+    (w c = 3 with c = 1 and with c = 3), raw8 masks of S = 257."""
+    path = _ring_file(tmp_path, 1)
+    rec = prep.host_part_ring(RC.job(corpus, "plain"), (path, 0, CAP, True))
+    assert rec[11] == (3, 3) and rec[9][0] == "raw8"
+    prep._layout_ex([rec], 256, CAP)
+
+    def edit(**kw):
+        r = list(rec)
+        for k, v in kw.items():
+            r[int(k[1:])] = v
+        return tuple(r)
+    for bad in (edit(f2=(257, 256)), edit(f2=(256, 1)), edit(f2=(256, 3), f11=(1, 1)), edit(f2=(256, 3), f11=(3, 1))):
+        with pytest.raises(ValueError, match="more than 256 rows or scanlines under 4 bytes"):
+            prep._layout_ex([bad], 256, CAP)
+    m = rec[9]
+    with pytest.raises(ValueError, match="filtered masks do not fit"):
+        prep._layout_ex([edit(f9=("raw8", 257, m[2], 7 * 257 * 258))], 256, CAP)
+    with pytest.raises(ValueError, match="filtered masks do not fit"):
+        prep._layout_ex([edit(f9=("raw8", 3, m[2], 7 * 3 * 4))], 256, CAP)
