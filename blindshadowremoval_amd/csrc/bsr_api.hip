@@ -28,6 +28,7 @@
 #include "stem7.h"
 #include "ucb_kernels.h"
 #include "ucb_rgb_kernels.h"
+#include "sfw_kernels.h"
 
 namespace {
 
@@ -1162,6 +1163,24 @@ int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks,
   DeviceGuard guard(device);
   HIP_TRY(guard.err);
   HIP_TRY(bsr::launch_ucb_post_rgb(rows9, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+size_t bsr_sfw_score_scratch_bytes(int B, int S) {
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
+  return (size_t)B * bsr::sfw_item_scratch_bytes(S);
+}
+
+int bsr_sfw_score(int device, const float* rows3, int B, int S, float* losses, double* auc, float* pred, float* label, int* status,
+                  void* scratch, void* stream) {
+  if (rows3 == nullptr || losses == nullptr || auc == nullptr || pred == nullptr || label == nullptr || status == nullptr || scratch == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_sfw_score: null argument");
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
+    return fail(BSR_ERR_ARG, "bsr_sfw_score: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_sfw_score: scratch must be 256-byte aligned");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_sfw_score(rows3, B, S, losses, auc, pred, label, status, scratch, static_cast<hipStream_t>(stream)));
   return BSR_OK;
 }
 

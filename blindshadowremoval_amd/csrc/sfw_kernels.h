@@ -1,0 +1,230 @@
+// The SFW scoring of the GSC model's FSRNet.test_step_sfw (/root/reference/train_test_GSC.py:808-832) ON THE DEVICE.
+//
+// Everything after the generator call that is arithmetic, for a batch of B items, on row 0 of each: mask_pred = dif * face; the label
+// plane (mask == 2); tf.image.ssim / tf.image.psnr of the one-channel mask (raw grey levels) against mask_pred; and the ROC AUC of
+// sklearn.metrics.roc_auc_score over [1, 0] ++ labels against [1, 0] ++ mask_pred (one forced sample of each class).
+// blindshadowremoval_amd/sfw_post.py is the host statement.
+//
+// The AUC is EXACT: AUC = U / (P N) with U the Mann-Whitney statistic under average ranks, and 2U = sum over positives of
+// (2 #negatives below + #negatives equal) is an integer, accumulated in uint64 with integer atomics (order-free, so deterministic).  The
+// one rounding is the final division, the same one fsrnet.roc_auc_score makes: the two are bit-identical.  Scores are compared as
+// order-preserving uint32 keys (sfw_key): -0.0 is mapped to +0.0 first (numpy and sklearn see a tie), subnormals keep their order (the
+// kernels are built without flush-to-zero).  A non-finite score sets the item's status (sklearn raises there).
+//
+// An item is S*S + 2 scores (65 538 at S = 256; 256 KiB of keys and labels), more than a workgroup's LDS, so:
+//   sfw_tile_kernel   grid (T, B), T = ceil(S*S / 4096) tiles: mask_pred and label of the tile's pixels (written out), its NEGATIVE keys
+//                     compacted and bitonic-sorted in LDS, written to the scratch with their count and the tile's non-finite count;
+//   sfw_rank_kernel   grid (T, B): each tile's positives binary-search every tile's sorted negatives (staged through LDS one tile at a
+//                     time) for their lower and upper bounds; per-wave reduction, one uint64 atomic per workgroup;
+//   sfw_ssim_kernel   ucb_ssim_tile with one channel (shared with the UCB chains), and
+//   sfw_finish_kernel grid (B), one wave: the SSIM / PSNR fold, the AUC division and the status word.
+// Every scratch word a later kernel reads is written by an earlier kernel of the same call (tile 0 of sfw_tile_kernel clears the
+// accumulators that sfw_rank_kernel adds into).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ucb_kernels.h"
+
+namespace bsr {
+
+constexpr int kSfwTile = 4096;           // pixels per tile: 16 KiB of keys in LDS; 16 tiles per 256x256 item, 256 workgroups per batch of 16
+constexpr int kSfwThreads = 1024;
+constexpr int SFW_NONFINITE = 3;         // status: a mask_pred value is NaN or infinite (the reference's roc_auc_score raises)
+
+__host__ __device__ inline int sfw_tiles(int S) { return (S * S + kSfwTile - 1) / kSfwTile; }
+
+struct SfwScratch {                      // per item, inside the caller's scratch block
+  unsigned long long* acc;               // [2] 2U, positives (including the forced one)
+  int* info;                             // [T][2] negatives, non-finite scores of the tile
+  double* ssim_part;                     // [2][nblk]
+  uint32_t* neg;                         // [T][kSfwTile] sorted negative keys of each tile (the first info[t][0] are valid)
+};
+
+__host__ __device__ inline size_t sfw_item_scratch_bytes(int S) {
+  const size_t T = (size_t)sfw_tiles(S);
+  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
+  const size_t b = 16 + ((T * 8 + 15) & ~size_t(15)) + 2 * nblk * 8 + T * kSfwTile * 4;
+  return (b + 255) & ~size_t(255);
+}
+
+__host__ __device__ inline SfwScratch sfw_scratch(void* base, int item, int S) {
+  const size_t T = (size_t)sfw_tiles(S);
+  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
+  unsigned char* p = static_cast<unsigned char*>(base) + (size_t)item * sfw_item_scratch_bytes(S);
+  SfwScratch s;
+  s.acc = reinterpret_cast<unsigned long long*>(p); p += 16;
+  s.info = reinterpret_cast<int*>(p); p += (T * 8 + 15) & ~size_t(15);
+  s.ssim_part = reinterpret_cast<double*>(p); p += 2 * nblk * 8;
+  s.neg = reinterpret_cast<uint32_t*>(p);
+  return s;
+}
+
+// Order-preserving key of a float32 score: unsigned comparison of keys == numeric comparison of the scores, with -0.0 == +0.0.
+__device__ __forceinline__ uint32_t sfw_key(float v) {
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) == 0u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// rows3: [B][S][S][3] float32 = mask (grey level after the crop resize, 0..255) | dif | face of row 0.
+__device__ __forceinline__ float sfw_pred(const float* px) {
+#pragma clang fp contract(off)
+  return px[1] * px[2];                                        // mask_pred = mask_pred * face (:808)
+}
+
+__global__ __launch_bounds__(kSfwThreads) void sfw_tile_kernel(const float* __restrict__ rows3, int S, void* scratch, float* __restrict__ pred,
+                                                               float* __restrict__ label) {
+  __shared__ uint32_t s_key[kSfwTile];
+  __shared__ int s_cnt, s_bad;
+  const int t = blockIdx.x, item = blockIdx.y, tid = threadIdx.x;
+  const int N = S * S;
+  const int base = t * kSfwTile, n = min(kSfwTile, N - base);
+  if (tid == 0) { s_cnt = 0; s_bad = 0; }
+  __syncthreads();
+  const float* r = rows3 + (size_t)item * N * 3;
+  for (int i = tid; i < n; i += kSfwThreads) {
+    const size_t p = (size_t)base + i;
+    const float m = r[p * 3];
+    const float pr = sfw_pred(r + p * 3);
+    const bool pos = m == 2.f;                                  // tf.cast(tf.equal(mask, 2), tf.float32) (:820)
+    pred[(size_t)item * N + p] = pr;
+    label[(size_t)item * N + p] = pos ? 1.f : 0.f;
+    if (!isfinite(pr)) atomicAdd(&s_bad, 1);
+    if (!pos) s_key[atomicAdd(&s_cnt, 1)] = sfw_key(pr);        // compaction order is arbitrary: the sort below fixes it
+  }
+  __syncthreads();
+  const int cnt = s_cnt;
+  for (int i = cnt + tid; i < kSfwTile; i += kSfwThreads) s_key[i] = 0xffffffffu;
+  __syncthreads();
+  for (int k = 2; k <= kSfwTile; k <<= 1) {                     // bitonic sort, ascending
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < kSfwTile; i += kSfwThreads) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint32_t a = s_key[i], b = s_key[ixj];
+          if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[ixj] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const SfwScratch sc = sfw_scratch(scratch, item, S);
+  uint32_t* dst = sc.neg + (size_t)t * kSfwTile;
+  for (int i = tid; i < cnt; i += kSfwThreads) dst[i] = s_key[i];
+  if (tid == 0) {
+    sc.info[2 * t] = cnt;
+    sc.info[2 * t + 1] = s_bad;
+    if (t == 0) { sc.acc[0] = 0ull; sc.acc[1] = 0ull; }
+  }
+}
+
+// #keys < k and #keys <= k in the sorted a[0, n)
+__device__ __forceinline__ void sfw_bounds(const uint32_t* a, int n, uint32_t k, int& lo_out, int& hi_out) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < k) lo = mid + 1; else hi = mid; }
+  lo_out = lo;
+  hi = n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= k) lo = mid + 1; else hi = mid; }
+  hi_out = lo;
+}
+
+constexpr int kSfwPer = kSfwTile / kSfwThreads;                // pixels per thread
+static_assert((kSfwTile & (kSfwTile - 1)) == 0 && kSfwTile % kSfwThreads == 0 && kSfwPer <= 32, "bitonic tile: a power of two, whole pixels per thread");
+
+__global__ __launch_bounds__(kSfwThreads) void sfw_rank_kernel(const float* __restrict__ rows3, int S, void* scratch) {
+  __shared__ uint32_t s_neg[kSfwTile];
+  __shared__ unsigned long long s_red[2][kSfwThreads / 64];
+  const int t = blockIdx.x, item = blockIdx.y, tid = threadIdx.x;
+  const int N = S * S, T = sfw_tiles(S);
+  const int base = t * kSfwTile, n = min(kSfwTile, N - base);
+  const float* r = rows3 + (size_t)item * N * 3;
+  const SfwScratch sc = sfw_scratch(scratch, item, S);
+  // this thread's pixels (kSfwPer of them, fixed register slots) and which are positive; thread 0 of tile 0 adds the forced positive (score 1)
+  uint32_t key[kSfwPer];
+  unsigned pos = 0u;
+#pragma unroll
+  for (int q = 0; q < kSfwPer; ++q) {
+    const int i = tid + q * kSfwThreads;
+    key[q] = 0u;
+    if (i < n) {
+      const size_t p = (size_t)base + i;
+      if (r[p * 3] == 2.f) { key[q] = sfw_key(sfw_pred(r + p * 3)); pos |= 1u << q; }
+    }
+  }
+  const bool forced = t == 0 && tid == 0;
+  const uint32_t k0 = sfw_key(0.f), k1 = sfw_key(1.f);          // the forced negative, the forced positive
+  unsigned long long u2 = forced ? 2ull : 0ull;                 // forced positive vs forced negative: 1 > 0
+#pragma unroll
+  for (int q = 0; q < kSfwPer; ++q)
+    if (pos & (1u << q)) u2 += key[q] > k0 ? 2ull : (key[q] == k0 ? 1ull : 0ull);
+  for (int tt = 0; tt < T; ++tt) {
+    const int cnt = sc.info[2 * tt];
+    __syncthreads();
+    for (int i = tid; i < cnt; i += kSfwThreads) s_neg[i] = sc.neg[(size_t)tt * kSfwTile + i];
+    __syncthreads();
+    int lo, hi;
+#pragma unroll
+    for (int q = 0; q < kSfwPer; ++q)
+      if (pos & (1u << q)) { sfw_bounds(s_neg, cnt, key[q], lo, hi); u2 += (unsigned long long)(2 * lo + (hi - lo)); }
+    if (forced) { sfw_bounds(s_neg, cnt, k1, lo, hi); u2 += (unsigned long long)(2 * lo + (hi - lo)); }
+  }
+  const int np = __popc(pos) + (forced ? 1 : 0);
+  unsigned long long pc = (unsigned long long)np;
+  for (int o = 32; o > 0; o >>= 1) { u2 += __shfl_xor(u2, o); pc += __shfl_xor(pc, o); }
+  const int wave = tid >> 6, lane = tid & 63;
+  if (lane == 0) { s_red[0][wave] = u2; s_red[1][wave] = pc; }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long a = 0ull, b = 0ull;
+    for (int w = 0; w < kSfwThreads / 64; ++w) { a += s_red[0][w]; b += s_red[1][w]; }
+    atomicAdd(&sc.acc[0], a);
+    atomicAdd(&sc.acc[1], b);
+  }
+}
+
+struct SfwSsimOperands {                 // ucb_ssim_tile's operands: the mask grey level and mask_pred, one channel
+  const float* r;
+  __device__ float x(size_t q, int) const { return r[q * 3]; }
+  __device__ float y(size_t q, int) const { return sfw_pred(r + q * 3); }
+};
+
+__global__ __launch_bounds__(256) void sfw_ssim_kernel(const float* __restrict__ rows3, int S, void* scratch) {
+  const int item = blockIdx.y;
+  ucb_ssim_tile<SfwSsimOperands, 1>(SfwSsimOperands{rows3 + (size_t)item * S * S * 3}, S, sfw_scratch(scratch, item, S).ssim_part);
+}
+
+__global__ __launch_bounds__(64) void sfw_finish_kernel(int S, void* scratch, float* __restrict__ losses, double* __restrict__ auc,
+                                                        int* __restrict__ status) {   // grid (B), one wave
+  const int item = blockIdx.x;
+  const SfwScratch sc = sfw_scratch(scratch, item, S);
+  if (threadIdx.x == 0) {
+    const int T = sfw_tiles(S);
+    long long neg = 1;                                          // the forced negative
+    int bad = 0;
+    for (int t = 0; t < T; ++t) { neg += sc.info[2 * t]; bad += sc.info[2 * t + 1]; }
+    const unsigned long long u2 = sc.acc[0], pos = sc.acc[1];
+    status[item] = bad ? SFW_NONFINITE : UCB_OK;
+    auc[item] = bad ? __builtin_nan("") : (double)u2 / (2.0 * (double)pos * (double)neg);
+  }
+  ucb_ssim_finish<1>(sc.ssim_part, S, true, losses + 2 * item);
+}
+
+inline hipError_t launch_sfw_score(const float* rows3, int B, int S, float* losses, double* auc, float* pred, float* label, int* status,
+                                   void* scratch, hipStream_t stream) {
+  const dim3 tiles((unsigned)sfw_tiles(S), (unsigned)B);
+  hipLaunchKernelGGL(sfw_tile_kernel, tiles, dim3(kSfwThreads), 0, stream, rows3, S, scratch, pred, label);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sfw_rank_kernel, tiles, dim3(kSfwThreads), 0, stream, rows3, S, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int st = (S + kSsimTile - 1) / kSsimTile;
+  hipLaunchKernelGGL(sfw_ssim_kernel, dim3((unsigned)(st * st), (unsigned)B), dim3(256), 0, stream, rows3, S, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sfw_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, S, scratch, losses, auc, status);
+  return hipGetLastError();
+}
+
+}  // namespace bsr

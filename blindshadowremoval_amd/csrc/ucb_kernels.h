@@ -559,8 +559,9 @@ constexpr int kSsimTile = 16, kSsimWin = 11, kSsimIn = kSsimTile + kSsimWin - 1;
 
 // The tile routine is shared by the GSC chain (ucb_ssim_kernel) and the RGB baseline's post-processing (ucb_rgb_kernels.h): `src`
 // says where the two operands live — src.x(q, c) / src.y(q, c) = channel c of pixel q of the ground truth / the composite.  Tile
-// blockIdx.x of the image writes its two partial sums to part[blockIdx.x] and part[nblk + blockIdx.x].
-template <typename Src>
+// blockIdx.x of the image writes its two partial sums to part[blockIdx.x] and part[nblk + blockIdx.x].  C: the operands' channel count
+// (3 for both UCB chains; the SFW scoring of sfw_kernels.h compares one-channel masks).
+template <typename Src, int C = 3>
 __device__ __forceinline__ void ucb_ssim_tile(const Src& src, int S, double* part) {
   __shared__ float s_x[kSsimIn][kSsimIn + 1], s_y[kSsimIn][kSsimIn + 1];
   __shared__ float s_v[5][kSsimTile][kSsimIn + 1];
@@ -576,7 +577,7 @@ __device__ __forceinline__ void ucb_ssim_tile(const Src& src, int S, double* par
     for (int i = 0; i < kSsimWin; ++i) g[i] = (float)(e[i] / sum);
   }
   double acc_ssim = 0.0, acc_se = 0.0;
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < C; ++c) {
     __syncthreads();
     for (int i = tid; i < kSsimIn * kSsimIn; i += 256) {
       const int yy = i / kSsimIn, xx = i % kSsimIn;
@@ -642,7 +643,8 @@ __global__ __launch_bounds__(256) void ucb_ssim_kernel(int S, void* scratch) {
   ucb_ssim_tile(UcbGscSsimOperands{sc.w, sc.out}, S, sc.ssim_part);
 }
 
-// The tiles' partial sums of one item -> loss2[0] = ssim, loss2[1] = psnr (NaN both when !ok).  One wave.
+// The tiles' partial sums of one item -> loss2[0] = ssim, loss2[1] = psnr (NaN both when !ok).  One wave.  C as in ucb_ssim_tile.
+template <int C = 3>
 __device__ __forceinline__ void ucb_ssim_finish(const double* part, int S, bool ok, float* loss2) {
   const int lane = threadIdx.x;
   const int tiles = (S + kSsimTile - 1) / kSsimTile, nblk = tiles * tiles;
@@ -652,8 +654,8 @@ __device__ __forceinline__ void ucb_ssim_finish(const double* part, int S, bool 
   if (lane != 0) return;
   const int M = S - kSsimWin + 1;
   if (!ok) { loss2[0] = __builtin_nanf(""); loss2[1] = __builtin_nanf(""); return; }
-  loss2[0] = (float)(a / ((double)M * M * 3.0));
-  loss2[1] = (float)(20.0 * log10(1.0) - 10.0 * log10(e / ((double)S * S * 3.0)));
+  loss2[0] = (float)(a / ((double)M * M * (double)C));
+  loss2[1] = (float)(20.0 * log10(1.0) - 10.0 * log10(e / ((double)S * S * (double)C)));
 }
 
 __global__ __launch_bounds__(64) void ucb_ssim_finish_kernel(int S, void* scratch, const int* __restrict__ status, float* __restrict__ losses, int B) {   // grid (B), one wave

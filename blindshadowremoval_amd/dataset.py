@@ -3,6 +3,11 @@
 helpers `face_crop_and_resize`, `generate_face_region`: /root/reference/utils.py:356-433, 255-276;
 `generate_uv_map`, `generate_offset_map`: /root/reference/warp.py:194-232).
 
+`Dataset(config, 'test', dset='sfw_gsc', rows=R)` is the GSC script's SFW loader (`parse_fn_test_sfw`, /root/reference/dataset.py:338-612):
+elements `[1,R,256,256,17]` for `FSRNet.testsfw`.  The reference's GSC `inputs` is inconsistent as committed (it lists `*.npy` and maps
+'sfw' to `parse_fn_test_sfw_video`); this follows its commented alternatives (dataset.py:57,66): list `*_label.png`, parse with
+`parse_fn_test_sfw`.  `FSRNet.testsfw_video` reads `dset='sfw_video'`: the GSC and TSM `parse_fn_test_sfw_video` are the same source.
+
 `Dataset(config, 'test', dset='sfw' | 'sfw_video')` is the counterpart of the TSM script's loaders
 (/root/reference/dataset_with_TSM.py:19-79, 225-287, 289-583): elements `[1,2,256,256,17]` (frame + mirror) / `[1,10,256,256,13]`
 (ten frames of a video) for `FSRNetTSM.testsfw` / `testsfw_video`.
@@ -284,6 +289,64 @@ def build_sfw_video(label_path: str, size: int = 256) -> Tuple[np.ndarray, np.nd
     return np.stack(rows, axis=0).astype(np.float32)[None], np.asarray(box, np.float32)[None], np.array([(os.path.join(folder, str(first)) + ".png").encode()])
 
 
+def _resize_to(a: np.ndarray, h: int, w: int) -> np.ndarray:
+    """cv2.resize(a, (w, h)) with INTER_LINEAR, float64 arithmetic (resize_linear's per-axis rule on a rectangle).  cv2 copies when the
+    size does not change, and so does this."""
+    a = np.asarray(a)
+    if a.shape[0] == h and a.shape[1] == w:
+        return a.copy()
+    img = np.ascontiguousarray(a, np.float64)
+    squeeze = img.ndim == 2
+    if squeeze:
+        img = img[:, :, None]
+
+    def axis(n, size):
+        src = np.maximum((np.arange(size) + 0.5) * (n / size) - 0.5, 0.0)
+        i0 = np.minimum(np.floor(src).astype(np.int64), n - 1)
+        return i0, np.minimum(i0 + 1, n - 1), src - i0
+    y0, y1, wy = axis(img.shape[0], h)
+    x0, x1, wx = axis(img.shape[1], w)
+    wx = wx[None, :, None]
+    top = img[y0][:, x0] * (1 - wx) + img[y0][:, x1] * wx
+    bot = img[y1][:, x0] * (1 - wx) + img[y1][:, x1] * wx
+    out = top * (1 - wy[:, None, None]) + bot * wy[:, None, None]
+    return out[:, :, 0] if squeeze else out
+
+
+def build_sfw_gsc(label_path: str, rows: int = 1, size: int = 256) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`parse_fn_test_sfw` of the GSC loader (/root/reference/dataset.py:338-612): `[rows, size, size, 17]` = [img3, cmap3, mask1, uvm3,
+    reg_in3, reg_out3, face1] per row.  Row 0 is the labelled frame (`<f>.png`, `<f>.npy`, `<f>_label.png` as the raw grey level,
+    `<f>_label_cmap.png`); rows 1..9 are the neighbour frames of `sfw_video_frames` (the same table as the video loader).  The cmap and
+    mask planes of a neighbour row are the PREVIOUS row's planes resized to the neighbour's image size (cv2.resize, INTER_LINEAR; the
+    mask stays 8-bit), a chain as in the reference — all frames of one video share their size, and then every row carries the labelled
+    frame's planes unchanged.  Resizing the 8-bit mask across sizes rounds a float64 interpolation to the nearest level (cv2 uses 11-bit
+    fixed-point weights there; the two can differ by one grey level).  The box returned is the LAST row's, as the reference overwrites it
+    (test_step_sfw never reads it).  `rows` = 1..10 (10 = the reference's element); the GSC generator couples no rows, so the loop
+    needs only row 0."""
+    if not 1 <= rows <= 10:
+        raise ValueError("an SFW element has 1 to 10 rows, got %d" % rows)
+    stem = label_path.rsplit(".", 1)[0]
+    frame_path = stem[:-6]                                              # strips "_label"
+    folder, frame = os.path.dirname(frame_path), int(os.path.basename(frame_path))
+    img = imread_rgb(frame_path + ".png")
+    cmap = imread_rgb(stem + "_cmap.png")
+    mask = np.rint(imread_gray(label_path)).astype(np.uint8)           # cv2.imread(_mask, 0)
+    out = []
+    for k, f in enumerate(sfw_video_frames(frame)[:rows]):
+        base = os.path.join(folder, str(f))
+        if k > 0:
+            if not os.path.isfile(base + ".png"):
+                raise FileNotFoundError("SFW element of frame %d needs %s.png (the reference blocks on input() here)" % (frame, base))
+            img = imread_rgb(base + ".png")
+            h, w = img.shape[:2]
+            cmap = _resize_to(cmap, h, w)
+            mask = np.clip(np.rint(_resize_to(mask, h, w)), 0, 255).astype(np.uint8)
+        crop, lm, box = face_crop_and_resize(np.concatenate([img, cmap, mask[:, :, None].astype(np.float64)], axis=2), np.load(base + ".npy"), size)
+        uvm, reg_in, reg_out, face = _maps(lm, size)
+        out.append(np.concatenate([crop, uvm, reg_in, reg_out, face], axis=2))
+    return np.stack(out, axis=0).astype(np.float32)[None], np.asarray(box, np.float32)[None], np.array([(frame_path + ".png").encode()])
+
+
 def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One dataset element `(img[1,R,size,size,16], box[1,4], name[1])` from a job `(lm_path, gt_path, sibling lm paths, size)`.
     Top-level so that worker processes can run it (the rows of an element never depend on another element)."""
@@ -294,6 +357,8 @@ def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         return host_part_ring(hjob, job[4]) if len(job) > 4 else host_part(hjob)            # job[4]: (ring file, slot, slot bytes)
     if gt_path == "<sfw>":
         return build_sfw_pair(lm_path, size)
+    if isinstance(gt_path, tuple) and gt_path[0] == "<sfw_gsc>":
+        return build_sfw_gsc(lm_path, gt_path[1], size)
     if gt_path == "<sfw_video>":
         return build_sfw_video(lm_path, size)
     img_path = os.path.splitext(lm_path)[0] + ".png"
@@ -317,8 +382,10 @@ class Dataset:
 
     def __init__(self, config, mode: str = "test", dset=None, ucb: bool = False, rows: int = 1, seed: int = 0,
                  workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16):
-        if mode != "test" or dset not in (None, "sfw", "sfw_video"):
-            raise NotImplementedError("only the test loaders are provided (GSC: dset=None; TSM: dset='sfw' | 'sfw_video'); training loaders are out of scope")
+        if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc"):
+            raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video'); training loaders are out of scope")
+        if dset == "sfw_gsc" and not 1 <= rows <= 10:
+            raise ValueError("dset='sfw_gsc' elements have 1 to 10 rows, got rows=%d" % rows)
         self.config, self.mode, self.ucb, self.rows, self.dset = config, mode, ucb, rows, dset
         self._rng = random.Random(seed)
         self._shard = None
@@ -371,8 +438,9 @@ class Dataset:
         self._started = True
         lo, hi = self._shard if self._shard is not None else (0, len(self.name_list))
         if self.dset is not None:                                          # TSM loaders: the element is a group of 2 / 10 coupled frames
+            kind = ("<sfw_gsc>", self.rows) if self.dset == "sfw_gsc" else "<" + self.dset + ">"          # GSC SFW: `rows` rows of a chain
             for label in self.name_list[lo:hi]:
-                yield (label, "<" + self.dset + ">", [], size)
+                yield (label, kind, [], size)
             return
         for i, lm_path in enumerate(self.name_list):
             if i >= hi:

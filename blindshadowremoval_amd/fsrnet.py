@@ -463,6 +463,7 @@ class FSRNet(object):
         self.return_figs = True                  # False: FSRNet.test returns (name, None, losses) — the figures are only written as PNG strips
         self._post_writes_png = False            # set by test(): the post-processing workers write the PNG strips themselves
         self._post_pool, self._post_pool_n = None, 0
+        self._sfw_dev = None                     # testsfw's device scoring (sfw_post_gpu.SfwScoreDevice), made on first use
 
     # -- what is model-specific in the loops (FSRNetRGB overrides these) ----------------------
     POST_FIGS = 7                                # figures per item of test()'s post-processing (train_test_GSC.py:744)
@@ -1049,6 +1050,142 @@ class FSRNet(object):
         self._post_writes_png = bool(postprocess and not self.return_figs)
         return self._loop(dataset_val, batch, ucb=True, postprocess=postprocess, mask_files=mask_files)
 
+    # -- SFW evaluation (train_test_GSC.py:750-838, 893-932) --------------------------------
+    def _sfw_rows(self, elements, split, all_rows: bool) -> Tuple[torch.Tensor, List[int]]:
+        """k elements [1,R,S,S,C] (any R) -> (their row 0s — or all their rows — stacked [M,S,S,C], the index of each element's row 0)."""
+        s = self.config.IMG_SIZE
+        ts, first, n = [], [], 0
+        for e in elements:
+            t = torch.as_tensor(np.asarray(e) if not isinstance(e, torch.Tensor) else e, dtype=torch.float32)
+            t = t.reshape(-1, s, s, t.shape[-1])
+            if t.shape[-1] != sum(split):
+                raise ValueError("an SFW element has %d channels per row here (%s), got %d" % (sum(split), split, t.shape[-1]))
+            if not all_rows:
+                t = t[:1]
+            first.append(n)
+            n += t.shape[0]
+            ts.append(t)
+        return torch.cat(ts, dim=0), first
+
+    def _sfw_steps(self, elements, video: bool, all_rows: bool = False, save_names: Optional[Sequence[str]] = None):
+        """test_step_sfw (video=False) / test_step_sfw_video for k elements in ONE forward.  The GSC generator couples no rows and every
+        output of the step reads row 0, so by default only row 0 of each element is forwarded; ``all_rows=True`` forwards every row, as
+        the reference does (same results).  On a GPU the scoring runs on the device (sfw_post_gpu) and the strips become PNG files there;
+        otherwise sfw_post.py on the host.  ``save_names``: write each element's strip under that name (Logging.save_img's file).
+        -> [(losses, figs | None)] per element; figs = row 0's [img, con, mask_pred * 2(, label)] as [1,S,S,C] tensors."""
+        from .sfw_post import SPLIT_SFW, SPLIT_VIDEO
+        split = SPLIT_VIDEO if video else SPLIT_SFW
+        rows, first = self._sfw_rows(elements, split, all_rows)
+        dev = "cuda:%d" % self.gen._device if getattr(self.gen, "_device", None) is not None else "cpu"
+        parts = torch.split(rows.to(dev), list(split), dim=3)
+        im, uv, face = parts[0], parts[1 if video else 3], parts[-1]
+        _, con_rgb, _, dif = self._generate(im.contiguous(), uv.contiguous(), False)          # :807 / :901 (chuck=1)
+        if getattr(self.gen, "dtype", "f32") != "f32":
+            self.gen.check_range()                 # 16-bit modes: an out-of-range activation is an error, never a silent inf
+        sel = torch.tensor(first, dtype=torch.long, device=dev)
+        im0, con0, dif0, face0 = (t.index_select(0, sel).contiguous() for t in (im, con_rgb, dif, face))
+        k = len(first)
+        if dev == "cpu":
+            from .sfw_post import sfw_postprocess, sfw_video_figs
+            mask0 = None if video else parts[2].index_select(0, sel)
+            out = []
+            for j in range(k):
+                a = [t[j].detach().float().numpy() for t in (im0, con0, dif0, face0)]
+                if video:
+                    losses, figs = {}, sfw_video_figs(*a)
+                else:
+                    losses, figs = sfw_postprocess(a[0], a[1], mask0[j].numpy(), a[2], a[3])
+                figs = [torch.from_numpy(f) for f in figs]
+                if save_names is not None:
+                    self.log.save_img(figs, save_names[j])
+                out.append((losses, figs if self.return_figs or save_names is None else None))
+            return out
+        shown = [im0, con0, (dif0, face0, 2.0)]                     # clip(con_rgb) and (dif * face) * 2 are the encoder's own arithmetic
+        if video:
+            losses_h = [{} for _ in range(k)]
+            label = pred = None
+        else:
+            from .sfw_post_gpu import SfwScoreDevice, raise_for_status
+            if self._sfw_dev is None:
+                self._sfw_dev = SfwScoreDevice(self.gen._device)
+            losses_d, auc_d, pred, label, status_d = self._sfw_dev.run(torch.cat([parts[2].index_select(0, sel), dif0, face0], dim=3))
+            shown.append(label)
+            lh, ah, sh = losses_d.cpu().numpy(), auc_d.cpu().numpy(), status_d.cpu().numpy()
+            raise_for_status(sh, list(save_names) if save_names is not None else [str(j) for j in range(k)])
+            losses_h = [{"ssim": float(lh[j, 0]), "psnr": float(lh[j, 1]), "auc": float(ah[j])} for j in range(k)]
+        if save_names is not None:
+            if self.log.gpu_png:
+                files = self.log.files_on_device(shown).cpu().numpy()
+                for fu in self.log.save_files(files, list(save_names)):
+                    fu.result()
+            else:
+                plain = [im0, torch.clamp(con0, 0, 1), dif0 * face0 * 2] + ([] if video else [label])
+                for j in range(k):
+                    self.log.save_img([f[j:j + 1] for f in plain], save_names[j])
+        out = []
+        for j in range(k):
+            figs = None
+            if self.return_figs or save_names is None:
+                figs = [im0[j:j + 1], torch.clamp(con0[j:j + 1], 0, 1), pred[j:j + 1] * 2 if pred is not None else dif0[j:j + 1] * face0[j:j + 1] * 2]
+                if not video:
+                    figs.append(label[j:j + 1])
+            out.append((losses_h[j], figs))
+        return out
+
+    def test_step_sfw(self, img, box=None, training: bool = False, all_rows: bool = False):
+        """train_test_GSC.py:799-838 for one element [1,R,S,S,17] (dset='sfw_gsc' of any R, or the TSM pair dset='sfw': row 0 is the same):
+        -> ({'ssim','psnr','auc'}, [img, con, mask_pred * 2, label]) of row 0.  The AUC is float64 (the reference stores it as float32)."""
+        return self._sfw_steps([img], video=False, all_rows=all_rows)[0]
+
+    def test_step_sfw_video(self, img, box=None, training: bool = False, all_rows: bool = False):
+        """train_test_GSC.py:893-932 for one element [1,10,S,S,13] (dset='sfw_video'): -> ({}, [img, con, mask_pred * 2]) of row 0."""
+        return self._sfw_steps([img], video=True, all_rows=all_rows)[0]
+
+    def _sfw_loop(self, dataset_val, video: bool, batch: int, all_rows: bool):
+        from .dist import rank_world
+        if rank_world(self.group)[1] > 1:
+            raise NotImplementedError("FSRNet.testsfw / testsfw_video run in one process: data-parallel SFW loops are not provided")
+        if batch < 1:
+            raise ValueError("batch must be >= 1 element per forward")
+        names = list(dataset_val.name_list)
+        self._restore()
+        start = time.time()
+        results: List[Tuple[str, Dict[str, float]]] = []
+        group: List[Tuple[int, str, object]] = []
+
+        def flush():
+            if not group:
+                return
+            out = self._sfw_steps([g[2] for g in group], video, all_rows, save_names=[g[1] for g in group])
+            for (step, name, _), (losses, _) in zip(group, out):
+                self.log.display(losses, 0, step, False, len(names))
+                results.append((name, losses))
+            group.clear()
+        try:
+            for step, img_name in enumerate(names):
+                element = next(dataset_val.feed)
+                group.append((step, _name(img_name), element[0]))
+                if len(group) >= batch:
+                    flush()
+            flush()
+        finally:
+            self.log.flush()
+        self.all_losses = list(results)
+        self.timings = {"total_s": time.time() - start, "items": len(results)}
+        print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
+        return results
+
+    def testsfw(self, dataset_val, batch: int = 16, all_rows: bool = False):
+        """train_test_GSC.py:750-772 + test_step_sfw :799-838 with ``batch`` elements per forward.  ``dataset_val``: Dataset(dset='sfw_gsc')
+        (any rows) or the TSM pair Dataset(dset='sfw').  Strips [img, con, mask_pred * 2, label] go to <CHECKPOINT_DIR>/test/; returns
+        [(name, {'ssim','psnr','auc'})] in list order (also ``all_losses``)."""
+        return self._sfw_loop(dataset_val, False, batch, all_rows)
+
+    def testsfw_video(self, dataset_val, batch: int = 16, all_rows: bool = False):
+        """train_test_GSC.py:774-797 + test_step_sfw_video :893-932 over Dataset(dset='sfw_video'): strips [img, con, mask_pred * 2];
+        returns [(name, {})]."""
+        return self._sfw_loop(dataset_val, True, batch, all_rows)
+
 
 class FSRNetRGB(FSRNet):
     """Inference harness of the paper's single-stage RGB baseline: ``FSRNet.test`` / ``test_step`` of /root/reference/train_RGB_test.py
@@ -1117,6 +1254,15 @@ class FSRNetRGB(FSRNet):
 
     def testFFHQ(self, *a, **k):
         raise NotImplementedError("train_RGB_test.py has no testFFHQ")
+
+    def _sfw_loop(self, *a, **k):
+        raise NotImplementedError("train_RGB_test.py's testsfw cannot run against model_RGB's generator; the RGB baseline has no SFW loop")
+
+    def test_step_sfw(self, *a, **k):
+        self._sfw_loop()
+
+    def test_step_sfw_video(self, *a, **k):
+        self._sfw_loop()
 
     def test_step(self, img, box, curr_mask, *other_masks, training: bool = False, all_rows: bool = False):
         """train_RGB_test.py:403-505 for one dataset element, post-processing on the host (ucb_post_rgb): ``curr_mask`` is the with-hair

@@ -12,6 +12,8 @@ into the same `<checkpoint-dir>/test/`, rank 0 prints the progress and the final
 with the loop's rate.  The process group is created by THIS process before it touches the GPU; nothing is re-exec'ed.
 Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random-weights SEED` (the reference ships no data shards).
 `--model rgb` runs the paper's single-stage RGB baseline instead (train_RGB_test.py's `main`: `FSRNetRGB.test`, `--loop ucb`, fp32 only).
+`--loop sfw` / `--loop sfw_video` run the GSC model's SFW evaluation (`FSRNet.testsfw` over Dataset(dset='sfw_gsc') /
+`FSRNet.testsfw_video` over Dataset(dset='sfw_video'): --data globs SFW video folders), in one process only.
 """
 from __future__ import annotations
 
@@ -25,7 +27,9 @@ import time
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model", choices=("gsc", "rgb"), default="gsc", help="gsc = FSRNet (train_test_GSC.py), rgb = FSRNetRGB (train_RGB_test.py: --loop ucb, --dtype f32 only)")
-    ap.add_argument("--loop", choices=("ffhq", "ucb"), required=True, help="ffhq = FSRNet.testFFHQ, ucb = FSRNet.test (post-processing + SSIM / PSNR)")
+    ap.add_argument("--loop", choices=("ffhq", "ucb", "sfw", "sfw_video"), required=True,
+                    help="ffhq = FSRNet.testFFHQ, ucb = FSRNet.test (post-processing + SSIM / PSNR), sfw = FSRNet.testsfw (SSIM / PSNR / AUC), "
+                         "sfw_video = FSRNet.testsfw_video")
     ap.add_argument("--data", action="append", required=True, help="glob of item folders (Config.DATA_DIR_TEST entry); repeatable")
     ap.add_argument("--checkpoint-dir", required=True, help="Config.CHECKPOINT_DIR: weights are restored from it, PNG strips go to <dir>/test/")
     ap.add_argument("--mask-root", default=".", help="parent of the UCB_input_images_*_masks_* folders (--loop ucb)")
@@ -41,6 +45,10 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.model == "rgb" and (args.loop != "ucb" or args.dtype != "f32"):
         sys.stderr.write("run_loop: --model rgb runs train_RGB_test.py's test loop only: --loop ucb --dtype f32 (it has no testFFHQ and no 16-bit path)\n")
+        return 2
+    sfw = args.loop in ("sfw", "sfw_video")
+    if sfw and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("BSR_LOOP_FORCE_DIST") == "1"):
+        sys.stderr.write("run_loop: --loop %s runs in one process (data-parallel SFW loops are not provided): launch it without a launcher\n" % args.loop)
         return 2
 
     # Before ANYTHING initialises the HIP / HSA runtime (torch.cuda.is_available() below already does): the runtime reads this at
@@ -86,9 +94,12 @@ def main(argv=None) -> int:
     # worker counts: sweeps on the 16-CPU GPU box (loop_bench.py).  With post-processing and PNG encoding on the device (the default) the
     # loader's workers — PNG decode, Delaunay meshes, the UCB masks — are the only host stage: 3/4 (UCB) / 5/8 (FFHQ) of this rank's share of the CPUs (the loop's own thread and its file writers need the rest)
     ds_kw = dict(workers=max(1, (ncpu * 5 // 8 if ucb else ncpu * 7 // 8) if args.host_post else max(1, ncpu * 3 // 4 if ucb else ncpu * 5 // 8)))
-    if not args.host_prep:
-        ds_kw.update(device_prep=local_rank, device_batch=args.batch)
-    ds = Dataset(cfg, "test", ucb=ucb, **ds_kw)
+    if sfw:
+        ds = Dataset(cfg, "test", dset="sfw_gsc" if args.loop == "sfw" else "sfw_video", workers=max(1, ncpu * 7 // 8))
+    else:
+        if not args.host_prep:
+            ds_kw.update(device_prep=local_rank, device_batch=args.batch)
+        ds = Dataset(cfg, "test", ucb=ucb, **ds_kw)
     if args.model == "rgb":
         fsr = FSRNetRGB(cfg, weights=init_weights(args.random_weights, variant="rgb") if args.random_weights is not None else None)
     else:
@@ -107,7 +118,10 @@ def main(argv=None) -> int:
             import torch.distributed as dist
             dist.barrier()
         t0 = time.perf_counter()
-        res = fsr.test(ds, batch=args.batch) if ucb else fsr.testFFHQ(ds, batch=args.batch)
+        if sfw:
+            res = (fsr.testsfw if args.loop == "sfw" else fsr.testsfw_video)(ds, batch=args.batch)
+        else:
+            res = fsr.test(ds, batch=args.batch) if ucb else fsr.testFFHQ(ds, batch=args.batch)
         torch.cuda.synchronize()
         if grouped:
             dist.barrier()
@@ -115,7 +129,8 @@ def main(argv=None) -> int:
         if rank == 0:
             n = len(fsr.all_losses)
             means = {k: s / max(c, 1) for k, (s, c) in fsr.log.losses.items()}
-            print("\n" + json.dumps({"loop": ("FSRNetRGB.test" if args.model == "rgb" else "FSRNet.test") if ucb else "FSRNet.testFFHQ", "items": n, "ranks": world, "process_group": (args.backend if grouped else None), "items_this_rank": len(res),
+            loop = {"sfw": "FSRNet.testsfw", "sfw_video": "FSRNet.testsfw_video"}.get(args.loop, "FSRNet.testFFHQ")
+            print("\n" + json.dumps({"loop": ("FSRNetRGB.test" if args.model == "rgb" else "FSRNet.test") if ucb else loop, "items": n, "ranks": world, "process_group": (args.backend if grouped else None), "items_this_rank": len(res),
                                      "images_per_sec": round(n / dt, 2), "seconds": round(dt, 3), "batch": args.batch, "dtype": args.dtype,
                                      "cpus_per_rank": ncpu, "post_and_png": "host" if args.host_post else "device", "means": means}))
     finally:

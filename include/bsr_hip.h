@@ -203,6 +203,18 @@ size_t bsr_ucb_post_rgb_scratch_bytes(int B, int S);
 int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
                      unsigned char* strips, float* figs, int* status, void* scratch, void* stream);
 
+/* The scoring of the GSC model's FSRNet.test_step_sfw on the device (added in ABI 8: additive, no existing signature changed): replaces
+ * /root/reference/train_test_GSC.py:808-832 after the generator call for a batch of B items.
+ * rows3: [B,S,S,3] float32 = mask (the label plane's grey level after the crop resize, 0..255) | dif | face of row 0 of each item.
+ * All device pointers.  losses: [B,2] float32 = ssim, psnr of the mask against mask_pred = dif * face (one channel, max_val 1);
+ * auc: [B] float64 = sklearn.metrics.roc_auc_score over [1, 0] ++ (mask == 2) against [1, 0] ++ mask_pred, exact (bit-identical to
+ * the Mann-Whitney form with average ranks); pred: [B,S,S] float32 mask_pred; label: [B,S,S] float32 (mask == 2);
+ * status: [B] int32 — 0 = done, 3 = a mask_pred value is NaN or infinite (auc NaN; the reference's roc_auc_score raises).
+ * scratch: bsr_sfw_score_scratch_bytes(B, S) bytes, 256-byte aligned (0 = unsupported S).  S in {32, 64, 128, 256}. */
+size_t bsr_sfw_score_scratch_bytes(int B, int S);
+int bsr_sfw_score(int device, const float* rows3, int B, int S, float* losses, double* auc, float* pred, float* label, int* status,
+                  void* scratch, void* stream);
+
 /* Test hook: the fused NonLocalBlock attention kernel alone (/root/reference/model.py:51-53).
  * qkv [B,tokens,384] (theta | phi | g, 128 channels each) -> y [B,tokens,128]; tokens % 128 == 0. */
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream);
