@@ -352,6 +352,9 @@ __global__ __launch_bounds__(512) void ucb_a23_kernel(int S, void* scratch) {   
   if (tid != 0) return;
   const float frac = (float)(3 * g->v[CNT_SR]) / (float)(3 * g->v[CNT_ROI]);
   const float mean_below = mean_num / (float)g->v[CNT_DEN];
+  // float32 comparisons, as the host statement's NumPy float32 scalars against Python floats under NumPy >= 2 (NEP 50).  Under NumPy 1.x
+  // they would be float64 comparisons, which differ only where frac is exactly float32(0.252), float32(0.3) or float32(0.295) (or
+  // mean_below float32(0.358) / float32(0.22)).  Kept as is; tests/ucb_edge_cases.py pins the float32 behaviour at those values.
   g->roi_off = ((0.252f < frac && frac < 0.268f) || (0.3f < frac && frac < 0.31f && mean_below > 0.358f) || (0.295f < frac && frac < 0.3f && mean_below > 0.22f)) ? 1 : 0;
   g->fr0 = g->fr1 = g->fc0 = g->fc1 = 0;
   if (g->forehead_rule) {

@@ -11,7 +11,7 @@ tests/golden/ucb_post_9156.npz, produced by executing the reference's own `test_
 (tools/make_ucb_post_fixture.py).
 """
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -72,11 +72,14 @@ def _bbox(mask2d: np.ndarray) -> Tuple[int, int, int, int]:
 
 
 def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mask_pred0: np.ndarray, box: np.ndarray,
-                    masks: Dict[str, np.ndarray]) -> Tuple[Dict[str, float], List[np.ndarray]]:
+                    masks: Dict[str, np.ndarray], trace: Optional[dict] = None) -> Tuple[Dict[str, float], List[np.ndarray]]:
     """img0 / gt0 / con_rgb0: [S,S,3]; mask_pred0: [S,S,1] (the generator's `dif`); box: [4]; masks: the seven [S,S,3] (or, from read_masks(grey=True), [S,S,1])
     {0,1} maps of MASK_DIRS.  Returns ({'ssim','psnr'}, figs) with figs as in train_test_GSC.py:744: input, composite,
-    2 x gated magnitude, ground truth, detected shadow mask, full prediction, nose image — each [1,S,S,3] float32."""
+    2 x gated magnitude, ground truth, detected shadow mask, full prediction, nose image — each [1,S,S,3] float32.
+    trace: an optional dict that receives the decisions taken (the rules' inputs and verdicts, the component counts) — for tests; the
+    outputs do not depend on it."""
     full = img0.shape[0]
+    tr = trace if trace is not None else {}
     box = np.asarray(box).reshape(4)
     size = int(box[3] - box[1])                                                            # :417-418
     rs = lambda a: resize_bilinear(a, size)
@@ -105,6 +108,7 @@ def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mas
     region = np.zeros((full, full, 3))
     region[int(upper_mouth):int(lower_mouth), int(left_mouth):int(right_mouth)] = 1
     mp = mp * np.logical_not(np.logical_and(mp < 0.02, region == 1)).astype(np.float32)
+    tr.update(mid_nose_height=mid_nose_height, mid_nose_width=mid_nose_width, upper_mouth=upper_mouth)
 
     hair = (face_hair - face).astype(np.float32)                                           # :501
     intensity = np.repeat(np.mean(tmp, axis=2, dtype=np.float32).reshape(full, full, 1), 3, axis=2)   # :525-526
@@ -112,6 +116,7 @@ def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mas
     threshold[hair > 0] = 0.02                                                             # :528
     threshold[np.logical_and(hair > 0, intensity < 0.13)] = 0.004                          # :529
 
+    tr.update(brow_sum=float(np.sum(brow)), forehead=bool(np.sum(brow) > 30), forehead_px=0, left_rule=False, left_px=0)
     if np.sum(brow) > 30:                                                                  # forehead (:533-544)
         forehead = face.copy()
         upper_brow = int(np.where(brow[:, :, 0] == 1)[0].min())
@@ -120,19 +125,30 @@ def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mas
         fm = np.zeros((full, full, 3))
         fm[int(f_top + 20):int(upper_brow - 40), int(f_left + 40):int(f_right - 40)] = 1
         threshold[np.logical_and(fm > 0, intensity < 0.4)] = -0.001
+        tr.update(forehead_rows=(int(f_top + 20), int(upper_brow - 40)), forehead_cols=(int(f_left + 40), int(f_right - 40)),
+                  forehead_px=int(np.sum(fm[:, :, 0] > 0)))
 
     below = np.zeros((full, full, 3), np.float32)                                          # mouth and below (:547-564)
     below[int(upper_mouth):full, :, :] = 1.0
     roi = below * face
     shadowed = (mp > 0.01).astype(np.float32)
     frac = np.sum(shadowed * roi, dtype=np.float32) / np.sum(roi, dtype=np.float32)
+    # frac and mean_below are NumPy float32 scalars compared with Python floats.  Under NumPy >= 2 (NEP 50) the comparison is done in
+    # float32, as the device does it (0.252f ...); under the NumPy 1.x of the reference's environment it would be done in float64.  The
+    # two differ only where frac rounds exactly to float32(0.252), float32(0.3) or float32(0.295) (and mean_below to float32(0.358) /
+    # float32(0.22)).  Not measured against NumPy 1.x; the current float32 behaviour is kept and pinned by tests/ucb_edge_cases.py.
+    rule = [False, False, False]
     if 0.252 < frac < 0.268:
         threshold[roi > 0] = 1.0
+        rule[0] = True
     mean_below = np.sum(np.mean(roi * tmp * shadowed, 2)) / np.sum(roi[:, :, 0] * shadowed[:, :, 0])
     if 0.3 < frac < 0.31 and mean_below > 0.358:
         threshold[roi > 0] = 1.0
+        rule[1] = True
     if 0.295 < frac < 0.3 and mean_below > 0.22:
         threshold[roi > 0] = 1.0
+        rule[2] = True
+    tr.update(frac=frac, mean_below=mean_below, below_rules=tuple(rule), roi_off=any(rule))
     if np.sum(brow) > 0:                                                                   # left eyebrow on the face edge (:565-579)
         left_brow = int(np.where(brow[:, :, 0] == 1)[1].min())
         _, _, left_face, right_face = _bbox(face[:, :, 0])
@@ -140,6 +156,7 @@ def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mas
             left_mask = np.zeros((full, full, 3))
             left_mask[:, 0:int(left_face * 0.8 + right_face * 0.2), :] = 1.0
             threshold[np.logical_and(brow * left_mask > 0, intensity > 0.1)] = 1.0
+            tr.update(left_rule=True, left_px=int(np.sum(np.logical_and(brow * left_mask > 0, intensity > 0.1)[:, :, 0])))
 
     detected = (mp > threshold.astype(np.float32)).astype(np.uint8)                        # :586-590
 
@@ -148,20 +165,36 @@ def ucb_postprocess(img0: np.ndarray, gt0: np.ndarray, con_rgb0: np.ndarray, mas
     labels, ncomp = ndimage.label(detected[:, :, 0], structure=[[0, 1, 0], [1, 1, 1], [0, 1, 0]])
     sizes = np.bincount(labels.reshape(-1), minlength=ncomp + 1)[1:]
     keep = np.zeros((full, full, 1))
+    tr.update(ncomp=int(ncomp), largest=0, min_size=None, n_kept=0, n_big=0, n_hair=0, n_negative_hair=0)
     if ncomp:
         min_size = 0.45 * np.max(sizes)
+        tr.update(largest=int(np.max(sizes)), min_size=min_size)
         for i in range(ncomp):
+            if sizes[i] < min_size:
+                continue
             comp = labels == i + 1
-            if sizes[i] >= min_size and np.sum(hair[:, :, 0] * comp) / sizes[i] < 0.8:
+            hair_frac = np.sum(hair[:, :, 0] * comp) / sizes[i]
+            tr["n_big"] += 1
+            tr["n_negative_hair"] += int(hair_frac < 0)
+            if hair_frac < 0.8:
                 keep[comp] = 1
+                tr["n_kept"] += 1
+            else:
+                tr["n_hair"] += 1
 
     # nose rule (:650-666)
     shadow_image = keep * np.mean(tmp, 2).reshape(full, full, 1)
     mean_intensity = np.sum(shadow_image) / np.sum(keep)
     frac_nose = np.sum((nose[:, :, 0:1] * shadow_image) > 0) / np.sum(nose[:, :, 0])
+    nose_windows = ((0.15 < frac_nose < 0.25), (0.30 < frac_nose < 0.31), (0.34 < frac_nose < 0.35))
+    tr.update(mean_intensity=mean_intensity, frac_nose=frac_nose, nose_windows=nose_windows, nose_hit=any(nose_windows), reach=None,
+              nose_cleared=0)
     if (0.15 < frac_nose < 0.25) or (0.30 < frac_nose < 0.31) or (0.34 < frac_nose < 0.35):
         reach = 5 if mean_intensity < 0.15 else 65
+        before = int(np.sum(keep))
         keep[int(mid_nose_height):int(lower_nose + reach), int(mid_nose_width - 35):int(mid_nose_width + 35)] = 0
+        tr.update(reach=reach, nose_rows=(int(mid_nose_height), int(lower_nose + reach)),
+                  nose_cols=(int(mid_nose_width - 35), int(mid_nose_width + 35)), nose_cleared=before - int(np.sum(keep)))
 
     detected3 = np.concatenate((keep, keep, keep), axis=2).astype(np.float32)              # :690-693
     full_pred = _pad(pred, size, full)                                                     # :711-712
