@@ -8,7 +8,12 @@ all-gather that re-assembles the consumed outputs (con_rgb + dif) on every rank,
 step's compute.  Rank 0 prints ONE JSON line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--dtype f32|f16] [--workload gsc256|tsm512]
-                    [--no-cpu-baseline] [--loop ffhq|ucb] [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--loop ffhq|ucb]]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  `--full`
+adds every side measurement and check to the same line, each outside the timed region: the repeated and seconds-long
+regions, two forwards in flight, the per-kernel roofline, the B = 16 and f32x3 lines, the CPU oracle's rate and the
+parity against it, the gather's own timings and its verification (N > 1) and, with --loop, the end-to-end loops.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this process a LAUNCHER: it starts N rank
 processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set) before anything touches
@@ -836,10 +841,12 @@ def run_rank(args):
     nlanes = args.streams if on_gpu else 1
     gens = [gen]
     lanes, lanes_verified = [None], True
-    if nlanes > 1:
+    if on_gpu:
         gens += [(GeneratorTSM if tsm else Generator)(device=local_rank, dtype=args.dtype).load_weights(weights) for _ in range(nlanes - 1)]
         from blindshadowremoval_amd.lanes import concurrent_streams
-        lanes, lanes_verified = concurrent_streams(local_rank, nlanes)       # streams SEEN to overlap (distinct hardware queues), not merely distinct objects
+        # streams SEEN to overlap (distinct hardware queues), not merely distinct objects.  With one lane nothing is probed; the timed
+        # region runs on lanes[0], a stream of its own, whether or not the two-lane side measurement follows
+        lanes, lanes_verified = concurrent_streams(local_rank, nlanes)
     g = torch.Generator(device="cpu").manual_seed(1234 + rank)
     inp = torch.rand(B, HW, HW, 3, generator=g).to(dev)       # synthetic, resident in HBM before timing
     uv = torch.rand(B, HW, HW, 3, generator=g).to(dev)
@@ -854,7 +861,7 @@ def run_rank(args):
         # The per-launch events of the roofline object are taken on rank 0 BEFORE the process group exists: with RCCL initialised the
         # same event-bracketed forwards run ~10 % longer (profiles/r3_bench_dist1.json of the earlier rounds: 5.64 vs 5.14 ms of kernel
         # time, frac 0.716 vs 0.793) although the timed region itself is unchanged — an artefact of event recording, not of the kernels.
-        if rank == 0 and on_gpu and not tsm:
+        if rank == 0 and on_gpu and not tsm and args.full:
             for _ in range(12):                     # the chip is cold here (in the single-process run the events follow the timed regions)
                 gen(inp, uv, out=outs[0])
             torch.cuda.synchronize()
@@ -947,7 +954,7 @@ def run_rank(args):
     reps = [elapsed] + [timed(args.steps, serial)[0] for _ in range(max(0, args.repeats - 1))]
     extra = {}
     sustained = None
-    if on_gpu and not args.no_sustained:
+    if on_gpu and args.full and not args.no_sustained:
         sustained = sustained_region(serial if not distributed else (lambda i: step(i, gather=False, lane=0)), local_rank, B, 1, elapsed / args.steps * 1e3)
         drain()
         if distributed:                                 # every rank ran its own region: report the slowest rank's rate times the world
@@ -964,7 +971,7 @@ def run_rank(args):
                                   "streams_seen_to_overlap": lanes_verified,
                                   "note": "NOT `value`: the same K steps alternating between two handles on two HIP streams (two forwards in flight, 2 x B images "
                                           "resident; ms_per_step is an inverse throughput there); every output is bit-identical to the forward running alone"}
-    if distributed and not args.no_gather:
+    if distributed and not args.no_gather and args.full:
         t_nog, _ = timed(args.steps, lambda i: step(i, gather=False))
 
         def gather_only(i):
@@ -1038,6 +1045,7 @@ def run_rank(args):
                         "ms_per_step_all": [round(r, 4) for r in rs], "note": "`value` is the FIRST timed region of exactly K steps; the others repeat it"},
         }
         result["value_mode"] = "one forward at a time"
+        result["full"] = args.full          # false: the line carries no side measurement (bench.py --full adds them)
         if sustained is not None:
             sustained["vs_value"] = round(sustained["value"] / result["value"], 4)
             sustained["note"] = ("the same step repeated for seconds after seconds of warm-up: `value` is %d steps (%.0f ms) on a chip that may still be "
@@ -1054,7 +1062,7 @@ def run_rank(args):
             result["stub"] = True
             result["roofline"] = None
             result["cpu_baseline"] = None
-        else:
+        elif args.full:
             if tsm:
                 # configs[4]'s per-rank shape priced with ITS work: 512x512 frames, the TSM channel plan, attention over 4096 tokens
                 set_workload(True, HW)
@@ -1111,19 +1119,23 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default 32; 8 for --workload tsm512)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of K steps each; `value` comes from the first")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="add every side measurement and check to the line (all outside the timed region): repeated and seconds-long regions, "
+                         "two forwards in flight, per-kernel roofline, the B = 16 and f32x3 lines, the CPU oracle's rate and parity, the gather's own "
+                         "timings and verification (N > 1), --loop.  Without it the run only sets up, warms up, times K steps and dumps")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of K steps each; `value` comes from the first (default 3 with --full, else 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's rate and the parity against it")
     ap.add_argument("--dtype", choices=("f32", "f32x3", "f16"), default="f32",
                     help="f32 = the measured path (BASELINE configs[1], fp32 matrix cores); f32x3 = split-precision fp32 on the fp16 matrix cores "
                          "(3x3-conv path; fp32-class accuracy); f16 = fp16 operands on the 3x3-conv path (configs[3])")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the f32x3 side measurement the default f32 run appends")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the seconds-long `sustained` region (and its clock trace)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the f32x3 and B = 16 side measurements the f32 run appends")
+    ap.add_argument("--no-sustained", action="store_true", help="--full: skip the seconds-long `sustained` region (and its clock trace)")
     ap.add_argument("--workload", choices=("gsc256", "tsm512"), default="gsc256",
                     help="gsc256 = BASELINE configs[1]/[3]; tsm512 = the per-rank shape of configs[4] (TSM generator, 512x512 frames)")
-    ap.add_argument("--streams", type=int, choices=(1, 2), default=2,
+    ap.add_argument("--streams", type=int, choices=(1, 2), default=None,
                     help="forwards in flight per GPU: 2 = consecutive steps alternate between two handles on two HIP streams, so one step's kernels "
                          "fill the tails and ramps of the other's one-round launches — reported as `two_in_flight` BESIDE `value`, which is always one forward at a time; "
-                         "1 = skip that side measurement")
+                         "1 = skip that side measurement (default 2 with --full, else 1)")
     ap.add_argument("--no-gather", action="store_true", help="skip the output all-gather (N>1)")
     ap.add_argument("--gather", choices=("rccl", "peer"), default="rccl",
                     help="N>1: how the outputs are re-assembled on every rank.  rccl = one asynchronous all_gather_into_tensor per step (RCCL kernels over "
@@ -1135,7 +1147,7 @@ def parse_args(argv=None):
                          "verification — with the REAL generator where only one GPU exists; the rate it prints is N forwards sharing a chip, not a scaling figure")
     ap.add_argument("--stub", action="store_true", help="CPU stand-in generator: tests the launcher / sharding / JSON contract, measures nothing")
     ap.add_argument("--loop", choices=("ffhq", "ucb"), default=None,
-                    help="also time the end-to-end FSRNet.testFFHQ / FSRNet.test loop (host prep + H2D + forward + post + PNG) on the shipped fixtures")
+                    help="--full: also time the end-to-end FSRNet.testFFHQ / FSRNet.test loop (host prep + H2D + forward + post + PNG) on the shipped fixtures")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step (gs, con_rgb, mask22, dif) as DIR/<name>.npy, float32, at most %d bytes in all; "
                          "when the whole batch is larger a fixed seeded sample of its rows is kept, listed as batch_rows in the result line (the default "
@@ -1145,6 +1157,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if args.loop is not None and not args.full:
+        ap.error("--loop is a side measurement: pass --full with it")
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.streams is None:
+        args.streams = 2 if args.full else 1
     if args.dump_outputs is not None:
         args.dump_outputs = os.path.abspath(args.dump_outputs)
         os.makedirs(args.dump_outputs, exist_ok=True)

@@ -1,4 +1,4 @@
-"""End-to-end rate of the reference's test loops on this box (bench.py --loop ffhq|ucb): host input preparation (Dataset, with and
+"""End-to-end rate of the reference's test loops on this box (bench.py --full --loop ffhq|ucb): host input preparation (Dataset, with and
 without the worker pool) -> host-to-device -> generator forward -> the reference's post-processing -> PNG strips, i.e.
 `FSRNet.testFFHQ` (train_test_GSC.py:840-890) / `FSRNet.test` (:360-748) as a user runs them — NOT the `value` of bench.py, which
 times the forward alone on resident inputs.  The fixtures bench.py points it at (tests/golden) are the reference's own sample data

@@ -13,7 +13,7 @@ no relay), on its own stream, behind an event of the forward that produced the s
   * reuse rule (two slots): `finish()` of step k is called before `push()` of step k + 1, and the data of step k - 1 must have been
     consumed by then — the barrier inside finish(k) therefore orders every rank's reads of slot (k+1) & 1 before anyone's next write.
 
-Verified like the RCCL path (every rank checks its own shard bit for bit and the others' by checksum; bench.py --gather peer).  The
+Verified like the RCCL path (every rank checks its own shard bit for bit and the others' by checksum; bench.py --full --gather peer).  The
 world-2 self-test (`python -m torch.distributed.run --nproc-per-node 2 -m blindshadowremoval_amd.peer_gather --device 0`) runs both
 ranks on ONE GPU — the IPC mapping and the protocol are the same, only the copies do not cross xGMI.
 """

@@ -16,7 +16,7 @@ def _run(args, env_extra=None, timeout=300):
 
 
 def test_gpus2_launches_two_ranks_over_gloo():
-    r = _run(["--gpus", "2", "--backend", "gloo", "--stub", "--batch", "2", "--steps", "2", "--warmup", "1", "--repeats", "2"])
+    r = _run(["--gpus", "2", "--backend", "gloo", "--stub", "--batch", "2", "--steps", "2", "--warmup", "1", "--repeats", "2", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -34,6 +34,25 @@ def test_gpus2_launches_two_ranks_over_gloo():
     assert j["config"]["forwards_in_flight"] == 1 and "two_in_flight" not in j      # the CPU stand-in has no streams: the two-lane side measurement only exists on a GPU
     # `value` is always one forward at a time (BASELINE configs[1]: ONE batch of 32 resident), and every line says so
     assert j["value_mode"] == "one forward at a time" and j["single_stream_value"] == j["value"] and "roofline_in_flight" not in j
+    assert j["full"] is True
+
+
+def test_plain_run_times_only_its_steps():
+    """Without --full the line is the headline alone: one timed region of K steps, no gather timings or verification, no side
+    objects; --loop is refused without --full."""
+    r = _run(["--gpus", "2", "--backend", "gloo", "--stub", "--batch", "2", "--steps", "3", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["full"] is False and j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "f32"
+    assert j["metric"].startswith("images/sec") and j["unit"] == "images/sec" and j["higher_is_better"] is True
+    assert abs(j["value"] - 4 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 1e-3
+    assert j["repeats"]["n"] == 1 and j["config"]["collective"].startswith("all_gather")
+    assert "allgather" not in j["config"] and "per_rank_images_per_sec" not in j["config"]
+    assert not any(k in j for k in ("sustained", "two_in_flight", "f32x3", "batch16", "loop"))
+    r = _run(["--backend", "gloo", "--stub", "--loop", "ucb"])
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_dump_outputs_writes_the_last_step_reproducibly(tmp_path):

@@ -1,7 +1,7 @@
 """How much of a `rocprofv3 --kernel-trace` run had TWO of the library's kernels on the chip at once — the profiler's view of
-`bench.py --streams 2` (two forwards in flight on two HIP streams).  Usage:
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/r3_prof_lanes -- python3 bench.py --no-cpu-baseline --no-secondary --repeats 1
-    python tools/lane_overlap.py gpurun_out/r3_prof_lanes > profiles/r3_lane_overlap.txt"""
+`bench.py --full --streams 2` (two forwards in flight on two HIP streams).  Usage:
+    rocprofv3 --kernel-trace --output-format csv -d <out>/prof_lanes -- python3 bench.py --full --no-cpu-baseline --no-secondary --repeats 1
+    python tools/lane_overlap.py <out>/prof_lanes > profiles/<tag>_lane_overlap.txt"""
 import glob
 import os
 import sys

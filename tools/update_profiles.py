@@ -1,9 +1,9 @@
 """Refresh profiles/<tag>_kernel_stats[_<dtype>].csv, profiles/<tag>_bench_n1[_<dtype>].json and the per-kernel table in
-profiles/README.md from a gpurun_out/ run of:
-    python bench.py [--dtype D] > gpurun_out/<bench>.json
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<prof> -- python3 bench.py [--dtype D] --no-cpu-baseline --no-secondary --repeats 1
+profiles/README.md from the output of:
+    python bench.py --full [--dtype D] > <out>/<bench>.json
+    rocprofv3 --kernel-trace --stats --output-format csv -d <out>/<prof> -- python3 bench.py --full [--dtype D] --no-cpu-baseline --no-secondary --repeats 1
 (the profiled command times 1 region of K steps: forwards = K + warm-up + the 3 event-timed ones of the roofline leg).
-Usage: python tools/update_profiles.py r2 gpurun_out/r2_bench.json gpurun_out/r2_prof [dtype]"""
+Usage: python tools/update_profiles.py r2 <out>/r2_bench.json <out>/r2_prof [dtype]"""
 import glob
 import json
 import os
@@ -35,11 +35,11 @@ for _, r in d.sort_values("us/fwd", ascending=False).iterrows():
 rows.append("| **sum** | %g | | **%.0f** |" % (d["launches/fwd"].sum(), d["us/fwd"].sum()))
 rf = b["roofline"]
 cb = b.get("cpu_baseline") or {}
-head = ("* `%s_bench_n1%s.json` — `python bench.py%s` (N = 1, %d steps, %d warm-up): **%.0f images/s**%s, %.3f ms per %d-image step "
+head = ("* `%s_bench_n1%s.json` — `python bench.py --full%s` (N = 1, %d steps, %d warm-up): **%.0f images/s**%s, %.3f ms per %d-image step "
         "(repeats: min %.3f / median %.3f ms); dominant kernel `%s`: **%.1f TFLOP/s = %.1f %% of its %.0f TFLOP/s matrix peak** "
         "(avg launch %.4f ms — compare the rocprofv3 average below; algorithmic HBM rate %.0f GB/s = %.1f %% of 8 TB/s; nearer roof: %s), whole 3x3-conv path %.1f TFLOP/s (%.1f %%), "
         "all kernels %.1f TFLOP/s; CPU oracle %s images/s on %s host threads.\n"
-        "* `%s_kernel_stats%s.csv` — `rocprofv3 --kernel-trace --stats -- python3 bench.py --streams 1%s --no-cpu-baseline --no-secondary --repeats 1` (%d forwards, one at a time: with two in flight a traced duration would include the time a kernel shares the chip). Per forward:\n\n"
+        "* `%s_kernel_stats%s.csv` — `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --streams 1%s --no-cpu-baseline --no-secondary --repeats 1` (%d forwards, one at a time: with two in flight a traced duration would include the time a kernel shares the chip). Per forward:\n\n"
         % (tag, sfx, "" if dtype == "f32" else " --dtype " + dtype, b["steps"], b["warmup"], b["value"],
            ((" with two forwards in flight (`single_stream`, one at a time: %.0f)" % b["single_stream"]["value"]) if b.get("single_stream") else
             (" one forward at a time (`two_in_flight`: %.0f)" % b["two_in_flight"]["value"]) if b.get("two_in_flight") else ""),
