@@ -28,6 +28,7 @@
 #include "stem7.h"
 #include "ucb_kernels.h"
 #include "ucb_rgb_kernels.h"
+#include "ucb_tsm_kernels.h"
 #include "sfw_kernels.h"
 
 namespace {
@@ -1163,6 +1164,25 @@ int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks,
   DeviceGuard guard(device);
   HIP_TRY(guard.err);
   HIP_TRY(bsr::launch_ucb_post_rgb(rows9, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+size_t bsr_ucb_post_tsm_scratch_bytes(int B, int S) {
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
+  return (size_t)B * bsr::ucb_tsm_item_scratch_bytes(S);
+}
+
+int bsr_ucb_post_tsm(int device, const float* rows, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
+                     double* nose_stats, unsigned char* strips, float* figs, int* status, void* scratch, void* stream) {
+  if (rows == nullptr || masks == nullptr || boxes == nullptr || losses == nullptr || nose_stats == nullptr || strips == nullptr ||
+      status == nullptr || scratch == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: null argument");
+  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
+    return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: scratch must be 256-byte aligned");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_ucb_post_tsm(rows, masks, boxes, B, S, losses, nose_stats, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
   return BSR_OK;
 }
 

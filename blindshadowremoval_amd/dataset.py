@@ -10,7 +10,10 @@ elements `[1,R,256,256,17]` for `FSRNet.testsfw`.  The reference's GSC `inputs` 
 
 `Dataset(config, 'test', dset='sfw' | 'sfw_video')` is the counterpart of the TSM script's loaders
 (/root/reference/dataset_with_TSM.py:19-79, 225-287, 289-583): elements `[1,2,256,256,17]` (frame + mirror) / `[1,10,256,256,13]`
-(ten frames of a video) for `FSRNetTSM.testsfw` / `testsfw_video`.
+(ten frames of a video) for `FSRNetTSM.testsfw` / `testsfw_video`.  `Dataset(config, 'test', dset='ucb_tsm', ucb=True)` is the TSM
+script's UCB loader (`parse_fn_test`, dataset_with_TSM.py:153-189): elements `[1,2,256,256,16]` (the UCB row + its mirror) for
+`FSRNetTSM.test`.  The reference lists `*_label.png` in test mode for every `dset` (:62) but then `np.load`s the listed path as a landmark
+file: this lists `*.npy`, as the GSC UCB loader does.
 
 It yields what `FSRNet.testFFHQ` / `test` consume: `.name_list` and `.feed`, an iterator of
 `(img[1,R,256,256,16], box[1,4], name)` with channel layout [img3, gt3, uvm3, reg_in3, reg_out3, face1]
@@ -347,6 +350,18 @@ def build_sfw_gsc(label_path: str, rows: int = 1, size: int = 256) -> Tuple[np.n
     return np.stack(out, axis=0).astype(np.float32)[None], np.asarray(box, np.float32)[None], np.array([(frame_path + ".png").encode()])
 
 
+def build_ucb_tsm_pair(lm_path: str, gt_path: str, size: int = 256) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`parse_fn_test` of /root/reference/dataset_with_TSM.py:153-189: one UCB item and its mirror as a group of two, `[1, 2, size, size, 16]`
+    = [img3, gt3, uvm3, reg_in3, reg_out3, face1] per row.  Row 0 is `build_row`'s row; row 1 is the horizontally flipped crop (input and
+    ground truth) with the uv, offset and face maps of the mirror landmarks."""
+    img_path = os.path.splitext(lm_path)[0] + ".png"
+    crop, lm, lm_m, box = face_crop_and_resize(np.concatenate([imread_rgb(img_path), imread_rgb(gt_path)], axis=2), np.load(lm_path), size,
+                                               with_mirror=True)
+    img1 = np.concatenate([crop, *_maps(lm, size)], axis=2)
+    img2 = np.concatenate([crop[:, ::-1, :], *_maps(lm_m, size)], axis=2)                       # cv2.flip(img, 1)
+    return np.stack([img1, img2], axis=0).astype(np.float32)[None], np.asarray(box, np.float32)[None], np.array([gt_path.encode()])
+
+
 def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One dataset element `(img[1,R,size,size,16], box[1,4], name[1])` from a job `(lm_path, gt_path, sibling lm paths, size)`.
     Top-level so that worker processes can run it (the rows of an element never depend on another element)."""
@@ -357,6 +372,8 @@ def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         return host_part_ring(hjob, job[4]) if len(job) > 4 else host_part(hjob)            # job[4]: (ring file, slot, slot bytes)
     if gt_path == "<sfw>":
         return build_sfw_pair(lm_path, size)
+    if isinstance(gt_path, tuple) and gt_path[0] == "<ucb_tsm>":
+        return build_ucb_tsm_pair(lm_path, gt_path[1], size)
     if isinstance(gt_path, tuple) and gt_path[0] == "<sfw_gsc>":
         return build_sfw_gsc(lm_path, gt_path[1], size)
     if gt_path == "<sfw_video>":
@@ -382,8 +399,11 @@ class Dataset:
 
     def __init__(self, config, mode: str = "test", dset=None, ucb: bool = False, rows: int = 1, seed: int = 0,
                  workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16):
-        if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc"):
-            raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video'); training loaders are out of scope")
+        if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc", "ucb_tsm"):
+            raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video' | 'ucb_tsm'); "
+                                      "training loaders are out of scope")
+        if dset == "ucb_tsm" and not ucb:
+            raise ValueError("dset='ucb_tsm' is the TSM script's UCB loader (parse_fn_test): it needs ucb=True")
         if dset == "sfw_gsc" and not 1 <= rows <= 10:
             raise ValueError("dset='sfw_gsc' elements have 1 to 10 rows, got rows=%d" % rows)
         self.config, self.mode, self.ucb, self.rows, self.dset = config, mode, ucb, rows, dset
@@ -409,7 +429,7 @@ class Dataset:
         # BSR_DEVICE_UNFILTER=0 / 1 overrides.
         self.device_unfilter: Optional[bool] = None
         self.name_list: List[str] = []
-        pattern = "*.npy" if dset is None else "*_label.png"               # dataset.py:55-61 | dataset_with_TSM.py:63
+        pattern = "*.npy" if dset in (None, "ucb_tsm") else "*_label.png"  # dataset.py:55-61 | dataset_with_TSM.py:63 (ucb_tsm: see the module docstring)
         for d in config.DATA_DIR_TEST:
             for folder in sorted(glob.glob(d), key=natural_key):
                 self.name_list += sorted(glob.glob(os.path.join(folder, pattern)), key=natural_key)
@@ -440,7 +460,7 @@ class Dataset:
         if self.dset is not None:                                          # TSM loaders: the element is a group of 2 / 10 coupled frames
             kind = ("<sfw_gsc>", self.rows) if self.dset == "sfw_gsc" else "<" + self.dset + ">"          # GSC SFW: `rows` rows of a chain
             for label in self.name_list[lo:hi]:
-                yield (label, kind, [], size)
+                yield (label, ("<ucb_tsm>", self._gt_path(label)) if self.dset == "ucb_tsm" else kind, [], size)
             return
         for i, lm_path in enumerate(self.name_list):
             if i >= hi:

@@ -1308,18 +1308,29 @@ def roc_auc_score(labels: np.ndarray, scores: np.ndarray) -> float:
 
 
 class FSRNetTSM(object):
-    """Inference harness of the temporal-sharing variant (/root/reference/train_with_TSM.py:619-748): `testsfw`
-    (image + mirror, frame = 2, shadow-segmentation AUC) and `testsfw_video` (10 video frames, frame = 10)."""
+    """Inference harness of the temporal-sharing variant (/root/reference/train_with_TSM.py:369-748): `test` (UCB: image + mirror,
+    frame = 2, post-processing, SSIM / PSNR and the nose statistics), `testsfw` (image + mirror, frame = 2, shadow-segmentation AUC) and
+    `testsfw_video` (10 video frames, frame = 10)."""
+    SPLIT_UCB = SPLIT_FFHQ                # img, gt, uv, reg, face           (train_with_TSM.py:426)
     SPLIT_SFW = (3, 3, 1, 3, 6, 1)        # img, cmap, mask, uv, reg, face   (train_with_TSM.py:675)
     SPLIT_VIDEO = (3, 3, 6, 1)            # img, uv, reg, face               (train_with_TSM.py:727)
 
-    def __init__(self, config: Config, weights: Optional[Dict[str, np.ndarray]] = None, dtype: str = "f32"):
+    def __init__(self, config: Config, weights: Optional[Dict[str, np.ndarray]] = None, dtype: str = "f32", gen=None):
+        """``gen``: a ready generator object to drive instead of constructing a ``GeneratorTSM`` (the CPU tests pass a stand-in).
+        ``dtype``: 'f32', 'f32x3' or 'f16', as ``GeneratorTSM``."""
         from .model import GeneratorTSM
         self.config = config
-        self.gen = GeneratorTSM(device=config.GPU_INDEX if torch.cuda.is_available() else None, dtype=dtype)
-        if weights is not None:
-            self.gen.load_weights(weights)
+        if gen is None:
+            gen = GeneratorTSM(device=config.GPU_INDEX if torch.cuda.is_available() else None, dtype=dtype)
+            if weights is not None:
+                gen.load_weights(weights)
+        self.gen = gen
         self.log = Logging(config, png_threads=4)
+        self.post_device = True                  # test()'s post-processing on the GPU when the generator lives on one (ucb_post_tsm_gpu); False: ucb_post_tsm.py
+        self.return_figs = True                  # False: test() returns figs = None (the strips are still written)
+        self.all_losses: List[Tuple[str, Dict[str, float]]] = []
+        self.timings: Dict[str, float] = {}
+        self._ucb_dev = None
 
     def _prep(self, img, n: int, split):
         s = self.config.IMG_SIZE
@@ -1411,6 +1422,129 @@ class FSRNetTSM(object):
 
     def testsfw(self, dataset_val, batch: int = 1):
         return self._loop(dataset_val, self.test_steps_sfw, batch)
+
+    # -- UCB (train_with_TSM.py:369-618) ------------------------------------------------------
+    def _device(self) -> Optional[int]:
+        return getattr(self.gen, "_device", None) if torch.cuda.is_available() else None
+
+    def test_steps(self, elements, boxes, mask_files, save_names: Optional[Sequence[str]] = None):
+        """train_with_TSM.py:418-618 for k elements in ONE forward.  Each element is [1,2,S,S,16] (Dataset(dset='ucb_tsm'): the UCB row and
+        its mirror) and runs as its own group of two frames: ``frame=2, share=True``.  The reference passes ``frame=1`` (:430), which its
+        ShareLayer cannot reshape for two rows (model_with_TSM.py:218); the older reshape it comments out (:217) put exactly these two rows
+        in one group, as ``test_step_sfw`` does (:676), and ``share`` = uniform() > 0 is True but for a draw of exactly 0.0.  Groups are
+        independent, so k elements per forward give each element the outputs of its own forward.  ``boxes``: k [4] crop boxes;
+        ``mask_files``: k dicts of mask paths (FSRNet._ucb_masks' form).  Post-processing on the device (ucb_post_tsm_gpu) when the
+        generator lives on a GPU and ``post_device``, else the host statement (ucb_post_tsm).  ``save_names``: write each strip under that
+        name (Logging.save_img's file).  -> [(losses, figs[8] | None, frac_nose_in_shadow, mean_intensity)] per element."""
+        from .ucb_post_tsm import MASKS, ucb_postprocess_tsm
+        k = len(elements)
+        im, gt, uv, reg, face = self._groups(elements, 2, self.SPLIT_UCB)
+        dev_idx = self._device()
+        dev = "cuda:%d" % dev_idx if dev_idx is not None else "cpu"
+        _, con, _, dif = self.gen(im.contiguous().to(dev), uv.contiguous().to(dev), reg.contiguous().to(dev), frame=2, share=True,
+                                  chuck=4, training=False)
+        if getattr(self.gen, "dtype", "f32") != "f32" and hasattr(self.gen, "check_range"):
+            self.gen.check_range()                 # 16-bit modes: an out-of-range activation is an error, never a silent inf
+        boxes = np.asarray([np.asarray(b, np.float32).reshape(-1)[:4] for b in boxes], np.float32).reshape(k, 4)
+        from PIL import Image
+        grey = [np.stack([np.asarray(Image.open(m[key]).convert("L")) for key in MASKS]) for m in mask_files]       # [3,S,S] uint8 each
+        out = []
+        if dev_idx is not None and self.post_device:
+            from .ucb_post_tsm_gpu import UcbPostTsmDevice, raise_for_status
+            if self._ucb_dev is None:
+                self._ucb_dev = UcbPostTsmDevice(dev_idx)
+            even, odd = slice(0, 2 * k, 2), slice(1, 2 * k, 2)
+            im_d, gt_d = im.to(dev), gt.to(dev)
+            rows = torch.cat([im_d[even], gt_d[even], con[even].float(), con[odd].float(), dif[even].float()], dim=3).contiguous()
+            masks = torch.from_numpy(np.stack(grey)).to(dev)
+            losses_d, stats_d, strips, figs_d, status = self._ucb_dev.run(rows, masks, torch.from_numpy(boxes).to(dev), want_figs=self.return_figs)
+            raise_for_status(status.cpu().numpy(), list(save_names) if save_names is not None else None)
+            if save_names is not None:
+                files = self.log.encode_strips(strips).cpu().numpy()
+                for fu in self.log.save_files(files, list(save_names)):
+                    fu.result()
+            lh, sh = losses_d.cpu().numpy(), stats_d.cpu().numpy()
+            figs_h = figs_d.cpu().numpy() if figs_d is not None else None
+            for j in range(k):
+                figs = [torch.from_numpy(figs_h[j, f:f + 1]) for f in range(8)] if figs_h is not None else None
+                out.append(({"ssim": float(lh[j, 0]), "psnr": float(lh[j, 1])}, figs, float(sh[j, 0]), float(sh[j, 1])))
+            return out
+        con_h, dif_h, im_h, gt_h = (t.detach().float().cpu().numpy() for t in (con, dif, im, gt))
+        for j in range(k):
+            m = {key: grey[j][i][:, :, None].astype(np.float64) / 255.0 for i, key in enumerate(MASKS)}
+            losses, figs, frac, mean = ucb_postprocess_tsm(im_h[2 * j], gt_h[2 * j], con_h[2 * j], con_h[2 * j + 1], dif_h[2 * j], boxes[j], m)
+            figs = [torch.from_numpy(f) for f in figs]
+            if save_names is not None:
+                self.log.save_img(figs, save_names[j])
+            out.append((losses, figs if self.return_figs else None, frac, mean))
+        return out
+
+    def test_step(self, img, box, curr_mask, curr_mask_no_hair, curr_mouth_mask, curr_nose_mask, *other_masks, training: bool = False):
+        """train_with_TSM.py:418-618 for one element [1,2,S,S,16] with the masks as arrays ([S,S,3] or [S,S,1] in [0, 1], as
+        cv2.imread(...)/255.0 gives them), post-processing on the host (ucb_post_tsm).  The mouth and the other masks the reference takes
+        are accepted and not read (it never reads them).  -> ({'ssim','psnr'}, figs[8] as [1,S,S,3] tensors, frac_nose_in_shadow,
+        mean_intensity)."""
+        from .ucb_post_tsm import ucb_postprocess_tsm
+        im, gt, uv, reg, face = self._groups([img], 2, self.SPLIT_UCB)
+        dev_idx = self._device()
+        dev = "cuda:%d" % dev_idx if dev_idx is not None else "cpu"
+        _, con, _, dif = self.gen(im.contiguous().to(dev), uv.contiguous().to(dev), reg.contiguous().to(dev), frame=2, share=True,
+                                  chuck=4, training=training)
+        con_h, dif_h = con.detach().float().cpu().numpy(), dif.detach().float().cpu().numpy()
+        m = {"face_hair": np.asarray(curr_mask), "face": np.asarray(curr_mask_no_hair), "nose": np.asarray(curr_nose_mask)}
+        losses, figs, frac, mean = ucb_postprocess_tsm(im[0].numpy(), gt[0].numpy(), con_h[0], con_h[1], dif_h[0],
+                                                      np.asarray(box, np.float32).reshape(-1)[:4], m)
+        return losses, [torch.from_numpy(f) for f in figs], frac, mean
+
+    def test(self, dataset_val, batch: int = 16, mask_files=None, mat_path: str = "frac_in_nose.mat"):
+        """train_with_TSM.py:369-416 + test_step :418-618 with ``batch`` elements (2 * batch rows) per forward.  ``dataset_val``:
+        Dataset(dset='ucb_tsm', ucb=True).  Masks: the sorted listing of the with-hair folder under Config.UCB_MASK_ROOT, the same file
+        name in the face and nose folders (FSRNet._ucb_masks), or ``mask_files``.  Strips of the eight figures go to <CHECKPOINT_DIR>/test/
+        under FSRNet.test's names.  Writes ``mat_path`` (scipy.io.savemat) with ``frac_in_nose`` and ``mean_intensity``, each of length
+        max(100, n) with zeros past n: the reference's fixed 100 (:384-385) would raise an IndexError past 100 items.
+        -> [(name, {'ssim','psnr'}, frac_nose_in_shadow, mean_intensity, figs[8] | None)] in list order (losses also in ``all_losses``)."""
+        from .dist import rank_world
+        if rank_world(None)[1] > 1:
+            raise NotImplementedError("FSRNetTSM.test runs in one process: data-parallel TSM loops are not provided")
+        if batch < 1:
+            raise ValueError("batch must be >= 1 element per forward")
+        if getattr(self.gen, "_handle", True) is None and self.gen.restore(self.config.CHECKPOINT_DIR) == 0 and self.gen._handle is None:
+            raise RuntimeError("no generator weights: checkpoint data shard missing under %s" % self.config.CHECKPOINT_DIR)
+        names = list(dataset_val.name_list)
+        masks = list(mask_files) if mask_files is not None else FSRNet._ucb_masks(self)
+        if len(masks) < len(names):
+            raise ValueError("%d UCB items but only %d mask files" % (len(names), len(masks)))
+        start = time.time()
+        results = []
+        group: List[Tuple[int, str, object, object]] = []
+
+        def flush():
+            if not group:
+                return
+            outs = self.test_steps([g[2] for g in group], [g[3] for g in group], [masks[g[0]] for g in group], save_names=[g[1] for g in group])
+            for (step, name, _, _), (losses, figs, frac, mean) in zip(group, outs):
+                self.log.display(losses, 0, step, False, len(names))
+                results.append((name, losses, frac, mean, figs))
+            group.clear()
+        try:
+            for step, img_name in enumerate(names):
+                element = next(dataset_val.feed)
+                group.append((step, _name(img_name), element[0], element[1]))
+                if len(group) >= batch:
+                    flush()
+            flush()
+        finally:
+            self.log.flush()
+        n = len(results)
+        frac_arr, mean_arr = np.zeros(max(100, n)), np.zeros(max(100, n))
+        for i, r in enumerate(results):
+            frac_arr[i], mean_arr[i] = r[2], r[3]
+        import scipy.io
+        scipy.io.savemat(mat_path, {"frac_in_nose": frac_arr, "mean_intensity": mean_arr})
+        self.all_losses = [(r[0], r[1]) for r in results]
+        self.timings = {"total_s": time.time() - start, "items": n}
+        print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
+        return results
 
     def testsfw_video(self, dataset_val, batch: int = 1):
         return self._loop(dataset_val, self.test_steps_sfw_video, batch)

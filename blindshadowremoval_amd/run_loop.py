@@ -14,6 +14,9 @@ Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random
 `--model rgb` runs the paper's single-stage RGB baseline instead (train_RGB_test.py's `main`: `FSRNetRGB.test`, `--loop ucb`, fp32 only).
 `--loop sfw` / `--loop sfw_video` run the GSC model's SFW evaluation (`FSRNet.testsfw` over Dataset(dset='sfw_gsc') /
 `FSRNet.testsfw_video` over Dataset(dset='sfw_video'): --data globs SFW video folders), in one process only.
+`--model tsm` runs the temporal-sharing model (train_with_TSM.py): `--loop ucb` (`FSRNetTSM.test` over Dataset(dset='ucb_tsm'), which
+also writes <checkpoint-dir>/frac_in_nose.mat), `--loop sfw` / `--loop sfw_video` (`FSRNetTSM.testsfw` / `testsfw_video` over
+Dataset(dset='sfw' | 'sfw_video')), in one process only.
 """
 from __future__ import annotations
 
@@ -26,7 +29,9 @@ import time
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--model", choices=("gsc", "rgb"), default="gsc", help="gsc = FSRNet (train_test_GSC.py), rgb = FSRNetRGB (train_RGB_test.py: --loop ucb, --dtype f32 only)")
+    ap.add_argument("--model", choices=("gsc", "rgb", "tsm"), default="gsc",
+                    help="gsc = FSRNet (train_test_GSC.py), rgb = FSRNetRGB (train_RGB_test.py: --loop ucb, --dtype f32 only), "
+                         "tsm = FSRNetTSM (train_with_TSM.py: --loop ucb | sfw | sfw_video, one process)")
     ap.add_argument("--loop", choices=("ffhq", "ucb", "sfw", "sfw_video"), required=True,
                     help="ffhq = FSRNet.testFFHQ, ucb = FSRNet.test (post-processing + SSIM / PSNR), sfw = FSRNet.testsfw (SSIM / PSNR / AUC), "
                          "sfw_video = FSRNet.testsfw_video")
@@ -47,8 +52,13 @@ def main(argv=None) -> int:
         sys.stderr.write("run_loop: --model rgb runs train_RGB_test.py's test loop only: --loop ucb --dtype f32 (it has no testFFHQ and no 16-bit path)\n")
         return 2
     sfw = args.loop in ("sfw", "sfw_video")
-    if sfw and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("BSR_LOOP_FORCE_DIST") == "1"):
-        sys.stderr.write("run_loop: --loop %s runs in one process (data-parallel SFW loops are not provided): launch it without a launcher\n" % args.loop)
+    tsm = args.model == "tsm"
+    if tsm and args.loop == "ffhq":
+        sys.stderr.write("run_loop: --model tsm runs train_with_TSM.py's loops: --loop ucb | sfw | sfw_video (it has no testFFHQ)\n")
+        return 2
+    if (sfw or tsm) and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("BSR_LOOP_FORCE_DIST") == "1"):
+        sys.stderr.write("run_loop: %s runs in one process (data-parallel %s loops are not provided): launch it without a launcher\n"
+                         % ("--model tsm" if tsm else "--loop " + args.loop, "TSM" if tsm else "SFW"))
         return 2
 
     # Before ANYTHING initialises the HIP / HSA runtime (torch.cuda.is_available() below already does): the runtime reads this at
@@ -82,7 +92,7 @@ def main(argv=None) -> int:
             dist.init_process_group("gloo", rank=rank, world_size=world)
 
     from .dataset import Dataset, cpu_share
-    from .fsrnet import Config, FSRNet, FSRNetRGB
+    from .fsrnet import Config, FSRNet, FSRNetRGB, FSRNetTSM
     from .weights import init_weights
     cfg = Config(local_rank)
     cfg.DATA_DIR_TEST = list(args.data)
@@ -94,12 +104,16 @@ def main(argv=None) -> int:
     # worker counts: sweeps on the 16-CPU GPU box (loop_bench.py).  With post-processing and PNG encoding on the device (the default) the
     # loader's workers — PNG decode, Delaunay meshes, the UCB masks — are the only host stage: 3/4 (UCB) / 5/8 (FFHQ) of this rank's share of the CPUs (the loop's own thread and its file writers need the rest)
     ds_kw = dict(workers=max(1, (ncpu * 5 // 8 if ucb else ncpu * 7 // 8) if args.host_post else max(1, ncpu * 3 // 4 if ucb else ncpu * 5 // 8)))
-    if sfw:
+    if tsm:
+        ds = Dataset(cfg, "test", dset={"ucb": "ucb_tsm", "sfw": "sfw", "sfw_video": "sfw_video"}[args.loop], ucb=ucb, workers=max(1, ncpu * 7 // 8))
+    elif sfw:
         ds = Dataset(cfg, "test", dset="sfw_gsc" if args.loop == "sfw" else "sfw_video", workers=max(1, ncpu * 7 // 8))
     else:
         if not args.host_prep:
             ds_kw.update(device_prep=local_rank, device_batch=args.batch)
         ds = Dataset(cfg, "test", ucb=ucb, **ds_kw)
+    if tsm:
+        return _run_tsm(args, cfg, ds)
     if args.model == "rgb":
         fsr = FSRNetRGB(cfg, weights=init_weights(args.random_weights, variant="rgb") if args.random_weights is not None else None)
     else:
@@ -140,6 +154,33 @@ def main(argv=None) -> int:
             import torch.distributed as dist
             dist.destroy_process_group()
     return rc
+
+
+def _run_tsm(args, cfg, ds) -> int:
+    """--model tsm: FSRNetTSM's loops in this process (FSRNetTSM has no worker pools to warm)."""
+    import torch
+    from .fsrnet import FSRNetTSM
+    from .weights import init_weights
+    fsr = FSRNetTSM(cfg, weights=init_weights(args.random_weights, variant="tsm") if args.random_weights is not None else None, dtype=args.dtype)
+    fsr.post_device = not args.host_post
+    fsr.return_figs = False
+    try:
+        ds.warm()
+        t0 = time.perf_counter()
+        if args.loop == "ucb":
+            res = fsr.test(ds, batch=args.batch, mat_path=os.path.join(cfg.CHECKPOINT_DIR, "frac_in_nose.mat"))
+        else:
+            res = (fsr.testsfw if args.loop == "sfw" else fsr.testsfw_video)(ds, batch=args.batch)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        means = {k: s / max(c, 1) for k, (s, c) in fsr.log.losses.items()}
+        print("\n" + json.dumps({"loop": {"ucb": "FSRNetTSM.test", "sfw": "FSRNetTSM.testsfw", "sfw_video": "FSRNetTSM.testsfw_video"}[args.loop],
+                                 "items": len(res), "ranks": 1, "images_per_sec": round(len(res) / dt, 2), "seconds": round(dt, 3), "batch": args.batch,
+                                 "dtype": args.dtype, "post": "host" if args.host_post else "device", "means": means}))
+    finally:
+        ds.close()
+        fsr.log.close()
+    return 0
 
 
 if __name__ == "__main__":

@@ -215,6 +215,21 @@ size_t bsr_sfw_score_scratch_bytes(int B, int S);
 int bsr_sfw_score(int device, const float* rows3, int B, int S, float* losses, double* auc, float* pred, float* label, int* status,
                   void* scratch, void* stream);
 
+/* The per-item post-processing of the temporal-sharing model's FSRNet.test_step on the device (added in ABI 8: additive, no existing
+ * signature changed): replaces /root/reference/train_with_TSM.py:441-614 after the generator call for a batch of B items — the flat
+ * threshold on dif * face_hair, the 4-connected components and their size / hair filter, the nose rule, the composites of the image and
+ * of its mirror, clip -> resize -> pad of the output, SSIM / PSNR, the eight figures as one strip.
+ * rows: [B,S,S,13] float32 = input 3 | ground truth 3 | con 3 of the image | con 3 of the mirror | dif 1 of the image; masks: [B,3,S,S]
+ * uint8 grey levels of the with-hair face, face and nose masks; boxes: [B,4] float32.  All device pointers.  losses: [B,2] float32 =
+ * ssim, psnr; nose_stats: [B,2] float64 = frac_nose_in_shadow, mean_intensity (NaN when the kept set is empty, NaN both for a failed
+ * item); strips: [B,S,8*S,3] uint8 RGB; figs: optional [B,8,S,S,3] float32 (may be NULL); status: [B] int32 — 0 = done, 1 = the nose
+ * mask has no pixel of level 255, 2 = the crop box is empty or does not fit S (black strip, NaN losses).
+ * scratch: bsr_ucb_post_tsm_scratch_bytes(B, S) bytes, 256-byte aligned (0 = unsupported S).  S in {32, 64, 128, 256}.  Every decision
+ * and figure is bit-identical to blindshadowremoval_amd/ucb_post_tsm.py, the host statement. */
+size_t bsr_ucb_post_tsm_scratch_bytes(int B, int S);
+int bsr_ucb_post_tsm(int device, const float* rows, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
+                     double* nose_stats, unsigned char* strips, float* figs, int* status, void* scratch, void* stream);
+
 /* Test hook: the fused NonLocalBlock attention kernel alone (/root/reference/model.py:51-53).
  * qkv [B,tokens,384] (theta | phi | g, 128 channels each) -> y [B,tokens,128]; tokens % 128 == 0. */
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream);
