@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -59,6 +60,22 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// ---- the post-processing entry points (bsr_ucb_post*, bsr_sfw_score): one S check, one set of argument checks ----
+bool post_size_ok(int B, int S) { return B > 0 && (S == 32 || S == 64 || S == 128 || S == 256); }
+
+// `name`'s checks of its required pointers, B / S and the scratch alignment, all before the device switch; then `launch` (which returns
+// a BSR_* code) on `device`.
+template <class Launch>
+int run_post(const char* name, std::initializer_list<const void*> required, int B, int S, const void* scratch, int device, Launch launch) {
+  for (const void* p : required)
+    if (p == nullptr) return fail(BSR_ERR_ARG, std::string(name) + ": null argument");
+  if (!post_size_ok(B, S)) return fail(BSR_ERR_ARG, std::string(name) + ": B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, std::string(name) + ": scratch must be 256-byte aligned");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  return launch();
+}
 
 // ---- packed-weight blob (written by blindshadowremoval_amd/pack.py) ----
 constexpr uint32_t kBlobMagic = 0x57525342u;  // "BSRW"
@@ -1131,77 +1148,44 @@ int bsr_png_encode_figs(int device, int n_figs, const float* const* figs, const 
   return BSR_OK;
 }
 
-size_t bsr_ucb_post_scratch_bytes(int B, int S) {
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
-  return (size_t)B * bsr::ucb_item_scratch_bytes(S);
-}
+size_t bsr_ucb_post_scratch_bytes(int B, int S) { return post_size_ok(B, S) ? (size_t)B * bsr::ucb_item_scratch_bytes(S) : 0; }
 
 int bsr_ucb_post(int device, const float* rows10, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
                  unsigned char* strips, float* figs, int* status, void* scratch, void* stream) {
-  if (rows10 == nullptr || masks == nullptr || boxes == nullptr || losses == nullptr || strips == nullptr || status == nullptr || scratch == nullptr)
-    return fail(BSR_ERR_ARG, "bsr_ucb_post: null argument");
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
-    return fail(BSR_ERR_ARG, "bsr_ucb_post: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_ucb_post: scratch must be 256-byte aligned");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_ucb_post(rows10, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_post("bsr_ucb_post", {rows10, masks, boxes, losses, strips, status, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_ucb_post(rows10, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
 }
 
-size_t bsr_ucb_post_rgb_scratch_bytes(int B, int S) {
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
-  return (size_t)B * bsr::ucb_rgb_item_scratch_bytes(S);
-}
+size_t bsr_ucb_post_rgb_scratch_bytes(int B, int S) { return post_size_ok(B, S) ? (size_t)B * bsr::ucb_rgb_item_scratch_bytes(S) : 0; }
 
 int bsr_ucb_post_rgb(int device, const float* rows9, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
                      unsigned char* strips, float* figs, int* status, void* scratch, void* stream) {
-  if (rows9 == nullptr || masks == nullptr || boxes == nullptr || losses == nullptr || strips == nullptr || status == nullptr || scratch == nullptr)
-    return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: null argument");
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
-    return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_ucb_post_rgb: scratch must be 256-byte aligned");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_ucb_post_rgb(rows9, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_post("bsr_ucb_post_rgb", {rows9, masks, boxes, losses, strips, status, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_ucb_post_rgb(rows9, masks, boxes, B, S, losses, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
 }
 
-size_t bsr_ucb_post_tsm_scratch_bytes(int B, int S) {
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
-  return (size_t)B * bsr::ucb_tsm_item_scratch_bytes(S);
-}
+size_t bsr_ucb_post_tsm_scratch_bytes(int B, int S) { return post_size_ok(B, S) ? (size_t)B * bsr::ucb_tsm_item_scratch_bytes(S) : 0; }
 
 int bsr_ucb_post_tsm(int device, const float* rows, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
                      double* nose_stats, unsigned char* strips, float* figs, int* status, void* scratch, void* stream) {
-  if (rows == nullptr || masks == nullptr || boxes == nullptr || losses == nullptr || nose_stats == nullptr || strips == nullptr ||
-      status == nullptr || scratch == nullptr)
-    return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: null argument");
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
-    return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_ucb_post_tsm: scratch must be 256-byte aligned");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_ucb_post_tsm(rows, masks, boxes, B, S, losses, nose_stats, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_post("bsr_ucb_post_tsm", {rows, masks, boxes, losses, nose_stats, strips, status, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_ucb_post_tsm(rows, masks, boxes, B, S, losses, nose_stats, strips, figs, status, scratch, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
 }
 
-size_t bsr_sfw_score_scratch_bytes(int B, int S) {
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256)) return 0;
-  return (size_t)B * bsr::sfw_item_scratch_bytes(S);
-}
+size_t bsr_sfw_score_scratch_bytes(int B, int S) { return post_size_ok(B, S) ? (size_t)B * bsr::sfw_item_scratch_bytes(S) : 0; }
 
 int bsr_sfw_score(int device, const float* rows3, int B, int S, float* losses, double* auc, float* pred, float* label, int* status,
                   void* scratch, void* stream) {
-  if (rows3 == nullptr || losses == nullptr || auc == nullptr || pred == nullptr || label == nullptr || status == nullptr || scratch == nullptr)
-    return fail(BSR_ERR_ARG, "bsr_sfw_score: null argument");
-  if (B <= 0 || (S != 32 && S != 64 && S != 128 && S != 256))
-    return fail(BSR_ERR_ARG, "bsr_sfw_score: B must be positive and S one of 32, 64, 128, 256 (reference: 256)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_sfw_score: scratch must be 256-byte aligned");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_sfw_score(rows3, B, S, losses, auc, pred, label, status, scratch, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_post("bsr_sfw_score", {rows3, losses, auc, pred, label, status, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_sfw_score(rows3, B, S, losses, auc, pred, label, status, scratch, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
 }
 
 int bsr_clock_trace(int device, unsigned long long* out, int samples, int spin, const int* stop, int* taken, void* stream) {

@@ -190,6 +190,12 @@ class Logging(object):
             self._pending = [f for f in self._pending if not f.done()]
         return futs
 
+    def write_files_now(self, files: torch.Tensor, names: Sequence[str]) -> None:
+        """save_files for PNG files built on the device ([B, file_bytes], e.g. files_on_device): copy them to the host, write them and
+        wait for the writes."""
+        for fu in self.save_files(files.cpu().numpy(), list(names)):
+            fu.result()
+
     def _png_path(self, fname: str) -> str:
         parts = fname.replace('\\', '/').split('/')
         stem = (parts[-2] + '_' if len(parts) > 1 else '') + parts[-1].split('.')[0]
@@ -431,6 +437,60 @@ def _name(x) -> str:
     return str(x)
 
 
+def _rows(element, s: int, n: int = -1) -> torch.Tensor:
+    """A dataset element (array or tensor of whole S x S rows, e.g. [1,R,S,S,C]) -> its rows as float32 [R,S,S,C]; `n`: R, when known."""
+    t = torch.as_tensor(np.asarray(element) if not isinstance(element, torch.Tensor) else element, dtype=torch.float32)
+    return t.reshape(n, s, s, t.shape[-1])
+
+
+def _check_batch(batch: int) -> None:
+    if batch < 1:
+        raise ValueError("batch must be >= 1 element per forward")
+
+
+def _ensure_weights(gen, checkpoint_dir: str, banner: bool = False) -> int:
+    """A generator without weights restores the latest checkpoint under `checkpoint_dir`: -> its epoch, or -1 when the weights were
+    supplied (a CPU stand-in without a `_handle` counts as such).  `banner`: print the reference's restore banner.  RuntimeError when
+    there are still no weights."""
+    last_epoch = gen.restore(checkpoint_dir) if getattr(gen, "_handle", True) is None else -1
+    if banner:
+        print('**********************************************************')
+        print('Restore from Epoch ' + (str(last_epoch) if last_epoch >= 0 else '(weights supplied)'))
+        print('**********************************************************')
+    if getattr(gen, "_handle", True) is None:
+        raise RuntimeError("no generator weights: checkpoint data shard missing under %s" % checkpoint_dir)
+    return last_epoch
+
+
+def _ucb_mask_files(config) -> List[Dict[str, str]]:
+    """Per-item UCB mask file paths in the reference's order: the sorted listing of the with-hair folder under Config.UCB_MASK_ROOT, the
+    same file name in the other six (train_test_GSC.py:372,386-392)."""
+    from .ucb_post import MASK_DIRS
+    root = config.UCB_MASK_ROOT
+    first = os.path.join(root, MASK_DIRS["face_hair"])
+    if not os.path.isdir(first):
+        raise FileNotFoundError("FSRNet.test needs the UCB mask folders under Config.UCB_MASK_ROOT (%s is missing)" % first)
+    return [{k: os.path.join(root, d, f) for k, d in MASK_DIRS.items()} for f in sorted(os.listdir(first))]
+
+
+def _grouped_loop(log: Logging, names: Sequence, feed, batch: int, run_group) -> None:
+    """The evaluation loops' walk over `names`: one element of `feed` per name, `batch` of them per call of run_group([(step, name,
+    element), ...]) — which reports its items (log.display) — then log.flush(), also on an exception, and the reference's epoch line."""
+    start = time.time()
+    group: List[Tuple[int, str, object]] = []
+    try:
+        for step, img_name in enumerate(names):
+            group.append((step, _name(img_name), next(feed)))
+            if len(group) >= batch:
+                run_group(group)
+                group = []
+        if group:
+            run_group(group)
+    finally:
+        log.flush()
+    print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
+
+
 class FSRNet(object):
     def __init__(self, config: Config, weights: Optional[Dict[str, np.ndarray]] = None, dtype: str = "f32", group=None, gen=None):
         """``group``: a torch.distributed process group; with one (or with the default group initialised — `torchrun`, one process per
@@ -565,23 +625,12 @@ class FSRNet(object):
 
     # -- checkpoint -------------------------------------------------------------------------
     def _restore(self) -> int:
-        last_epoch = self.gen.restore(self.config.CHECKPOINT_DIR) if self.gen._handle is None else -1
-        if not self.log.quiet:
-            print('**********************************************************')
-            print('Restore from Epoch ' + (str(last_epoch) if last_epoch >= 0 else '(weights supplied)'))
-            print('**********************************************************')
-        if self.gen._handle is None:
-            raise RuntimeError("no generator weights: checkpoint data shard missing under %s" % self.config.CHECKPOINT_DIR)
-        return last_epoch
+        return _ensure_weights(self.gen, self.config.CHECKPOINT_DIR, banner=not self.log.quiet)
 
     # -- steps ------------------------------------------------------------------------------
     def _split(self, img: torch.Tensor, rows: Optional[int]) -> Tuple[torch.Tensor, ...]:
-        s = self.config.IMG_SIZE
-        img = torch.as_tensor(np.asarray(img) if not isinstance(img, torch.Tensor) else img, dtype=torch.float32)
-        img = img.reshape(-1, s, s, img.shape[-1])                         # [10,256,256,16] (train_test_GSC.py:866)
-        if rows is not None:
-            img = img[:rows]
-        return torch.split(img, list(SPLIT_FFHQ), dim=3)
+        """img, gt, uv, reg, face of the element's first `rows` rows (None: all) — [10,256,256,16] (train_test_GSC.py:866)."""
+        return torch.split(_rows(img, self.config.IMG_SIZE)[:rows], list(SPLIT_FFHQ), dim=3)
 
     def test_step_FFHQ(self, img, box=None, training: bool = False, all_rows: bool = False):
         """train_test_GSC.py:863-890 for one dataset element."""
@@ -601,14 +650,7 @@ class FSRNet(object):
 
     # -- loops ------------------------------------------------------------------------------
     def _ucb_masks(self) -> List[Dict[str, str]]:
-        """Per-item mask file paths in the reference's order: the sorted listing of the with-hair folder, the same file name in
-        the other six (train_test_GSC.py:372,386-392)."""
-        from .ucb_post import MASK_DIRS
-        root = self.config.UCB_MASK_ROOT
-        first = os.path.join(root, MASK_DIRS["face_hair"])
-        if not os.path.isdir(first):
-            raise FileNotFoundError("FSRNet.test needs the UCB mask folders under Config.UCB_MASK_ROOT (%s is missing)" % first)
-        return [{k: os.path.join(root, d, f) for k, d in MASK_DIRS.items()} for f in sorted(os.listdir(first))]
+        return _ucb_mask_files(self.config)
 
     @staticmethod
     def _read_masks(paths: Dict[str, str]) -> Dict[str, np.ndarray]:
@@ -1032,9 +1074,7 @@ class FSRNet(object):
         return base
 
     def _split_row0(self, img) -> torch.Tensor:
-        s = self.config.IMG_SIZE
-        t = torch.as_tensor(np.asarray(img) if not isinstance(img, torch.Tensor) else img, dtype=torch.float32)
-        return t.reshape(-1, s, s, t.shape[-1])[:1]
+        return _rows(img, self.config.IMG_SIZE)[:1]
 
     def testFFHQ(self, dataset_val, batch: int = 16):
         """train_test_GSC.py:840-860.  ``dataset_val`` needs ``.feed`` (iterator of (img[1,10,256,256,16], box, name))
@@ -1051,22 +1091,6 @@ class FSRNet(object):
         return self._loop(dataset_val, batch, ucb=True, postprocess=postprocess, mask_files=mask_files)
 
     # -- SFW evaluation (train_test_GSC.py:750-838, 893-932) --------------------------------
-    def _sfw_rows(self, elements, split, all_rows: bool) -> Tuple[torch.Tensor, List[int]]:
-        """k elements [1,R,S,S,C] (any R) -> (their row 0s — or all their rows — stacked [M,S,S,C], the index of each element's row 0)."""
-        s = self.config.IMG_SIZE
-        ts, first, n = [], [], 0
-        for e in elements:
-            t = torch.as_tensor(np.asarray(e) if not isinstance(e, torch.Tensor) else e, dtype=torch.float32)
-            t = t.reshape(-1, s, s, t.shape[-1])
-            if t.shape[-1] != sum(split):
-                raise ValueError("an SFW element has %d channels per row here (%s), got %d" % (sum(split), split, t.shape[-1]))
-            if not all_rows:
-                t = t[:1]
-            first.append(n)
-            n += t.shape[0]
-            ts.append(t)
-        return torch.cat(ts, dim=0), first
-
     def _sfw_steps(self, elements, video: bool, all_rows: bool = False, save_names: Optional[Sequence[str]] = None):
         """test_step_sfw (video=False) / test_step_sfw_video for k elements in ONE forward.  The GSC generator couples no rows and every
         output of the step reads row 0, so by default only row 0 of each element is forwarded; ``all_rows=True`` forwards every row, as
@@ -1075,7 +1099,14 @@ class FSRNet(object):
         -> [(losses, figs | None)] per element; figs = row 0's [img, con, mask_pred * 2(, label)] as [1,S,S,C] tensors."""
         from .sfw_post import SPLIT_SFW, SPLIT_VIDEO
         split = SPLIT_VIDEO if video else SPLIT_SFW
-        rows, first = self._sfw_rows(elements, split, all_rows)
+        ts, first = [], []                         # each element's row 0 (or all its rows), the index of its row 0 in their stack
+        for e in elements:
+            t = _rows(e, self.config.IMG_SIZE)
+            if t.shape[-1] != sum(split):
+                raise ValueError("an SFW element has %d channels per row here (%s), got %d" % (sum(split), split, t.shape[-1]))
+            first.append(sum(u.shape[0] for u in ts))
+            ts.append(t if all_rows else t[:1])
+        rows = torch.cat(ts, dim=0)
         dev = "cuda:%d" % self.gen._device if getattr(self.gen, "_device", None) is not None else "cpu"
         parts = torch.split(rows.to(dev), list(split), dim=3)
         im, uv, face = parts[0], parts[1 if video else 3], parts[-1]
@@ -1115,9 +1146,7 @@ class FSRNet(object):
             losses_h = [{"ssim": float(lh[j, 0]), "psnr": float(lh[j, 1]), "auc": float(ah[j])} for j in range(k)]
         if save_names is not None:
             if self.log.gpu_png:
-                files = self.log.files_on_device(shown).cpu().numpy()
-                for fu in self.log.save_files(files, list(save_names)):
-                    fu.result()
+                self.log.write_files_now(self.log.files_on_device(shown), save_names)
             else:
                 plain = [im0, torch.clamp(con0, 0, 1), dif0 * face0 * 2] + ([] if video else [label])
                 for j in range(k):
@@ -1145,34 +1174,20 @@ class FSRNet(object):
         from .dist import rank_world
         if rank_world(self.group)[1] > 1:
             raise NotImplementedError("FSRNet.testsfw / testsfw_video run in one process: data-parallel SFW loops are not provided")
-        if batch < 1:
-            raise ValueError("batch must be >= 1 element per forward")
+        _check_batch(batch)
         names = list(dataset_val.name_list)
         self._restore()
         start = time.time()
         results: List[Tuple[str, Dict[str, float]]] = []
-        group: List[Tuple[int, str, object]] = []
 
-        def flush():
-            if not group:
-                return
-            out = self._sfw_steps([g[2] for g in group], video, all_rows, save_names=[g[1] for g in group])
+        def run_group(group):
+            out = self._sfw_steps([g[2][0] for g in group], video, all_rows, save_names=[g[1] for g in group])
             for (step, name, _), (losses, _) in zip(group, out):
                 self.log.display(losses, 0, step, False, len(names))
                 results.append((name, losses))
-            group.clear()
-        try:
-            for step, img_name in enumerate(names):
-                element = next(dataset_val.feed)
-                group.append((step, _name(img_name), element[0]))
-                if len(group) >= batch:
-                    flush()
-            flush()
-        finally:
-            self.log.flush()
+        _grouped_loop(self.log, names, dataset_val.feed, batch, run_group)
         self.all_losses = list(results)
         self.timings = {"total_s": time.time() - start, "items": len(results)}
-        print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
         return results
 
     def testsfw(self, dataset_val, batch: int = 16, all_rows: bool = False):
@@ -1332,16 +1347,9 @@ class FSRNetTSM(object):
         self.timings: Dict[str, float] = {}
         self._ucb_dev = None
 
-    def _prep(self, img, n: int, split):
-        s = self.config.IMG_SIZE
-        t = torch.as_tensor(np.asarray(img) if not isinstance(img, torch.Tensor) else img, dtype=torch.float32)
-        return torch.split(t.reshape(n, s, s, t.shape[-1]), list(split), dim=3)
-
     def _groups(self, elements, n: int, split):
         """Stack k elements of n coupled frames each into one [k*n, S, S, C] batch, split by channels."""
-        s = self.config.IMG_SIZE
-        ts = [torch.as_tensor(np.asarray(e) if not isinstance(e, torch.Tensor) else e, dtype=torch.float32).reshape(n, s, s, -1) for e in elements]
-        return torch.split(torch.cat(ts, dim=0), list(split), dim=3)
+        return torch.split(torch.cat([_rows(e, self.config.IMG_SIZE, n) for e in elements], dim=0), list(split), dim=3)
 
     def test_steps_sfw(self, elements, training: bool = False):
         """train_with_TSM.py:668-707 for k elements in ONE forward: each element = [2,256,256,17] (image + mirror) is its own
@@ -1391,33 +1399,17 @@ class FSRNetTSM(object):
     def _loop(self, dataset_val, steps_fn, batch: int = 1):
         """The reference's loop (train_with_TSM.py:619-666, 709-718) with `batch` ELEMENTS per forward (1 = the reference's own
         element-by-element form; config[4]'s "batch = 64 frames" is 32 SFW pairs or 6 ten-frame video groups)."""
-        if self.gen._handle is None and self.gen.restore(self.config.CHECKPOINT_DIR) == 0 and self.gen._handle is None:
-            raise RuntimeError("no generator weights: checkpoint data shard missing under %s" % self.config.CHECKPOINT_DIR)
-        if batch < 1:
-            raise ValueError("batch must be >= 1 element per forward")
-        start = time.time()
+        _ensure_weights(self.gen, self.config.CHECKPOINT_DIR)
+        _check_batch(batch)
         names = list(dataset_val.name_list)
         results = []
-        group: List[Tuple[int, str, object]] = []
 
-        def flush():
-            if not group:
-                return
-            for (step, name, _), (losses, figs) in zip(group, steps_fn([g[2] for g in group], training=False)):
+        def run_group(group):
+            for (step, name, _), (losses, figs) in zip(group, steps_fn([g[2][0] for g in group], training=False)):
                 self.log.display(losses, 0, step, False, len(names))
                 self.log.save_img(figs, name)
                 results.append((name, losses, figs))
-            group.clear()
-        try:
-            for step, img_name in enumerate(names):
-                element = next(dataset_val.feed)
-                group.append((step, _name(img_name), element[0]))
-                if len(group) >= batch:
-                    flush()
-            flush()
-        finally:
-            self.log.flush()
-        print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
+        _grouped_loop(self.log, names, dataset_val.feed, batch, run_group)
         return results
 
     def testsfw(self, dataset_val, batch: int = 1):
@@ -1460,9 +1452,7 @@ class FSRNetTSM(object):
             losses_d, stats_d, strips, figs_d, status = self._ucb_dev.run(rows, masks, torch.from_numpy(boxes).to(dev), want_figs=self.return_figs)
             raise_for_status(status.cpu().numpy(), list(save_names) if save_names is not None else None)
             if save_names is not None:
-                files = self.log.encode_strips(strips).cpu().numpy()
-                for fu in self.log.save_files(files, list(save_names)):
-                    fu.result()
+                self.log.write_files_now(self.log.encode_strips(strips), save_names)
             lh, sh = losses_d.cpu().numpy(), stats_d.cpu().numpy()
             figs_h = figs_d.cpu().numpy() if figs_d is not None else None
             for j in range(k):
@@ -1499,42 +1489,28 @@ class FSRNetTSM(object):
     def test(self, dataset_val, batch: int = 16, mask_files=None, mat_path: str = "frac_in_nose.mat"):
         """train_with_TSM.py:369-416 + test_step :418-618 with ``batch`` elements (2 * batch rows) per forward.  ``dataset_val``:
         Dataset(dset='ucb_tsm', ucb=True).  Masks: the sorted listing of the with-hair folder under Config.UCB_MASK_ROOT, the same file
-        name in the face and nose folders (FSRNet._ucb_masks), or ``mask_files``.  Strips of the eight figures go to <CHECKPOINT_DIR>/test/
+        name in the face and nose folders (_ucb_mask_files), or ``mask_files``.  Strips of the eight figures go to <CHECKPOINT_DIR>/test/
         under FSRNet.test's names.  Writes ``mat_path`` (scipy.io.savemat) with ``frac_in_nose`` and ``mean_intensity``, each of length
         max(100, n) with zeros past n: the reference's fixed 100 (:384-385) would raise an IndexError past 100 items.
         -> [(name, {'ssim','psnr'}, frac_nose_in_shadow, mean_intensity, figs[8] | None)] in list order (losses also in ``all_losses``)."""
         from .dist import rank_world
         if rank_world(None)[1] > 1:
             raise NotImplementedError("FSRNetTSM.test runs in one process: data-parallel TSM loops are not provided")
-        if batch < 1:
-            raise ValueError("batch must be >= 1 element per forward")
-        if getattr(self.gen, "_handle", True) is None and self.gen.restore(self.config.CHECKPOINT_DIR) == 0 and self.gen._handle is None:
-            raise RuntimeError("no generator weights: checkpoint data shard missing under %s" % self.config.CHECKPOINT_DIR)
+        _check_batch(batch)
+        _ensure_weights(self.gen, self.config.CHECKPOINT_DIR)
         names = list(dataset_val.name_list)
-        masks = list(mask_files) if mask_files is not None else FSRNet._ucb_masks(self)
+        masks = list(mask_files) if mask_files is not None else _ucb_mask_files(self.config)
         if len(masks) < len(names):
             raise ValueError("%d UCB items but only %d mask files" % (len(names), len(masks)))
         start = time.time()
         results = []
-        group: List[Tuple[int, str, object, object]] = []
 
-        def flush():
-            if not group:
-                return
-            outs = self.test_steps([g[2] for g in group], [g[3] for g in group], [masks[g[0]] for g in group], save_names=[g[1] for g in group])
-            for (step, name, _, _), (losses, figs, frac, mean) in zip(group, outs):
+        def run_group(group):
+            outs = self.test_steps([g[2][0] for g in group], [g[2][1] for g in group], [masks[g[0]] for g in group], save_names=[g[1] for g in group])
+            for (step, name, _), (losses, figs, frac, mean) in zip(group, outs):
                 self.log.display(losses, 0, step, False, len(names))
                 results.append((name, losses, frac, mean, figs))
-            group.clear()
-        try:
-            for step, img_name in enumerate(names):
-                element = next(dataset_val.feed)
-                group.append((step, _name(img_name), element[0], element[1]))
-                if len(group) >= batch:
-                    flush()
-            flush()
-        finally:
-            self.log.flush()
+        _grouped_loop(self.log, names, dataset_val.feed, batch, run_group)
         n = len(results)
         frac_arr, mean_arr = np.zeros(max(100, n)), np.zeros(max(100, n))
         for i, r in enumerate(results):
@@ -1543,7 +1519,6 @@ class FSRNetTSM(object):
         scipy.io.savemat(mat_path, {"frac_in_nose": frac_arr, "mean_intensity": mean_arr})
         self.all_losses = [(r[0], r[1]) for r in results]
         self.timings = {"total_s": time.time() - start, "items": n}
-        print('\n*****Time for epoch {} is {} sec*****'.format(1, int(time.time() - start)))
         return results
 
     def testsfw_video(self, dataset_val, batch: int = 1):

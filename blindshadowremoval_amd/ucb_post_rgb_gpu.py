@@ -3,50 +3,27 @@ binding of bsr_ucb_post_rgb (csrc/ucb_rgb_kernels.h).  blindshadowremoval_amd/uc
 every figure of the two is bit-identical (tests/test_ucb_post_rgb_gpu.py); this module has no CPU fallback."""
 from __future__ import annotations
 
-import ctypes
-from typing import Optional
-
 import torch
 
-from . import _lib
+from . import post_gpu
 from .ucb_post_gpu import raise_for_status  # noqa: F401  (re-exported: the same status codes as bsr_ucb_post)
 
 
-class UcbPostRgbDevice:
+class UcbPostRgbDevice(post_gpu.PostDevice):
     """Reusable runner for one device: keeps its scratch buffer between calls."""
-
-    def __init__(self, device: int):
-        self.device = int(device)
-        self._scratch: Optional[torch.Tensor] = None
+    SYMBOL = "bsr_ucb_post_rgb"
+    SIZE_TEXT = "bsr_ucb_post_rgb supports S in {32, 64, 128, 256} (reference: 256), got %(s)d"
 
     def run(self, rows9: torch.Tensor, masks: torch.Tensor, boxes: torch.Tensor, want_figs: bool = False):
         """rows9: [B,S,S,9] float32 (input 3 | gt 3 | con 3), masks: [B,S,S] uint8 grey levels of the with-hair face mask, boxes: [B,4]
         float32 — all on this device.  -> (losses [B,2] float32 = ssim | psnr, strips [B,S,3S,3] uint8, figs [B,3,S,S,3] float32 | None,
         status [B] int32), on the device, asynchronous on the current stream.  Check `status` (raise_for_status) once it is on the host."""
-        dev = torch.device("cuda", self.device)
-        for name, t, dt, nd in (("rows9", rows9, torch.float32, 4), ("masks", masks, torch.uint8, 3), ("boxes", boxes, torch.float32, 2)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd or t.device != dev:
-                raise TypeError("%s must be a %s tensor with %d dims on %s" % (name, dt, nd, dev))
-        rows9, masks, boxes = rows9.contiguous(), masks.contiguous(), boxes.contiguous()
+        rows9, masks, boxes = self.inputs(("rows9", rows9, torch.float32, 4), ("masks", masks, torch.uint8, 3), ("boxes", boxes, torch.float32, 2))
         b, s = rows9.shape[0], rows9.shape[1]
         if rows9.shape != (b, s, s, 9) or masks.shape != (b, s, s) or boxes.shape != (b, 4):
             raise ValueError("shapes: rows9 [B,S,S,9], masks [B,S,S], boxes [B,4]; got %s %s %s" % (tuple(rows9.shape), tuple(masks.shape), tuple(boxes.shape)))
-        lib = _lib.load()
-        need = int(lib.bsr_ucb_post_rgb_scratch_bytes(b, s))
-        if need == 0:
-            raise ValueError("bsr_ucb_post_rgb supports S in {32, 64, 128, 256} (reference: 256), got %d" % s)
-        if self._scratch is None or self._scratch.numel() < need + 256:
-            self._scratch = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-        base = self._scratch.data_ptr()
-        base += (-base) % 256
-        losses = torch.empty((b, 2), dtype=torch.float32, device=dev)
-        strips = torch.empty((b, s, 3 * s, 3), dtype=torch.uint8, device=dev)
-        figs = torch.empty((b, 3, s, s, 3), dtype=torch.float32, device=dev) if want_figs else None
-        status = torch.empty((b,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(self.device):
-            rc = lib.bsr_ucb_post_rgb(self.device, ctypes.c_void_p(rows9.data_ptr()), ctypes.c_void_p(masks.data_ptr()), ctypes.c_void_p(boxes.data_ptr()),
-                                      b, s, ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(strips.data_ptr()),
-                                      ctypes.c_void_p(figs.data_ptr()) if figs is not None else None, ctypes.c_void_p(status.data_ptr()),
-                                      ctypes.c_void_p(base), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "bsr_ucb_post_rgb")
+        scratch = self.scratch(b, s)
+        losses, strips, status = self.empty((b, 2), torch.float32), self.empty((b, s, 3 * s, 3), torch.uint8), self.empty((b,), torch.int32)
+        figs = self.empty((b, 3, s, s, 3), torch.float32) if want_figs else None
+        self.call(rows9, masks, boxes, b, s, losses, strips, figs, status, scratch)
         return losses, strips, figs, status
