@@ -31,6 +31,7 @@
 #include "ucb_rgb_kernels.h"
 #include "ucb_tsm_kernels.h"
 #include "sfw_kernels.h"
+#include "wino_conv2.h"
 
 namespace {
 
@@ -199,6 +200,7 @@ size_t plan_floats(const Variant& v, size_t B, size_t H, size_t W) {
 struct bsr_handle {
   int device = 0;
   float* d_blob = nullptr;
+  float* d_wino = nullptr;       // fp32 GSC / TSM handles: the Winograd weight streams of res0..5.conv2 (wino_conv2.h), derived from the blob's direct images at bsr_create
   std::unordered_map<std::string, LayerW> layers;
   Variant var = kGSC;
   int dtype = BSR_DTYPE_F32;     // BSR_DTYPE_F16 / BSR_DTYPE_F32X3: 16-bit matrix cores on the 3x3 / stride-2 / transposed 3x3 layers (igemm_h16.h), fp32 kernels elsewhere
@@ -225,6 +227,7 @@ struct bsr_handle {
   bool conv3_f16 = true;         // env BSR_CONV3_F16=0: the f16 mode's 3x3 / transposed 3x3 layers on igemm_h16_kernel<.., NSPLIT = 1> (the form small test shapes
                                  // and A/B measurements compare against; same operands, another summation order)
   bool fuse_attw = true;         // env BSR_FUSE_ATTW=0: attention and the `w` GEMM as two launches (A/B measurements, bit-identity tests)
+  bool wino_conv2 = true;        // env BSR_WINO_CONV2=0: the fp32 res*.conv2 on the direct implicit-GEMM kernel instead of the Winograd F(2x2, 3x3) one (A/B measurements, the two-forms test)
   bool timing = false;
   std::vector<hipEvent_t> ev;    // event pool, pairs
   std::vector<int> ev_class;
@@ -237,6 +240,30 @@ namespace {
 const char* const kRangeMsg =
     "an activation exceeded the fp16 range (|x| >= 65520) in a forward of this 16-bit-mode handle: its outputs are not trustworthy "
     "(inf / NaN where the fp32 path stays finite).  Re-run those inputs on a BSR_DTYPE_F32 handle; bsr_check_range() clears the condition";
+
+// Winograd F(2x2, 3x3) filter transform U = G g G^T of a 128 -> 128 3x3 layer (Lavin & Gray 2016), in float64, rounded once:
+// the layer's direct image [4 chunks][9 taps (a, b)][128 cout][32 + 4 channels] -> the stream of wino_conv2.h,
+// [8 chunks][16 positions 4 xi + nu][128 cout][16 channels].  blindshadowremoval_amd/pack.py: pack_wino states the same in numpy.
+constexpr size_t kWinoFloats = 8 * 16 * 128 * 16;
+void wino_filter_transform(const float* direct, float* out) {
+  static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+  for (int k = 0; k < 128; ++k)
+    for (int n = 0; n < 128; ++n) {
+      double t[4][3];
+      for (int x = 0; x < 4; ++x)
+        for (int b = 0; b < 3; ++b) {
+          double acc = 0.0;
+          for (int a = 0; a < 3; ++a) acc += G[x][a] * (double)direct[((size_t)((k / 32) * 9 + a * 3 + b) * 128 + n) * 36 + k % 32];
+          t[x][b] = acc;
+        }
+      for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) {
+          double acc = 0.0;
+          for (int b = 0; b < 3; ++b) acc += t[x][b] * G[y][b];
+          out[((size_t)((k / 16) * 16 + 4 * x + y) * 128 + n) * 16 + k % 16] = (float)acc;
+        }
+    }
+}
 
 int find_layer(bsr_handle* h, const char* name, int nchunk, int taps, int ldp, int n_min, LayerW* out) {
   auto it = h->layers.find(name);
@@ -589,6 +616,7 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   if (const char* e_ = getenv("BSR_CONV3_F16")) h->conv3_f16 = atoi(e_) != 0;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   if (const char* e_ = getenv("BSR_CONV1_GEMM")) h->conv1_gemm = atoi(e_) != 0;
+  if (const char* e_ = getenv("BSR_WINO_CONV2")) h->wino_conv2 = atoi(e_) != 0;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), nbytes);
   if (e == hipSuccess) e = hipMemcpy(h->d_blob, blob, nbytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -657,6 +685,19 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     if (dtype == BSR_DTYPE_F32) h->var = nch == 13 ? kTSM : kGSC;
     else h->var = nch == 10 ? kTSM16 : kGSC16;
   }
+  if (dtype == BSR_DTYPE_F32) {      // the Winograd streams of res0..5.conv2, once per handle (kept whatever BSR_WINO_CONV2 says: 6 MB)
+    std::vector<float> u(6 * kWinoFloats);
+    for (int i = 0; i < 6; ++i) {
+      char nm[32];
+      snprintf(nm, sizeof nm, "res%d.conv2", i);
+      LayerW l;
+      if (find_layer(h, nm, 4, 9, 36, 128, &l) != BSR_OK || l.n_pad != 128) { bsr_destroy(h); return fail(BSR_ERR_BLOB, std::string("bsr_create: layer '") + nm + "' is not a [4][9][128][36] image"); }
+      wino_filter_transform(reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(l.w) - reinterpret_cast<const uint8_t*>(h->d_blob))), u.data() + i * kWinoFloats);
+    }
+    e = hipMalloc(reinterpret_cast<void**>(&h->d_wino), u.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_wino, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: Winograd weights: ") + hipGetErrorString(e)); }
+  }
   *out = h;
   return BSR_OK;
 }
@@ -667,6 +708,7 @@ void bsr_destroy(bsr_handle* h) {
   for (hipEvent_t e : h->ev) hipEventDestroy(e);
   if (h->ws) hipFree(h->ws);
   if (h->d_blob) hipFree(h->d_blob);
+  if (h->d_wino) hipFree(h->d_wino);
   if (h->range_flag) hipHostFree(h->range_flag);
   delete h;
 }
@@ -861,8 +903,25 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     // the block's skip: y3x = y3 + pad(x), so that the `w` GEMM below reads ONE residual.
     // (The two as ONE launch — the conv2 tile through LDS into a GEMM tail — was built in round 4, bit-identical and no faster: profiles/HISTORY.md;
     // sources at git e99927a.)
+    // fp32: conv2 in Winograd F(2x2, 3x3) form (wino_conv2.h: 2.25x fewer matrix instructions), at EVERY batch and image size, so that
+    // an image gets the same bits in any batch; BSR_WINO_CONV2=0 keeps the direct kernel.  The 16-bit modes keep theirs.
     snprintf(nm, sizeof nm, "res%d.conv2", i);
-    L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, ws + p.t2, 128, 0, 128, 1);
+    if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) {
+      if (L.rc == BSR_OK) {
+        LayerW l;
+        L.rc = find_layer(h, nm, 4, 9, 36, 128, &l);      // for its bias; the weights are the handle's transformed stream
+        if (L.rc == BSR_OK && (H8 % 4 != 0 || W8 % 32 != 0)) L.rc = fail(BSR_ERR_ARG, std::string("layer '") + nm + "': feature map is not a multiple of the 4x32 tile");
+        if (L.rc == BSR_OK) {
+          bsr::WinoArgs a{};
+          a.in = ws + p.t1; a.out = ws + p.t2; a.w = h->d_wino + (size_t)i * kWinoFloats; a.bias = l.b; a.H = H8; a.W = W8; a.in_cs = 128; a.out_cs = 128; a.act = 1;
+          L.begin(K_CONV3, nm);
+          L.check(bsr::launch_wino_conv2(a, B, s), nm);
+          L.end();
+        }
+      }
+    } else {
+      L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, ws + p.t2, 128, 0, 128, 1);
+    }
     snprintf(nm, sizeof nm, "res%d.c3q", i);
     L.gemm<3, 4>(K_CONV1, nm, ws + p.t2, 128, ncell, y3, CS_Y3X, 288 + 384, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X);
     // z = y3 + BN(w(att)); out = LeakyReLU(pad(x) + pad(z))  (model.py:56-59, 105-113) = LeakyReLU(y3x + BN(w(att))).
@@ -1247,6 +1306,23 @@ int bsr_debug_attention_rgb(const float* qkv, float* y, int B, int tokens, void*
   if (qkv == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: null argument");
   if (B <= 0 || tokens <= 0 || tokens % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: tokens must be a positive multiple of 32");
   HIP_TRY(bsr::launch_nonlocal_attention256(qkv, y, B, tokens, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int nw, void* stream) {
+  if (x == nullptr || w == nullptr || bias == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: null argument");
+  if (B <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: H must be a positive multiple of 4 and W of 32");
+  if ((long long)B * H * W * 128 * 4 >= (1LL << 31)) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: tensor too large");
+  if (nw != 0 && nw != 2 && nw != 4) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: nw must be 0 (automatic), 2 or 4 waves per workgroup");
+  bsr::WinoArgs a{};
+  a.in = x; a.out = y; a.w = w; a.bias = bias; a.H = H; a.W = W; a.in_cs = 128; a.out_cs = 128; a.act = 1;
+  HIP_TRY(bsr::launch_wino_conv2(a, B, static_cast<hipStream_t>(stream), nw));
+  return BSR_OK;
+}
+
+int bsr_debug_wino_filter(const float* direct, float* out) {
+  if (direct == nullptr || out == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_filter: null argument");
+  wino_filter_transform(direct, out);
   return BSR_OK;
 }
 

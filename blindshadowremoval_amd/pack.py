@@ -199,6 +199,35 @@ def pack_w4(kernel_tkn: np.ndarray, bias: np.ndarray):
     return arr, b
 
 
+# Winograd F(2x2, 3x3) filter transform matrix (Lavin & Gray 2016): U = G g G^T
+WINO_G = np.array([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]])
+WINO_CC = 16          # channels per K chunk of csrc/wino_conv2.h
+
+
+def wino_filter_transform(kernel_tkn: np.ndarray, dtype=np.float32) -> np.ndarray:
+    """A folded 3x3 kernel [9 = (a, b), K, N] -> its 16 transform-position matrices U[4 xi + nu] = sum_ab G[xi, a] g[a, b] G[nu, b],
+    [16, K, N], computed in float64 and rounded ONCE to ``dtype`` (float32 for the kernel)."""
+    taps, k, n = kernel_tkn.shape
+    assert taps == 9
+    g = kernel_tkn.astype(np.float64).reshape(3, 3, k, n)
+    return np.einsum("xa,abkn,yb->xykn", WINO_G, g, WINO_G).reshape(16, k, n).astype(dtype)
+
+
+def pack_wino(kernel_tkn: np.ndarray, bias: np.ndarray):
+    """res*.conv2 ([9, 128, 128] folded) as the weight stream of csrc/wino_conv2.h: [K chunk][transform position][cout][WINO_CC
+    channels] float32, unpadded (the kernel adds the LDS bank pad when it stages a step).  Returns ([8, 16, 128, 16], [128] bias).
+
+    The blob's layout is pinned (one image per layer), so the stream is not a blob entry: bsr_create derives it, once per handle, from
+    the float32 weights of the layer's direct image with this very arithmetic (bsr_api.hip: wino_filter_transform, float64, rounded
+    once).  This function is its statement — it transforms the float32-rounded folded weights, as the library does — and what the
+    kernel's test hook is fed; tests/test_wino_pack_cpu.py holds the library's transform to it."""
+    taps, k, n = kernel_tkn.shape
+    assert k % WINO_CC == 0
+    u = wino_filter_transform(kernel_tkn.astype(np.float32))                                    # [16, K, N]
+    arr = np.ascontiguousarray(u.reshape(16, k // WINO_CC, WINO_CC, n).transpose(1, 0, 3, 2))    # [chunk, pos, n, cc]
+    return arr, bias.astype(np.float32)
+
+
 def layer_matrices(w: Dict[str, np.ndarray]) -> "Dict[str, Tuple[np.ndarray, np.ndarray]]":
     """Folded [taps, K, N] kernels + biases (float64) of every MFMA layer, in kernel K/N order."""
     out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}

@@ -248,6 +248,14 @@ int bsr_debug_attention_split(const void* qkv_split, float* y, int B, int tokens
 /* The fp32 kernel with a given workgroup shape: qw = query waves per workgroup (4 = 128 queries, 2 = 64, 1 = 32; 0 = what the
  * forward picks for this batch: the largest block that still gives every CU a workgroup).  All shapes give bit-identical outputs. */
 int bsr_debug_attention_qw(const float* qkv, float* y, int B, int tokens, int qw, void* stream);
+/* Test hook (additive in ABI 8, no existing signature changed): the Winograd F(2x2, 3x3) kernel of the fp32 res*.conv2 alone
+ * (csrc/wino_conv2.h).  x [B,H,W,128] -> y [B,H,W,128] = LeakyReLU_0.3(conv3x3_SAME(x) + bias); w = the [8][16][128][16] transformed
+ * weights of blindshadowremoval_amd.pack.pack_wino (what bsr_create derives from the blob), bias [128]; H % 4 == 0, W % 32 == 0 (device pointers).  nw = waves per workgroup:
+ * 4 (128 output channels), 2 (64), 0 = what the forward picks for this grid.  Both shapes give bit-identical outputs. */
+int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int nw, void* stream);
+/* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct image of each res<i>.conv2 of an
+ * fp32 blob.  direct = the layer's [4][9][128][36] image (HOST pointer), out = [8][16][128][16] floats (HOST pointer). */
+int bsr_debug_wino_filter(const float* direct, float* out);
 
 /* Measurement hook (ABI 7): one wave on `stream` writes (shader cycle counter, 100-MHz real-time counter) pairs to out[2 * samples] every
  * spin x ~3.4 us until *stop (device memory, written from another stream) is non-zero or `samples` pairs are taken; *taken receives the
