@@ -11,6 +11,7 @@
 
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -99,100 +100,81 @@ struct LayerW {
 
 enum KClass { K_CONV3 = 0, K_CONVT = 1, K_CONV1 = 2, K_ATT = 3, K_CONV7 = 4, K_GLUE = 5, K_CONVT_NI2 = 6 };
 
-constexpr int CS_Y3X = 288;  // y3x = conv3 output + block input, all 9 channel tiles kept (TSM inputs are wider than 257: model_with_TSM.py:105-113)
-
-// Channel plan of the bottleneck trunk.  GSC (/root/reference/model.py:238,259): xa = cat[x 96 | uv 3], blocks 0-2 are 257
-// wide, xh = cat[x_hole 257 | bmask | uv 3].  TSM (/root/reference/model_with_TSM.py:272,293) inserts the ShareLayer output:
+// Channel plan of a generator.  GSC (/root/reference/model.py:238,259): xa = cat[x 96 | uv 3], blocks 0-2 are 257 wide,
+// xh = cat[x_hole 257 | bmask | uv 3].  TSM (/root/reference/model_with_TSM.py:272,293) inserts the ShareLayer output:
 // xa = cat[x 96 | x_share 192 | uv 3] = 291, blocks 0-2 keep 291, xh = cat[x_hole 291 | bmask | x_share 582 | uv 3] = 877.
 struct Variant {
-  bool tsm;
+  bool tsm, rgb;
   int c_a, cs_a, uv_a;        // res0 input: real channels, stride, uv slot
   int c_r, cs_r;              // blocks 0-2 output
   int c_h, cs_h, uv_h;        // blocks 3-5 input/output, uv slot
-  bool rgb = false;           // the single-stage RGB baseline (model_RGB.py): its own plan and forward (PlanRGB, forward_rgb)
+  // the GSC / TSM values of the rest; the single-stage RGB baseline (model_RGB.py) states its own
+  int d = 128, nblk = 6;      // bottleneck width, number of blocks
+  int cs_c3 = 128, cs_c2 = 160;   // c3 = [up2 | x2], c2 = [up1 | x3]: the skip concatenations are channel slices
+  int cs_y3x = 288;           // y3x = conv3 output + block input, all 9 channel tiles kept (TSM inputs are wider than 257: model_with_TSM.py:105-113)
+  int cs_y = 64, cs_qh = 16;  // the last decoder layer's output; the 7x1 head's (kx, co) partial sums
 };
-constexpr Variant kGSC{false, 99, 120, 96, 257, 264, 261, 264, 258};
+constexpr Variant kGSC{false, false, 99, 120, 96, 257, 264, 261, 264, 258};
 // 16-bit matrix-core modes (BSR_DTYPE_F16 / BSR_DTYPE_F32X3): K chunks are 32 channels, so the 257 / 261-wide tensors get stride 288
-constexpr Variant kGSC16{false, 99, 128, 96, 257, 288, 261, 288, 258};
-constexpr Variant kTSM{true, 291, 312, 288, 291, 312, 877, 888, 874};
-constexpr Variant kTSM16{true, 291, 320, 288, 291, 320, 877, 896, 874};          // TSM widths at the 16-bit kernels' 32-channel granularity
+constexpr Variant kGSC16{false, false, 99, 128, 96, 257, 288, 261, 288, 258};
+constexpr Variant kTSM{true, false, 291, 312, 288, 291, 312, 877, 888, 874};
+constexpr Variant kTSM16{true, false, 291, 320, 288, 291, 320, 877, 896, 874};   // TSM widths at the 16-bit kernels' 32-channel granularity
 // RGB baseline (/root/reference/model_RGB.py:198-266): xa = cat[x 96 | uv 3] at stride 128, blocks 0-2 are 513 wide (stride 544); no
-// blocks 3-5, no xh (c_h / cs_h / uv_h unused)
-constexpr Variant kRGB{false, 99, 128, 96, 513, 544, 0, 0, 0, true};
+// blocks 3-5, no xh (c_h / cs_h / uv_h are 0).  c3 = [up2 128 | x2 64] (:252), c2 = [up1 192 | x3 64] (:251), y3x<i> = [y3 513 | 0] + pad(x)
+constexpr Variant kRGB{false, true, 99, 128, 96, 513, 544, 0, 0, 0, 256, 3, 192, 256, 544, 128, 32};
+constexpr int CS_Y3X = kGSC.cs_y3x;
 constexpr int CS_CF = 64;    // f = clr_up3 output; the gs channel of cat[gs, f] (model.py:267) is read from the gs output
+// the names the RGB forward reads its row by
+constexpr int RGB_CS_R = kRGB.cs_r, RGB_CS_A = kRGB.cs_a, RGB_D = kRGB.d, RGB_CS_C3 = kRGB.cs_c3, RGB_CS_C2 = kRGB.cs_c2, RGB_CS_QH = kRGB.cs_qh;
 
-struct Plan {  // float offsets into the workspace for a (B,H,W) problem
-  size_t x1, c3, c2, xa, t1, t2, y3[6], qkv, att[6], r[6], xh, ybuf, qh, f1, f2, cf, probe, reg32, share, total;
+struct Region {
+  size_t off, floats;
+};
+// Float offsets into the workspace for a (B,H,W) problem; a slot the variant does not have is zero-sized.  qkv = theta | phi | g, d each.
+struct Plan {
+  size_t x1, c3, c2, xa, t1, t2, y3[6], qkv, att[6], r[6], xh, ybuf, qh, f1, f2, cf, probe, reg32, share, yh, con, total;
+  // A new shape moves every buffer.  All of them are fully rewritten by their producers each forward, pad channels included, except the
+  // channel-pad lanes of the buffers listed here, which must read as exact zeros (they are the K pad of the 1x1 layers and feed the
+  // residuals).  GSC / TSM: the 1/8-resolution concat buffers xa, xh, r0..r5 (real channels < stride); RGB: xa (channels 99-127).
+  Region zero[8];
+  int nzero;
 };
 
-Plan make_plan(size_t B, size_t H, size_t W, const Variant& v = kGSC) {
-  Plan p;
+Plan make_plan(size_t B, size_t H, size_t W, const Variant& v) {
+  Plan p{};
   size_t off = 0;
-  auto take = [&](size_t floats) {
+  auto take = [&](size_t floats, bool keep_zero = false) {
     size_t o = off;
     off += (floats + 63) & ~size_t(63);
+    if (keep_zero && floats != 0) p.zero[p.nzero++] = {o, floats};
     return o;
   };
   const size_t px = B * H * W, cells = px / 64;
+  const size_t px2 = v.rgb ? 0 : px;      // GSC / TSM: the second stage (colour decoder, bmask probe)
+  const size_t px1 = px - px2;            // RGB: the head's two 3-channel images (conv2's output, and the copy of con that bsr_probe reads)
   p.x1 = take(px * 32);
-  p.c3 = take(px / 4 * 128);
-  p.c2 = take(px / 16 * 160);
-  p.xa = take(cells * v.cs_a);
-  p.t1 = take(cells * 128);
-  p.t2 = take(cells * 128);
-  for (int i = 0; i < 6; ++i) p.y3[i] = take(cells * CS_Y3X);
-  p.qkv = take(cells * 384);
-  for (int i = 0; i < 6; ++i) p.att[i] = take(cells * 128);
-  for (int i = 0; i < 6; ++i) p.r[i] = take(cells * (i < 3 ? v.cs_r : v.cs_h));
-  p.xh = take(cells * v.cs_h);
-  p.ybuf = take(px * 64);
-  p.qh = take(px * 16);
-  p.f1 = take(px / 16 * 128);
-  p.f2 = take(px / 4 * 96);
-  p.cf = take(px * CS_CF);
-  p.probe = take(cells * 2);
+  p.c3 = take(px / 4 * v.cs_c3);
+  p.c2 = take(px / 16 * v.cs_c2);
+  p.xa = take(cells * v.cs_a, true);
+  p.t1 = take(cells * v.d);
+  p.t2 = take(cells * v.d);
+  for (int i = 0; i < v.nblk; ++i) p.y3[i] = take(cells * v.cs_y3x);
+  p.qkv = take(cells * 3 * v.d);
+  for (int i = 0; i < v.nblk; ++i) p.att[i] = take(cells * v.d);
+  for (int i = 0; i < v.nblk; ++i) p.r[i] = take(cells * (i < 3 ? v.cs_r : v.cs_h), !v.rgb);
+  p.xh = take(cells * v.cs_h, true);
+  p.ybuf = take(px * v.cs_y);
+  p.qh = take(px * v.cs_qh);
+  p.f1 = take(px2 / 16 * 128);
+  p.f2 = take(px2 / 4 * 96);
+  p.cf = take(px2 * CS_CF);
+  p.probe = take(px2 / 64 * 2);
   p.reg32 = take(v.tsm ? cells * 4 : 0);
   p.share = take(v.tsm ? cells * 2 * v.c_r : 0);
+  p.yh = take(px1 * 3);
+  p.con = take(px1 * 3);
   p.total = off;
   return p;
-}
-
-// Workspace of the RGB forward.  Concatenations are channel slices: c3 = [up2 128 | x2 64] (model_RGB.py:252), c2 = [up1 192 | x3 64]
-// (:251); y3x<i> = [y3 513 | 0] + pad(x) at stride 544; qkv = theta | phi | g, 256 each; qh = the 7x1 head's (kx, co) partial sums.
-struct PlanRGB {
-  size_t x1, c3, c2, xa, t1, t2, y3[3], qkv, att[3], r[3], ybuf, qh, yh, con, total;
-};
-constexpr int RGB_CS_R = 544, RGB_CS_A = 128, RGB_D = 256, RGB_CS_C3 = 192, RGB_CS_C2 = 256, RGB_CS_QH = 32;
-
-PlanRGB make_plan_rgb(size_t B, size_t H, size_t W) {
-  PlanRGB p;
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    size_t o = off;
-    off += (floats + 63) & ~size_t(63);
-    return o;
-  };
-  const size_t px = B * H * W, cells = px / 64;
-  p.x1 = take(px * 32);
-  p.c3 = take(px / 4 * RGB_CS_C3);
-  p.c2 = take(px / 16 * RGB_CS_C2);
-  p.xa = take(cells * RGB_CS_A);
-  p.t1 = take(cells * RGB_D);
-  p.t2 = take(cells * RGB_D);
-  for (int i = 0; i < 3; ++i) p.y3[i] = take(cells * RGB_CS_R);
-  p.qkv = take(cells * 3 * RGB_D);
-  for (int i = 0; i < 3; ++i) p.att[i] = take(cells * RGB_D);
-  for (int i = 0; i < 3; ++i) p.r[i] = take(cells * RGB_CS_R);
-  p.ybuf = take(px * 128);
-  p.qh = take(px * RGB_CS_QH);
-  p.yh = take(px * 3);
-  p.con = take(px * 3);
-  p.total = off;
-  return p;
-}
-
-size_t plan_floats(const Variant& v, size_t B, size_t H, size_t W) {
-  return v.rgb ? make_plan_rgb(B, H, W).total : make_plan(B, H, W, v).total;
 }
 
 }  // namespace
@@ -209,8 +191,7 @@ struct bsr_handle {
   const float* clr_gs_w = nullptr;
   float* ws = nullptr;
   size_t ws_floats = 0;
-  Plan plan{};
-  PlanRGB plan_rgb{};            // RGB handles: the plan of the last forward
+  Plan plan{};                   // of the last forward
   const float* rgb_tail_w = nullptr;   // RGB: conv3 (7x7, 3 -> 3) HWIO weights + bias, 444 floats
   const float* rgb_head_b = nullptr;   // RGB: conv2 bias, 3 floats
   int B = 0, H = 0, W = 0;       // shape of the last forward
@@ -279,6 +260,32 @@ int find_layer(bsr_handle* h, const char* name, int nchunk, int taps, int ldp, i
   return BSR_OK;
 }
 
+// Run-time value -> template argument: f is a generic lambda, called once with the constants of the value.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// The fp32-input kernels' two precision parameters.  prec: 0 = fp32 matrix instructions, 2 = fp16 ones (split precision in f32x3, and
+// wherever the f16 mode does not take plain fp16 operands); half: the f16 mode's fp16 activation tensor on the kernel's other side.
+template <class F>
+void with_dtype(int dtype, F f) {
+  if (dtype == BSR_DTYPE_F32) f(int_c<0>{}, std::false_type{});
+  else if (dtype == BSR_DTYPE_F16) f(int_c<2>{}, std::true_type{});
+  else f(int_c<2>{}, std::false_type{});
+}
+// io of the f16 mode's 3x3 layers: bit 0 = `in` is an fp16 tensor, bit 1 = `out` is written as fp16 (the fp16 activation pack of configs[3])
+template <class F>
+void with_io(int io, F f) {
+  if (io == 3) f(int_c<3>{});
+  else if (io == 2) f(int_c<2>{});
+  else if (io == 1) f(int_c<1>{});
+  else f(int_c<0>{});
+}
+
+bsr::WinoArgs wino_args(const float* in, float* out, const float* w, const float* bias, int H, int W) {
+  bsr::WinoArgs a{};
+  a.in = in; a.out = out; a.w = w; a.bias = bias; a.H = H; a.W = W; a.in_cs = 128; a.out_cs = 128; a.act = 1;
+  return a;
+}
+
 struct Launcher {
   bsr_handle* h;
   hipStream_t s;
@@ -309,7 +316,7 @@ struct Launcher {
   }
 
   // KH,KW,S,TR,TH,TW,WM,WN,MI,NI,CC,PF_IN
-  // io (f16 mode only): bit 0 = `in` is an fp16 tensor, bit 1 = `out` is written as fp16 (the fp16 activation pack of configs[3])
+  // io: f16 mode only (with_io)
   template <int KH, int KW, int S, bool TR, int NI, int CC, int INB>
   void conv(int cls, const char* name, const float* in, int in_cs, int in_coff, int k_pad, int H, int W, float* out, int out_cs,
             int out_coff, int n_store, int act, int io = 0) {
@@ -363,10 +370,7 @@ struct Launcher {
         if (rc != BSR_OK) return;
         a.w = l3.w; a.bias = l3.b; a.nchunk = k_pad / 32; a.n_pad = nblk * 64;
         begin(cls, name);
-        if (io == 3) check(bsr::launch_conv3_f16<TR, 3>(a, h->B, s), name);
-        else if (io == 2) check(bsr::launch_conv3_f16<TR, 2>(a, h->B, s), name);
-        else if (io == 1) check(bsr::launch_conv3_f16<TR, 1>(a, h->B, s), name);
-        else check(bsr::launch_conv3_f16<TR, 0>(a, h->B, s), name);
+        with_io(io, [&](auto io_c) { check(bsr::launch_conv3_f16<TR, io_c.value>(a, h->B, s), name); });
         end();
         return;
       }
@@ -385,13 +389,16 @@ struct Launcher {
       check(bsr::launch_igemm_conv<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CC, INB>(a, h->B, s), name);
     else if (nsplit == 2)
       check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 2>(a, h->B, s), name);
-    else if constexpr (k33) {
-      if (io == 3) check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 1, 3>(a, h->B, s), name);
-      else if (io == 2) check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 1, 2>(a, h->B, s), name);
-      else if (io == 1) check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 1, 1>(a, h->B, s), name);
-      else check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 1, 0>(a, h->B, s), name);
-    }
+    else if constexpr (k33)
+      with_io(io, [&](auto io_c) { check(bsr::launch_igemm_h16<KH, KW, S, TR, 4, 32, 4, 1, 1, NI, CCH, INB, 1, io_c.value>(a, h->B, s), name); });
     end();
+  }
+  bsr::ConvArgs gemm_args(const LayerW& l, const float* in, int in_cs, float* out, int out_cs, int n_store, int act) const {
+    bsr::ConvArgs a{};
+    a.in = in; a.in_cs = in_cs; a.out = out; a.out_cs = out_cs;
+    a.w = l.w; a.bias = l.b; a.nchunk = l.nchunk; a.n_pad = l.n_pad; a.n_store = n_store; a.act = act;
+    a.range_flag = h->range_flag;
+    return a;
   }
   // 1x1 conv as a resident-activation GEMM (K = NCH*32) over all N
   // MINW: waves per SIMD the kernel's register budget is sized for (gemm_nloop.h); 1 for the K = 256 GEMMs of the RGB bottleneck
@@ -418,12 +425,9 @@ struct Launcher {
     rc = find_layer(h, name, NCH, 1, 36, (tiles + NI - 1) * 32, &l);   // the last group of a range may read (zero) rows past its tiles
     if (rc != BSR_OK) return;
     if (pixels % C::BM != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': pixel count is not a multiple of 128"); return; }
-    bsr::ConvArgs a{};
-    a.in = in; a.in_cs = in_cs; a.in_coff = 0; a.out = out; a.out_cs = out_cs; a.out_coff = 0;
-    a.w = l.w; a.bias = l.b; a.nchunk = l.nchunk; a.n_pad = l.n_pad; a.n_store = n_store; a.act = act;
+    bsr::ConvArgs a = gemm_args(l, in, in_cs, out, out_cs, n_store, act);
     a.res1 = res1; a.res1_cs = res1_cs; a.res1_c = res1_c;
     a.out2 = out2; a.out2_cs = out2_cs; a.n_split = n_split; a.n_store1 = n_store1;
-    a.range_flag = h->range_flag;
     a.out2_split = (h->dtype != BSR_DTYPE_F32 && out2 != nullptr) ? 1 : 0;      // conv3 | theta|phi|g of the 16-bit modes: qkv in the split layout of attention_h16.h
     begin(cls, name);
     if (h->dtype == BSR_DTYPE_F32)
@@ -432,6 +436,44 @@ struct Launcher {
       check(bsr::launch_gemm_nloop<NI, NCH, 2>(a, pixels, kNSplit, s), name);      // split-precision in both 16-bit modes
     else
       rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': the RGB bottleneck GEMMs are fp32 only");
+    end();
+  }
+  // res*.conv1 (K = NCH*32 -> 128, + LeakyReLU) of the 16-bit modes, split precision: ONE workgroup per CU and all of N per workgroup
+  // (gemm_nloop.h, MINW = 1, no N split).  forward_impl's conv1_gemm decides when it runs.
+  template <int NCH>
+  void gemm_all_n(const char* name, const float* in, size_t pixels, float* out) {
+    if (rc != BSR_OK) return;
+    LayerW l;
+    rc = find_layer(h, name, NCH, 1, 36, 128, &l);
+    if (rc != BSR_OK) return;
+    begin(K_CONV1, name);
+    check(bsr::launch_gemm_nloop<4, NCH, 2, 1>(gemm_args(l, in, NCH * 32, out, 128, 128, 1), pixels, 1, s), name);
+    end();
+  }
+
+  // conv1 = Conv(32, 7x7) + BN + LeakyReLU (model.py:203,230; model_RGB.py:230): dedicated stem kernel (7 row taps x 21 contiguous floats).
+  // Split precision in both 16-bit modes; f16 stores x1 as fp16.
+  void stem(const float* in, int H, int W, float* out) {
+    if (rc != BSR_OK) return;
+    LayerW l;
+    rc = find_layer(h, "conv1", 1, 7, h->dtype != BSR_DTYPE_F32 ? 36 : 28, 32, &l);
+    if (rc != BSR_OK) return;
+    bsr::StemArgs a{in, out, l.w, l.b, H, W, 0, 0, 0, h->range_flag};
+    begin(K_CONV7, "conv1");
+    with_dtype(h->dtype, [&](auto prec, auto half) { check(bsr::launch_stem7<4, prec.value, half.value>(a, h->B, s), "conv1"); });
+    end();
+  }
+
+  // fp32 res<i>.conv2 (3x3, 128 -> 128, + BN + LeakyReLU) in Winograd F(2x2, 3x3) form (wino_conv2.h).  The blob's layer gives the bias;
+  // the weights are the handle's transformed stream.
+  void wino(const char* name, int i, const float* in, int H, int W, float* out) {
+    if (rc != BSR_OK) return;
+    LayerW l;
+    rc = find_layer(h, name, 4, 9, 36, 128, &l);
+    if (rc != BSR_OK) return;
+    if (H % 4 != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': feature map is not a multiple of the 4x32 tile"); return; }
+    begin(K_CONV3, name);
+    check(bsr::launch_wino_conv2(wino_args(in, out, h->d_wino + (size_t)i * kWinoFloats, l.b, H, W), h->B, s), name);
     end();
   }
 
@@ -464,22 +506,16 @@ struct Launcher {
     a.pad_t = 3; a.pad_l = 0;
     a.inputs = inputs; a.gs_out = gs; a.mask22 = mask22; a.b_mask = h->head_bias[0]; a.b_con = h->head_bias[1];
     a.range_flag = h->range_flag;
-    const int dt = h->dtype;
     int resident = 0;
     check(bsr::launch_conv_n16<7, 1, false, false, 2, 0, false, true>(a, h->B, s, &resident), "heads");      // query: resident workgroup slots
     const bool fuse = rc == BSR_OK && h->fuse_heads && bsr::conv_n16_fuse_pays(h->B, H, 8, resident);
     begin(K_CONV7, "heads");
-    if (fuse) {
-      if (dt == BSR_DTYPE_F32) check(bsr::launch_conv_n16<7, 1, false, false, 2, 0, false, true>(a, h->B, s), "heads");
-      else if (dt == BSR_DTYPE_F16) check(bsr::launch_conv_n16<7, 1, false, false, 2, 2, true, true>(a, h->B, s), "heads");
-      else check(bsr::launch_conv_n16<7, 1, false, false, 2, 2, false, true>(a, h->B, s), "heads");
-      end();
-      return;
-    }
-    if (dt == BSR_DTYPE_F32) check(bsr::launch_conv_n16<7, 1, false, false, 2, 0>(a, h->B, s), "heads");
-    else if (dt == BSR_DTYPE_F16) check(bsr::launch_conv_n16<7, 1, false, false, 2, 2, true>(a, h->B, s), "heads");
-    else check(bsr::launch_conv_n16<7, 1, false, false, 2, 2>(a, h->B, s), "heads");
+    with_dtype(h->dtype, [&](auto prec, auto half) {
+      if (fuse) check(bsr::launch_conv_n16<7, 1, false, false, 2, prec.value, half.value, true>(a, h->B, s), "heads");
+      else check(bsr::launch_conv_n16<7, 1, false, false, 2, prec.value, half.value>(a, h->B, s), "heads");
+    });
     end();
+    if (fuse) return;
     begin(K_GLUE, "heads_post");
     hipLaunchKernelGGL(bsr::heads_post_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, qh, inputs, h->head_bias[0], h->head_bias[1], gs,
                        mask22, W, npix);
@@ -502,70 +538,38 @@ struct Launcher {
     a.range_flag = h->range_flag;
     if (H % (4 * RW) != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': image is not a multiple of its tile"); return; }
     begin(cls, name);
-    if (h->dtype == BSR_DTYPE_F32)
-      check(bsr::launch_conv_n16<KH, KW, GS, TAIL, RW, 0>(a, h->B, s), name);
-    else if (h->dtype == BSR_DTYPE_F16)
-      check(bsr::launch_conv_n16<KH, KW, GS, TAIL, RW, 2, true>(a, h->B, s), name);      // f16 mode: its input tensor is fp16
-    else
-      check(bsr::launch_conv_n16<KH, KW, GS, TAIL, RW, 2>(a, h->B, s), name);            // split precision
+    with_dtype(h->dtype, [&](auto prec, auto half) { check(bsr::launch_conv_n16<KH, KW, GS, TAIL, RW, prec.value, half.value>(a, h->B, s), name); });
     end();
   }
 };
 
-// RGB: as ensure_workspace below.  On a new shape only the pad lanes of xa (channels 99-127, the K pad of res0.conv1 and the residual
-// of res0) need clearing; every other buffer is fully rewritten by its producers each forward, pad channels included.
-int ensure_workspace_rgb(bsr_handle* h, int B, int H, int W, hipStream_t s) {
-  const PlanRGB p = make_plan_rgb(B, H, W);
-  bool fresh = false;
-  if (p.total > h->ws_floats) {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h->ws) HIP_TRY(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), p.total * sizeof(float)));
-    h->ws_floats = p.total;
-    h->B = 0;
-    fresh = true;
-  }
-  if (fresh) {
-    HIP_TRY(hipMemsetAsync(h->ws, 0, p.total * sizeof(float), s));
-    h->ran = false;
-  } else if (B != h->B || H != h->H || W != h->W) {
-    HIP_TRY(hipMemsetAsync(h->ws + p.xa, 0, (size_t)B * H * W / 64 * RGB_CS_A * sizeof(float), s));
-    h->ran = false;
-  }
-  h->plan_rgb = p;
-  h->B = B; h->H = H; h->W = W;
+// Make the workspace hold at least `floats`.  A new allocation holds arbitrary bits (NaN x zero weight = NaN): all of it is cleared once,
+// and the handle forgets its last shape.  A forward waits for its own stream and clears on it; bsr_reserve (device_wide) waits for
+// the whole device and returns with the clear done.
+int grow_workspace(bsr_handle* h, size_t floats, bool device_wide, hipStream_t s) {
+  if (floats <= h->ws_floats) return BSR_OK;
+  if (device_wide) HIP_TRY(hipDeviceSynchronize());
+  else HIP_TRY(hipStreamSynchronize(s));
+  if (h->ws) HIP_TRY(hipFree(h->ws));
+  h->ws = nullptr;
+  h->ws_floats = 0;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), floats * sizeof(float)));
+  h->ws_floats = floats;
+  h->B = 0;
+  h->ran = false;
+  if (device_wide) HIP_TRY(hipMemset(h->ws, 0, floats * sizeof(float)));
+  else HIP_TRY(hipMemsetAsync(h->ws, 0, floats * sizeof(float), s));
   return BSR_OK;
 }
 
 int ensure_workspace(bsr_handle* h, int B, int H, int W, hipStream_t s) {
-  if (h->var.rgb) return ensure_workspace_rgb(h, B, H, W, s);
-  Plan p = make_plan(B, H, W, h->var);
-  bool fresh = false;
-  if (p.total > h->ws_floats) {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h->ws) HIP_TRY(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), p.total * sizeof(float)));
-    h->ws_floats = p.total;
-    h->B = 0;
-    fresh = true;
-  }
-  if (fresh) {
-    // a new allocation holds arbitrary bits (NaN x zero weight = NaN): clear all of it once
-    HIP_TRY(hipMemsetAsync(h->ws, 0, p.total * sizeof(float), s));
-    h->ran = false;
-  } else if (B != h->B || H != h->H || W != h->W) {
-    // A new shape moves every buffer.  All of them are fully rewritten by their producers each forward except the channel-pad
-    // lanes of the 1/8-resolution concat buffers (xa, xh, r0..r5: real channels < stride), which must read as exact zeros:
-    // clear just those (a few MB per image instead of the whole workspace).
-    const size_t cells = (size_t)B * H * W / 64;
-    const Variant& v = h->var;
-    HIP_TRY(hipMemsetAsync(h->ws + p.xa, 0, cells * v.cs_a * sizeof(float), s));
-    HIP_TRY(hipMemsetAsync(h->ws + p.xh, 0, cells * v.cs_h * sizeof(float), s));
-    for (int i = 0; i < 6; ++i) HIP_TRY(hipMemsetAsync(h->ws + p.r[i], 0, cells * (i < 3 ? v.cs_r : v.cs_h) * sizeof(float), s));
+  const Plan p = make_plan(B, H, W, h->var);
+  const bool fresh = p.total > h->ws_floats;
+  const int rc = grow_workspace(h, p.total, false, s);
+  if (rc != BSR_OK) return rc;
+  if (!fresh && (B != h->B || H != h->H || W != h->W)) {
+    // a new shape in the old allocation: only the plan's pad-lane regions (a few MB per image instead of the whole workspace)
+    for (int i = 0; i < p.nzero; ++i) HIP_TRY(hipMemsetAsync(h->ws + p.zero[i].off, 0, p.zero[i].floats * sizeof(float), s));
     h->ran = false;
   }
   h->plan = p;
@@ -590,7 +594,7 @@ const char* bsr_last_error(void) { return g_last_error.c_str(); }
 
 size_t bsr_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return make_plan(B, H, W).total * sizeof(float);
+  return make_plan(B, H, W, kGSC).total * sizeof(float);
 }
 
 int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t nbytes, int dtype) {
@@ -611,12 +615,11 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   bsr_handle* h = new bsr_handle();
   h->device = device;
   h->dtype = dtype;
-  if (const char* e_ = getenv("BSR_FUSE_HEADS")) h->fuse_heads = atoi(e_) != 0;
-  if (const char* e_ = getenv("BSR_FUSE_ATTW")) h->fuse_attw = atoi(e_) != 0;
-  if (const char* e_ = getenv("BSR_CONV3_F16")) h->conv3_f16 = atoi(e_) != 0;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
-  if (const char* e_ = getenv("BSR_CONV1_GEMM")) h->conv1_gemm = atoi(e_) != 0;
-  if (const char* e_ = getenv("BSR_WINO_CONV2")) h->wino_conv2 = atoi(e_) != 0;
+  const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
+                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}};
+  for (const auto& sw : switches)
+    if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), nbytes);
   if (e == hipSuccess) e = hipMemcpy(h->d_blob, blob, nbytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -717,19 +720,7 @@ int bsr_reserve(bsr_handle* h, int B, int H, int W) {
   if (h == nullptr || B <= 0 || H <= 0 || W <= 0) return fail(BSR_ERR_ARG, "bsr_reserve: bad argument");
   DeviceGuard guard(h->device);
   HIP_TRY(guard.err);
-  const size_t total = plan_floats(h->var, B, H, W);
-  if (total > h->ws_floats) {
-    HIP_TRY(hipDeviceSynchronize());
-    if (h->ws) HIP_TRY(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->ws), total * sizeof(float)));
-    HIP_TRY(hipMemset(h->ws, 0, total * sizeof(float)));
-    h->ws_floats = total;
-    h->B = 0;
-    h->ran = false;
-  }
-  return BSR_OK;
+  return grow_workspace(h, make_plan(B, H, W, h->var).total, true, nullptr);
 }
 
 int bsr_check_range(bsr_handle* h, void* stream) {
@@ -788,8 +779,19 @@ int bsr_timing_entry(bsr_handle* h, int i, char* name, size_t name_cap, float* m
 
 size_t bsr_handle_workspace_bytes(const bsr_handle* h, int B, int H, int W) {
   if (h == nullptr || B <= 0 || H <= 0 || W <= 0) return 0;
-  return plan_floats(h->var, B, H, W) * sizeof(float);
+  return make_plan(B, H, W, h->var).total * sizeof(float);
 }
+
+// The forwards' image-size check, before anything is enqueued.  The entry point's name is part of each literal.  (For these H and W
+// multiples the token multiple always holds: (H/8)(W/8) = 128 (H/32)(W/256); it is stated because the attention kernels rely on it.)
+static int check_image_size(int H, int W, const char* hw_text, const char* token_text) {
+  if (H <= 0 || W <= 0 || H % 32 != 0 || W % 256 != 0) return fail(BSR_ERR_ARG, hw_text);
+  if (((H / 8) * (W / 8)) % 128 != 0) return fail(BSR_ERR_ARG, token_text);
+  return BSR_OK;
+}
+#define BSR_CHECK_IMAGE_SIZE(entry, H, W)                                                                                          \
+  check_image_size(H, W, entry ": H must be a multiple of 32 and W a multiple of 256 (reference: 256x256)",                         \
+                   entry ": (H/8)*(W/8) must be a multiple of 128")
 
 static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, const float* reg, int frame, int share, int B, int H, int W,
                         float* gs, float* con_rgb, float* mask22, float* dif, void* stream, float* packed = nullptr) {
@@ -804,14 +806,14 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     return fail(BSR_ERR_ARG, V.tsm ? "bsr_forward: this handle holds TSM weights: call bsr_forward_tsm" : "bsr_forward_tsm: this handle holds GSC weights: call bsr_forward");
   if (V.tsm && (frame <= 0 || B % frame != 0 || H != W))
     return fail(BSR_ERR_ARG, "bsr_forward_tsm: B must be a multiple of frame and the image square (warp.py assumes a square map)");
-  if (H <= 0 || W <= 0 || H % 32 != 0 || W % 256 != 0)
-    return fail(BSR_ERR_ARG, "bsr_forward: H must be a multiple of 32 and W a multiple of 256 (reference: 256x256)");
+  int rc = BSR_CHECK_IMAGE_SIZE("bsr_forward", H, W);
+  if (rc != BSR_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->range_flag != nullptr && *reinterpret_cast<volatile unsigned*>(h->range_flag) != 0u)
     return fail(BSR_ERR_RANGE, kRangeMsg);      // an earlier forward overflowed fp16: sticky until bsr_check_range() acknowledges it
   DeviceGuard guard(h->device);
   HIP_TRY(guard.err);
-  int rc = ensure_workspace(h, B, H, W, s);
+  rc = ensure_workspace(h, B, H, W, s);
   if (rc != BSR_OK) return rc;
   h->ev_used = 0;
   const Plan& p = h->plan;
@@ -822,23 +824,7 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
   auto glue_begin = [&](const char* what) { L.begin(K_GLUE, what); };
   auto glue_end = [&](const char* what) { L.check(hipGetLastError(), what); L.end(); };
 
-  // conv1 = Conv(32, 7x7) + BN + LeakyReLU (model.py:203,230): dedicated stem kernel (7 row taps x 21 contiguous floats)
-  {
-    LayerW l;
-    const bool x3 = h->dtype != BSR_DTYPE_F32;                     // split precision in both 16-bit modes
-    L.rc = find_layer(h, "conv1", 1, 7, x3 ? 36 : 28, 32, &l);
-    if (L.rc == BSR_OK) {
-      bsr::StemArgs a{inputs, ws + p.x1, l.w, l.b, H, W, 0, 0, 0, h->range_flag};
-      L.begin(K_CONV7, "conv1");
-      if (h->dtype == BSR_DTYPE_F16)
-        L.check((bsr::launch_stem7<4, 2, true>(a, B, s)), "conv1");                 // x1 stored as fp16
-      else if (x3)
-        L.check(bsr::launch_stem7<4, 2>(a, B, s), "conv1");
-      else
-        L.check(bsr::launch_stem7<4, 0>(a, B, s), "conv1");
-      L.end();
-    }
-  }
+  L.stem(inputs, H, W, ws + p.x1);
   // down1..3 = Conv(stride 2) (model.py:207-209,231-233); x2 / x3 land in their skip-concat slots (model.py:244-245)
   // f16 mode (the fp16 pack of BASELINE configs[3]): the full- / half- / quarter-resolution tensors between the 3x3-conv layers —
   // x1, c3 = [up2 | x2], c2 = [up1 | x3], y, f1, f2, f — live in HBM as fp16 (same workspace slots, first half used); the
@@ -876,17 +862,8 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     if (h->dtype == BSR_DTYPE_F32) return false;      // fp32: the implicit-GEMM kernel (the resident form over 24-channel chunks was built and is no faster: profiles/HISTORY.md round 5)
     if (ncell % 128 != 0 || (long long)(ncell / 128) * 2 < bsr::device_cu_count()) return false;
     if (x_cs != 128 && x_cs != 288) return false;
-    LayerW l;
-    L.rc = find_layer(h, nm, x_cs / 32, 1, 36, 128, &l);
-    if (L.rc != BSR_OK) return true;
-    bsr::ConvArgs a{};
-    a.in = x; a.in_cs = x_cs; a.in_coff = 0; a.out = ws + p.t1; a.out_cs = 128; a.out_coff = 0;
-    a.w = l.w; a.bias = l.b; a.nchunk = l.nchunk; a.n_pad = l.n_pad; a.n_store = 128; a.act = 1;
-    a.range_flag = h->range_flag;
-    L.begin(K_CONV1, nm);
-    if (x_cs == 128) L.check(bsr::launch_gemm_nloop<4, 4, 2, 1>(a, ncell, 1, s), nm);
-    else L.check(bsr::launch_gemm_nloop<4, 9, 2, 1>(a, ncell, 1, s), nm);
-    L.end();
+    if (x_cs == 128) L.gemm_all_n<4>(nm, x, ncell, ws + p.t1);
+    else L.gemm_all_n<9>(nm, x, ncell, ws + p.t1);
     return true;
   };
 
@@ -906,22 +883,8 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     // fp32: conv2 in Winograd F(2x2, 3x3) form (wino_conv2.h: 2.25x fewer matrix instructions), at EVERY batch and image size, so that
     // an image gets the same bits in any batch; BSR_WINO_CONV2=0 keeps the direct kernel.  The 16-bit modes keep theirs.
     snprintf(nm, sizeof nm, "res%d.conv2", i);
-    if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) {
-      if (L.rc == BSR_OK) {
-        LayerW l;
-        L.rc = find_layer(h, nm, 4, 9, 36, 128, &l);      // for its bias; the weights are the handle's transformed stream
-        if (L.rc == BSR_OK && (H8 % 4 != 0 || W8 % 32 != 0)) L.rc = fail(BSR_ERR_ARG, std::string("layer '") + nm + "': feature map is not a multiple of the 4x32 tile");
-        if (L.rc == BSR_OK) {
-          bsr::WinoArgs a{};
-          a.in = ws + p.t1; a.out = ws + p.t2; a.w = h->d_wino + (size_t)i * kWinoFloats; a.bias = l.b; a.H = H8; a.W = W8; a.in_cs = 128; a.out_cs = 128; a.act = 1;
-          L.begin(K_CONV3, nm);
-          L.check(bsr::launch_wino_conv2(a, B, s), nm);
-          L.end();
-        }
-      }
-    } else {
-      L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, ws + p.t2, 128, 0, 128, 1);
-    }
+    if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) L.wino(nm, i, ws + p.t1, H8, W8, ws + p.t2);
+    else L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, ws + p.t2, 128, 0, 128, 1);
     snprintf(nm, sizeof nm, "res%d.c3q", i);
     L.gemm<3, 4>(K_CONV1, nm, ws + p.t2, 128, ncell, y3, CS_Y3X, 288 + 384, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X);
     // z = y3 + BN(w(att)); out = LeakyReLU(pad(x) + pad(z))  (model.py:56-59, 105-113) = LeakyReLU(y3x + BN(w(att))).
@@ -972,7 +935,6 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
       glue_end("lrelu_copy");
     }
   };
-  if ((H8 * W8) % 128 != 0) return fail(BSR_ERR_ARG, "bsr_forward: (H/8)*(W/8) must be a multiple of 128");
   res_block(0, ws + p.xa, V.cs_a, V.c_a);
   res_block(1, ws + p.r[0], V.cs_r, V.c_r);
   res_block(2, ws + p.r[1], V.cs_r, V.c_r);
@@ -1014,36 +976,24 @@ int bsr_forward_rgb(bsr_handle* h, const float* inputs, const float* uv, int B, 
     return fail(BSR_ERR_ARG, h->var.tsm ? "bsr_forward_rgb: this handle holds TSM weights: call bsr_forward_tsm"
                                         : "bsr_forward_rgb: this handle holds GSC weights: call bsr_forward");
   if (B <= 0) return fail(BSR_ERR_ARG, "bsr_forward_rgb: B must be positive");
-  if (H <= 0 || W <= 0 || H % 32 != 0 || W % 256 != 0)
-    return fail(BSR_ERR_ARG, "bsr_forward_rgb: H must be a multiple of 32 and W a multiple of 256 (reference: 256x256)");
-  const int H8 = H / 8, W8 = W / 8;
-  if ((H8 * W8) % 128 != 0) return fail(BSR_ERR_ARG, "bsr_forward_rgb: (H/8)*(W/8) must be a multiple of 128");
+  int rc = BSR_CHECK_IMAGE_SIZE("bsr_forward_rgb", H, W);
+  if (rc != BSR_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(h->device);
   HIP_TRY(guard.err);
-  int rc = ensure_workspace(h, B, H, W, s);
+  rc = ensure_workspace(h, B, H, W, s);
   if (rc != BSR_OK) return rc;
   h->ev_used = 0;
   h->att_in_lds = false;
-  const PlanRGB& p = h->plan_rgb;
+  const Plan& p = h->plan;
   float* ws = h->ws;
   const size_t npix = (size_t)B * H * W, ncell = npix / 64;
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
   Launcher L{h, s};
   auto glue_begin = [&](const char* what) { L.begin(K_GLUE, what); };
   auto glue_end = [&](const char* what) { L.check(hipGetLastError(), what); L.end(); };
 
-  // conv1 (model_RGB.py:230): the GSC stem kernel
-  {
-    LayerW l;
-    L.rc = find_layer(h, "conv1", 1, 7, 28, 32, &l);
-    if (L.rc == BSR_OK) {
-      bsr::StemArgs a{inputs, ws + p.x1, l.w, l.b, H, W, 0, 0, 0, nullptr};
-      L.begin(K_CONV7, "conv1");
-      L.check(bsr::launch_stem7<4, 0>(a, B, s), "conv1");
-      L.end();
-    }
-  }
+  L.stem(inputs, H, W, ws + p.x1);      // conv1 (model_RGB.py:230): the GSC stem kernel
   // down1..3 (:231-233); x2 / x3 land in their skip-concat slots (:251-252)
   L.conv<3, 3, 2, false, 2, 16, 1>(K_CONV3, "down1", ws + p.x1, 32, 0, 32, H, W, ws + p.c3, RGB_CS_C3, 128, 64, 1);
   L.conv<3, 3, 2, false, 2, 16, 1>(K_CONV3, "down2", ws + p.c3, RGB_CS_C3, 128, 64, H2, W2, ws + p.c2, RGB_CS_C2, 192, 64, 1);
@@ -1314,9 +1264,7 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
   if (B <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: H must be a positive multiple of 4 and W of 32");
   if ((long long)B * H * W * 128 * 4 >= (1LL << 31)) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: tensor too large");
   if (nw != 0 && nw != 2 && nw != 4) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: nw must be 0 (automatic), 2 or 4 waves per workgroup");
-  bsr::WinoArgs a{};
-  a.in = x; a.out = y; a.w = w; a.bias = bias; a.H = H; a.W = W; a.in_cs = 128; a.out_cs = 128; a.act = 1;
-  HIP_TRY(bsr::launch_wino_conv2(a, B, static_cast<hipStream_t>(stream), nw));
+  HIP_TRY(bsr::launch_wino_conv2(wino_args(x, y, w, bias, H, W), B, static_cast<hipStream_t>(stream), nw));
   return BSR_OK;
 }
 
@@ -1330,81 +1278,82 @@ int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* str
   return bsr_debug_attention_dtype(qkv, y, B, tokens, BSR_DTYPE_F32, stream);
 }
 
-int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, int shape4[4], void* stream) {
-  if (h == nullptr || name == nullptr || dst == nullptr || shape4 == nullptr) return fail(BSR_ERR_ARG, "bsr_probe: null argument");
-  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_probe: no forward has run on this handle");
-  DeviceGuard guard(h->device);
-  HIP_TRY(guard.err);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// bsr_probe's name tables: where a named intermediate of the last forward lies in the workspace.  half: an fp16 tensor (f16 mode).
+struct ProbeSrc { size_t off; int hh, ww, cs, coff, c; bool half; };
+
+// `prefix` followed by one digit below n: the digit, else -1
+static int probe_index(const std::string& nm, const char* prefix, int n) {
+  const size_t len = strlen(prefix);
+  if (nm.size() == len + 1 && nm.compare(0, len, prefix) == 0 && nm[len] >= '0' && nm[len] < '0' + n) return nm[len] - '0';
+  return -1;
+}
+
+static int probe_src_rgb(const bsr_handle* h, const std::string& nm, ProbeSrc* src) {
   const Plan& p = h->plan;
-  const int B = h->B, H = h->H, W = h->W;
-  struct Src { size_t off; int hh, ww, cs, coff, c; bool half; };
-  if (h->var.rgb) {      // the RGB forward's probes (its workspace plan: PlanRGB)
-    const PlanRGB& q = h->plan_rgb;
-    std::string nm(name);
-    Src src{};
-    int i = -1;
-    if (nm.size() >= 4 && nm[nm.size() - 1] >= '0' && nm[nm.size() - 1] <= '2') i = nm[nm.size() - 1] - '0';
-    const std::string stem = i >= 0 ? nm.substr(0, nm.size() - 1) : nm;
-    if (nm == "x1") src = {q.x1, H, W, 32, 0, 32, false};
-    else if (nm == "x2") src = {q.c3, H / 2, W / 2, RGB_CS_C3, 128, 64, false};
-    else if (nm == "x3") src = {q.c2, H / 4, W / 4, RGB_CS_C2, 192, 64, false};
-    else if (nm == "x0") src = {q.xa, H / 8, W / 8, RGB_CS_A, 0, 99, false};
-    else if (i >= 0 && stem == "res") src = {q.r[i], H / 8, W / 8, RGB_CS_R, 0, 513, false};
-    else if (i >= 0 && stem == "att") src = {q.att[i], H / 8, W / 8, RGB_D, 0, RGB_D, false};
-    else if (i >= 0 && stem == "y3x") src = {q.y3[i], H / 8, W / 8, RGB_CS_R, 0, 513, false};
-    else if (nm == "up1") src = {q.c2, H / 4, W / 4, RGB_CS_C2, 0, 192, false};
-    else if (nm == "up2") src = {q.c3, H / 2, W / 2, RGB_CS_C3, 0, 128, false};
-    else if (nm == "up3") src = {q.ybuf, H, W, 128, 0, 128, false};
-    else if (nm == "y") src = {q.yh, H, W, 3, 0, 3, false};
-    else if (nm == "con") src = {q.con, H, W, 3, 0, 3, false};
-    else return fail(BSR_ERR_STATE, std::string("bsr_probe: unknown probe '") + name + "' for an RGB handle");
-    const size_t npix = (size_t)B * src.hh * src.ww;
-    shape4[0] = B; shape4[1] = src.hh; shape4[2] = src.ww; shape4[3] = src.c;
-    if (npix * src.c > cap_floats) return fail(BSR_ERR_ARG, "bsr_probe: destination too small");
-    hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, s, h->ws + src.off, src.cs, src.coff,
-                       src.c, dst, npix, 0);
-    HIP_TRY(hipGetLastError());
-    return BSR_OK;
-  }
-  const bool p16 = h->dtype == BSR_DTYPE_F16;          // the tensors the f16 mode keeps as fp16 (forward_impl)
-  Src src{};
-  std::string nm(name);
-  auto res_idx = [&](const char* prefix) -> int {
-    size_t n = strlen(prefix);
-    if (nm.size() == n + 1 && nm.compare(0, n, prefix) == 0 && nm[n] >= '0' && nm[n] <= '5') return nm[n] - '0';
-    return -1;
-  };
+  const int H = h->H, W = h->W;
   int i;
-  if (nm == "x1") src = {p.x1, H, W, 32, 0, 32, p16};
-  else if (nm == "x2") src = {p.c3, H / 2, W / 2, 128, 64, 64, p16};
-  else if (nm == "x3") src = {p.c2, H / 4, W / 4, 160, 96, 64, p16};
-  else if (nm == "x0") src = {p.xa, H / 8, W / 8, h->var.cs_a, 0, h->var.c_a};
-  else if ((i = res_idx("res")) >= 0) src = {p.r[i], H / 8, W / 8, i < 3 ? h->var.cs_r : h->var.cs_h, 0, i < 3 ? h->var.c_r : h->var.c_h};
-  else if ((i = res_idx("att")) >= 0) {
+  if (nm == "x1") *src = {p.x1, H, W, 32, 0, 32};
+  else if (nm == "x2") *src = {p.c3, H / 2, W / 2, RGB_CS_C3, 128, 64};
+  else if (nm == "x3") *src = {p.c2, H / 4, W / 4, RGB_CS_C2, 192, 64};
+  else if (nm == "x0") *src = {p.xa, H / 8, W / 8, RGB_CS_A, 0, 99};
+  else if ((i = probe_index(nm, "res", 3)) >= 0) *src = {p.r[i], H / 8, W / 8, RGB_CS_R, 0, 513};
+  else if ((i = probe_index(nm, "att", 3)) >= 0) *src = {p.att[i], H / 8, W / 8, RGB_D, 0, RGB_D};
+  else if ((i = probe_index(nm, "y3x", 3)) >= 0) *src = {p.y3[i], H / 8, W / 8, RGB_CS_R, 0, 513};
+  else if (nm == "up1") *src = {p.c2, H / 4, W / 4, RGB_CS_C2, 0, 192};
+  else if (nm == "up2") *src = {p.c3, H / 2, W / 2, RGB_CS_C3, 0, 128};
+  else if (nm == "up3") *src = {p.ybuf, H, W, 128, 0, 128};
+  else if (nm == "y") *src = {p.yh, H, W, 3, 0, 3};
+  else if (nm == "con") *src = {p.con, H, W, 3, 0, 3};
+  else return fail(BSR_ERR_STATE, "bsr_probe: unknown probe '" + nm + "' for an RGB handle");
+  return BSR_OK;
+}
+
+static int probe_src_gsc(const bsr_handle* h, const std::string& nm, ProbeSrc* src) {
+  const Plan& p = h->plan;
+  const Variant& v = h->var;
+  const int H = h->H, W = h->W;
+  const bool p16 = h->dtype == BSR_DTYPE_F16;          // the tensors the f16 mode keeps as fp16 (forward_impl)
+  int i;
+  if (nm == "x1") *src = {p.x1, H, W, 32, 0, 32, p16};
+  else if (nm == "x2") *src = {p.c3, H / 2, W / 2, 128, 64, 64, p16};
+  else if (nm == "x3") *src = {p.c2, H / 4, W / 4, 160, 96, 64, p16};
+  else if (nm == "x0") *src = {p.xa, H / 8, W / 8, v.cs_a, 0, v.c_a};
+  else if ((i = probe_index(nm, "res", 6)) >= 0) *src = {p.r[i], H / 8, W / 8, i < 3 ? v.cs_r : v.cs_h, 0, i < 3 ? v.c_r : v.c_h};
+  else if ((i = probe_index(nm, "att", 6)) >= 0) {
     // fused attention + w (fp32, full batches): the attention output stays in LDS, the att<i> slots hold whatever an earlier
     // forward left there — refuse rather than hand out stale data
     if (h->att_in_lds)
       return fail(BSR_ERR_STATE, "bsr_probe: att<i> does not exist for the last forward — attention and the `w` GEMM ran as one launch and the "
                                  "attention output never left LDS (create the handle with BSR_FUSE_ATTW=0 in the environment to probe it)");
-    src = {p.att[i], H / 8, W / 8, 128, 0, 128};
+    *src = {p.att[i], H / 8, W / 8, 128, 0, 128};
   }
-  else if ((i = res_idx("y3x")) >= 0) src = {p.y3[i], H / 8, W / 8, CS_Y3X, 0, CS_Y3X};
-  else if (nm == "up1") src = {p.c2, H / 4, W / 4, 160, 0, 96, p16};
-  else if (nm == "up2") src = {p.c3, H / 2, W / 2, 128, 0, 64, p16};
-  else if (nm == "y") src = {p.ybuf, H, W, 64, 0, 64, p16};
-  else if (nm == "d32") src = {p.probe, H / 8, W / 8, 2, 0, 1};
-  else if (nm == "bmask") src = {p.probe, H / 8, W / 8, 2, 1, 1};
-  else if (nm == "xh") src = {p.xh, H / 8, W / 8, h->var.cs_h, 0, h->var.c_h};
-  else if (nm == "f1") src = {p.f1, H / 4, W / 4, 128, 0, 128, p16};
-  else if (nm == "f2") src = {p.f2, H / 2, W / 2, 96, 0, 96, p16};
-  else if (nm == "f") src = {p.cf, H, W, CS_CF, 0, 64, p16};
-  else return fail(BSR_ERR_STATE, std::string("bsr_probe: unknown probe '") + name + "'");
-  const size_t npix = (size_t)B * src.hh * src.ww;
-  shape4[0] = B; shape4[1] = src.hh; shape4[2] = src.ww; shape4[3] = src.c;
+  else if ((i = probe_index(nm, "y3x", 6)) >= 0) *src = {p.y3[i], H / 8, W / 8, CS_Y3X, 0, CS_Y3X};
+  else if (nm == "up1") *src = {p.c2, H / 4, W / 4, 160, 0, 96, p16};
+  else if (nm == "up2") *src = {p.c3, H / 2, W / 2, 128, 0, 64, p16};
+  else if (nm == "y") *src = {p.ybuf, H, W, 64, 0, 64, p16};
+  else if (nm == "d32") *src = {p.probe, H / 8, W / 8, 2, 0, 1};
+  else if (nm == "bmask") *src = {p.probe, H / 8, W / 8, 2, 1, 1};
+  else if (nm == "xh") *src = {p.xh, H / 8, W / 8, v.cs_h, 0, v.c_h};
+  else if (nm == "f1") *src = {p.f1, H / 4, W / 4, 128, 0, 128, p16};
+  else if (nm == "f2") *src = {p.f2, H / 2, W / 2, 96, 0, 96, p16};
+  else if (nm == "f") *src = {p.cf, H, W, CS_CF, 0, 64, p16};
+  else return fail(BSR_ERR_STATE, "bsr_probe: unknown probe '" + nm + "'");
+  return BSR_OK;
+}
+
+int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, int shape4[4], void* stream) {
+  if (h == nullptr || name == nullptr || dst == nullptr || shape4 == nullptr) return fail(BSR_ERR_ARG, "bsr_probe: null argument");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_probe: no forward has run on this handle");
+  DeviceGuard guard(h->device);
+  HIP_TRY(guard.err);
+  ProbeSrc src{};
+  const int rc = h->var.rgb ? probe_src_rgb(h, name, &src) : probe_src_gsc(h, name, &src);
+  if (rc != BSR_OK) return rc;
+  const size_t npix = (size_t)h->B * src.hh * src.ww;
+  shape4[0] = h->B; shape4[1] = src.hh; shape4[2] = src.ww; shape4[3] = src.c;
   if (npix * src.c > cap_floats) return fail(BSR_ERR_ARG, "bsr_probe: destination too small");
-  hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, s, h->ws + src.off, src.cs, src.coff,
-                     src.c, dst, npix, src.half ? 1 : 0);
+  hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     h->ws + src.off, src.cs, src.coff, src.c, dst, npix, src.half ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
 }

@@ -23,6 +23,8 @@ from .tf_bundle import latest_checkpoint, load_generator_weights
 
 
 class Generator:
+    _NAME = "Generator"      # the class name the "no weights" refusal states (GeneratorTSM says Generator too)
+
     def __init__(self, downsize: int = 1, n_res: int = 6, device: Optional[int] = None, dtype: str = "f32"):
         """``dtype``: "f32" (fp32 matrix cores — the measured path and the default), "f32x3" (split-precision fp32 on the fp16 matrix
         cores: same end-to-end tolerance, ~1.9x faster, activations must stay below 65520 in magnitude — a violation is detected on
@@ -79,6 +81,29 @@ class Generator:
             pass
 
     # -- forward ----------------------------------------------------------------------------
+    def _require_weights(self) -> None:
+        if self._handle is None:
+            raise RuntimeError("%s has no weights: call load_weights() or restore() first" % self._NAME)
+
+    def _prepare(self, inputs, uv, same_size: bool = True):
+        """The checks every forward starts with, in their order; returns (dev, inputs, uv, B, H, W) with both tensors on the device.
+        ``same_size=False``: the TSM path, which checks ``reg`` next and then states its own (square) size rule."""
+        self._require_weights()
+        dev = self._device
+        inputs = self._check_input(inputs, "inputs", dev)
+        uv = self._check_input(uv, "uv", dev)
+        B, H, W, _ = inputs.shape
+        if same_size:
+            if uv.shape != inputs.shape:
+                raise ValueError("inputs %s and uv %s must have the same shape" % (tuple(inputs.shape), tuple(uv.shape)))
+            if H % 32 or W % 256:
+                raise ValueError("H must be a multiple of 32 and W of 256 (reference IMG_SIZE = 256), got %dx%d" % (H, W))
+        return dev, inputs, uv, B, H, W
+
+    @staticmethod
+    def _new_outputs(B: int, H: int, W: int, device):
+        return tuple(torch.empty((B, H, W, c), dtype=torch.float32, device=device) for c in (1, 3, 3, 1))      # gs, con_rgb, mask22, dif
+
     def _check_input(self, t: torch.Tensor, name: str, dev: int) -> torch.Tensor:
         if not isinstance(t, torch.Tensor):
             t = torch.as_tensor(np.asarray(t))
@@ -113,24 +138,9 @@ class Generator:
         if training:
             raise NotImplementedError("only the inference path (training=False) is implemented "
                                       "(/root/reference/train_test_GSC.py:404,856)")
-        if self._handle is None:
-            raise RuntimeError("Generator has no weights: call load_weights() or restore() first")
-        dev = self._device
-        inputs = self._check_input(inputs, "inputs", dev)
-        uv = self._check_input(uv, "uv", dev)
-        if uv.shape != inputs.shape:
-            raise ValueError("inputs %s and uv %s must have the same shape" % (tuple(inputs.shape), tuple(uv.shape)))
-        B, H, W, _ = inputs.shape
-        if H % 32 or W % 256:
-            raise ValueError("H must be a multiple of 32 and W of 256 (reference IMG_SIZE = 256), got %dx%d" % (H, W))
+        dev, inputs, uv, B, H, W = self._prepare(inputs, uv)
         with torch.cuda.device(dev):
-            if out is None:
-                gs = torch.empty((B, H, W, 1), dtype=torch.float32, device=inputs.device)
-                con_rgb = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
-                mask22 = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
-                dif = torch.empty((B, H, W, 1), dtype=torch.float32, device=inputs.device)
-            else:
-                gs, con_rgb, mask22, dif = self._check_out(out, B, H, W, dev)
+            gs, con_rgb, mask22, dif = self._new_outputs(B, H, W, inputs.device) if out is None else self._check_out(out, B, H, W, dev)
             stream = torch.cuda.current_stream().cuda_stream
             if packed_out is not None:
                 if (not isinstance(packed_out, torch.Tensor) or tuple(packed_out.shape) != (B, H, W, 4) or packed_out.dtype != torch.float32
@@ -152,26 +162,18 @@ class Generator:
         (call site /root/reference/train_with_TSM.py:676).  Needs TSM weights (291-channel ``res_stack/0/conv1``)."""
         if training:
             raise NotImplementedError("only the inference path (training=False) is implemented")
-        if self._handle is None:
-            raise RuntimeError("Generator has no weights: call load_weights() or restore() first")
-        dev = self._device
-        inputs = self._check_input(inputs, "inputs", dev)
-        uv = self._check_input(uv, "uv", dev)
+        dev, inputs, uv, B, H, W = self._prepare(inputs, uv, same_size=False)
         if not isinstance(reg, torch.Tensor):
             reg = torch.as_tensor(np.asarray(reg))
         if reg.dim() != 4 or reg.shape[-1] != 6 or reg.shape[:3] != inputs.shape[:3] or reg.dtype != torch.float32:
             raise ValueError("reg must be float32 [B,H,W,6] (reg_in | reg_out), got %s %s" % (tuple(reg.shape), reg.dtype))
         reg = reg.to("cuda:%d" % dev).contiguous()
-        B, H, W, _ = inputs.shape
         if H != W or H % 256:
             raise ValueError("the TSM path needs square images with H a multiple of 256, got %dx%d" % (H, W))
         if frame <= 0 or B % frame:
             raise ValueError("batch %d is not a multiple of frame %d" % (B, frame))
         with torch.cuda.device(dev):
-            gs = torch.empty((B, H, W, 1), dtype=torch.float32, device=inputs.device)
-            con_rgb = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
-            mask22 = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
-            dif = torch.empty((B, H, W, 1), dtype=torch.float32, device=inputs.device)
+            gs, con_rgb, mask22, dif = self._new_outputs(B, H, W, inputs.device)
             stream = torch.cuda.current_stream().cuda_stream
             rc = self._lib.bsr_forward_tsm(self._handle, inputs.data_ptr(), uv.data_ptr(), reg.data_ptr(), B, H, W, int(frame), 1 if share else 0,
                                            gs.data_ptr(), con_rgb.data_ptr(), mask22.data_ptr(), dif.data_ptr(), stream)
@@ -184,8 +186,7 @@ class Generator:
         the last call converted an activation of magnitude >= 65520 to fp16 (its outputs hold inf / NaN where the fp32 path stays
         finite: discard them and re-run on a ``dtype="f32"`` generator).  The kernels detect this on the device (bsr_check_range in
         include/bsr_hip.h); without a call the NEXT forward after a completed overflowing one raises instead.  No-op for "f32"."""
-        if self._handle is None:
-            raise RuntimeError("Generator has no weights: call load_weights() or restore() first")
+        self._require_weights()
         with torch.cuda.device(self._device):
             rc = self._lib.bsr_check_range(self._handle, torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "bsr_check_range")
@@ -193,8 +194,7 @@ class Generator:
     def peek_range(self) -> None:
         """``check_range`` for a pipelined caller: no stream synchronisation and the condition is not cleared — raises
         ``_lib.RangeError`` if any forward that has COMPLETED so far overflowed fp16 (bsr_peek_range).  No-op for "f32"."""
-        if self._handle is None:
-            raise RuntimeError("Generator has no weights: call load_weights() or restore() first")
+        self._require_weights()
         _lib.check(self._lib.bsr_peek_range(self._handle), "bsr_peek_range")
 
     # -- test / measurement hooks -----------------------------------------------------------
@@ -253,6 +253,7 @@ class GeneratorRGB(Generator):
         con = gen(inputs, uv, reg, chuck=4, training=False)
 
     ``reg`` and ``chuck`` are accepted and unused, as in the reference's ``call``.  fp32 only (``dtype="f32"``)."""
+    _NAME = "GeneratorRGB"
 
     def __init__(self, downsize: int = 1, n_res: int = 6, device: Optional[int] = None, dtype: str = "f32"):
         if dtype != "f32":
@@ -270,16 +271,7 @@ class GeneratorRGB(Generator):
         """``out``: optional caller-supplied [B,H,W,3] float32 CUDA tensor for ``con``.  Returns ``con`` [B,H,W,3]."""
         if training:
             raise NotImplementedError("only the inference path (training=False) is implemented (/root/reference/train_RGB_test.py:414)")
-        if self._handle is None:
-            raise RuntimeError("GeneratorRGB has no weights: call load_weights() or restore() first")
-        dev = self._device
-        inputs = self._check_input(inputs, "inputs", dev)
-        uv = self._check_input(uv, "uv", dev)
-        if uv.shape != inputs.shape:
-            raise ValueError("inputs %s and uv %s must have the same shape" % (tuple(inputs.shape), tuple(uv.shape)))
-        B, H, W, _ = inputs.shape
-        if H % 32 or W % 256:
-            raise ValueError("H must be a multiple of 32 and W of 256 (reference IMG_SIZE = 256), got %dx%d" % (H, W))
+        dev, inputs, uv, B, H, W = self._prepare(inputs, uv)
         with torch.cuda.device(dev):
             if out is None:
                 con = torch.empty((B, H, W, 3), dtype=torch.float32, device=inputs.device)
@@ -296,8 +288,7 @@ class GeneratorRGB(Generator):
 
     def reserve(self, B: int, H: int, W: int) -> None:
         """Allocate the workspace for forwards up to [B,H,W] now: later forwards of that size allocate nothing (bsr_reserve)."""
-        if self._handle is None:
-            raise RuntimeError("GeneratorRGB has no weights: call load_weights() or restore() first")
+        self._require_weights()
         _lib.check(self._lib.bsr_reserve(self._handle, int(B), int(H), int(W)), "bsr_reserve")
 
     def workspace_bytes(self, B: int, H: int, W: int) -> int:
