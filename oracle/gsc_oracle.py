@@ -300,11 +300,17 @@ class GeneratorTSMOracle(GeneratorOracle):
             probes.update(x1=x1, x2=x2, x3=x3, x_share1=x_share, x0=x)
         for i in range(self.n_res // 2):
             x = self.res_bottleneck(x, i, probes)
-        if probes is not None:
-            probes["res2"] = x
+            if probes is not None:
+                probes["res%d" % i] = x
         y = self.convt_block(x, "up1")
+        if probes is not None:
+            probes["up1"] = y
         y = self.convt_block(torch.cat([y, x3], dim=3), "up2")
+        if probes is not None:
+            probes["up2"] = y
         y = self.convt_block(torch.cat([y, x2], dim=3), "up3")
+        if probes is not None:
+            probes["y"] = y
         gs, mask22, dif, d32 = self.heads(y, inputs)
         bmask = (d32 > BMASK_THRESHOLD).to(self.dtype)                        # :289
         if probes is not None:
@@ -315,12 +321,12 @@ class GeneratorTSMOracle(GeneratorOracle):
         x_share = share_layer(x_hole, reg, frame, share)                      # :292
         x = torch.cat([x_hole, bmask, x_share, uv_s], dim=3)                  # :293
         if probes is not None:
-            probes.update(x_share2=x_share)
+            probes.update(x_share2=x_share, xh=x)
         for i in range(self.n_res // 2, self.n_res):
             x = self.res_bottleneck(x, i, probes)
-        if probes is not None:
-            probes["res5"] = x
-        f = self.colour_decoder(x)
+            if probes is not None:
+                probes["res%d" % i] = x
+        f = self.colour_decoder(x, probes)
         con_rgb, dif2 = self.colour_tail(gs, f, inputs)
         return gs, con_rgb, mask22, dif2
 
