@@ -26,6 +26,7 @@
 #include "igemm_h16.h"
 #include "png_kernels.h"
 #include "prep_kernels.h"
+#include "prep_group_kernels.h"
 #include "rgb_head.h"
 #include "stem7.h"
 #include "ucb_kernels.h"
@@ -1086,7 +1087,34 @@ int bsr_prep_rows(int device, const void* d_blob, size_t blob_bytes, size_t rows
   hipLaunchKernelGGL(bsr::prep_rows_kernel, grid, dim3(256), 0, s, blob, reinterpret_cast<const bsr::PrepRow*>(blob + rows_off),
                      reinterpret_cast<const double*>(blob + grid_off), S, out, hull_tmp);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bsr::prep_blur_kernel, grid, dim3(256), 0, s, hull_tmp, S, out);
+  hipLaunchKernelGGL(bsr::prep_blur_kernel, grid, dim3(256), 0, s, hull_tmp, S, 16, out);
+  HIP_TRY(hipGetLastError());
+  return BSR_OK;
+}
+
+int bsr_prep_groups(int device, const void* d_blob, size_t blob_bytes, size_t groups_off, size_t grid_off, int B, int S, int planes, float* out,
+                    float* hull_tmp, void* stream) {
+  if (d_blob == nullptr || out == nullptr || hull_tmp == nullptr) return fail(BSR_ERR_ARG, "bsr_prep_groups: null argument");
+  if (B <= 0 || S <= 0 || (S * S) % 256 != 0) return fail(BSR_ERR_ARG, "bsr_prep_groups: B must be positive and S*S a multiple of 256");
+  if (planes != 6 && planes != 7) return fail(BSR_ERR_ARG, "bsr_prep_groups: planes must be 6 (img3, gt3) or 7 (img3, cmap3, label1)");
+  if (groups_off % 8 != 0 || grid_off % 8 != 0) return fail(BSR_ERR_ARG, "bsr_prep_groups: table offsets must be 8-byte aligned");
+  // as in bsr_prep_rows: the two tables the kernels index directly must lie inside the blob; prep.py validates what the records point to
+  if (groups_off > blob_bytes || (size_t)B * sizeof(bsr::PrepGroup) > blob_bytes - groups_off || grid_off > blob_bytes ||
+      (size_t)S * sizeof(double) > blob_bytes - grid_off)
+    return fail(BSR_ERR_ARG, "bsr_prep_groups: the group / grid tables do not fit in blob_bytes");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned char* blob = static_cast<const unsigned char*>(d_blob);
+  const bsr::PrepGroup* groups = reinterpret_cast<const bsr::PrepGroup*>(blob + groups_off);
+  const double* lin = reinterpret_cast<const double*>(blob + grid_off);
+  const dim3 grid((unsigned)(S * S / 256), (unsigned)B);
+  if (planes == 6)
+    hipLaunchKernelGGL(bsr::prep_groups_kernel<6>, grid, dim3(256), 0, s, blob, groups, lin, S, out, hull_tmp);
+  else
+    hipLaunchKernelGGL(bsr::prep_groups_kernel<7>, grid, dim3(256), 0, s, blob, groups, lin, S, out, hull_tmp);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(bsr::prep_blur_kernel, dim3((unsigned)(S * S / 256), 2u * (unsigned)B), dim3(256), 0, s, hull_tmp, S, planes + 10, out);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
 }

@@ -37,61 +37,17 @@ struct PrepRow {            // one row of the batch; offsets are bytes from the 
   int32_t ntri[4];
 };
 
-// kernel 1: everything but the blur.  grid (S*S / 256, B); block 256.  hull: [B][S][S] raw hull mask (0 / 1) for kernel 2.
-__global__ __launch_bounds__(256) void prep_rows_kernel(const unsigned char* __restrict__ blob, const PrepRow* __restrict__ rows,
-                                                        const double* __restrict__ grid, int S, float* __restrict__ out, float* __restrict__ hull) {
-  __shared__ double s_tri[kPrepMaxTri * kPrepTriDoubles];
-  __shared__ int s_cnt[4];
-  const PrepRow& row = rows[blockIdx.y];                        // read in place (wave-uniform scalar loads): a private copy indexed by the mesh number would live in scratch
-  const int bpr = S / 16;                                       // S * S % 256 == 0 <=> S % 16 == 0 (checked by bsr_prep_rows)
-  const int by = blockIdx.x / bpr, bx = blockIdx.x % bpr;
-  const int oy = by * 16 + (threadIdx.x >> 4), ox = bx * 16 + (threadIdx.x & 15);
-  const int pix = oy * S + ox;
-  float* o = out + ((size_t)blockIdx.y * S * S + pix) * 16;
-
-  // ---- crop + INTER_LINEAR resize of image and ground truth (dataset.resize_linear: float64, (1-w) a + w b per axis, x first) ----
-  {
-    const int n = row.box[2] - row.box[0];                        // the crop is square: side 2 * int(length)
-    const double scale = (double)n / (double)S;
-    auto axis = [&](int oidx, int& i0, int& i1, double& wgt) {
-      double src = ((double)oidx + 0.5) * scale - 0.5;
-      src = src > 0.0 ? src : 0.0;
-      int f = (int)floor(src);
-      i0 = f < n - 1 ? f : n - 1;
-      i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
-      wgt = src - (double)i0;
-    };
-    int y0, y1, x0, x1;
-    double wy, wx;
-    axis(oy, y0, y1, wy);
-    axis(ox, x0, x1, wx);
-    auto tap = [&](const unsigned char* im, int cy, int cx, int c) -> double {      // crop pixel (cy, cx): image pixel or 0 outside
-      const int iy = cy + row.box[1], ix = cx + row.box[0];
-      if (iy < 0 || iy >= row.h || ix < 0 || ix >= row.w) return 0.0;
-      return (double)im[((size_t)iy * row.w + ix) * 3 + c] / 255.0;
-    };
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      const unsigned char* im = blob + (which ? row.gt_off : row.img_off);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        double v = 0.0;
-        if (n > 0) {
-          const double top = tap(im, y0, x0, c) * (1.0 - wx) + tap(im, y0, x1, c) * wx;
-          const double bot = tap(im, y1, x0, c) * (1.0 - wx) + tap(im, y1, x1, c) * wx;
-          v = top * (1.0 - wy) + bot * wy;
-        }
-        o[which * 3 + c] = (float)v;
-      }
-    }
-  }
-
-  // ---- the four meshes ----
-  const double px = grid[ox], py = grid[oy];                      // np.meshgrid(linspace(0,1,S), linspace(0,1,S)): x varies along columns
+// The four meshes of ONE set of landmarks at the grid point (px, py) of the calling thread, whose workgroup covers the 16x16-pixel block
+// (by, bx): tri_off / ntri are the four entries of a record, read in place (wave-uniform scalar loads: a private copy indexed by the mesh
+// number would live in scratch).  o: the pixel's nine interpolated channels (uvm3, reg_in3, reg_out3); hull_px: its raw hull value (0 / 1)
+// for the blur.  Shared by the row kernel and the group kernel (csrc/prep_group_kernels.h), so that a row both compute has the same bits.
+__device__ __forceinline__ void prep_meshes(const unsigned char* __restrict__ blob, const int64_t* tri_off, const int32_t* ntri,
+                                            const double* __restrict__ grid, int bx, int by, double px, double py, double* s_tri, int* s_cnt,
+                                            float* __restrict__ o, float* __restrict__ hull_px) {
 #pragma unroll 1
   for (int m = 0; m < 4; ++m) {
-    const int nt = row.ntri[m] < kPrepMaxTri ? row.ntri[m] : kPrepMaxTri;
-    const double* t = reinterpret_cast<const double*>(blob + row.tri_off[m]);
+    const int nt = ntri[m] < kPrepMaxTri ? ntri[m] : kPrepMaxTri;
+    const double* t = reinterpret_cast<const double*>(blob + tri_off[m]);
     __syncthreads();                                              // the previous mesh's triangles are no longer read
     // triangle threadIdx.x against this block's box [gx0, gx1] x [gy0, gy1] (grid is increasing): keep it unless an edge function is
     // below -1e-9 on the whole box (its maximum over a box is at a corner)
@@ -146,23 +102,77 @@ __global__ __launch_bounds__(256) void prep_rows_kernel(const unsigned char* __r
     const double z2 = (cf[6] * px + cf[7] * py) + cf[8];
     const double nan = __builtin_nan("");
     if (m == 0) {                       // uv map: np.nan_to_num -> 0 outside the landmark hull (warp.py:231)
-      o[6] = inside ? (float)z0 : 0.f;
-      o[7] = inside ? (float)z1 : 0.f;
-      o[8] = inside ? (float)z2 : 0.f;
+      o[0] = inside ? (float)z0 : 0.f;
+      o[1] = inside ? (float)z1 : 0.f;
+      o[2] = inside ? (float)z2 : 0.f;
     } else if (m == 1 || m == 2) {      // offset maps: [my, mx, mx * 0], NOT nan_to_num'ed (warp.py:212-213; the anchors cover the square)
       const double my = inside ? z0 : nan, mx = inside ? z1 : nan;
-      o[6 + 3 * m] = (float)my;
-      o[7 + 3 * m] = (float)mx;
-      o[8 + 3 * m] = (float)(mx * 0.0);
+      o[3 * m] = (float)my;
+      o[1 + 3 * m] = (float)mx;
+      o[2 + 3 * m] = (float)(mx * 0.0);
     } else {                            // face hull: interpolated x coordinate > 0 (utils.py:272-273; nan -> 0 -> false)
-      hull[(size_t)blockIdx.y * S * S + pix] = (inside && z0 > 0.0) ? 1.f : 0.f;
+      *hull_px = (inside && z0 > 0.0) ? 1.f : 0.f;
     }
   }
 }
 
+// kernel 1: everything but the blur.  grid (S*S / 256, B); block 256.  hull: [B][S][S] raw hull mask (0 / 1) for kernel 2.
+__global__ __launch_bounds__(256) void prep_rows_kernel(const unsigned char* __restrict__ blob, const PrepRow* __restrict__ rows,
+                                                        const double* __restrict__ grid, int S, float* __restrict__ out, float* __restrict__ hull) {
+  __shared__ double s_tri[kPrepMaxTri * kPrepTriDoubles];
+  __shared__ int s_cnt[4];
+  const PrepRow& row = rows[blockIdx.y];                        // read in place (wave-uniform scalar loads): a private copy indexed by the mesh number would live in scratch
+  const int bpr = S / 16;                                       // S * S % 256 == 0 <=> S % 16 == 0 (checked by bsr_prep_rows)
+  const int by = blockIdx.x / bpr, bx = blockIdx.x % bpr;
+  const int oy = by * 16 + (threadIdx.x >> 4), ox = bx * 16 + (threadIdx.x & 15);
+  const int pix = oy * S + ox;
+  float* o = out + ((size_t)blockIdx.y * S * S + pix) * 16;
+
+  // ---- crop + INTER_LINEAR resize of image and ground truth (dataset.resize_linear: float64, (1-w) a + w b per axis, x first) ----
+  {
+    const int n = row.box[2] - row.box[0];                        // the crop is square: side 2 * int(length)
+    const double scale = (double)n / (double)S;
+    auto axis = [&](int oidx, int& i0, int& i1, double& wgt) {
+      double src = ((double)oidx + 0.5) * scale - 0.5;
+      src = src > 0.0 ? src : 0.0;
+      int f = (int)floor(src);
+      i0 = f < n - 1 ? f : n - 1;
+      i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+      wgt = src - (double)i0;
+    };
+    int y0, y1, x0, x1;
+    double wy, wx;
+    axis(oy, y0, y1, wy);
+    axis(ox, x0, x1, wx);
+    auto tap = [&](const unsigned char* im, int cy, int cx, int c) -> double {      // crop pixel (cy, cx): image pixel or 0 outside
+      const int iy = cy + row.box[1], ix = cx + row.box[0];
+      if (iy < 0 || iy >= row.h || ix < 0 || ix >= row.w) return 0.0;
+      return (double)im[((size_t)iy * row.w + ix) * 3 + c] / 255.0;
+    };
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+      const unsigned char* im = blob + (which ? row.gt_off : row.img_off);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        if (n > 0) {
+          const double top = tap(im, y0, x0, c) * (1.0 - wx) + tap(im, y0, x1, c) * wx;
+          const double bot = tap(im, y1, x0, c) * (1.0 - wx) + tap(im, y1, x1, c) * wx;
+          v = top * (1.0 - wy) + bot * wy;
+        }
+        o[which * 3 + c] = (float)v;
+      }
+    }
+  }
+
+  // ---- the four meshes ----
+  prep_meshes(blob, row.tri_off, row.ntri, grid, bx, by, grid[ox], grid[oy], s_tri, s_cnt, o + 6, hull + (size_t)blockIdx.y * S * S + pix);
+}
+
 // kernel 2: cv2.GaussianBlur(mask, (5,5), 0) = [1,4,6,4,1]/16 separable, BORDER_REFLECT_101, columns first then rows as
-// dataset.gaussian_blur5 sums them (float64) -> channel 15
-__global__ __launch_bounds__(256) void prep_blur_kernel(const float* __restrict__ hull, int S, float* __restrict__ out) {
+// dataset.gaussian_blur5 sums them (float64) -> the last of the C channels of a pixel (15 of a row's 16; C - 1 of a group's 16 / 17).
+// grid (S*S / 256, planes of hull)
+__global__ __launch_bounds__(256) void prep_blur_kernel(const float* __restrict__ hull, int S, int C, float* __restrict__ out) {
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int oy = pix / S, ox = pix % S;
   const float* hm = hull + (size_t)blockIdx.y * S * S;
@@ -177,7 +187,7 @@ __global__ __launch_bounds__(256) void prep_blur_kernel(const float* __restrict_
     for (int j = 0; j < 5; ++j) tmp = tmp + k[j] * (double)hm[(size_t)yy * S + refl(ox + j - 2)];
     acc = acc + k[i] * tmp;
   }
-  out[((size_t)blockIdx.y * S * S + pix) * 16 + 15] = (float)acc;
+  out[((size_t)blockIdx.y * S * S + pix) * C + (C - 1)] = (float)acc;
 }
 
 // ---- PNG scanline reconstruction on the device (round 6) ----

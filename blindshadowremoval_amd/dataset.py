@@ -366,6 +366,10 @@ def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One dataset element `(img[1,R,size,size,16], box[1,4], name[1])` from a job `(lm_path, gt_path, sibling lm paths, size)`.
     Top-level so that worker processes can run it (the rows of an element never depend on another element)."""
     lm_path, gt_path, siblings, size = job[:4]
+    if isinstance(gt_path, tuple) and gt_path[0] == "<device_group>":      # the host half of a device-prepared TSM group (prep.host_part_group)
+        from .prep import host_part_group, host_part_ring
+        hjob = (lm_path, gt_path[1], size) + ((gt_path[2],) if len(gt_path) > 2 else ())
+        return host_part_ring(hjob, job[4], group=True) if len(job) > 4 else host_part_group(hjob)
     if isinstance(gt_path, tuple) and gt_path[0] == "<device>":            # the host half of a device-prepared row (prep.py)
         from .prep import host_part, host_part_ring
         hjob = (lm_path, gt_path[1], size) + ((gt_path[2],) if len(gt_path) > 2 else ())
@@ -398,7 +402,8 @@ class Dataset:
     min(cpu_count, 16)."""
 
     def __init__(self, config, mode: str = "test", dset=None, ucb: bool = False, rows: int = 1, seed: int = 0,
-                 workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16):
+                 workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16,
+                 device_groups: Optional[int] = None):
         if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc", "ucb_tsm"):
             raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video' | 'ucb_tsm'); "
                                       "training loaders are out of scope")
@@ -414,7 +419,7 @@ class Dataset:
         self.workers = int(workers)
         # elements the workers may run ahead of the consumer: two per worker on the host path; four with device preparation, whose
         # consumer (the pipelined FSRNet loop) spends milliseconds at a time away from the feed
-        self.prefetch = int(prefetch) if prefetch is not None else max(2, (4 if device_prep is not None else 2) * self.workers)
+        self.prefetch = int(prefetch) if prefetch is not None else max(2, (4 if (device_prep is not None or device_groups is not None) else 2) * self.workers)
         self._pool = None
         # device_prep = GPU index: rows are prepared ON THE DEVICE (prep.py / csrc/prep_kernels.h) in groups of `device_batch`; the
         # workers then only decode PNGs and triangulate, and `feed` yields (img CUDA tensor [1,1,S,S,16], box[1,4], name) — the
@@ -422,6 +427,20 @@ class Dataset:
         self.device_prep, self.device_batch = device_prep, int(device_batch)
         if device_prep is not None and (rows != 1 or dset is not None):
             raise NotImplementedError("device_prep prepares row 0 of the GSC loaders (rows=1, dset=None)")
+        # device_groups = GPU index: the TSM loaders' groups of two rows (dset='ucb_tsm' | 'sfw': an item and its mirror image) are
+        # prepared on the device (prep.host_part_group / csrc/prep_group_kernels.h, bsr_prep_groups); `feed` yields (img CUDA tensor
+        # [1,2,S,S,16 | 17], box[1,4], name[, masks]) — build_ucb_tsm_pair's / build_sfw_pair's values to 1e-6
+        self.device_groups = device_groups
+        if device_groups is not None:
+            if device_prep is not None:
+                raise ValueError("device_prep and device_groups are two loaders' switches: pass one")
+            if dset is None:
+                raise NotImplementedError("device_groups prepares the TSM loaders' groups (dset='ucb_tsm' | 'sfw'); the GSC loaders' rows "
+                                          "(dset=None) are prepared by device_prep")
+            if dset not in ("ucb_tsm", "sfw"):
+                raise NotImplementedError("device_groups prepares the groups of dset='ucb_tsm' and dset='sfw'; dset=%r (%s) has no device "
+                                          "preparation" % (dset, "a chain of resizes per row" if dset == "sfw_gsc" else "ten frames per element"))
+        self._device = device_prep if device_prep is not None else device_groups       # the GPU the elements are prepared on, or None
         self.ucb_mask_files: Optional[List[Dict[str, str]]] = None       # per item of name_list: the seven mask paths (FSRNet.test sets it; device_prep only)
         # round 6: PNG scanline reconstruction on the device (prep.host_part_ring / bsr_png_unfilter) instead of in the workers.  None =
         # where it pays: the UCB loop (two photographs and seven masks per item: the loop waits for its loader; +5-10 % measured) and not
@@ -459,8 +478,15 @@ class Dataset:
         lo, hi = self._shard if self._shard is not None else (0, len(self.name_list))
         if self.dset is not None:                                          # TSM loaders: the element is a group of 2 / 10 coupled frames
             kind = ("<sfw_gsc>", self.rows) if self.dset == "sfw_gsc" else "<" + self.dset + ">"          # GSC SFW: `rows` rows of a chain
-            for label in self.name_list[lo:hi]:
-                yield (label, ("<ucb_tsm>", self._gt_path(label)) if self.dset == "ucb_tsm" else kind, [], size)
+            for i, label in enumerate(self.name_list[lo:hi], lo):
+                if self.device_groups is not None:
+                    # as for the GSC rows below: FSRNetTSM.test's mask files are decoded by the worker that reads the item
+                    masks = self.ucb_mask_files[i] if self.ucb_mask_files is not None and self.dset == "ucb_tsm" else None
+                    what = ("<device_group>", self._gt_path(label)) + ((masks,) if masks is not None else ()) if self.dset == "ucb_tsm" \
+                        else ("<device_group>", "<sfw>")
+                    yield self._ring_job((label, what, [], size), masks is not None)
+                else:
+                    yield (label, ("<ucb_tsm>", self._gt_path(label)) if self.dset == "ucb_tsm" else kind, [], size)
             return
         for i, lm_path in enumerate(self.name_list):
             if i >= hi:
@@ -476,27 +502,30 @@ class Dataset:
                 # ucb_mask_files (set by FSRNet.test for its device post-processing): the item's seven mask PNGs are decoded by the same
                 # worker that decodes its image, and travel bit-packed
                 masks = self.ucb_mask_files[i] if self.ucb_mask_files is not None else None
-                job = (lm_path, ("<device>", gt) + ((masks,) if masks is not None else ()), sibs, size)
-                ring = getattr(self, "_ring", None)
-                if ring is not None:
-                    # the k-th device job of this Dataset writes slot k mod nslots; that slot last held job k - nslots, whose batch has
-                    # been handed to the copy engine long ago (nslots >= prefetch + 3 batches) — its copy must have FINISHED
-                    k = self._ring_seq
-                    self._ring_seq += 1
-                    if k >= ring.nslots:
-                        while self._ring_copies and self._ring_copies[0][0] <= k - ring.nslots:       # batches that ended before that job: older copies
-                            self._ring_copies.pop(0)
-                        if not self._ring_copies:
-                            raise RuntimeError("loader ring: slot %d is still waiting for its batch (ring of %d slots too small)" % (k % ring.nslots, ring.nslots))
-                        if not self._ring_copies[0][2]:
-                            self._ring_copies[0][1].synchronize()
-                            self._ring_copies[0][2] = True
-                    unf = self.device_unfilter if self.device_unfilter is not None else (self.ucb and masks is not None)
-                    unf = {"0": False, "1": True}.get(os.environ.get("BSR_DEVICE_UNFILTER", ""), unf)
-                    job = job + ((ring.path_for_workers, k % ring.nslots, ring.cap, bool(unf)),)
-                yield job
+                yield self._ring_job((lm_path, ("<device>", gt) + ((masks,) if masks is not None else ()), sibs, size), masks is not None)
             else:
                 yield (lm_path, gt, sibs, size)
+
+    def _ring_job(self, job, has_masks: bool):
+        """A device job, with its slot of the loaders' ring when there is one."""
+        ring = getattr(self, "_ring", None)
+        if ring is None:
+            return job
+        # the k-th device job of this Dataset writes slot k mod nslots; that slot last held job k - nslots, whose batch has
+        # been handed to the copy engine long ago (nslots >= prefetch + 3 batches) — its copy must have FINISHED
+        k = self._ring_seq
+        self._ring_seq += 1
+        if k >= ring.nslots:
+            while self._ring_copies and self._ring_copies[0][0] <= k - ring.nslots:       # batches that ended before that job: older copies
+                self._ring_copies.pop(0)
+            if not self._ring_copies:
+                raise RuntimeError("loader ring: slot %d is still waiting for its batch (ring of %d slots too small)" % (k % ring.nslots, ring.nslots))
+            if not self._ring_copies[0][2]:
+                self._ring_copies[0][1].synchronize()
+                self._ring_copies[0][2] = True
+        unf = self.device_unfilter if self.device_unfilter is not None else (self.ucb and has_masks)
+        unf = {"0": False, "1": True}.get(os.environ.get("BSR_DEVICE_UNFILTER", ""), unf)
+        return job + ((ring.path_for_workers, k % ring.nslots, ring.cap, bool(unf)),)
 
     def _close_pool(self) -> None:
         pool, self._pool = self._pool, None
@@ -522,24 +551,30 @@ class Dataset:
         if self.workers > 0 and self._pool is None:
             self._pool = _SelectPool(self.workers)
             self._pool.warm("rows")
-        if self.device_prep is not None and getattr(self, "_dp", None) is None:
-            from .prep import DevicePrep
-            self._dp = DevicePrep(self.device_prep, self.config.IMG_SIZE)
+        if self._device is not None and getattr(self, "_dp", None) is None:
+            self._dp = self._device_prep()
             self._dp.warm(max(8 << 20, self.device_batch * (2 * 3 * self.config.IMG_SIZE ** 2 + (64 << 10)) * 5 // 4))
         self._ensure_ring()
+
+    def _device_prep(self):
+        from .prep import DevicePrep
+        planes = None if self.device_groups is None else (6 if self.dset == "ucb_tsm" else 7)
+        return DevicePrep(self._device, self.config.IMG_SIZE, planes=planes)
 
     def _ensure_ring(self) -> None:
         """Device preparation with worker processes: the workers write their results into a page-locked shared-memory ring
         (prep.SlotRing / host_part_ring) instead of pickling ~0.5 MB per item through their pipes.  BSR_LOADER_RING=0 keeps the pipes."""
-        if (self.device_prep is None or self.workers <= 0 or getattr(self, "_ring", None) is not None or getattr(self, "_started", False)
+        # (of the groups only the UCB ones: an SFW group's label is a palette or grey file decoded in the worker, it goes through the pipe)
+        if (self._device is None or self.dset == "sfw" or self.workers <= 0 or getattr(self, "_ring", None) is not None or getattr(self, "_started", False)
                 or os.environ.get("BSR_LOADER_RING", "1") == "0"):
             return
-        from .prep import SlotRing
+        from .prep import RING_CAP, SlotRing
         if self._pool is None:
             self._pool = _SelectPool(self.workers)
         b = max(1, self.device_batch)
         try:
-            ring = SlotRing(((self.prefetch + 3 * b + b - 1) // b) * b)
+            # a group's slot also holds the mirror's four tables: with filtered photographs and masks ~1.0 MB, past one RING_CAP
+            ring = SlotRing(((self.prefetch + 3 * b + b - 1) // b) * b, *((3 * RING_CAP // 2,) if self.device_groups is not None else ()))
         except OSError as e:                      # no room in /dev/shm: the pipes it is
             self.ring_error = str(e)
             return
@@ -561,11 +596,10 @@ class Dataset:
             pass
 
     def _iterate(self):
-        if self.device_prep is None:
+        if self._device is None:
             yield from self._iterate_host()
             return
-        from .prep import DevicePrep
-        dp = self._dp if getattr(self, "_dp", None) is not None else DevicePrep(self.device_prep, self.config.IMG_SIZE)
+        dp = self._dp if getattr(self, "_dp", None) is not None else self._device_prep()
         self._ensure_ring()
         dp.ring = getattr(self, "_ring", None)
         group = []
@@ -577,10 +611,11 @@ class Dataset:
             if dp.ring is not None:
                 self._ring_copies.append([self._emitted, dp.last_copy, False])       # jobs < _emitted have left their slots once this event is done
             for i in range(len(group)):
+                el = out[i:i + 1] if self.device_groups is not None else out[i:i + 1][None]       # [1,2,S,S,C] | [1,1,S,S,16]
                 if masks[i] is not None:      # + the item's seven segmentation masks (bit-packed or grey levels, host or device: prep.pack_masks / rows_ex)
-                    yield out[i:i + 1][None], boxes[i][None], np.array([names[i]]), masks[i]
+                    yield el, boxes[i][None], np.array([names[i]]), masks[i]
                 else:
-                    yield out[i:i + 1][None], boxes[i][None], np.array([names[i]])
+                    yield el, boxes[i][None], np.array([names[i]])
         try:
             for part in self._iterate_host():
                 group.append(part)

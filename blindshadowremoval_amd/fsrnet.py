@@ -1346,6 +1346,7 @@ class FSRNetTSM(object):
         self.all_losses: List[Tuple[str, Dict[str, float]]] = []
         self.timings: Dict[str, float] = {}
         self._ucb_dev = None
+        self.statuses: List[int] = []            # bsr_ucb_post_tsm's status word per item of the last test(), in list order (device post-processing)
 
     def _groups(self, elements, n: int, split):
         """Stack k elements of n coupled frames each into one [k*n, S, S, C] batch, split by channels."""
@@ -1364,10 +1365,11 @@ class FSRNetTSM(object):
         con_rgb = torch.clamp(con_rgb, 0, 1)
         im_d = im.to(dev)
         pred_host = mask_pred.detach().cpu()
+        mask_host = mask.cpu()                   # (device-prepared elements, Dataset(device_groups=...), arrive as CUDA tensors)
         out = []
         for j in range(k):
             g = slice(2 * j, 2 * j + 2)
-            m0 = mask[2 * j]
+            m0 = mask_host[2 * j]
             label = (m0 == 2).float()                                               # :685
             pred0 = pred_host[2 * j]
             mse = float(((m0 - pred0) ** 2).mean())
@@ -1425,7 +1427,8 @@ class FSRNetTSM(object):
         ShareLayer cannot reshape for two rows (model_with_TSM.py:218); the older reshape it comments out (:217) put exactly these two rows
         in one group, as ``test_step_sfw`` does (:676), and ``share`` = uniform() > 0 is True but for a draw of exactly 0.0.  Groups are
         independent, so k elements per forward give each element the outputs of its own forward.  ``boxes``: k [4] crop boxes;
-        ``mask_files``: k dicts of mask paths (FSRNet._ucb_masks' form).  Post-processing on the device (ucb_post_tsm_gpu) when the
+        ``mask_files``: k dicts of mask paths (FSRNet._ucb_masks' form), or k packed mask records of the loader (prep.pack_masks / the
+        device views of DevicePrep.rows_ex: what Dataset(device_groups=...) yields with each element).  Post-processing on the device (ucb_post_tsm_gpu) when the
         generator lives on a GPU and ``post_device``, else the host statement (ucb_post_tsm).  ``save_names``: write each strip under that
         name (Logging.save_img's file).  -> [(losses, figs[8] | None, frac_nose_in_shadow, mean_intensity)] per element."""
         from .ucb_post_tsm import MASKS, ucb_postprocess_tsm
@@ -1438,8 +1441,14 @@ class FSRNetTSM(object):
         if getattr(self.gen, "dtype", "f32") != "f32" and hasattr(self.gen, "check_range"):
             self.gen.check_range()                 # 16-bit modes: an out-of-range activation is an error, never a silent inf
         boxes = np.asarray([np.asarray(b, np.float32).reshape(-1)[:4] for b in boxes], np.float32).reshape(k, 4)
-        from PIL import Image
-        grey = [np.stack([np.asarray(Image.open(m[key]).convert("L")) for key in MASKS]) for m in mask_files]       # [3,S,S] uint8 each
+        masks_d = None
+        if mask_files and all(isinstance(m, tuple) for m in mask_files):         # decoded by the loader, seven per item in prep.MASK_ORDER
+            from .prep import MASK_ORDER, unpack_masks
+            masks_d = unpack_masks(list(mask_files), dev)[:, [MASK_ORDER.index(key) for key in MASKS]].contiguous()
+            grey = masks_d.cpu().numpy() if not (dev_idx is not None and self.post_device) else None
+        else:
+            from PIL import Image
+            grey = [np.stack([np.asarray(Image.open(m[key]).convert("L")) for key in MASKS]) for m in mask_files]       # [3,S,S] uint8 each
         out = []
         if dev_idx is not None and self.post_device:
             from .ucb_post_tsm_gpu import UcbPostTsmDevice, raise_for_status
@@ -1448,9 +1457,11 @@ class FSRNetTSM(object):
             even, odd = slice(0, 2 * k, 2), slice(1, 2 * k, 2)
             im_d, gt_d = im.to(dev), gt.to(dev)
             rows = torch.cat([im_d[even], gt_d[even], con[even].float(), con[odd].float(), dif[even].float()], dim=3).contiguous()
-            masks = torch.from_numpy(np.stack(grey)).to(dev)
+            masks = masks_d if masks_d is not None else torch.from_numpy(np.stack(grey)).to(dev)
             losses_d, stats_d, strips, figs_d, status = self._ucb_dev.run(rows, masks, torch.from_numpy(boxes).to(dev), want_figs=self.return_figs)
-            raise_for_status(status.cpu().numpy(), list(save_names) if save_names is not None else None)
+            status_h = status.cpu().numpy()
+            self.statuses.extend(int(v) for v in status_h)
+            raise_for_status(status_h, list(save_names) if save_names is not None else None)
             if save_names is not None:
                 self.log.write_files_now(self.log.encode_strips(strips), save_names)
             lh, sh = losses_d.cpu().numpy(), stats_d.cpu().numpy()
@@ -1488,7 +1499,7 @@ class FSRNetTSM(object):
 
     def test(self, dataset_val, batch: int = 16, mask_files=None, mat_path: str = "frac_in_nose.mat"):
         """train_with_TSM.py:369-416 + test_step :418-618 with ``batch`` elements (2 * batch rows) per forward.  ``dataset_val``:
-        Dataset(dset='ucb_tsm', ucb=True).  Masks: the sorted listing of the with-hair folder under Config.UCB_MASK_ROOT, the same file
+        Dataset(dset='ucb_tsm', ucb=True[, device_groups=gpu]: the groups then arrive as CUDA tensors and nothing is copied).  Masks: the sorted listing of the with-hair folder under Config.UCB_MASK_ROOT, the same file
         name in the face and nose folders (_ucb_mask_files), or ``mask_files``.  Strips of the eight figures go to <CHECKPOINT_DIR>/test/
         under FSRNet.test's names.  Writes ``mat_path`` (scipy.io.savemat) with ``frac_in_nose`` and ``mean_intensity``, each of length
         max(100, n) with zeros past n: the reference's fixed 100 (:384-385) would raise an IndexError past 100 items.
@@ -1502,11 +1513,18 @@ class FSRNetTSM(object):
         masks = list(mask_files) if mask_files is not None else _ucb_mask_files(self.config)
         if len(masks) < len(names):
             raise ValueError("%d UCB items but only %d mask files" % (len(names), len(masks)))
+        if getattr(dataset_val, "device_groups", None) is not None and not getattr(dataset_val, "_started", False):
+            from .prep import MASK_ORDER
+            if all(set(MASK_ORDER) <= set(m) for m in masks[:len(names)]):
+                dataset_val.ucb_mask_files = masks      # the loader's workers read the masks next to the photographs, as for FSRNet.test
         start = time.time()
         results = []
+        self.statuses = []                       # of this call's items, like all_losses
 
         def run_group(group):
-            outs = self.test_steps([g[2][0] for g in group], [g[2][1] for g in group], [masks[g[0]] for g in group], save_names=[g[1] for g in group])
+            # an element of a device-prepared dataset brings its masks along (the 4th entry)
+            outs = self.test_steps([g[2][0] for g in group], [g[2][1] for g in group], [g[2][3] if len(g[2]) > 3 else masks[g[0]] for g in group],
+                                   save_names=[g[1] for g in group])
             for (step, name, _), (losses, figs, frac, mean) in zip(group, outs):
                 self.log.display(losses, 0, step, False, len(names))
                 results.append((name, losses, frac, mean, figs))

@@ -25,6 +25,11 @@ MAX_TRI = 256
 ROW_DTYPE = np.dtype([("img_off", "<i8"), ("gt_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("box", "<i4", (4,)),
                       ("tri_off", "<i8", (4,)), ("ntri", "<i4", (4,))], align=True)
 assert ROW_DTYPE.itemsize == 88
+# a TSM loader's group of two rows (csrc/prep_group_kernels.h PrepGroup): two RGB8 images, one grey8 plane (the SFW label; unread with
+# six planes), the box, the four meshes of the item's landmarks and the four of the mirror landmarks
+GROUP_DTYPE = np.dtype([("img_off", "<i8"), ("gt_off", "<i8"), ("aux_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("box", "<i4", (4,)),
+                        ("tri_off", "<i8", (8,)), ("ntri", "<i4", (8,))], align=True)
+assert GROUP_DTYPE.itemsize == 144
 
 
 def _imread_u8(path: str) -> np.ndarray:
@@ -100,6 +105,25 @@ def crop_box(lm0: np.ndarray) -> Tuple[List[int], np.ndarray]:
     lm[:, 0] = lm[:, 0] - np.float32(box[0])
     lm[:, 1] = lm[:, 1] - np.float32(box[1])
     return box, lm / np.float32(length * 2)
+
+
+def crop_box_pair(lm0: np.ndarray, w: int) -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """Crop box, normalised landmarks and normalised MIRROR landmarks of dataset.face_crop_and_resize(with_mirror=True) for an image
+    `w` pixels wide, without touching pixels: the same float32 statements in the same order."""
+    raw = np.array(lm0, np.float32)
+    box, lm = crop_box(raw)
+    lm_m = np.array(raw, np.float32)
+    lm_m[:, 0] = np.float32(w) - lm_m[:, 0]
+    lm_m = lm_m[D.LM_REVERSE, :]
+    lm_m[:, 0] = lm_m[:, 0] - np.float32(w - box[2])
+    lm_m[:, 1] = lm_m[:, 1] - np.float32(box[1])
+    return box, lm, lm_m / np.float32(_box_length(raw) * 2)
+
+
+def _box_length(lm: np.ndarray) -> float:
+    """face_crop_and_resize's half-length of the crop (float64 after the `* 1.4`)."""
+    two = np.float32(2)
+    return float(max((lm[:, 0].max() - lm[:, 0].min()) / two, (lm[:, 1].max() - lm[:, 1].min()) / two)) * 1.4
 
 
 MASK_ORDER = ("face_hair", "face", "mouth", "nose", "eyebrow", "eye", "glasses")      # train_test_GSC.py:386-392 (= the keys of ucb_post.MASK_DIRS)
@@ -201,6 +225,37 @@ def host_part(job, raw: bool = False):
     return out + (masks,) if masks is not None else out
 
 
+def host_part_group(job, raw: bool = False):
+    """The host half of one TSM group (an item and its mirror image, csrc/prep_group_kernels.h), in host_part's form with EIGHT triangle
+    tables — meshes(lm) + meshes(lm_m) of face_crop_and_resize(with_mirror=True) — so that the ring and the blob code carry it like a row:
+    (lm_path, gt_path, size[, mask paths]) -> (img, gt, box, [8 tables], name[, packed masks]): dataset.build_ucb_tsm_pair's group;
+    (label_path, "<sfw>", size)            -> (img, cmap, box, [8 tables], name, None, label u8 [h,w]): dataset.build_sfw_pair's group
+    (decoded in the worker: the label is a palette or grey file whose levels travel as they are).
+    The reg_in mesh of the canonical landmarks is the one cached triangulation (_REF_TRI) for both rows and every item."""
+    masks = None
+    if len(job) > 3:
+        masks = pack_masks(job[3], raw=raw)
+        job = job[:3]
+    lm_path, gt_path, size = job
+    if gt_path == "<sfw>":
+        from .pngio import read_grey_u8
+        stem = lm_path.rsplit(".", 1)[0]
+        frame = stem[:-6]                                                 # strips "_label"
+        img, cmap, label = _imread_u8(frame + ".png"), _imread_u8(stem + "_cmap.png"), np.ascontiguousarray(read_grey_u8(lm_path))
+        if cmap.shape != img.shape or label.shape != img.shape[:2]:
+            raise ValueError("the planes of SFW frame %s differ in size" % frame)
+        box, lm, lm_m = crop_box_pair(np.load(frame + ".npy"), img.shape[1])
+        return (img, cmap, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), (frame + ".png").encode(), None, label)
+    img_path = os.path.splitext(lm_path)[0] + ".png"
+    read = _imread_raw if raw else _imread_u8
+    img, gt = read(img_path), read(gt_path)
+    if gt.shape != img.shape:
+        raise ValueError("ground truth %s and image %s differ in size" % (gt_path, img_path))
+    box, lm, lm_m = crop_box_pair(np.load(lm_path), img.shape[1])
+    out = (img, gt, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), gt_path.encode())
+    return out + (masks,) if masks is not None else out
+
+
 RING_CAP = 1 << 20        # bytes of one slot of the loaders' shared-memory ring (a 256x256 UCB item with ground truth, tables and masks: ~0.55 MB)
 _RING_VIEWS: dict = {}
 
@@ -209,8 +264,8 @@ def _is_ring(part) -> bool:
     return isinstance(part[0], str)
 
 
-def host_part_ring(job, ring):
-    """`host_part(job)` written INTO slot `slot` of the shared-memory ring the parent page-locked (SlotRing) instead of pickled through
+def host_part_ring(job, ring, group: bool = False):
+    """`host_part(job)` (group: `host_part_group(job)`, eight tables instead of four) written INTO slot `slot` of the shared-memory ring the parent page-locked (SlotRing) instead of pickled through
     the worker's pipe: -> ("ring", slot, (h, w), has_gt, image offsets, table offsets, table lengths, box, name, mask record | None,
     bytes used) — a few hundred bytes.  The loop's own thread then neither reads, unpickles nor repacks the ~0.5 MB of an item (0.1 ms
     per item of the one thread every batch goes through): the slot goes to the device as it lies, by one copy per batch.  An item that
@@ -219,8 +274,9 @@ def host_part_ring(job, ring):
     (bsr_png_unfilter) when the job's ring tuple says so (its 4th element: dataset.Dataset.device_unfilter)."""
     path, slot, cap = ring[:3]
     use_raw = bool(ring[3]) if len(ring) > 3 else False       # dataset.Dataset.device_unfilter decides
-    part = host_part(job, raw=use_raw)
+    part = (host_part_group if group else host_part)(job, raw=use_raw)
     img, gt, box, tabs, name = part[:5]
+    nt = len(tabs)
     masks = part[5] if len(part) > 5 else None
     # the device kernel takes images of at most UNFILTER_MAX_ROWS rows whose scanlines hold at least one dword; anything else is decoded
     # here.  "raw8" masks stay as they are: _masks_raw only made them for S x S grey files the kernel takes, whatever the images are
@@ -245,8 +301,8 @@ def host_part_ring(job, ring):
         raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         view[base + o:base + o + raw.size] = raw
     k = 2 if gt is not None else 1
-    mrec = None if masks is None else (masks[0], int(masks[2]), offs[k + 4], int(masks[1].nbytes))
-    return ("ring", int(slot), (int(img.shape[0]), int(img.shape[1])), gt is not None, tuple(offs[:k]), tuple(offs[k:k + 4]),
+    mrec = None if masks is None else (masks[0], int(masks[2]), offs[k + nt], int(masks[1].nbytes))
+    return ("ring", int(slot), (int(img.shape[0]), int(img.shape[1])), gt is not None, tuple(offs[:k]), tuple(offs[k:k + nt]),
             tuple(int(t.shape[0]) for t in tabs), np.asarray(box, np.int32), name, mrec, off, rawc)
 
 
@@ -313,14 +369,15 @@ def _layout(parts, size: int):
     return total, rows_off, grid_off, pieces
 
 
-def _layout_ex(parts, size: int, cap: int):
-    """Offsets of every section of the blob (all 8-byte aligned): -> (total bytes, rows_off, grid_off, [(offset, array)], head bytes,
+def _layout_ex(parts, size: int, cap: int, group: bool = False):
+    """group = True: the parts are host_part_group's and the records GROUP_DTYPE (eight tables, the label plane).  Offsets of every section of the blob (all 8-byte aligned): -> (total bytes, rows_off, grid_off, [(offset, array)], head bytes,
     ring cells, (unfilter table offset, records)).  Items that came through the pipe are packed behind the records (the `head`, staged
     by the caller); every ring item gets one `cap`-byte cell behind the head, in batch order — cells = [(part index, slot, cell
     offset)] — which the caller fills with the slot's bytes.  Ring images that lie in their slot as filtered scanlines (round 6) get
     a record in the unfilter table (in the head) and an output area behind the cells, where the row records then point."""
     B = len(parts)
-    rows = np.zeros(B, ROW_DTYPE)
+    dtype, nt = (GROUP_DTYPE, 8) if group else (ROW_DTYPE, 4)
+    rows = np.zeros(B, dtype)
     pieces = []
     off = 0
 
@@ -329,7 +386,7 @@ def _layout_ex(parts, size: int, cap: int):
         o = off
         off += (nbytes + 7) & ~7
         return o
-    rows_off = take(B * ROW_DTYPE.itemsize)
+    rows_off = take(B * dtype.itemsize)
     grid_off = take(size * 8)
     pieces.append((grid_off, np.linspace(0, 1, size).astype("<f8")))
     for i, part in enumerate(parts):
@@ -346,6 +403,14 @@ def _layout_ex(parts, size: int, cap: int):
         else:
             r["gt_off"] = r["img_off"]
         r["box"] = box
+        if len(tabs) != nt:
+            raise ValueError("prep blob: item %d carries %d triangle tables, the record takes %d" % (i, len(tabs), nt))
+        if group:
+            if len(part) > 6:                  # the SFW label plane
+                r["aux_off"] = take(part[6].nbytes)
+                pieces.append((int(r["aux_off"]), part[6]))
+            else:
+                r["aux_off"] = r["img_off"]
         for m, t in enumerate(tabs):
             r["tri_off"][m] = take(t.nbytes)
             r["ntri"][m] = t.shape[0]
@@ -370,8 +435,8 @@ def _layout_ex(parts, size: int, cap: int):
         has_gt = np.array([p[3] for p in rp], bool)
         io0 = np.array([p[4][0] for p in rp], np.int64)
         io1 = np.where(has_gt, np.array([p[4][-1] for p in rp], np.int64), io0)
-        toff = np.array([p[5] for p in rp], np.int64).reshape(n, 4)
-        ntri = np.array([p[6] for p in rp], np.int64).reshape(n, 4)
+        toff = np.array([p[5] for p in rp], np.int64).reshape(n, nt)
+        ntri = np.array([p[6] for p in rp], np.int64).reshape(n, nt)
         used = np.array([p[10] for p in rp], np.int64)
         rawc = np.array([(tuple(p[11]) + (0, 0))[:2] if len(p) > 11 else (0, 0) for p in rp], np.int64).reshape(n, 2)
         rawc[:, 1] = np.where(has_gt, rawc[:, 1], rawc[:, 0])
@@ -423,6 +488,8 @@ def _layout_ex(parts, size: int, cap: int):
                 mask_out = {ring_idx[int(j)]: (int(o), int(S_)) for j, o, S_ in zip(mj, mout, mS)}
         rows["img_off"][sel] = img_at
         rows["gt_off"][sel] = gt_at
+        if group:
+            rows["aux_off"][sel] = img_at      # ring groups are UCB items: six planes, the label plane is not read
         rows["box"][sel] = np.stack([np.asarray(p[7], np.int32).reshape(4) for p in rp])
         rows["tri_off"][sel] = bases[:, None] + toff
         rows["ntri"][sel] = ntri
@@ -431,6 +498,8 @@ def _layout_ex(parts, size: int, cap: int):
     h64, w64 = rows["h"].astype(np.int64), rows["w"].astype(np.int64)
     ends = np.maximum(np.maximum(rows["img_off"], rows["gt_off"]) + h64 * w64 * 3, (rows["tri_off"] + rows["ntri"].astype(np.int64) * (TRI_DOUBLES * 8)).max(axis=1))
     lows = np.minimum(np.minimum(rows["img_off"], rows["gt_off"]), rows["tri_off"].min(axis=1))
+    if group:
+        ends, lows = np.maximum(ends, rows["aux_off"] + h64 * w64), np.minimum(lows, rows["aux_off"])
     bad = (lows < 0) | (ends > off) | (rows["ntri"].max(axis=1) > MAX_TRI) | (rows["ntri"].min(axis=1) < 0) | (h64 < 0) | (w64 < 0)
     if bad.any():
         raise ValueError("prep blob: row %d points outside the %d-byte blob" % (int(np.argmax(bad)), off))
@@ -452,10 +521,24 @@ def pack_batch(parts, size: int):
     return buf.tobytes(), rows_off, grid_off
 
 
-class DevicePrep:
-    """`rows(parts)` -> packed `[B,S,S,16]` float32 CUDA tensor (+ the crop boxes) for a list of `host_part` results."""
+def pack_group_batch(parts, size: int):
+    """One blob for bsr_prep_groups: [group records | grid | images | triangle tables], every section 8-byte aligned."""
+    total, rows_off, grid_off, pieces, _, cells, _ = _layout_ex(parts, size, RING_CAP, group=True)
+    if cells:
+        raise ValueError("pack_group_batch: ring items need DevicePrep.rows_ex")
+    buf = np.zeros(total, np.uint8)
+    pack_into(buf, pieces)
+    return buf.tobytes(), rows_off, grid_off
 
-    def __init__(self, device: int = 0, size: int = 256):
+
+class DevicePrep:
+    """`rows(parts)` -> packed `[B,S,S,16]` float32 CUDA tensor (+ the crop boxes) for a list of `host_part` results.
+    `planes` = 6 | 7: the parts are `host_part_group` results and the tensor is `[B,2,S,S,planes+10]` (bsr_prep_groups)."""
+
+    def __init__(self, device: int = 0, size: int = 256, planes: Optional[int] = None):
+        if planes not in (None, 6, 7):
+            raise ValueError("DevicePrep: planes is None (rows), 6 (UCB groups) or 7 (SFW groups), got %r" % (planes,))
+        self.planes = planes
         import torch
         from . import _lib
         if not torch.cuda.is_available():
@@ -481,9 +564,22 @@ class DevicePrep:
         B, S = len(parts), self.size
         ring = getattr(self, "ring", None)
         cap = ring.cap if ring is not None else RING_CAP
-        total, rows_off, grid_off, pieces, head, cells, (unf_off, n_unf, mask_out) = _layout_ex(parts, S, cap)
+        total, rows_off, grid_off, pieces, head, cells, (unf_off, n_unf, mask_out) = _layout_ex(parts, S, cap, group=self.planes is not None)
+
+        def launch(stream):
+            """the preparation kernels on `stream`: -> (out, return code)"""
+            if self.planes is None:
+                out = torch.empty((B, S, S, 16), dtype=torch.float32, device=dev)
+                tmp = torch.empty((B, S, S), dtype=torch.float32, device=dev)
+                return out, self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, out.data_ptr(), tmp.data_ptr(), stream)
+            out = torch.empty((B, 2, S, S, self.planes + 10), dtype=torch.float32, device=dev)
+            tmp = torch.empty((2 * B, S, S), dtype=torch.float32, device=dev)
+            return out, self._lib.bsr_prep_groups(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, self.planes, out.data_ptr(),
+                                                  tmp.data_ptr(), stream)
         if cells and ring is None:
             raise RuntimeError("DevicePrep.rows_ex: ring records without a ring")
+        if cells and self.planes == 7:           # a ring record has no label plane: its aux_off points at the photograph
+            raise ValueError("DevicePrep.rows_ex: SFW groups (planes=7) do not travel through the ring")
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
             # two pinned staging buffers used alternately: the sections are copied straight into page-locked memory and go to the
@@ -518,12 +614,9 @@ class DevicePrep:
                 # bandwidth-bound kernel that shares the chip with the previous batch's forward instead of standing in line behind it
                 side = os.environ.get("BSR_PREP_SIDE", "1") != "0"
                 if side:
-                    out = torch.empty((B, S, S, 16), dtype=torch.float32, device=dev)
-                    tmp = torch.empty((B, S, S), dtype=torch.float32, device=dev)
                     if n_unf:                      # the filtered images of the ring items become RGB8 where their row records point
                         self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf_off, n_unf, self._h2d.cuda_stream), "bsr_png_unfilter")
-                    rc = self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, out.data_ptr(), tmp.data_ptr(),
-                                                 self._h2d.cuda_stream)
+                    out, rc = launch(self._h2d.cuda_stream)
                     done = torch.cuda.Event()
                     done.record()
             if side:
@@ -533,13 +626,10 @@ class DevicePrep:
                 main.wait_event(ev)
             d_blob.record_stream(main)             # allocated on the side stream, read by the compute stream (the mask views; the kernel when it runs there)
             if not side:
-                out = torch.empty((B, S, S, 16), dtype=torch.float32, device=dev)
-                tmp = torch.empty((B, S, S), dtype=torch.float32, device=dev)
                 if n_unf:
                     self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf_off, n_unf, main.cuda_stream), "bsr_png_unfilter")
-                rc = self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, out.data_ptr(), tmp.data_ptr(),
-                                             main.cuda_stream)
-        self._check(rc, "bsr_prep_rows")
+                out, rc = launch(main.cuda_stream)
+        self._check(rc, "bsr_prep_rows" if self.planes is None else "bsr_prep_groups")
         boxes = np.stack([np.asarray(p[7] if _is_ring(p) else p[2], np.float32) for p in parts], axis=0)
         names = [p[8] if _is_ring(p) else p[4] for p in parts]
         masks = [(p[5] if len(p) > 5 else None) if not _is_ring(p) else None for p in parts]

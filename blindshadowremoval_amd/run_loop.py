@@ -16,7 +16,8 @@ Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random
 `FSRNet.testsfw_video` over Dataset(dset='sfw_video'): --data globs SFW video folders), in one process only.
 `--model tsm` runs the temporal-sharing model (train_with_TSM.py): `--loop ucb` (`FSRNetTSM.test` over Dataset(dset='ucb_tsm'), which
 also writes <checkpoint-dir>/frac_in_nose.mat), `--loop sfw` / `--loop sfw_video` (`FSRNetTSM.testsfw` / `testsfw_video` over
-Dataset(dset='sfw' | 'sfw_video')), in one process only.
+Dataset(dset='sfw' | 'sfw_video')), in one process only; the groups of `--loop ucb | sfw` are prepared on the device
+(Dataset(device_groups=gpu)) unless `--host-prep` is given.
 """
 from __future__ import annotations
 
@@ -41,7 +42,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--dtype", choices=("f32", "f32x3", "f16"), default="f32")
     ap.add_argument("--random-weights", type=int, default=None, metavar="SEED", help="seeded random-init weights in the checkpoint layout instead of a restore")
-    ap.add_argument("--host-prep", action="store_true", help="prepare the rows on the host (default: on the device, prep.py)")
+    ap.add_argument("--host-prep", action="store_true", help="prepare the rows on the host (default: on the device, prep.py; --model tsm: its "
+                                                             "--loop ucb | sfw groups — sfw_video is always prepared on the host)")
     ap.add_argument("--host-post", action="store_true", help="rounds 2-4 forms: UCB post-processing in worker processes and PNG encoding on the host "
                                                              "(default: both on the device — ucb_post_gpu.py, gpu_png.py)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl")
@@ -105,7 +107,10 @@ def main(argv=None) -> int:
     # loader's workers — PNG decode, Delaunay meshes, the UCB masks — are the only host stage: 3/4 (UCB) / 5/8 (FFHQ) of this rank's share of the CPUs (the loop's own thread and its file writers need the rest)
     ds_kw = dict(workers=max(1, (ncpu * 5 // 8 if ucb else ncpu * 7 // 8) if args.host_post else max(1, ncpu * 3 // 4 if ucb else ncpu * 5 // 8)))
     if tsm:
-        ds = Dataset(cfg, "test", dset={"ucb": "ucb_tsm", "sfw": "sfw", "sfw_video": "sfw_video"}[args.loop], ucb=ucb, workers=max(1, ncpu * 7 // 8))
+        tsm_kw = dict(workers=max(1, ncpu * 7 // 8))
+        if args.loop != "sfw_video" and not args.host_prep:
+            tsm_kw = dict(workers=max(1, ncpu * 3 // 4), device_groups=local_rank, device_batch=args.batch)
+        ds = Dataset(cfg, "test", dset={"ucb": "ucb_tsm", "sfw": "sfw", "sfw_video": "sfw_video"}[args.loop], ucb=ucb, **tsm_kw)
     elif sfw:
         ds = Dataset(cfg, "test", dset="sfw_gsc" if args.loop == "sfw" else "sfw_video", workers=max(1, ncpu * 7 // 8))
     else:
@@ -176,7 +181,8 @@ def _run_tsm(args, cfg, ds) -> int:
         means = {k: s / max(c, 1) for k, (s, c) in fsr.log.losses.items()}
         print("\n" + json.dumps({"loop": {"ucb": "FSRNetTSM.test", "sfw": "FSRNetTSM.testsfw", "sfw_video": "FSRNetTSM.testsfw_video"}[args.loop],
                                  "items": len(res), "ranks": 1, "images_per_sec": round(len(res) / dt, 2), "seconds": round(dt, 3), "batch": args.batch,
-                                 "dtype": args.dtype, "post": "host" if args.host_post else "device", "means": means}))
+                                 "dtype": args.dtype, "prep": "device" if getattr(ds, "device_groups", None) is not None else "host",
+                                 "post": "host" if args.host_post else "device", "means": means}))
     finally:
         ds.close()
         fsr.log.close()

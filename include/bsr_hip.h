@@ -137,6 +137,18 @@ int bsr_timing_entry(bsr_handle* h, int i, char* name, size_t name_cap, float* m
 int bsr_prep_rows(int device, const void* d_blob, size_t blob_bytes, size_t rows_off, size_t grid_off, int B, int S, float* out, float* hull_tmp,
                   void* stream);
 
+/* Input preparation of B groups of two rows — an item and its mirror image, the elements of the TSM loaders (dataset_with_TSM.py
+ * parse_fn_test, parse_fn_test_sfw) — in one launch chain.  d_blob as for bsr_prep_rows, with B group records at groups_off
+ * (csrc/prep_group_kernels.h PrepGroup, 144 bytes: { int64 img_off, gt_off, aux_off; int32 h, w, box[4]; int64 tri_off[8]; int32 ntri[8] }
+ * — two RGB8 images, one grey8 plane, the crop box, the four meshes of bsr_prep_rows for the item's landmarks and the four for the
+ * mirror landmarks).  planes = 6: out [B,2,S,S,16] = img3 | gt3 | uvm3 | reg_in3 | reg_out3 | face1 (aux_off unread); planes = 7: out
+ * [B,2,S,S,17] = img3 | cmap3 | label1 | ... with the label plane's grey levels undivided.  Row 0 of a group has the bits bsr_prep_rows
+ * gives the same item; row 1 holds row 0's crop planes mirrored in x and the mirror meshes' channels.  hull_tmp: [2B,S,S] float32
+ * scratch.  BSR_ERR_ARG for a null pointer, B <= 0, S*S not a multiple of 256, planes other than 6 / 7, unaligned offsets or tables that
+ * leave blob_bytes; the builder of the blob keeps what the records point to inside it (prep.py).  Added under ABI 8. */
+int bsr_prep_groups(int device, const void* d_blob, size_t blob_bytes, size_t groups_off, size_t grid_off, int B, int S, int planes, float* out,
+                    float* hull_tmp, void* stream);
+
 /* PNG scanline reconstruction (RFC 2083 section 6) of n images on the device — what cv2.imread / PIL do after inflating a file
  * (/root/reference/dataset.py:151,622: the images parse_fn_test / parse_fn_test_FFHQ read), moved behind the copy to the device so that a
  * loader's worker stops at the inflated stream.  d_blob (device, blob_bytes): at items_off (8-byte aligned) n records
