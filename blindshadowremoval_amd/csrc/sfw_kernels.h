@@ -16,15 +16,12 @@
 //                     compacted and bitonic-sorted in LDS, written to the scratch with their count and the tile's non-finite count;
 //   sfw_rank_kernel   grid (T, B): each tile's positives binary-search every tile's sorted negatives (staged through LDS one tile at a
 //                     time) for their lower and upper bounds; per-wave reduction, one uint64 atomic per workgroup;
-//   sfw_ssim_kernel   ucb_ssim_tile with one channel (shared with the UCB chains), and
+//   sfw_ssim_kernel   ucb_ssim_tile with one channel (post_common.h, shared with the UCB chains), and
 //   sfw_finish_kernel grid (B), one wave: the SSIM / PSNR fold, the AUC division and the status word.
 // Every scratch word a later kernel reads is written by an earlier kernel of the same call (tile 0 of sfw_tile_kernel clears the
 // accumulators that sfw_rank_kernel adds into).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "ucb_kernels.h"
+#include "post_common.h"
 
 namespace bsr {
 
@@ -34,31 +31,24 @@ constexpr int SFW_NONFINITE = 3;         // status: a mask_pred value is NaN or 
 
 __host__ __device__ inline int sfw_tiles(int S) { return (S * S + kSfwTile - 1) / kSfwTile; }
 
-struct SfwScratch {                      // per item, inside the caller's scratch block
+struct SfwScratch {                      // per item, inside the caller's scratch block, in layout order
   unsigned long long* acc;               // [2] 2U, positives (including the forced one)
   int* info;                             // [T][2] negatives, non-finite scores of the tile
   double* ssim_part;                     // [2][nblk]
   uint32_t* neg;                         // [T][kSfwTile] sorted negative keys of each tile (the first info[t][0] are valid)
+  __host__ __device__ static SfwScratch carve(ScratchCarver& c, int S) {
+    const size_t T = (size_t)sfw_tiles(S);
+    SfwScratch s;
+    s.acc = c.take<unsigned long long>(2);
+    s.info = c.take<int>(2 * T);
+    c.align(16);
+    s.ssim_part = c.take<double>(2 * (size_t)ssim_tiles(S));
+    s.neg = c.take<uint32_t>(T * kSfwTile);
+    return s;
+  }
 };
-
-__host__ __device__ inline size_t sfw_item_scratch_bytes(int S) {
-  const size_t T = (size_t)sfw_tiles(S);
-  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
-  const size_t b = 16 + ((T * 8 + 15) & ~size_t(15)) + 2 * nblk * 8 + T * kSfwTile * 4;
-  return (b + 255) & ~size_t(255);
-}
-
-__host__ __device__ inline SfwScratch sfw_scratch(void* base, int item, int S) {
-  const size_t T = (size_t)sfw_tiles(S);
-  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
-  unsigned char* p = static_cast<unsigned char*>(base) + (size_t)item * sfw_item_scratch_bytes(S);
-  SfwScratch s;
-  s.acc = reinterpret_cast<unsigned long long*>(p); p += 16;
-  s.info = reinterpret_cast<int*>(p); p += (T * 8 + 15) & ~size_t(15);
-  s.ssim_part = reinterpret_cast<double*>(p); p += 2 * nblk * 8;
-  s.neg = reinterpret_cast<uint32_t*>(p);
-  return s;
-}
+__host__ __device__ inline size_t sfw_item_scratch_bytes(int S) { return item_scratch_bytes<SfwScratch>(S); }
+__host__ __device__ inline SfwScratch sfw_scratch(void* base, int item, int S) { return item_scratch<SfwScratch>(base, item, S); }
 
 // Order-preserving key of a float32 score: unsigned comparison of keys == numeric comparison of the scores, with -0.0 == +0.0.
 __device__ __forceinline__ uint32_t sfw_key(float v) {
@@ -217,14 +207,9 @@ inline hipError_t launch_sfw_score(const float* rows3, int B, int S, float* loss
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sfw_rank_kernel, tiles, dim3(kSfwThreads), 0, stream, rows3, S, scratch);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const int st = (S + kSsimTile - 1) / kSsimTile;
-  hipLaunchKernelGGL(sfw_ssim_kernel, dim3((unsigned)(st * st), (unsigned)B), dim3(256), 0, stream, rows3, S, scratch);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sfw_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, S, scratch, losses, auc, status);
-  return hipGetLastError();
+  return launch_ssim_tail(
+      B, S, [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(sfw_ssim_kernel, grid, block, 0, stream, rows3, S, scratch); },
+      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(sfw_finish_kernel, grid, block, 0, stream, S, scratch, losses, auc, status); });
 }
 
 }  // namespace bsr

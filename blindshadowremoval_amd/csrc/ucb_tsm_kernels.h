@@ -7,16 +7,14 @@
 // (:548-565); then the composites of both generator rows (:579-580), clip -> resize -> pad of row 0's composite, SSIM / PSNR against
 // the resized ground truth (:588-600), and the eight figures (:614) as one uint8 strip.
 //
-// The machinery is the GSC chain's: union-find over agent-scope atomics (uf_union / uf_find), numpy's pairwise order for the two float64
-// sums that feed decisions (ucb_leaf_sum / ucb_tree_sum: the nose mask's sum and the shadow intensity), py_slice, the bilinear lerp
-// order of ucb_resize_kernel, ucb_ssim_tile / ucb_ssim_finish.  The hair sums of the components are exact: every hair value is a float32
-// multiple of 2^-31 of magnitude <= 1, so they are summed as int64 multiples of 2^-31 by atomics, in any order.
+// The machinery is post_common.h's, shared with the GSC chain: the connected components (cc_seed / cc_join / cc_root_sums / cc_largest
+// over agent-scope atomics), numpy's pairwise order for the two float64 sums that feed decisions (ucb_leaf_sum / ucb_tree_sum: the nose
+// mask's sum and the shadow intensity), py_slice, BilinearTap, put_figure, ucb_ssim_tile / ucb_ssim_finish.  The hair sums of the
+// components are exact: every hair value is a float32 multiple of 2^-31 of magnitude <= 1, so they are summed as int64 multiples of
+// 2^-31 by atomics, in any order.
 // Pixel stages: grid (S*S/256, B), 256 threads, pixel p = blockIdx.x * 256 + tid.  Item stages: grid (B).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "ucb_kernels.h"
+#include "post_common.h"
 
 namespace bsr {
 
@@ -30,9 +28,14 @@ struct UcbTsmVars {
   int v[TSM_NVARS];
   int fail, size, nose_hit, ra, rb, ca, cb;
 };
-static_assert(sizeof(UcbTsmVars) <= 256, "variable block");
 
-struct UcbTsmScratch {                   // per item, inside the caller's scratch block (N = S*S)
+struct UcbTsmVarRule {                   // which of v are min / max targets (post_common.h: vars_init, wg_vars_begin / wg_vars_end)
+  static constexpr int kCount = TSM_NVARS, kMaxSize = TSM_MAX_SIZE;
+  __device__ static bool is_min(int k) { return k == TSM_NOSE_R0 || k == TSM_NOSE_C0; }
+  __device__ static bool is_max(int k) { return k == TSM_NOSE_R1 || k == TSM_NOSE_C1 || k == TSM_MAX_SIZE; }
+};
+
+struct UcbTsmScratch {                   // per item, inside the caller's scratch block (N = S*S), in layout order
   double* ssim_part;                     // [2][nblk]
   double* leaf_sh;                       // [N / 128] leaf sums of the shadow intensity
   double* leaf_nose;                     // [N / 128] leaf sums of the nose mask
@@ -44,61 +47,33 @@ struct UcbTsmScratch {                   // per item, inside the caller's scratc
   unsigned* csize;                       // [N] component sizes (at the root)
   unsigned char* keep;                   // [N] detected, then kept
   UcbTsmVars* vars;
-};
-
-__host__ __device__ inline size_t ucb_tsm_item_scratch_bytes(int S) {
-  const size_t N = (size_t)S * S;
-  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
-  size_t b = 2 * nblk * 8 + 2 * (N / 128) * 8 + N * 8 + 3 * N * 3 * 4 + 2 * N * 4 + N;
-  b = (b + 7) & ~size_t(7);
-  b += 256;                                                    // the variable block
-  return (b + 255) & ~size_t(255);
-}
-
-__host__ __device__ inline UcbTsmScratch ucb_tsm_scratch(void* base, int item, int S) {
-  const size_t N = (size_t)S * S;
-  const size_t nblk = (size_t)((S + kSsimTile - 1) / kSsimTile) * ((S + kSsimTile - 1) / kSsimTile);
-  unsigned char* p = static_cast<unsigned char*>(base) + (size_t)item * ucb_tsm_item_scratch_bytes(S);
-  UcbTsmScratch s;
-  s.ssim_part = reinterpret_cast<double*>(p); p += 2 * nblk * 8;
-  s.leaf_sh = reinterpret_cast<double*>(p); p += (N / 128) * 8;
-  s.leaf_nose = reinterpret_cast<double*>(p); p += (N / 128) * 8;
-  s.chair = reinterpret_cast<long long*>(p); p += N * 8;
-  s.gt = reinterpret_cast<float*>(p); p += N * 3 * 4;
-  s.out = reinterpret_cast<float*>(p); p += N * 3 * 4;
-  s.comp = reinterpret_cast<float*>(p); p += N * 3 * 4;
-  s.label = reinterpret_cast<unsigned*>(p); p += N * 4;
-  s.csize = reinterpret_cast<unsigned*>(p); p += N * 4;
-  s.keep = p; p += N;
-  p = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 7) & ~uintptr_t(7));
-  s.vars = reinterpret_cast<UcbTsmVars*>(p);
-  return s;
-}
-
-__device__ inline float tsm_mask(const unsigned char* m) { return (float)((double)*m / 255.0); }      // cv2.imread(...) / 255.0, then float32
-__device__ inline bool tsm_is_min(int k) { return k == TSM_NOSE_R0 || k == TSM_NOSE_C0; }
-__device__ inline bool tsm_is_max(int k) { return k == TSM_NOSE_R1 || k == TSM_NOSE_C1 || k == TSM_MAX_SIZE; }
-
-__device__ inline void tsm_wg_vars_begin(int* s_v, int tid) {
-  if (tid < TSM_NVARS) s_v[tid] = tsm_is_min(tid) ? 0x7fffffff : (tsm_is_max(tid) ? -1 : 0);
-  __syncthreads();
-}
-__device__ inline void tsm_wg_vars_end(const int* s_v, UcbTsmVars* g, int tid) {
-  __syncthreads();
-  if (tid < TSM_NVARS) {
-    const int x = s_v[tid];
-    if (tsm_is_min(tid)) { if (x != 0x7fffffff) atomicMin(&g->v[tid], x); }
-    else if (tsm_is_max(tid)) { if (x != -1) atomicMax(&g->v[tid], x); }
-    else if (x != 0) atomicAdd(&g->v[tid], x);
+  __host__ __device__ static UcbTsmScratch carve(ScratchCarver& c, int S) {
+    const size_t N = (size_t)S * S;
+    UcbTsmScratch s;
+    s.ssim_part = c.take<double>(2 * (size_t)ssim_tiles(S));
+    s.leaf_sh = c.take<double>(N / 128);
+    s.leaf_nose = c.take<double>(N / 128);
+    s.chair = c.take<long long>(N);
+    s.gt = c.take<float>(N * 3);
+    s.out = c.take<float>(N * 3);
+    s.comp = c.take<float>(N * 3);
+    s.label = c.take<unsigned>(N);
+    s.csize = c.take<unsigned>(N);
+    s.keep = c.take<unsigned char>(N);
+    c.align(8);
+    s.vars = c.take_block<UcbTsmVars, 256>();
+    return s;
   }
-}
+};
+__host__ __device__ inline size_t ucb_tsm_item_scratch_bytes(int S) { return item_scratch_bytes<UcbTsmScratch>(S); }
+__host__ __device__ inline UcbTsmScratch ucb_tsm_scratch(void* base, int item, int S) { return item_scratch<UcbTsmScratch>(base, item, S); }
 
 // rows: [B][S][S][13] float32; masks: [B][3][S][S] uint8 grey levels (face_hair, face, nose: one of cv2.imread's three equal channels);
 // boxes: [B][4] float32
 __global__ void ucb_tsm_init_kernel(const float* __restrict__ boxes, int S, void* scratch) {       // grid (B), 64 threads
   const int item = blockIdx.x, tid = threadIdx.x;
   UcbTsmVars* g = ucb_tsm_scratch(scratch, item, S).vars;
-  if (tid < TSM_NVARS) g->v[tid] = tsm_is_min(tid) ? 0x7fffffff : (tsm_is_max(tid) && tid != TSM_MAX_SIZE ? -1 : 0);
+  vars_init<UcbTsmVarRule>(g, tid);
   if (tid == 0) {
     const int size = ucb_box_size(boxes + 4 * item);
     g->size = size;
@@ -117,73 +92,39 @@ __global__ __launch_bounds__(256) void ucb_tsm_s1_kernel(const float* __restrict
   const int N = S * S;
   const UcbTsmScratch sc = ucb_tsm_scratch(scratch, item, S);
   if (sc.vars->fail) return;
-  tsm_wg_vars_begin(s_v, tid);
+  wg_vars_begin<UcbTsmVarRule>(s_v, tid);
   const int y = p / S, x = p % S;
   const unsigned char* m = masks + (size_t)item * kUcbTsmMasks * N;
-  const float mp = rows[((size_t)item * N + p) * kUcbTsmRowCh + 12] * tsm_mask(m + p);
+  const float mp = rows[((size_t)item * N + p) * kUcbTsmRowCh + 12] * mask_level(m[p]);
   const bool det = mp > 0.01f;
   sc.keep[p] = det ? 1 : 0;
   const unsigned char nose = m[2 * (size_t)N + p];
   ucb_wave_box(s_v, nose == 255, y, x, TSM_NOSE_R0, TSM_NOSE_R1, TSM_NOSE_C0, TSM_NOSE_C1, TSM_NOSE_CNT);
   s_d[tid] = (double)nose / 255.0;
-  // a detected pixel starts out pointing at the first pixel of its run inside this wave (as ucb_s4_kernel): stage 2 only joins runs
-  const int lane = tid & 63;
-  const unsigned long long km = __ballot(det);
-  const bool left = lane > 0 && x > 0 && ((km >> (lane - 1)) & 1ull);
-  const unsigned long long heads = __ballot(det && !left);
-  unsigned start = (unsigned)p;
-  if (det) start = (unsigned)(p - lane + 63 - __clzll(heads & ((2ull << lane) - 1ull)));
-  __hip_atomic_store(sc.label + p, start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(sc.csize + p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(sc.chair + p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  tsm_wg_vars_end(s_v, sc.vars, tid);                            // (its barrier also publishes s_d)
+  cc_seed(det, p, x, sc.label, sc.csize, sc.chair);
+  wg_vars_end<UcbTsmVarRule>(s_v, sc.vars, tid);                            // (its barrier also publishes s_d)
   if (tid < 2) sc.leaf_nose[blockIdx.x * 2 + tid] = ucb_leaf_sum<double>(s_d + 128 * tid);
 }
 
-// stage 2: 4-connected components (:524): join runs with their left and upper neighbours (as ucb_s5a_kernel) ...
+// stage 2: 4-connected components (:524): join runs with their left and upper neighbours ...
 __global__ __launch_bounds__(256) void ucb_tsm_s2a_kernel(int S, void* scratch) {
   const int item = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   const UcbTsmScratch sc = ucb_tsm_scratch(scratch, item, S);
-  if (sc.vars->fail || !sc.keep[p]) return;
-  const int y = p / S, x = p % S;
-  const bool left = x > 0 && sc.keep[p - 1];
-  if (left && (threadIdx.x & 63) == 0) uf_union(sc.label, (unsigned)p, (unsigned)(p - 1));
-  if (y > 0 && sc.keep[p - S] && !(left && sc.keep[p - S - 1])) uf_union(sc.label, (unsigned)p, (unsigned)(p - S));
+  if (sc.vars->fail) return;
+  cc_join(sc.label, sc.keep, p, S);
 }
-
-__device__ inline long long tsm_wave_add64(long long v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 
 // ... then sizes and hair sums at the roots
 __global__ __launch_bounds__(256) void ucb_tsm_s2b_kernel(const unsigned char* __restrict__ masks, int S, void* scratch) {
-#pragma clang fp contract(off)
   const int item = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   const int N = S * S;
   const UcbTsmScratch sc = ucb_tsm_scratch(scratch, item, S);
   if (sc.vars->fail) return;
-  const bool k = sc.keep[p] != 0;
-  unsigned root = (unsigned)p;
-  long long hair = 0;
-  if (k) {
-    root = uf_find(sc.label, (unsigned)p);
-    __hip_atomic_store(sc.label + p, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned char* m = masks + (size_t)item * kUcbTsmMasks * N;
+  const unsigned char* m = masks + (size_t)item * kUcbTsmMasks * N;
+  cc_root_sums(sc.label, sc.csize, sc.chair, sc.keep[p] != 0, p, [&] {
     const float h = (float)((double)m[p] / 255.0 - (double)m[(size_t)N + p] / 255.0);         // tf.cast(curr_mask - curr_mask_no_hair, float32)
-    hair = (long long)((double)h * 2147483648.0);                                              // exact: h is a multiple of 2^-31
-  }
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(k);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const unsigned r = (unsigned)__shfl((int)root, leader);
-    const bool mine = k && root == r;
-    const unsigned long long m = __ballot(mine);
-    const long long hs = tsm_wave_add64(mine ? hair : 0ll);
-    if (lane == leader) {
-      atomicAdd(&sc.csize[r], (unsigned)__popcll(m));
-      if (hs != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&sc.chair[r]), (unsigned long long)hs);
-    }
-    todo &= ~m;
-  }
+    return (long long)((double)h * 2147483648.0);                                              // exact: h is a multiple of 2^-31
+  });
 }
 
 __global__ __launch_bounds__(256) void ucb_tsm_s2c_kernel(int S, void* scratch) {       // the largest component
@@ -191,9 +132,7 @@ __global__ __launch_bounds__(256) void ucb_tsm_s2c_kernel(int S, void* scratch) 
   const int item = blockIdx.y, tid = threadIdx.x, p = blockIdx.x * 256 + tid;
   const UcbTsmScratch sc = ucb_tsm_scratch(scratch, item, S);
   if (sc.vars->fail) return;
-  tsm_wg_vars_begin(s_v, tid);
-  if (sc.keep[p] && uf_load(sc.label + p) == (unsigned)p) atomicMax(&s_v[TSM_MAX_SIZE], (int)uf_load(sc.csize + p));
-  tsm_wg_vars_end(s_v, sc.vars, tid);
+  cc_largest<UcbTsmVarRule>(s_v, sc.vars, sc.label, sc.csize, sc.keep, p, tid);
 }
 
 // stage 3: the keep filter (:533-546) and the sums of the nose rule (:549-552)
@@ -205,13 +144,13 @@ __global__ __launch_bounds__(256) void ucb_tsm_s3_kernel(const float* __restrict
   const int N = S * S;
   const UcbTsmScratch sc = ucb_tsm_scratch(scratch, item, S);
   if (sc.vars->fail) return;
-  tsm_wg_vars_begin(s_v, tid);
+  wg_vars_begin<UcbTsmVarRule>(s_v, tid);
   const double min_size = 0.6 * (double)sc.vars->v[TSM_MAX_SIZE];
   unsigned char k = 0;
   if (sc.keep[p]) {
     const unsigned root = uf_load(sc.label + p);
     const unsigned sz = uf_load(sc.csize + root);
-    const long long hs = __hip_atomic_load(sc.chair + root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long hs = uf_load(sc.chair + root);
     if ((double)sz >= min_size && ((double)hs * 4.656612873077392578125e-10) / (double)sz < 0.8) k = 1;      // hs * 2^-31
   }
   sc.keep[p] = k;                                               // only this thread reads keep[p] in this launch
@@ -225,7 +164,7 @@ __global__ __launch_bounds__(256) void ucb_tsm_s3_kernel(const float* __restrict
     if (m_k) atomicAdd(&s_v[TSM_KEEP_CNT], __popcll(m_k));
     if (m_n) atomicAdd(&s_v[TSM_NOSE_SH], __popcll(m_n));
   }
-  tsm_wg_vars_end(s_v, sc.vars, tid);                            // (its barrier also publishes s_d)
+  wg_vars_end<UcbTsmVarRule>(s_v, sc.vars, tid);                            // (its barrier also publishes s_d)
   if (tid < 2) sc.leaf_sh[blockIdx.x * 2 + tid] = ucb_leaf_sum<double>(s_d + 128 * tid);
 }
 
@@ -265,19 +204,6 @@ __global__ __launch_bounds__(512) void ucb_tsm_a3_kernel(int S, void* scratch, d
 
 __device__ inline float tsm_max(float a, float b) { return (isnan(a) || a >= b) ? a : b; }        // np.maximum
 
-// figure k of pixel (y, x): the strip byte (utils.py:217-233: clip, * 255, round half to even) and, when asked, the float figure
-__device__ inline void tsm_put(unsigned char* strip, float* figs, int S, int item, int k, int y, int x, const float* f) {
-  const int N = S * S;
-  unsigned char* dst = strip + ((size_t)y * (kUcbTsmFigs * S) + (size_t)k * S + x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) dst[c] = (unsigned char)rintf(fminf(fmaxf(f[c], 0.f), 1.f) * 255.f);
-  if (figs != nullptr) {
-    float* fd = figs + (((size_t)item * kUcbTsmFigs + k) * N + (size_t)y * S + x) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) fd[c] = f[c];
-  }
-}
-
 // stage 4: the nose rule applied, the composites of both rows (:579-580) and the six figures that are not resized (:614).
 // strips: [B][S][8 S][3] uint8; figs: optional [B][8][S][S][3] float32; status: [B]
 __global__ __launch_bounds__(256) void ucb_tsm_s4_kernel(const float* __restrict__ rows, const unsigned char* __restrict__ masks, int S, void* scratch,
@@ -292,7 +218,7 @@ __global__ __launch_bounds__(256) void ucb_tsm_s4_kernel(const float* __restrict
   if (p == 0) status[item] = g->fail;
   if (g->fail) {                                                // a black strip; NaN losses are left to the finish kernel
     const float zero[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < kUcbTsmFigs; ++k) tsm_put(strip, figs, S, item, k, y, x, zero);
+    for (int k = 0; k < kUcbTsmFigs; ++k) put_figure<kUcbTsmFigs>(strip, figs, S, item, k, y, x, zero);
     return;
   }
   const int xm = S - 1 - x, pm = y * S + xm;                    // the mirrored pixel
@@ -302,7 +228,7 @@ __global__ __launch_bounds__(256) void ucb_tsm_s4_kernel(const float* __restrict
   const float d = final_keep(p, x) ? 1.f : 0.f, dm = final_keep(pm, xm) ? 1.f : 0.f;
   const float* r = rows + ((size_t)item * N + p) * kUcbTsmRowCh;
   const float* rm = rows + ((size_t)item * N + pm) * kUcbTsmRowCh;
-  const float mp2 = (r[12] * tsm_mask(masks + (size_t)item * kUcbTsmMasks * N + p)) * 2.f;
+  const float mp2 = (r[12] * mask_level(masks[(size_t)item * kUcbTsmMasks * N + p])) * 2.f;
   float f0[3], f2[3], f4[3], f5[3], f6[3], f7[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -313,16 +239,16 @@ __global__ __launch_bounds__(256) void ucb_tsm_s4_kernel(const float* __restrict
     sc.comp[(size_t)p * 3 + c] = fminf(fmaxf(orig, 0.f), 1.f);
     f0[c] = tmp; f2[c] = mp2; f4[c] = d; f5[c] = flipped; f6[c] = flipflip; f7[c] = tsm_max(orig, flipflip);
   }
-  tsm_put(strip, figs, S, item, 0, y, x, f0);
-  tsm_put(strip, figs, S, item, 2, y, x, f2);
-  tsm_put(strip, figs, S, item, 4, y, x, f4);
-  tsm_put(strip, figs, S, item, 5, y, x, f5);
-  tsm_put(strip, figs, S, item, 6, y, x, f6);
-  tsm_put(strip, figs, S, item, 7, y, x, f7);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 0, y, x, f0);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 2, y, x, f2);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 4, y, x, f4);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 5, y, x, f5);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 6, y, x, f6);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 7, y, x, f7);
 }
 
-// stage 5: output = pad(resize(clip(orig))), gt_sc = pad(resize(gt0)) (:441,454,588-590) — TensorFlow's half-pixel bilinear weights
-// and lerp order, exactly as ucb_resize_kernel — the SSIM operands and figures 1 and 3
+// stage 5: output = pad(resize(clip(orig))), gt_sc = pad(resize(gt0)) (:441,454,588-590, BilinearTap), the SSIM operands and
+// figures 1 and 3
 __global__ __launch_bounds__(256) void ucb_tsm_s5_kernel(const float* __restrict__ rows, int S, void* scratch,
                                                          unsigned char* __restrict__ strips, float* __restrict__ figs) {
 #pragma clang fp contract(off)
@@ -335,46 +261,19 @@ __global__ __launch_bounds__(256) void ucb_tsm_s5_kernel(const float* __restrict
   const int size = g->size;
   float o[3] = {0.f, 0.f, 0.f}, gt[3] = {0.f, 0.f, 0.f};
   if (!g->fail && oy < size && ox < size) {
-    const float scale = (float)S / (float)size;
-    const float sy = ((float)oy + 0.5f) * scale - 0.5f, sx = ((float)ox + 0.5f) * scale - 0.5f;
-    const float fy = floorf(sy), fx = floorf(sx);
-    const int y0 = max((int)fy, 0), y1 = min((int)ceilf(sy), S - 1);
-    const int x0 = max((int)fx, 0), x1 = min((int)ceilf(sx), S - 1);
-    const float yl = sy - fy, xl = sx - fx;
-    auto lerp = [&](float a, float b, float c, float d) {
-      const float top = a + (b - a) * xl;
-      const float bottom = c + (d - c) * xl;
-      return top + (bottom - top) * yl;
-    };
+    const BilinearTap t(oy, ox, size, S);
     const float* r = rows + (size_t)item * N * kUcbTsmRowCh;
-    const size_t q00 = (size_t)y0 * S + x0, q01 = (size_t)y0 * S + x1, q10 = (size_t)y1 * S + x0, q11 = (size_t)y1 * S + x1;
+    const size_t q00 = (size_t)t.y0 * S + t.x0, q01 = (size_t)t.y0 * S + t.x1, q10 = (size_t)t.y1 * S + t.x0, q11 = (size_t)t.y1 * S + t.x1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      o[c] = lerp(sc.comp[q00 * 3 + c], sc.comp[q01 * 3 + c], sc.comp[q10 * 3 + c], sc.comp[q11 * 3 + c]);
-      gt[c] = lerp(r[q00 * kUcbTsmRowCh + 3 + c], r[q01 * kUcbTsmRowCh + 3 + c], r[q10 * kUcbTsmRowCh + 3 + c], r[q11 * kUcbTsmRowCh + 3 + c]);
+      o[c] = t.lerp(sc.comp[q00 * 3 + c], sc.comp[q01 * 3 + c], sc.comp[q10 * 3 + c], sc.comp[q11 * 3 + c]);
+      gt[c] = t.lerp(r[q00 * kUcbTsmRowCh + 3 + c], r[q01 * kUcbTsmRowCh + 3 + c], r[q10 * kUcbTsmRowCh + 3 + c], r[q11 * kUcbTsmRowCh + 3 + c]);
     }
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) { sc.gt[(size_t)p * 3 + c] = gt[c]; sc.out[(size_t)p * 3 + c] = o[c]; }
-  tsm_put(strip, figs, S, item, 1, oy, ox, o);
-  tsm_put(strip, figs, S, item, 3, oy, ox, gt);
-}
-
-struct UcbTsmSsimOperands {              // ucb_ssim_tile's operands: gt_sc and the output, [N][3] each
-  const float* gt;
-  const float* out;
-  __device__ float x(size_t q, int c) const { return gt[q * 3 + c]; }
-  __device__ float y(size_t q, int c) const { return out[q * 3 + c]; }
-};
-
-__global__ __launch_bounds__(256) void ucb_tsm_ssim_kernel(int S, void* scratch) {
-  const UcbTsmScratch sc = ucb_tsm_scratch(scratch, blockIdx.y, S);
-  ucb_ssim_tile(UcbTsmSsimOperands{sc.gt, sc.out}, S, sc.ssim_part);
-}
-
-__global__ __launch_bounds__(64) void ucb_tsm_ssim_finish_kernel(int S, void* scratch, const int* __restrict__ status, float* __restrict__ losses) {   // grid (B), one wave
-  const int item = blockIdx.x;
-  ucb_ssim_finish(ucb_tsm_scratch(scratch, item, S).ssim_part, S, status[item] == UCB_OK, losses + 2 * item);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 1, oy, ox, o);
+  put_figure<kUcbTsmFigs>(strip, figs, S, item, 3, oy, ox, gt);
 }
 
 inline hipError_t launch_ucb_post_tsm(const float* rows, const unsigned char* masks, const float* boxes, int B, int S, float* losses,
@@ -390,14 +289,9 @@ inline hipError_t launch_ucb_post_tsm(const float* rows, const unsigned char* ma
   hipLaunchKernelGGL(ucb_tsm_a3_kernel, it, dim3(512), 0, stream, S, scratch, nose_stats);
   hipLaunchKernelGGL(ucb_tsm_s4_kernel, px, dim3(256), 0, stream, rows, masks, S, scratch, strips, figs, status);
   hipLaunchKernelGGL(ucb_tsm_s5_kernel, px, dim3(256), 0, stream, rows, S, scratch, strips, figs);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const int tiles = (S + kSsimTile - 1) / kSsimTile;
-  hipLaunchKernelGGL(ucb_tsm_ssim_kernel, dim3((unsigned)(tiles * tiles), (unsigned)B), dim3(256), 0, stream, S, scratch);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ucb_tsm_ssim_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, S, scratch, status, losses);
-  return hipGetLastError();
+  return launch_ssim_tail(
+      B, S, [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(ssim_pair_kernel<UcbTsmScratch>, grid, block, 0, stream, S, scratch); },
+      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(ssim_finish_kernel<UcbTsmScratch>, grid, block, 0, stream, S, scratch, status, losses); });
 }
 
 }  // namespace bsr

@@ -62,6 +62,12 @@ def resize_bilinear(x: np.ndarray, size: int) -> np.ndarray:
     return (top + (bottom - top) * yl[:, None, None]).astype(np.float32)
 
 
+def strip_of(figs: List[np.ndarray]) -> np.ndarray:
+    """Logging.get_imgs of the figures: clip, * 255, round half to even, side by side -> uint8 [S, len(figs) * S, 3]."""
+    cols = [np.clip(f[0], 0.0, 1.0) * np.float32(255) for f in figs]
+    return np.rint(np.concatenate(cols, axis=1)).astype(np.uint8)
+
+
 def _pad(x: np.ndarray, size: int, full: int) -> np.ndarray:
     return np.pad(x, [[0, full - size], [0, full - size], [0, 0]])
 

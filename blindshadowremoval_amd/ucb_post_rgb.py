@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .metrics import psnr as _psnr, ssim as _ssim
-from .ucb_post import _pad, read_masks, resize_bilinear
+from .ucb_post import _pad, read_masks, resize_bilinear, strip_of
 
 FIGS = 3          # tmp, out, gt_sc (train_RGB_test.py:502)
 
@@ -47,12 +47,6 @@ def ucb_postprocess_rgb(img0: np.ndarray, gt0: np.ndarray, con0: np.ndarray, box
     losses = {"ssim": float(_ssim(g, o).sum()), "psnr": float(_psnr(g, o).sum())}          # :481-482
     figs = [tmp, out, gt_sc]                                                               # :502
     return losses, [np.asarray(f, np.float32).reshape(1, full, full, 3) for f in figs]
-
-
-def strip_of(figs: List[np.ndarray]) -> np.ndarray:
-    """Logging.get_imgs of the figures: clip, * 255, round half to even, side by side -> uint8 [S, len(figs) * S, 3]."""
-    cols = [np.clip(f[0], 0.0, 1.0) * np.float32(255) for f in figs]
-    return np.rint(np.concatenate(cols, axis=1)).astype(np.uint8)
 
 
 def run_post_job_rgb(job: dict):

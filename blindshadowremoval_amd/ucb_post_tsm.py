@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from .metrics import psnr as _psnr, ssim as _ssim
-from .ucb_post import _pad, resize_bilinear
+from .ucb_post import _pad, resize_bilinear, strip_of  # noqa: F401  (re-exported: the figures' strip, as the GSC and RGB steps lay it out)
 
 FIGS = 8                  # train_with_TSM.py:614
 MASKS = ("face_hair", "face", "nose")     # the masks the step reads (MASK_DIRS keys)
@@ -99,10 +99,3 @@ def ucb_postprocess_tsm(img0: np.ndarray, gt0: np.ndarray, con0: np.ndarray, con
     mp3 = np.broadcast_to(mp, (full, full, 3))
     figs = [tmp, out, mp3 * np.float32(2), gt_sc, d, flipped, _flip(flipped), np.maximum(orig, _flip(flipped))]      # :614
     return losses, [np.ascontiguousarray(f, np.float32).reshape(1, full, full, 3) for f in figs], float(frac), float(mean_intensity)
-
-
-def strip_of(figs: List[np.ndarray]) -> np.ndarray:
-    """Logging.get_imgs of the figures: clip, * 255, round half to even, side by side -> uint8 [S, len(figs) * S, 3]."""
-    cols = [np.clip(f[0], 0.0, 1.0) * np.float32(255) for f in figs]
-    return np.rint(np.concatenate(cols, axis=1)).astype(np.uint8)
-
