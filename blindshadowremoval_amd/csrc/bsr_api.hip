@@ -34,6 +34,7 @@
 #include "ucb_tsm_kernels.h"
 #include "sfw_kernels.h"
 #include "wino_conv2.h"
+#include "wild_crop_kernels.h"
 
 namespace {
 
@@ -575,6 +576,16 @@ int ensure_workspace(bsr_handle* h, int B, int H, int W, hipStream_t s) {
   }
   h->plan = p;
   h->B = B; h->H = H; h->W = W;
+  return BSR_OK;
+}
+
+// Records of a table that lies in device memory, read back for validation: the copy is ordered behind whatever `stream` still has to do
+// to the blob (the upload of the table itself), and the host waits for it.
+template <typename T>
+int read_records(const unsigned char* blob, size_t off, int n, hipStream_t s, std::vector<T>* out) {
+  out->resize((size_t)n);
+  HIP_TRY(hipMemcpyAsync(out->data(), blob + off, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return BSR_OK;
 }
 
@@ -1130,6 +1141,65 @@ int bsr_png_unfilter(int device, void* d_blob, size_t blob_bytes, size_t items_o
   unsigned char* blob = static_cast<unsigned char*>(d_blob);
   hipLaunchKernelGGL(bsr::png_unfilter_kernel, dim3((unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), blob,
                      reinterpret_cast<const bsr::UnfilterItem*>(blob + items_off));
+  HIP_TRY(hipGetLastError());
+  return BSR_OK;
+}
+
+int bsr_png_unfilter_tall(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, void* stream) {
+  if (d_blob == nullptr) return fail(BSR_ERR_ARG, "bsr_png_unfilter_tall: null argument");
+  if (n <= 0 || n > 65535 || items_off % 8 != 0) return fail(BSR_ERR_ARG, "bsr_png_unfilter_tall: n must be 1..65535 and items_off 8-byte aligned");
+  if (items_off > blob_bytes || (size_t)n * sizeof(bsr::UnfilterTallItem) > blob_bytes - items_off)
+    return fail(BSR_ERR_ARG, "bsr_png_unfilter_tall: the item table does not fit in blob_bytes");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  unsigned char* blob = static_cast<unsigned char*>(d_blob);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::vector<bsr::UnfilterTallItem> items;
+  if (int rc = read_records(blob, items_off, n, s, &items)) return rc;
+  const long long total = (long long)blob_bytes, slack = bsr::kUnfilterSlack;
+  for (int i = 0; i < n; ++i) {
+    const bsr::UnfilterTallItem& it = items[(size_t)i];
+    const bool shape = (it.c == 1 || it.c == 3 || it.c == 4) && it.h >= 1 && it.h <= 65535 && it.w >= 1 && it.w <= 65535 && (long long)it.w * it.c >= 4 &&
+                       it.rows_needed >= 0 && (it.grey_out == 0 || it.c == 1);
+    if (!shape) return fail(BSR_ERR_ARG, "bsr_png_unfilter_tall: a record needs c in {1,3,4}, 1 <= h, w <= 65535, w c >= 4, rows_needed >= 0, grey_out with c = 1 only");
+    const long long raw = (long long)it.h * (1 + (long long)it.w * it.c), outb = (long long)it.h * it.w * (it.grey_out ? 1 : 3);
+    // the kernel reads its rows four pixels at a time: kUnfilterSlack readable bytes around the scanlines and behind the output area
+    if (it.raw_off < slack || it.raw_off > total || raw + slack > total - it.raw_off || it.out_off < 0 || it.out_off > total || outb + slack > total - it.out_off)
+      return fail(BSR_ERR_ARG, "bsr_png_unfilter_tall: a record points outside the blob (16 bytes of the blob must surround the scanlines and follow the output)");
+  }
+  hipLaunchKernelGGL(bsr::png_unfilter_tall_kernel, dim3((unsigned)n), dim3(256), 0, s, blob, reinterpret_cast<const bsr::UnfilterTallItem*>(blob + items_off));
+  HIP_TRY(hipGetLastError());
+  return BSR_OK;
+}
+
+int bsr_crop_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, void* stream) {
+  if (d_blob == nullptr) return fail(BSR_ERR_ARG, "bsr_crop_faces: null argument");
+  if (n <= 0 || n > 65535 || items_off % 8 != 0) return fail(BSR_ERR_ARG, "bsr_crop_faces: n must be 1..65535 and items_off 8-byte aligned");
+  if (S != 32 && S != 64 && S != 128 && S != 256) return fail(BSR_ERR_ARG, "bsr_crop_faces: S must be 32, 64, 128 or 256");
+  if (items_off > blob_bytes || (size_t)n * sizeof(bsr::CropItem) > blob_bytes - items_off)
+    return fail(BSR_ERR_ARG, "bsr_crop_faces: the item table does not fit in blob_bytes");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  unsigned char* blob = static_cast<unsigned char*>(d_blob);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::vector<bsr::CropItem> items;
+  if (int rc = read_records(blob, items_off, n, s, &items)) return rc;
+  const long long total = (long long)blob_bytes, outb = 3ll * S * S;
+  for (int i = 0; i < n; ++i) {
+    const bsr::CropItem& it = items[(size_t)i];
+    if (it.h < 1 || it.h > 65535 || it.w < 1 || it.w > 65535 || it.preset_x < 0 || it.preset_y < 0 || it.preset_x > (1 << 20) || it.preset_y > (1 << 20))
+      return fail(BSR_ERR_ARG, "bsr_crop_faces: a record needs 1 <= h, w <= 65535 and presets in 0..2^20");
+    const long long srcb = 3ll * it.h * it.w;
+    if (it.src_off < 0 || it.src_off > total || srcb > total - it.src_off || it.out_off < 0 || it.out_off > total || outb > total - it.out_off)
+      return fail(BSR_ERR_ARG, "bsr_crop_faces: a record points outside the blob");
+    // the box against what it is cut from: the photograph itself (8-bit branch) or the padded canvas around it
+    const bool padded = it.preset_x != 0 || it.preset_y != 0;
+    const long long cw = padded ? (long long)it.w + 2ll * it.preset_x + 2 : it.w, ch = padded ? (long long)it.h + 2ll * it.preset_y + 2 : it.h;
+    if (it.box[0] < 0 || it.box[1] < 0 || it.box[2] <= it.box[0] || it.box[3] <= it.box[1] || it.box[2] > cw || it.box[3] > ch)
+      return fail(BSR_ERR_ARG, "bsr_crop_faces: a record's box is empty or leaves its canvas");
+  }
+  hipLaunchKernelGGL(bsr::crop_faces_kernel, dim3((unsigned)((S / 16) * (S / 16)), (unsigned)n), dim3(256), 0, s, blob,
+                     reinterpret_cast<const bsr::CropItem*>(blob + items_off), S);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
 }

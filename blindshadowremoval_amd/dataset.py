@@ -217,16 +217,34 @@ def generate_offset_map(source: np.ndarray, target: np.ndarray, size: int) -> np
 
 def build_row(img_path: str, lm_path: str, gt_path: Optional[str] = None, size: int = 256) -> Tuple[np.ndarray, np.ndarray]:
     """One `[size,size,16]` row + crop box, in the order of dataset.py:627-638."""
-    uv, lm_ref = _face_model()
     img = imread_rgb(img_path)
-    gt = imread_rgb(gt_path) if gt_path else img
+    return _row_of(img, imread_rgb(gt_path) if gt_path else img, np.load(lm_path), size)
+
+
+def _row_of(img: np.ndarray, gt: np.ndarray, lm0: np.ndarray, size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """build_row behind its file reads: photograph and ground truth as float64 in [0, 1], the landmark file's array."""
+    uv, lm_ref = _face_model()
     both = np.concatenate([img, gt], axis=2)
-    crop, lm, box = face_crop_and_resize(both, np.load(lm_path), size)
+    crop, lm, box = face_crop_and_resize(both, lm0, size)
     face = generate_face_region(lm, size)
     uvm = generate_uv_map(lm, uv, size)
     reg_in = generate_offset_map(lm, lm_ref, size)
     reg_out = generate_offset_map(lm_ref, lm, size)
     return np.concatenate([crop, uvm, reg_in, reg_out, face], axis=2).astype(np.float32), np.asarray(box, np.float32)
+
+
+def build_row_uncropped(img_path: str, size: int = 256):
+    """One row from an UNCROPPED photograph `<name>.png` with `<name>.npy` beside it: the reference's two procedures back to back —
+    dataprocess.py (wild_crop.crop_face: the 256 x 256 face and its landmarks, what the script writes to a folder) and then
+    parse_fn_test_FFHQ on that folder (build_row) — without the folder.  None where the script skips the photograph."""
+    from .pngio import read_rgb_u8
+    from .wild_crop import crop_face
+    res = crop_face(read_rgb_u8(img_path), np.load(os.path.splitext(img_path)[0] + ".npy"))
+    if res is None:
+        return None
+    face, lm256, _ = res
+    img = face.astype(np.float64) / 255.0                                # imread_rgb of the file the script writes (PNG is lossless)
+    return _row_of(img, img, lm256, size)
 
 
 def _maps(lm: np.ndarray, size: int):
@@ -374,6 +392,17 @@ def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         from .prep import host_part, host_part_ring
         hjob = (lm_path, gt_path[1], size) + ((gt_path[2],) if len(gt_path) > 2 else ())
         return host_part_ring(hjob, job[4]) if len(job) > 4 else host_part(hjob)            # job[4]: (ring file, slot, slot bytes)
+    if gt_path == "<uncropped_device>":                                    # lm_path is the photograph's .png here (name_list of uncropped=True)
+        from .prep import host_part_uncropped
+        part = host_part_uncropped((lm_path, size))
+        if part is None:
+            raise ValueError("%s fails dataprocess.py's size rule: Dataset(uncropped=True) lists no such item" % lm_path)
+        return part
+    if gt_path == "<uncropped>":
+        res = build_row_uncropped(lm_path, size)
+        if res is None:
+            raise ValueError("%s fails dataprocess.py's size rule: Dataset(uncropped=True) lists no such item" % lm_path)
+        return res[0][None, None], res[1][None], np.array([lm_path.encode()])
     if gt_path == "<sfw>":
         return build_sfw_pair(lm_path, size)
     if isinstance(gt_path, tuple) and gt_path[0] == "<ucb_tsm>":
@@ -403,7 +432,7 @@ class Dataset:
 
     def __init__(self, config, mode: str = "test", dset=None, ucb: bool = False, rows: int = 1, seed: int = 0,
                  workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16,
-                 device_groups: Optional[int] = None):
+                 device_groups: Optional[int] = None, uncropped: bool = False):
         if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc", "ucb_tsm"):
             raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video' | 'ucb_tsm'); "
                                       "training loaders are out of scope")
@@ -447,7 +476,23 @@ class Dataset:
         # the FFHQ one (one photograph per item: the GPU side is the longer one there, and the kernel is 0.17 ms per batch of it; -3 %).
         # BSR_DEVICE_UNFILTER=0 / 1 overrides.
         self.device_unfilter: Optional[bool] = None
+        # uncropped = True: DATA_DIR_TEST globs name the .png files of in-the-wild photographs (a folder such as sample_uncropped_images/,
+        # each with its 68 landmarks in a .npy beside it) instead of item folders; every element is dataprocess.py's crop (wild_crop.py)
+        # followed by the FFHQ loader's row — on the host, or with device_prep from the inflated scanlines on (prep.rows_uncropped).
+        # name_list holds the photographs dataprocess.py keeps (`length > 250`, decided from the landmarks alone)
+        self.uncropped = bool(uncropped)
+        if self.uncropped and (ucb or rows != 1 or dset is not None or device_groups is not None):
+            raise ValueError("uncropped=True is the FFHQ loader over uncropped photographs: ucb=False, rows=1, dset=None, no device_groups")
         self.name_list: List[str] = []
+        if self.uncropped:
+            from .wild_crop import MIN_LENGTH, box_length
+            for d in config.DATA_DIR_TEST:
+                for f in sorted(glob.glob(d), key=natural_key):
+                    lm_path = os.path.splitext(f)[0] + ".npy"
+                    if f.endswith(".png") and os.path.isfile(lm_path) and box_length(np.load(lm_path)) > MIN_LENGTH:
+                        self.name_list.append(f)
+            self.feed: Iterator = self._iterate()
+            return
         pattern = "*.npy" if dset in (None, "ucb_tsm") else "*_label.png"  # dataset.py:55-61 | dataset_with_TSM.py:63 (ucb_tsm: see the module docstring)
         for d in config.DATA_DIR_TEST:
             for folder in sorted(glob.glob(d), key=natural_key):
@@ -487,6 +532,10 @@ class Dataset:
                     yield self._ring_job((label, what, [], size), masks is not None)
                 else:
                     yield (label, ("<ucb_tsm>", self._gt_path(label)) if self.dset == "ucb_tsm" else kind, [], size)
+            return
+        if self.uncropped:                                                 # (no ring: a photograph's scanlines are ~3 MB, they take the pipe)
+            for img_path in self.name_list[lo:hi]:
+                yield (img_path, "<uncropped_device>" if self.device_prep is not None else "<uncropped>", [], size)
             return
         for i, lm_path in enumerate(self.name_list):
             if i >= hi:
@@ -565,7 +614,7 @@ class Dataset:
         """Device preparation with worker processes: the workers write their results into a page-locked shared-memory ring
         (prep.SlotRing / host_part_ring) instead of pickling ~0.5 MB per item through their pipes.  BSR_LOADER_RING=0 keeps the pipes."""
         # (of the groups only the UCB ones: an SFW group's label is a palette or grey file decoded in the worker, it goes through the pipe)
-        if (self._device is None or self.dset == "sfw" or self.workers <= 0 or getattr(self, "_ring", None) is not None or getattr(self, "_started", False)
+        if (self._device is None or self.dset == "sfw" or getattr(self, "uncropped", False) or self.workers <= 0 or getattr(self, "_ring", None) is not None or getattr(self, "_started", False)
                 or os.environ.get("BSR_LOADER_RING", "1") == "0"):
             return
         from .prep import RING_CAP, SlotRing
@@ -606,7 +655,7 @@ class Dataset:
         self._emitted = 0
 
         def emit():
-            out, boxes, masks, names = dp.rows_ex(group)
+            out, boxes, masks, names = dp.rows_uncropped(group) if self.uncropped else dp.rows_ex(group)
             self._emitted += len(group)
             if dp.ring is not None:
                 self._ring_copies.append([self._emitted, dp.last_copy, False])       # jobs < _emitted have left their slots once this event is done

@@ -47,6 +47,16 @@ assert UNFILTER_DTYPE.itemsize == 32          # csrc/prep_kernels.h UnfilterItem
 UNFILTER_MAX_ROWS = 256                       # csrc/prep_kernels.h kUnfilterMaxRows: one workgroup, one thread per row
 
 
+# in-the-wild photographs (csrc/wild_crop_kernels.h): the tall reconstruction's record (UNFILTER_DTYPE + rows_needed) and the crop's
+UNFILTER_TALL_DTYPE = np.dtype([("raw_off", "<i8"), ("out_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("c", "<i4"), ("grey_out", "<i4"),
+                                ("rows_needed", "<i4"), ("pad", "<i4")], align=True)
+assert UNFILTER_TALL_DTYPE.itemsize == 40     # UnfilterTallItem
+CROP_DTYPE = np.dtype([("src_off", "<i8"), ("out_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("box", "<i4", (4,)), ("preset_x", "<i4"),
+                       ("preset_y", "<i4")], align=True)
+assert CROP_DTYPE.itemsize == 48              # CropItem
+UNFILTER_SLACK = 16                           # csrc/prep_kernels.h kUnfilterSlack: readable bytes around filtered scanlines
+
+
 def _tri_table(tri, zs: Sequence[np.ndarray]) -> np.ndarray:
     """[ntri, 18] float64: three edge functions (normalised barycentrics l_i = A_i x + B_i y + C_i) + up to three channels of
     plane coefficients (a, b, c), the latter from matplotlib's own `calculate_plane_coefficients` (what LinearTriInterpolator uses)."""
@@ -254,6 +264,85 @@ def host_part_group(job, raw: bool = False):
     box, lm, lm_m = crop_box_pair(np.load(lm_path), img.shape[1])
     out = (img, gt, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), gt_path.encode())
     return out + (masks,) if masks is not None else out
+
+
+def host_part_uncropped(job, raw: bool = True):
+    """The host half of one UNCROPPED photograph (dataset.Dataset(uncropped=True, device_prep=gpu)): (png_path, size) -> (img, None, box of
+    the row, [4 triangle tables], name, (crop box, preset_x, preset_y)) or None where dataprocess.py skips the photograph.  Everything
+    but `img` comes from the landmarks alone: wild_crop.crop_geometry (the script's box, presets and landmarks in the crop's
+    coordinates), then — as the FFHQ loader does with the folder the script wrote — crop_box and meshes of those landmarks.  img: the
+    file's inflated, still filtered scanlines (pngio.RawScanlines: the device reconstructs and crops them) or, for a file that is no
+    plain 8-bit PNG, the decoded photograph."""
+    from . import wild_crop
+    img_path, size = job
+    img = (_imread_raw if raw else _imread_u8)(img_path)
+    if hasattr(img, "raw") and img.w * img.c < 4:
+        img = img.decode()
+    geo = wild_crop.crop_geometry(np.load(os.path.splitext(img_path)[0] + ".npy"), img.shape[0], img.shape[1])
+    if geo is None:
+        return None
+    cbox, preset_x, preset_y, lm256 = geo
+    box, lm = crop_box(lm256)
+    return (img, None, np.asarray(box, np.int32), meshes(lm), img_path.encode(), (np.asarray(cbox, np.int32), preset_x, preset_y))
+
+
+def _layout_uncropped(parts, size: int):
+    """The blob of a batch of host_part_uncropped results: [row records | grid | crop records | tall records | per item: scanlines with
+    their slack (or the decoded photograph) and the four tables] — the `head`, staged by the caller — then, device only, the
+    reconstructed photographs and the S x S crops the row records point to.  -> (total, head, rows_off, grid_off, crop_off, tall_off,
+    number of tall records, pieces)."""
+    B = len(parts)
+    rows, crops = np.zeros(B, ROW_DTYPE), np.zeros(B, CROP_DTYPE)
+    n_tall = sum(1 for p in parts if hasattr(p[0], "raw"))
+    talls = np.zeros(n_tall, UNFILTER_TALL_DTYPE)
+    pieces, off = [], 0
+
+    def take(nbytes: int) -> int:
+        nonlocal off
+        o = off
+        off += (int(nbytes) + 7) & ~7
+        return o
+    rows_off, grid_off, crop_off, tall_off = take(rows.nbytes), take(size * 8), take(crops.nbytes), take(max(n_tall, 1) * UNFILTER_TALL_DTYPE.itemsize)
+    pieces.append((grid_off, np.linspace(0, 1, size).astype("<f8")))
+    k = 0
+    for i, part in enumerate(parts):
+        img, _, box, tabs, _, (cbox, preset_x, preset_y) = part[:6]
+        if len(tabs) != 4:
+            raise ValueError("prep blob: item %d carries %d triangle tables, the record takes 4" % (i, len(tabs)))
+        c = crops[i]
+        c["h"], c["w"], c["box"], c["preset_x"], c["preset_y"] = img.shape[0], img.shape[1], cbox, preset_x, preset_y
+        if hasattr(img, "raw"):
+            t = talls[k]
+            k += 1
+            take(UNFILTER_SLACK)
+            t["raw_off"] = take(img.raw.nbytes)
+            take(UNFILTER_SLACK)
+            pieces.append((int(t["raw_off"]), img.raw))
+            t["h"], t["w"], t["c"] = img.h, img.w, img.c
+            # the lowest photograph row a tap of the crop can touch is the box's last one
+            t["rows_needed"] = min(max(int(cbox[3]) - int(preset_y), 1), img.h)
+        else:
+            c["src_off"] = take(img.nbytes)
+            pieces.append((int(c["src_off"]), img))
+        r = rows[i]
+        r["h"] = r["w"] = size
+        r["box"] = box
+        for m, tab in enumerate(tabs):
+            if tab.shape[0] > MAX_TRI:
+                raise ValueError("a mesh has %d triangles (> %d)" % (tab.shape[0], MAX_TRI))
+            r["tri_off"][m] = take(tab.nbytes)
+            r["ntri"][m] = tab.shape[0]
+            pieces.append((int(r["tri_off"][m]), tab))
+    head = off
+    k = 0
+    for i, part in enumerate(parts):
+        if hasattr(part[0], "raw"):
+            talls[k]["out_off"] = crops[i]["src_off"] = take(part[0].h * part[0].w * 3 + UNFILTER_SLACK)
+            k += 1
+    for i in range(B):
+        crops[i]["out_off"] = rows[i]["img_off"] = rows[i]["gt_off"] = take(size * size * 3)
+    pieces += [(rows_off, rows), (crop_off, crops)] + ([(tall_off, talls)] if n_tall else [])
+    return off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces
 
 
 RING_CAP = 1 << 20        # bytes of one slot of the loaders' shared-memory ring (a 256x256 UCB item with ground truth, tables and masks: ~0.55 MB)
@@ -644,3 +733,46 @@ class DevicePrep:
                 v = d_blob[base + moff:base + moff + nbytes]
                 masks[i] = ("dev_" + kind, v.view(7, -1) if kind == "bits" else v.view(7, ms, ms), ms)
         return out, boxes, masks, names
+
+    def rows_uncropped(self, parts):
+        """rows_ex for host_part_uncropped results (they come through the workers' pipes: a 1024 x 1024 photograph is three ring slots):
+        the scanlines go to the device as they were inflated, and bsr_png_unfilter_tall -> bsr_crop_faces -> bsr_prep_rows run behind the
+        copy in one stream; the crop's output is the row record's image.  -> (rows [B,S,S,16], boxes, [None] * B, names)."""
+        if self.planes is not None:
+            raise ValueError("DevicePrep.rows_uncropped prepares rows (planes=None)")
+        torch = self._torch
+        B, S = len(parts), self.size
+        total, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces = _layout_uncropped(parts, S)
+        dev = "cuda:%d" % self.device
+        with torch.cuda.device(self.device):
+            k = self._turn = (getattr(self, "_turn", 0) + 1) & 1
+            stage = self._stage[k]
+            if stage is None or stage.numel() < head:
+                stage = self._stage[k] = torch.empty(max(head, 1 << 22) * 5 // 4, dtype=torch.uint8).pin_memory()
+            if self._copied[k] is not None:
+                self._copied[k].synchronize()
+            pack_into(stage.numpy(), pieces)
+            main = torch.cuda.current_stream()
+            if getattr(self, "_h2d", None) is None:
+                self._h2d = torch.cuda.Stream(device=self.device)
+            with torch.cuda.stream(self._h2d):
+                st = self._h2d.cuda_stream
+                d_blob = torch.empty(total, dtype=torch.uint8, device=dev)
+                d_blob[:head].copy_(stage[:head], non_blocking=True)
+                ev = self._copied[k] = self.last_copy = torch.cuda.Event()
+                ev.record()
+                if n_tall:
+                    self._check(self._lib.bsr_png_unfilter_tall(self.device, d_blob.data_ptr(), total, tall_off, n_tall, st), "bsr_png_unfilter_tall")
+                self._check(self._lib.bsr_crop_faces(self.device, d_blob.data_ptr(), total, crop_off, B, S, st), "bsr_crop_faces")
+                out = torch.empty((B, S, S, 16), dtype=torch.float32, device=dev)
+                tmp = torch.empty((B, S, S), dtype=torch.float32, device=dev)
+                rc = self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, out.data_ptr(), tmp.data_ptr(), st)
+                done = torch.cuda.Event()
+                done.record()
+            main.wait_event(done)
+            out.record_stream(main)
+            tmp.record_stream(main)
+            d_blob.record_stream(main)
+        self._check(rc, "bsr_prep_rows")
+        boxes = np.stack([np.asarray(p[2], np.float32) for p in parts], axis=0)
+        return out, boxes, [None] * B, [p[4] for p in parts]

@@ -11,6 +11,8 @@ and `FSRNet` shards `dataset.name_list` contiguously over the ranks (fsrnet.py);
 into the same `<checkpoint-dir>/test/`, rank 0 prints the progress and the final running means over ALL items, and one JSON line
 with the loop's rate.  The process group is created by THIS process before it touches the GPU; nothing is re-exec'ed.
 Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random-weights SEED` (the reference ships no data shards).
+`--loop ffhq --uncropped`: --data globs uncropped photographs (`sample_uncropped_images/*.png`, landmarks in a .npy beside each); the
+reference's dataprocess.py crop runs inside the loader (Dataset(uncropped=True), wild_crop.py), on the device unless `--host-prep`.
 `--model rgb` runs the paper's single-stage RGB baseline instead (train_RGB_test.py's `main`: `FSRNetRGB.test`, `--loop ucb`, fp32 only).
 `--loop sfw` / `--loop sfw_video` run the GSC model's SFW evaluation (`FSRNet.testsfw` over Dataset(dset='sfw_gsc') /
 `FSRNet.testsfw_video` over Dataset(dset='sfw_video'): --data globs SFW video folders), in one process only.
@@ -44,6 +46,9 @@ def main(argv=None) -> int:
     ap.add_argument("--random-weights", type=int, default=None, metavar="SEED", help="seeded random-init weights in the checkpoint layout instead of a restore")
     ap.add_argument("--host-prep", action="store_true", help="prepare the rows on the host (default: on the device, prep.py; --model tsm: its "
                                                              "--loop ucb | sfw groups — sfw_video is always prepared on the host)")
+    ap.add_argument("--uncropped", action="store_true", help="--loop ffhq only: --data globs the .png files of uncropped photographs (each with its 68 "
+                                                             "landmarks in a .npy beside it); dataprocess.py's crop runs in the loader (wild_crop.py; on the "
+                                                             "device unless --host-prep)")
     ap.add_argument("--host-post", action="store_true", help="rounds 2-4 forms: UCB post-processing in worker processes and PNG encoding on the host "
                                                              "(default: both on the device — ucb_post_gpu.py, gpu_png.py)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl")
@@ -55,6 +60,10 @@ def main(argv=None) -> int:
         return 2
     sfw = args.loop in ("sfw", "sfw_video")
     tsm = args.model == "tsm"
+    if args.uncropped and (args.loop != "ffhq" or args.model != "gsc"):
+        sys.stderr.write("run_loop: --uncropped feeds uncropped photographs to FSRNet.testFFHQ: --model gsc --loop ffhq (the other loops read "
+                         "data sets that come cropped)\n")
+        return 2
     if tsm and args.loop == "ffhq":
         sys.stderr.write("run_loop: --model tsm runs train_with_TSM.py's loops: --loop ucb | sfw | sfw_video (it has no testFFHQ)\n")
         return 2
@@ -116,7 +125,7 @@ def main(argv=None) -> int:
     else:
         if not args.host_prep:
             ds_kw.update(device_prep=local_rank, device_batch=args.batch)
-        ds = Dataset(cfg, "test", ucb=ucb, **ds_kw)
+        ds = Dataset(cfg, "test", ucb=ucb, uncropped=args.uncropped, **ds_kw)
     if tsm:
         return _run_tsm(args, cfg, ds)
     if args.model == "rgb":

@@ -159,6 +159,27 @@ int bsr_prep_groups(int device, const void* d_blob, size_t blob_bytes, size_t gr
  * filtered image (a thread reads its row four pixels at a time).  ABI 8. */
 int bsr_png_unfilter(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, void* stream);
 
+/* bsr_png_unfilter for files of any height (an uncropped photograph of the reference's "Preprocessing New Images" procedure,
+ * /root/reference/dataprocess.py:25, is 1024 rows).  Same blob conventions; n records of 40 bytes at items_off:
+ * { int64 raw_off, out_off; int32 h, w, c, grey_out, rows_needed, pad } — 1 <= h <= 65535, w c >= 4; one workgroup per image walks it in
+ * bands of 256 rows, the last reconstructed row of a band being the row above the next.  rows_needed > 0 stops the walk after that many
+ * rows (the rows below a crop box are never read); 0 = all.  The output equals the host reconstruction bit for bit.  This entry reads the
+ * records back (it synchronises `stream`) and checks every one against blob_bytes BEFORE it launches: offsets, sizes, 16 bytes of the
+ * blob in front of and behind the scanlines and behind the [h][w][3 | 1] output area; BSR_ERR_ARG and nothing launched otherwise.
+ * Added under ABI 8. */
+int bsr_png_unfilter_tall(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, void* stream);
+
+/* The crop of /root/reference/dataprocess.py:39-62,72 on the device: n records of 48 bytes at items_off (8-byte aligned)
+ * { int64 src_off, out_off; int32 h, w, box[4], preset_x, preset_y } — src_off: an RGB8 photograph [h][w][3] in the blob, out_off: where
+ * the RGB8 crop [S][S][3] is written, box = x0, y0, x1, y1.  preset_x == preset_y == 0: the box lies in the photograph and the resize
+ * is OpenCV's 8-bit INTER_LINEAR (fixed point); otherwise the box is in the coordinates of the reference's float64 zero canvas of
+ * (h + 2 preset_y + 2) x (w + 2 preset_x + 2) pixels with the photograph at (preset_y, preset_x) — implied, never materialised — and the
+ * resize is the floating INTER_LINEAR on doubles, rounded half-even and saturated to a byte.  Every byte equals
+ * blindshadowremoval_amd/wild_crop.py's host statement.  S = 32, 64, 128 or 256.  The entry reads the records back (it synchronises
+ * `stream`) and validates each against blob_bytes before launching — offsets, h w 3, S S 3, the box against its canvas — so that no
+ * record can make the kernel read or write outside the blob: BSR_ERR_ARG and nothing launched otherwise.  Added under ABI 8. */
+int bsr_crop_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped

@@ -38,15 +38,55 @@ def alone_ms(fn, jobs, n=6):
     return round((time.process_time() - c0) / min(n, len(jobs)) * 1e3, 2)
 
 
+def uncropped_stage(args):
+    """The one host stage the uncropped FFHQ loader adds, alone, in the table's units: its jobs through the loops' own pool."""
+    from blindshadowremoval_amd.dataset import Dataset, _SelectPool, build_element, usable_cpus
+    from blindshadowremoval_amd.fsrnet import Config
+    cfg = Config(0)
+    cfg.DATA_DIR_TEST = [args.uncropped]
+    ncpu = usable_cpus()
+    nw = args.workers or ncpu
+    ds = Dataset(cfg, "test", uncropped=True, **({} if args.host_prep else dict(device_prep=0)))      # only used for its job list (no GPU call is made)
+    base = list(ds._jobs())
+    if not base:
+        raise SystemExit("no photograph of %s passes dataprocess.py's size rule" % args.uncropped)
+    n = args.items
+    jobs = [base[i % len(base)] for i in range(n)]
+    name = "uncropped_loader_full_host" if args.host_prep else "uncropped_loader_host_half"
+    what = ("dataset.build_row_uncropped per item (decode, wild_crop.crop_face, the whole row on the CPU)" if args.host_prep else
+            "prep.host_part_uncropped per item (inflate only; box, landmarks and meshes from the .npy; the filtered scanlines through the pipe)")
+    pool = _SelectPool(nw)
+    try:
+        pool.warm("rows")
+        run_stage(pool, jobs[:nw])
+        dt, cpu = run_stage(pool, jobs)
+    finally:
+        pool.shutdown()
+    res = {"usable_cpus": ncpu, "worker_processes": nw, "items_per_stage": n, "photographs": len(base),
+           "stages": {name: {"items_per_sec": round(n / dt, 1), "driver_cpu_ms_per_item": round(cpu / n * 1e3, 3),
+                             "job_cpu_ms_alone": alone_ms(build_element, jobs, 3), "what": what}}}
+    line = json.dumps(res, indent=1)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--items", type=int, default=400)
     ap.add_argument("--workers", type=int, default=0, help="worker processes (default: one per usable CPU)")
+    ap.add_argument("--uncropped", default=None, metavar="GLOB", help="only the loader stage of run_loop --loop ffhq --uncropped over these .png files "
+                                                                      "(Dataset(uncropped=True): the device route's host half, or with --host-prep the whole host route)")
+    ap.add_argument("--host-prep", action="store_true", help="with --uncropped: the host route (decode, crop, the whole row) instead of the device route's host half")
     args = ap.parse_args()
     import numpy as np
     from blindshadowremoval_amd.dataset import Dataset, _SelectPool, usable_cpus
     from blindshadowremoval_amd.fsrnet import Config, FSRNet
+    if args.uncropped:
+        return uncropped_stage(args)
     golden = os.path.join(ROOT, "tests", "golden")
     ncpu = usable_cpus()
     nw = args.workers or ncpu
