@@ -132,7 +132,8 @@ constexpr int RGB_CS_R = kRGB.cs_r, RGB_CS_A = kRGB.cs_a, RGB_D = kRGB.d, RGB_CS
 struct Region {
   size_t off, floats;
 };
-// Float offsets into the workspace for a (B,H,W) problem; a slot the variant does not have is zero-sized.  qkv = theta | phi | g, d each.
+// Float offsets into the workspace for a (B,H,W) problem; a slot the variant does not have is zero-sized.  qkv = theta | phi | g, d each
+// (fp32 GSC / TSM: q' | t2 | g, with conv2 writing t2 there and the t2 slot unused — forward_impl's res_block).
 struct Plan {
   size_t x1, c3, c2, xa, t1, t2, y3[6], qkv, att[6], r[6], xh, ybuf, qh, f1, f2, cf, probe, reg32, share, yh, con, total;
   // A new shape moves every buffer.  All of them are fully rewritten by their producers each forward, pad channels included, except the
@@ -185,6 +186,7 @@ struct bsr_handle {
   int device = 0;
   float* d_blob = nullptr;
   float* d_wino = nullptr;       // fp32 GSC / TSM handles: the Winograd weight streams of res0..5.conv2 (wino_conv2.h), derived from the blob's direct images at bsr_create
+  float* d_keys = nullptr;       // fp32 GSC / TSM handles: the res0..5.c3q images with theta composed onto phi, N = [y3 | q' | g] (keys_compose), derived from the blob's at bsr_create
   std::unordered_map<std::string, LayerW> layers;
   Variant var = kGSC;
   int dtype = BSR_DTYPE_F32;     // BSR_DTYPE_F16 / BSR_DTYPE_F32X3: 16-bit matrix cores on the 3x3 / stride-2 / transposed 3x3 layers (igemm_h16.h), fp32 kernels elsewhere
@@ -211,6 +213,8 @@ struct bsr_handle {
                                  // and A/B measurements compare against; same operands, another summation order)
   bool fuse_attw = true;         // env BSR_FUSE_ATTW=0: attention and the `w` GEMM as two launches (A/B measurements, bit-identity tests)
   bool wino_conv2 = true;        // env BSR_WINO_CONV2=0: the fp32 res*.conv2 on the direct implicit-GEMM kernel instead of the Winograd F(2x2, 3x3) one (A/B measurements, the two-forms test)
+  bool keys_conv2 = true;        // env BSR_KEYS_CONV2=0: the fp32 attention with phi projected by res*.c3q (N = 672, conv2's output in a buffer of its own) instead of conv2's
+                                 // output as the keys (A/B measurements, the two-forms test)
   bool timing = false;
   std::vector<hipEvent_t> ev;    // event pool, pairs
   std::vector<int> ev_class;
@@ -248,6 +252,38 @@ void wino_filter_transform(const float* direct, float* out) {
     }
 }
 
+// res<i>.c3q with conv2's output t2 as the attention keys.  The block's logits are f_ij = theta_i . phi_j with theta = t2 Wq + bq and
+// phi = t2 Wk + bk (model.py:33-53; Wq, Wk, bq, bk = columns 288..415 / 416..543 of the blob's conv3-composed c3q image), so
+//   f_ij = (theta_i Wk^T) . t2_j + theta_i . bk,
+// and the softmax over j removes the second term exactly.  With q'_i = t2_i (Wq Wk^T) + bq Wk^T — a 128 -> 128 affine map — the keys are
+// t2 itself and the GEMM computes N = [y3 288 | q' 128 | g 128]: 17 channel tiles instead of 21.  Wq Wk^T and bq Wk^T in float64 from
+// the image's float32 values, rounded once.  c3q = the blob's [4][1][768][36] image and [768] bias (HOST pointers) -> out_w
+// [4][1][kKeysNPad][36] (two zero tiles of slack for the NI = 3 group reads), out_b [kKeysNPad].  blindshadowremoval_amd/pack.py:
+// compose_keys_c3q states the same in numpy.
+constexpr int kKeysN = 288 + 256, kKeysNPad = kKeysN + 64, kC3qNPad = 768;
+constexpr size_t kKeysFloats = (size_t)4 * kKeysNPad * 36 + kKeysNPad;      // image, then bias
+void keys_compose(const float* c3q_w, const float* c3q_b, float* out_w, float* out_b) {
+  auto src = [&](int k, int n) -> const float& { return c3q_w[((size_t)(k / 32) * kC3qNPad + n) * 36 + k % 32]; };
+  memset(out_w, 0, (size_t)4 * kKeysNPad * 36 * sizeof(float));
+  memset(out_b, 0, kKeysNPad * sizeof(float));
+  for (int ch = 0; ch < 4; ++ch) {
+    memcpy(out_w + (size_t)ch * kKeysNPad * 36, c3q_w + (size_t)ch * kC3qNPad * 36, (size_t)288 * 36 * sizeof(float));                                  // y3
+    memcpy(out_w + ((size_t)ch * kKeysNPad + 416) * 36, c3q_w + ((size_t)ch * kC3qNPad + 544) * 36, (size_t)128 * 36 * sizeof(float));      // g
+  }
+  memcpy(out_b, c3q_b, 288 * sizeof(float));
+  memcpy(out_b + 416, c3q_b + 544, 128 * sizeof(float));
+  for (int m = 0; m < 128; ++m) {                 // column m of Wq Wk^T: sum over the theta / phi channel c, in channel order
+    for (int k = 0; k < 128; ++k) {
+      double acc = 0.0;
+      for (int c = 0; c < 128; ++c) acc += (double)src(k, 288 + c) * (double)src(m, 416 + c);
+      out_w[((size_t)(k / 32) * kKeysNPad + 288 + m) * 36 + k % 32] = (float)acc;
+    }
+    double acc = 0.0;
+    for (int c = 0; c < 128; ++c) acc += (double)c3q_b[288 + c] * (double)src(m, 416 + c);
+    out_b[288 + m] = (float)acc;
+  }
+}
+
 int find_layer(bsr_handle* h, const char* name, int nchunk, int taps, int ldp, int n_min, LayerW* out) {
   auto it = h->layers.find(name);
   if (it == h->layers.end()) return fail(BSR_ERR_BLOB, std::string("blob has no layer '") + name + "'");
@@ -282,9 +318,9 @@ void with_io(int io, F f) {
   else f(int_c<0>{});
 }
 
-bsr::WinoArgs wino_args(const float* in, float* out, const float* w, const float* bias, int H, int W) {
+bsr::WinoArgs wino_args(const float* in, float* out, const float* w, const float* bias, int H, int W, int out_cs = 128) {
   bsr::WinoArgs a{};
-  a.in = in; a.out = out; a.w = w; a.bias = bias; a.H = H; a.W = W; a.in_cs = 128; a.out_cs = 128; a.act = 1;
+  a.in = in; a.out = out; a.w = w; a.bias = bias; a.H = H; a.W = W; a.in_cs = 128; a.out_cs = out_cs; a.act = 1;
   return a;
 }
 
@@ -407,7 +443,8 @@ struct Launcher {
   template <int NI, int NCH, int MINW = 2>
   void gemm(int cls, const char* name, const float* in, int in_cs, size_t pixels, float* out, int out_cs, int n_store, int act,
             const float* res1 = nullptr, int res1_cs = 0, int res1_c = 0,
-            float* out2 = nullptr, int out2_cs = 0, int n_split = 0, int n_store1 = 0) {
+            float* out2 = nullptr, int out2_cs = 0, int n_split = 0, int n_store1 = 0, const LayerW* image = nullptr, int out2_gap_at = 0,
+            int out2_gap = 0) {      // image: a [NCH][1][n_pad][36] image of the handle's own in place of the blob's layer `name`
     if (rc != BSR_OK) return;
     using C = bsr::GemmNLoopCfg<NI, NCH>;
     LayerW l;
@@ -424,12 +461,14 @@ struct Launcher {
       kNSplit = BSR_NL_NSPLIT > most ? most : BSR_NL_NSPLIT;
 #endif
     }
-    rc = find_layer(h, name, NCH, 1, 36, (tiles + NI - 1) * 32, &l);   // the last group of a range may read (zero) rows past its tiles
+    if (image == nullptr) rc = find_layer(h, name, NCH, 1, 36, (tiles + NI - 1) * 32, &l);   // the last group of a range may read (zero) rows past its tiles
+    else if (image->nchunk == NCH && image->ldp == 36 && image->n_pad >= (tiles + NI - 1) * 32) l = *image;
+    else rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': the handle's image does not fit the kernel");
     if (rc != BSR_OK) return;
     if (pixels % C::BM != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': pixel count is not a multiple of 128"); return; }
     bsr::ConvArgs a = gemm_args(l, in, in_cs, out, out_cs, n_store, act);
     a.res1 = res1; a.res1_cs = res1_cs; a.res1_c = res1_c;
-    a.out2 = out2; a.out2_cs = out2_cs; a.n_split = n_split; a.n_store1 = n_store1;
+    a.out2 = out2; a.out2_cs = out2_cs; a.n_split = n_split; a.n_store1 = n_store1; a.out2_gap_at = out2_gap_at; a.out2_gap = out2_gap;
     a.out2_split = (h->dtype != BSR_DTYPE_F32 && out2 != nullptr) ? 1 : 0;      // conv3 | theta|phi|g of the 16-bit modes: qkv in the split layout of attention_h16.h
     begin(cls, name);
     if (h->dtype == BSR_DTYPE_F32)
@@ -468,14 +507,14 @@ struct Launcher {
 
   // fp32 res<i>.conv2 (3x3, 128 -> 128, + BN + LeakyReLU) in Winograd F(2x2, 3x3) form (wino_conv2.h).  The blob's layer gives the bias;
   // the weights are the handle's transformed stream.
-  void wino(const char* name, int i, const float* in, int H, int W, float* out) {
+  void wino(const char* name, int i, const float* in, int H, int W, float* out, int out_cs = 128) {
     if (rc != BSR_OK) return;
     LayerW l;
     rc = find_layer(h, name, 4, 9, 36, 128, &l);
     if (rc != BSR_OK) return;
     if (H % 4 != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': feature map is not a multiple of the 4x32 tile"); return; }
     begin(K_CONV3, name);
-    check(bsr::launch_wino_conv2(wino_args(in, out, h->d_wino + (size_t)i * kWinoFloats, l.b, H, W), h->B, s), name);
+    check(bsr::launch_wino_conv2(wino_args(in, out, h->d_wino + (size_t)i * kWinoFloats, l.b, H, W, out_cs), h->B, s), name);
     end();
   }
 
@@ -629,7 +668,8 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   h->dtype = dtype;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
-                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}};
+                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2},
+                                                            {"BSR_KEYS_CONV2", &h->keys_conv2}};
   for (const auto& sw : switches)
     if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), nbytes);
@@ -712,6 +752,19 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     e = hipMalloc(reinterpret_cast<void**>(&h->d_wino), u.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_wino, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: Winograd weights: ") + hipGetErrorString(e)); }
+    // the res0..5.c3q images for conv2's output as the attention keys, once per handle (kept whatever BSR_KEYS_CONV2 says: 2 MB)
+    std::vector<float> q(6 * kKeysFloats);
+    auto host = [&](const float* dev) { return reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(dev) - reinterpret_cast<const uint8_t*>(h->d_blob))); };
+    for (int i = 0; i < 6; ++i) {
+      char nm[32];
+      snprintf(nm, sizeof nm, "res%d.c3q", i);
+      LayerW l;
+      if (find_layer(h, nm, 4, 1, 36, kC3qNPad, &l) != BSR_OK || l.n_pad != kC3qNPad) { bsr_destroy(h); return fail(BSR_ERR_BLOB, std::string("bsr_create: layer '") + nm + "' is not a [4][1][768][36] image"); }
+      keys_compose(host(l.w), host(l.b), q.data() + i * kKeysFloats, q.data() + i * kKeysFloats + (size_t)4 * kKeysNPad * 36);
+    }
+    e = hipMalloc(reinterpret_cast<void**>(&h->d_keys), q.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_keys, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: composed c3q weights: ") + hipGetErrorString(e)); }
   }
   *out = h;
   return BSR_OK;
@@ -724,6 +777,7 @@ void bsr_destroy(bsr_handle* h) {
   if (h->ws) hipFree(h->ws);
   if (h->d_blob) hipFree(h->d_blob);
   if (h->d_wino) hipFree(h->d_wino);
+  if (h->d_keys) hipFree(h->d_keys);
   if (h->range_flag) hipHostFree(h->range_flag);
   delete h;
 }
@@ -894,11 +948,26 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     // sources at git e99927a.)
     // fp32: conv2 in Winograd F(2x2, 3x3) form (wino_conv2.h: 2.25x fewer matrix instructions), at EVERY batch and image size, so that
     // an image gets the same bits in any batch; BSR_WINO_CONV2=0 keeps the direct kernel.  The 16-bit modes keep theirs.
+    // fp32: conv2's output t2 IS the attention's key tensor (keys_compose: theta composed onto phi, exact under the softmax), so conv2
+    // writes it into the key slot of the qkv rows, [q' | t2 | g] at stride 384, and c3q — N = [y3 288 | q' 128 | g 128], 17 channel tiles
+    // instead of 21 — reads its A operand from there and writes q' and g around it: no workgroup of that launch writes the key
+    // columns, so the in-place form has no read-after-write hazard.  The attention kernels see the layout they always had.
+    // BSR_KEYS_CONV2=0 keeps phi projected (N = 672, t2 in a buffer of its own); the 16-bit modes have that form only.
+    const bool keys = h->dtype == BSR_DTYPE_F32 && h->keys_conv2;
+    float* t2_row = keys ? ws + p.qkv : ws + p.t2;
+    const int t2_cs = keys ? 384 : 128, t2_coff = keys ? 128 : 0;
+    float* t2 = t2_row + t2_coff;
     snprintf(nm, sizeof nm, "res%d.conv2", i);
-    if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) L.wino(nm, i, ws + p.t1, H8, W8, ws + p.t2);
-    else L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, ws + p.t2, 128, 0, 128, 1);
+    if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) L.wino(nm, i, ws + p.t1, H8, W8, t2, t2_cs);
+    else L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, t2_row, t2_cs, t2_coff, 128, 1);
     snprintf(nm, sizeof nm, "res%d.c3q", i);
-    L.gemm<3, 4>(K_CONV1, nm, ws + p.t2, 128, ncell, y3, CS_Y3X, 288 + 384, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X);
+    if (keys) {
+      const float* img = h->d_keys + (size_t)i * kKeysFloats;
+      const LayerW lk{img, img + (size_t)4 * kKeysNPad * 36, 4, 1, kKeysNPad, 36};
+      L.gemm<3, 4>(K_CONV1, nm, t2, t2_cs, ncell, y3, CS_Y3X, kKeysN, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X, &lk, 128, 128);
+    } else {
+      L.gemm<3, 4>(K_CONV1, nm, t2, t2_cs, ncell, y3, CS_Y3X, 288 + 384, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X);
+    }
     // z = y3 + BN(w(att)); out = LeakyReLU(pad(x) + pad(z))  (model.py:56-59, 105-113) = LeakyReLU(y3x + BN(w(att))).
     // ONE launch — the `w` GEMM runs as the tail of the attention kernel on the workgroup's own 128 pixels (attention.h /
     // attention_h16.h, FUSEW; the attention output never goes to HBM).  fp32 small batches (the 4- / 2-wave attention shapes) keep the
@@ -1369,6 +1438,12 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
 int bsr_debug_wino_filter(const float* direct, float* out) {
   if (direct == nullptr || out == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_filter: null argument");
   wino_filter_transform(direct, out);
+  return BSR_OK;
+}
+
+int bsr_debug_keys_compose(const float* c3q_w, const float* c3q_b, float* out_w, float* out_b) {
+  if (c3q_w == nullptr || c3q_b == nullptr || out_w == nullptr || out_b == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_keys_compose: null argument");
+  keys_compose(c3q_w, c3q_b, out_w, out_b);
   return BSR_OK;
 }
 

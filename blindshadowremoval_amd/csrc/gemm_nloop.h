@@ -1,6 +1,6 @@
 // 1x1-convolution GEMM with a RESIDENT activation tile: out[px][n] = act(sum_k x[px][k] * W[k][n] + b[n] (+ residuals)).
 //
-// The bottleneck blocks run three K = 128 GEMMs per block with wide N (conv3 | theta|phi|g : N = 672, w : N = 288;
+// The bottleneck blocks run three K = 128 GEMMs per block with wide N (conv3 | theta|phi|g : N = 672 — fp32: conv3 | q'|g : N = 544, the keys are conv2's output —, w : N = 288;
 // /root/reference/model.py:86,10-13,101-102,56-59).  With one workgroup per (128-pixel, 96-channel) tile the K loop is only four
 // steps long and prologue + epilogue cost as much as the MFMAs.  Here a workgroup owns 128 pixels for a long run of
 // N tiles (blockIdx.y splits the tiles in NSPLIT ranges so two workgroups share a CU): each wave keeps the A fragments
@@ -32,7 +32,7 @@ struct GemmNLoopCfg {
 
 // ConvArgs use: in/in_cs/in_coff (K = NCH*32 channels), pixels flattened (multiple of 128),
 // w packed [NCH][1][n_pad][36] with n_pad >= 32 * (tiles + NI - 1), bias[n_pad], out/out_cs/out_coff/n_store
-// (+ out2/n_split/n_store1), act, res1 (one residual, channels [0, res1_c)).  tiles_x = tiles per blockIdx.y range.
+// (+ out2/n_split/n_store1/out2_gap_at/out2_gap), act, res1 (one residual, channels [0, res1_c)).  tiles_x = tiles per blockIdx.y range.
 // MINW = waves per SIMD the register budget is sized for.  2 (default): two workgroups share a CU.  1 (round 5, res*.conv1 in the 16-bit
 // modes: K = 288, N = 128): ONE workgroup per CU keeps 32 pixels x 288 channels per wave resident — 36 16-byte loads per lane, all in
 // flight at once (147 KB per CU: the input is read exactly once, at full memory-level parallelism) — and computes all of N from them.
@@ -298,7 +298,10 @@ __global__ __launch_bounds__(256, MINW) void gemm_nloop_kernel(ConvArgs p) {
       const unsigned vb = n_ok ? (second ? lane_out2 : lane_out) : kLaneOff;
       const unsigned cs4 = (second ? (unsigned)p.out2_cs : (unsigned)p.out_cs) * 4u;
       const unsigned vj[4] = {vb, vb + cs4, vb + 2u * cs4, vb + 3u * cs4};
-      unsigned so = (second ? (unsigned)(nt - p.n_split) : (unsigned)nt) * 4u;
+      // second range: a tile at or past out2_gap_at skips out2_gap channels (wave-uniform; res*.c3q leaves the key slot of the qkv rows,
+      // which holds this GEMM's own A operand, unwritten)
+      const int n2 = nt - p.n_split;
+      unsigned so = (second ? (unsigned)(n2 + (n2 >= p.out2_gap_at ? p.out2_gap : 0)) : (unsigned)nt) * 4u;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
 #pragma unroll

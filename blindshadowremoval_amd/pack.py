@@ -228,6 +228,38 @@ def pack_wino(kernel_tkn: np.ndarray, bias: np.ndarray):
     return arr, bias.astype(np.float32)
 
 
+KEYS_N = 288 + 256        # [y3 288 | q' 128 | g 128]
+KEYS_N_PAD = KEYS_N + 64  # + two zero tiles of slack (gemm_nloop group reads, NI = 3)
+
+
+def compose_keys(wq: np.ndarray, bq: np.ndarray, wk: np.ndarray):
+    """theta composed onto phi's weights.  With theta = t Wq + bq and phi = t Wk + bk the NonLocalBlock's logits are
+    theta_i . phi_j = (theta_i Wk^T) . t_j + theta_i . bk, and the softmax over j removes the second term exactly: with
+    q'_i = t_i (Wq Wk^T) + bq Wk^T,  softmax_j(theta_i . phi_j) = softmax_j(q'_i . t_j) — the keys are t itself.
+    wq, wk [K, D], bq [D] -> (Wq Wk^T [K, K], bq Wk^T [K]) in float64."""
+    wq, wk, bq = wq.astype(np.float64), wk.astype(np.float64), bq.astype(np.float64)
+    return wq @ wk.T, bq @ wk.T
+
+
+def compose_keys_c3q(c3q_w: np.ndarray, c3q_b: np.ndarray):
+    """A res<i>.c3q blob entry ([4, 1, 768, 36] image, [768] bias: N = [y3 288 | theta | phi | g | slack]) -> the image of the fp32
+    forward that takes conv2's output as the attention keys: ([4, 1, KEYS_N_PAD, 36], [KEYS_N_PAD]), N = [y3 288 | q' 128 | g 128 | 0].
+
+    The blob's layout is pinned, so this image is not a blob entry: bsr_create derives it, once per handle, from the float32 values of
+    the blob's image with this very arithmetic (bsr_api.hip: keys_compose — float64 sums, rounded once).  This function is its
+    statement; tests/test_keys_conv2_cpu.py holds the library to it."""
+    assert c3q_w.shape == (4, 1, 768, 36) and c3q_b.shape == (768,)
+    kn = c3q_w[:, 0, :, :32].transpose(0, 2, 1).reshape(128, 768)          # [K, N] float32
+    a, ab = compose_keys(kn[:, 288:416], c3q_b[288:416], kn[:, 416:544])
+    out = np.zeros((4, 1, KEYS_N_PAD, 36), np.float32)
+    out[:, :, :288] = c3q_w[:, :, :288]
+    out[:, 0, 288:416, :32] = a.astype(np.float32).reshape(4, 32, 128).transpose(0, 2, 1)
+    out[:, :, 416:544] = c3q_w[:, :, 544:672]
+    b = np.zeros(KEYS_N_PAD, np.float32)
+    b[:288], b[288:416], b[416:544] = c3q_b[:288], ab.astype(np.float32), c3q_b[544:672]
+    return out, b
+
+
 def layer_matrices(w: Dict[str, np.ndarray]) -> "Dict[str, Tuple[np.ndarray, np.ndarray]]":
     """Folded [taps, K, N] kernels + biases (float64) of every MFMA layer, in kernel K/N order."""
     out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}

@@ -289,6 +289,11 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
 /* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct image of each res<i>.conv2 of an
  * fp32 blob.  direct = the layer's [4][9][128][36] image (HOST pointer), out = [8][16][128][16] floats (HOST pointer). */
 int bsr_debug_wino_filter(const float* direct, float* out);
+/* Test hook (additive, host only, no GPU call): the image bsr_create derives from each res<i>.c3q of an fp32 GSC / TSM blob for the
+ * attention that takes conv2's output as its keys (env BSR_KEYS_CONV2, default on): N = [y3 288 | q' 128 | g 128 | 64 zero] with
+ * q' = theta composed onto phi's weights in float64 (blindshadowremoval_amd.pack.compose_keys_c3q).  c3q_w = the layer's [4][1][768][36]
+ * image, c3q_b = its [768] bias, out_w = [4][1][608][36] floats, out_b = [608] floats (all HOST pointers). */
+int bsr_debug_keys_compose(const float* c3q_w, const float* c3q_b, float* out_w, float* out_b);
 
 /* Measurement hook (ABI 7): one wave on `stream` writes (shader cycle counter, 100-MHz real-time counter) pairs to out[2 * samples] every
  * spin x ~3.4 us until *stop (device memory, written from another stream) is non-zero or `samples` pairs are taken; *taken receives the
