@@ -1374,7 +1374,8 @@ int bsr_clock_trace(int device, unsigned long long* out, int samples, int spin, 
 }
 
 int bsr_debug_split_qkv(const float* qkv, void* qkv_split, int B, int tokens, void* stream) {
-  if (qkv == nullptr || qkv_split == nullptr || B <= 0 || tokens <= 0) return fail(BSR_ERR_ARG, "bsr_debug_split_qkv: bad argument");
+  if (qkv == nullptr || qkv_split == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_split_qkv: null argument");
+  if (B <= 0 || tokens <= 0 || tokens % 128 != 0) return fail(BSR_ERR_ARG, "bsr_debug_split_qkv: tokens must be a positive multiple of 128");
   const size_t pairs = (size_t)B * tokens * 192;
   hipLaunchKernelGGL(bsr::a4_split_qkv_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), qkv,
                      static_cast<char*>(qkv_split), pairs);

@@ -275,7 +275,8 @@ int bsr_debug_attention_dtype(const float* qkv, float* y, int B, int tokens, int
 /* The two steps of the F32X3 / F16 case above, separately (ABI 7): the kernel of the 16-bit modes (csrc/attention_h16.h) reads theta | phi | g
  * as the conv3|theta|phi|g GEMM leaves them in those modes — per token 3 x [128 fp16 hi | 128 fp16 lo] (1536 bytes, hi = fp16(x),
  * lo = fp16(x - hi), theta pre-scaled by log2 e).  bsr_debug_split_qkv converts an fp32 [B,tokens,384] tensor to that layout (same size
- * in bytes), bsr_debug_attention_split runs the attention kernel on it; pv1 != 0 = the P.V product with the hi planes only. */
+ * in bytes), bsr_debug_attention_split runs the attention kernel on it; pv1 != 0 = the P.V product with the hi planes only.
+ * Both refuse B <= 0 and tokens that are not a positive multiple of 128 before anything is launched. */
 int bsr_debug_split_qkv(const float* qkv, void* qkv_split, int B, int tokens, void* stream);
 int bsr_debug_attention_split(const void* qkv_split, float* y, int B, int tokens, int pv1, void* stream);
 /* The fp32 kernel with a given workgroup shape: qw = query waves per workgroup (4 = 128 queries, 2 = 64, 1 = 32; 0 = what the
