@@ -20,6 +20,7 @@ EXPORTS = ("bsr_create", "bsr_forward", "bsr_forward_tsm", "bsr_workspace_bytes"
            "bsr_get_timing", "bsr_timing_launches", "bsr_timing_entry", "bsr_handle_workspace_bytes", "bsr_debug_attention", "bsr_debug_attention_dtype", "bsr_debug_attention_qw", "bsr_debug_split_qkv", "bsr_clock_trace", "bsr_debug_attention_split", "bsr_destroy", "bsr_last_error", "bsr_abi_version", "bsr_check_range", "bsr_prep_rows", "bsr_prep_groups", "bsr_png_unfilter", "bsr_forward_packed", "bsr_source_sha", "bsr_peek_range", "bsr_png_file_bytes", "bsr_png_scratch_bytes", "bsr_png_encode", "bsr_png_encode_figs", "bsr_ucb_post_scratch_bytes", "bsr_ucb_post",
            "bsr_forward_rgb", "bsr_debug_attention_rgb", "bsr_ucb_post_rgb_scratch_bytes", "bsr_ucb_post_rgb",
            "bsr_sfw_score_scratch_bytes", "bsr_sfw_score", "bsr_ucb_post_tsm_scratch_bytes", "bsr_ucb_post_tsm", "bsr_debug_wino_conv", "bsr_debug_wino_filter", "bsr_debug_keys_compose",
+           "bsr_debug_values_compose",      # + bsr_debug_attention_kv1, which tests/test_cabi.py's header scan (names without digits) cannot see
            "bsr_png_unfilter_tall", "bsr_crop_faces")
 
 
@@ -145,6 +146,10 @@ def load() -> ctypes.CDLL:
         raise RuntimeError("libbsr_hip.so has no bsr_debug_keys_compose: rebuild (`python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no fallback") from None
     lib.bsr_debug_keys_compose.restype = c_i
+    lib.bsr_debug_values_compose.argtypes = [c_v, c_v, c_v, c_v, c_v, c_v]
+    lib.bsr_debug_values_compose.restype = c_i
+    lib.bsr_debug_attention_kv1.argtypes = [c_v, c_v, c_i, c_i, c_i, c_v]
+    lib.bsr_debug_attention_kv1.restype = c_i
     lib.bsr_peek_range.argtypes = [c_v]
     lib.bsr_peek_range.restype = c_i
     lib.bsr_destroy.argtypes = [c_v]

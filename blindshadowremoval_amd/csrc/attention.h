@@ -54,9 +54,17 @@ constexpr int kAttWSmemBytes = AttWCfg::SMEM_FLOATS * 4;
 static_assert(kAttWSmemBytes <= 160 * 1024 && kAttWSmemBytes >= kAttSmemBytes, "LDS budget of the fused tail");
 static_assert(4 * 66 * 64 <= kTailAFloats && kTailLdA == kAttLdK, "the merge scratch sits under the attention tile, clear of the weight ring");
 
-template <int QW, bool FUSEW = false>
+// KV1 (fp32 GSC / TSM forwards with conv2's output as keys AND values, bsr_api.hip: values_compose): rows are [q | kv] at stride 2 D and
+// ONE 32-key LDS tile serves both products — half the buffer loads and LDS writes of the key loop, one register set.  The tile is the
+// padded key tile; the P.V fragment read takes it at that row stride.  Same matrix operands in the same order as the three-slot form
+// on [q | x | x] rows: the same bits.
+template <int QW, bool FUSEW = false, bool KV1 = false>
 __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int tokens, AttWArgs wa) {
   static_assert(!FUSEW || QW == 4, "the fused w tail is the 8-wave shape's");
+  constexpr int RS = (KV1 ? 2 : 3) * kAttD;                    // floats per token row
+  constexpr int STAGE = KV1 ? kAttKT * kAttLdK : kAttStageFloats;      // one staged 32-key tile
+  constexpr int LDV = KV1 ? kAttLdK : kAttD;                   // row stride of the value tile
+  static_assert(QW * 66 * 64 <= 4 * STAGE, "merge scratch fits the staging buffers");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = QW * 128;                                 // threads
   constexpr int SV = 2048 / NT;                                // float4 per operand and thread that stage one tile pair
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
       qb = b % qblocks;
     }
   }
-  const float* base = qkv + (size_t)img * tokens * (3 * kAttD);
+  const float* base = qkv + (size_t)img * tokens * RS;
   const int q = qb * (QW * 32) + wq * 32 + r;
 #if BSR_ATT_PRIO
   if (grp == (BSR_ATT_PRIO - 1)) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);      // see attention_x3.h
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
   f32x4 qf[kAttD / 8];
 #pragma unroll
   for (int g = 0; g < kAttD / 8; ++g)
-    qf[g] = *reinterpret_cast<const f32x4*>(base + (size_t)q * (3 * kAttD) + g * 8 + 4 * h) * 1.4426950408889634f;   // log2(e): softmax in base 2
+    qf[g] = *reinterpret_cast<const f32x4*>(base + (size_t)q * RS + g * 8 + 4 * h) * 1.4426950408889634f;   // log2(e): softmax in base 2
 
   f32x16 o[4];
 #pragma unroll
@@ -104,7 +112,7 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
   // of a thread belongs to tile 2p + ((tid + i * NT) >> 10)
   constexpr int V4_PER_TILE = kAttKT * kAttD / 4;       // 1024
   constexpr int NV = V4_PER_TILE / NT;                  // distinct (key, channel) positions per thread: float4 i and i + NV are the same position of the pair's two tiles
-  f32x4 kreg[SV], vreg[SV];
+  f32x4 kreg[SV], vreg[KV1 ? 1 : SV];
   // K / V rows through a raw buffer over this image's qkv: the thread's part of an address is one of NV constant VGPR offsets, the
   // tile is the SGPR offset, phi / g are the instruction's immediate offsets — no 64-bit multiply-add per row inside the key loop (VALU
   // instructions there stand between this wave's MFMAs and take fp32 lanes from its partner's)
@@ -114,14 +122,14 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int idx = (tid + i * NT) & (V4_PER_TILE - 1);
-    kv_voff[i] = (unsigned)(((idx / (kAttD / 4)) * (3 * kAttD) + (idx % (kAttD / 4)) * 4) * 4);
+    kv_voff[i] = (unsigned)(((idx / (kAttD / 4)) * RS + (idx % (kAttD / 4)) * 4) * 4);
   }
   auto fetch = [&](int pr) {
 #pragma unroll
     for (int i = 0; i < SV; ++i) {
-      const unsigned soff = (unsigned)((2 * pr + (i / NV)) * kAttKT * (3 * kAttD) * 4);      // (tid + i * NT) >> 10 == i / NV for tid < NT
+      const unsigned soff = (unsigned)((2 * pr + (i / NV)) * kAttKT * RS * 4);      // (tid + i * NT) >> 10 == i / NV for tid < NT
       kreg[i] = __builtin_bit_cast(f32x4, (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_voff[i % NV] + (unsigned)(kAttD * 4), soff, 0));
-      vreg[i] = __builtin_bit_cast(f32x4, (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_voff[i % NV] + (unsigned)(2 * kAttD * 4), soff, 0));
+      if constexpr (!KV1) vreg[i] = __builtin_bit_cast(f32x4, (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(kv_rsrc, kv_voff[i % NV] + (unsigned)(2 * kAttD * 4), soff, 0));
     }
   };
   auto publish = [&](int pbuf) {
@@ -129,10 +137,9 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
     for (int i = 0; i < SV; ++i) {
       const int idx = (tid + i * NT) & (V4_PER_TILE - 1), sel = (tid + i * NT) >> 10;
       const int key = idx / (kAttD / 4), c4 = idx % (kAttD / 4);
-      float* sk = smem + (2 * pbuf + sel) * kAttStageFloats;
-      float* sv = sk + kAttKT * kAttLdK;
+      float* sk = smem + (2 * pbuf + sel) * STAGE;
       *reinterpret_cast<f32x4*>(sk + key * kAttLdK + c4 * 4) = kreg[i];
-      *reinterpret_cast<f32x4*>(sv + key * kAttD + c4 * 4) = vreg[i];
+      if constexpr (!KV1) *reinterpret_cast<f32x4*>(sk + kAttKT * kAttLdK + key * kAttD + c4 * 4) = vreg[i];
     }
   };
 
@@ -146,8 +153,8 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
   auto pair_step = [&](int pr, auto pbuf_const) {
     constexpr int pbuf = decltype(pbuf_const)::value;
     if (pr + 1 < npair) fetch(pr + 1);
-    const float* sk = smem + (2 * pbuf + grp) * kAttStageFloats;      // this wave's tile of the pair
-    const float* sv = sk + kAttKT * kAttLdK;
+    const float* sk = smem + (2 * pbuf + grp) * STAGE;      // this wave's tile of the pair
+    const float* sv = KV1 ? sk : sk + kAttKT * kAttLdK;
 
     // S^T tile: rows = keys (A from LDS), cols = queries (B from registers)
     f32x16 s;
@@ -193,7 +200,7 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int key = (i & 3) + 8 * (i >> 2) + 4 * h;
-      const f32x4 vf = *reinterpret_cast<const f32x4*>(sv + key * kAttD + 4 * r);
+      const f32x4 vf = *reinterpret_cast<const f32x4*>(sv + key * LDV + 4 * r);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[dt], s[i], o[dt], 0, 0, 0);
     }
@@ -271,9 +278,11 @@ __global__ __launch_bounds__(QW * 128, QW == 4 ? 2 : 1) void nonlocal_attention_
   }
 }
 
-template <int QW>
+template <int QW, bool KV1 = false>
 inline hipError_t launch_nonlocal_attention_qw(const float* qkv, float* out, int batch, int tokens, hipStream_t stream) {
-  auto kern = nonlocal_attention_kernel<QW, false>;
+  // KV1 needs half the staging LDS; the launch asks for the same kAttSmemBytes, so that a CU holds one workgroup in either form and
+  // attention_auto_qw's cost model (and every measured small-batch shape) stays what it was
+  auto kern = nonlocal_attention_kernel<QW, false, KV1>;
   static PerDeviceOnce once;
   const int dev = PerDeviceOnce::current();
   if (dev < 0 || !once.done[dev]) {
@@ -300,9 +309,10 @@ inline int attention_auto_qw(int batch, int tokens) {
 }
 
 // attention + `w` GEMM tail in one launch (the 8-wave shape; callers use it when attention_auto_qw() == 4)
+template <bool KV1 = false>
 inline hipError_t launch_nonlocal_attention_w(const float* qkv, int batch, int tokens, const AttWArgs& wa, hipStream_t stream) {
   if (tokens % (4 * kAttKT) != 0 || wa.n_pad * 32 < AttWCfg::BIAS_FLOATS * 32 || wa.n_pad < 12 * 32 || wa.n_store > 288 || wa.res_c > 288 || wa.out2 != nullptr) return hipErrorInvalidValue;
-  auto kern = nonlocal_attention_kernel<4, true>;
+  auto kern = nonlocal_attention_kernel<4, true, KV1>;
   static PerDeviceOnce once;
   const int dev = PerDeviceOnce::current();
   if (dev < 0 || !once.done[dev]) {
@@ -319,12 +329,13 @@ inline hipError_t launch_nonlocal_attention_w(const float* qkv, int batch, int t
 // shape (two waves share each SIMD), ~80 us for the 4- and 2-wave shapes (one wave per SIMD) — B = 32: 256 x 8 waves, one round;
 // B = 16: 256 x 4 waves; B = 10: 160 x 4 waves (not 320 x 2: two rounds); B <= 8: x 2 waves.  Every variant computes the same
 // arithmetic in the same order per query, so the choice does not change a single bit of the output.
+template <bool KV1 = false>
 inline hipError_t launch_nonlocal_attention(const float* qkv, float* out, int batch, int tokens, hipStream_t stream, int qw = 0) {
   if (tokens % (4 * kAttKT) != 0) return hipErrorInvalidValue;      // 128-query blocks; the key loop takes two 64-key pairs per trip
   if (qw == 0) qw = attention_auto_qw(batch, tokens);
-  if (qw == 4) return launch_nonlocal_attention_qw<4>(qkv, out, batch, tokens, stream);
-  if (qw == 2) return launch_nonlocal_attention_qw<2>(qkv, out, batch, tokens, stream);
-  if (qw == 1) return launch_nonlocal_attention_qw<1>(qkv, out, batch, tokens, stream);
+  if (qw == 4) return launch_nonlocal_attention_qw<4, KV1>(qkv, out, batch, tokens, stream);
+  if (qw == 2) return launch_nonlocal_attention_qw<2, KV1>(qkv, out, batch, tokens, stream);
+  if (qw == 1) return launch_nonlocal_attention_qw<1, KV1>(qkv, out, batch, tokens, stream);
   return hipErrorInvalidValue;
 }
 

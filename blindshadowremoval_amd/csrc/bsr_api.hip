@@ -133,7 +133,8 @@ struct Region {
   size_t off, floats;
 };
 // Float offsets into the workspace for a (B,H,W) problem; a slot the variant does not have is zero-sized.  qkv = theta | phi | g, d each
-// (fp32 GSC / TSM: q' | t2 | g, with conv2 writing t2 there and the t2 slot unused — forward_impl's res_block).
+// (fp32 GSC / TSM: q' | t2 | g, with conv2 writing t2 there and the t2 slot unused; with t2 as the values too the rows are q' | t2 at
+// stride 2 d in the same slot — forward_impl's res_block).
 struct Plan {
   size_t x1, c3, c2, xa, t1, t2, y3[6], qkv, att[6], r[6], xh, ybuf, qh, f1, f2, cf, probe, reg32, share, yh, con, total;
   // A new shape moves every buffer.  All of them are fully rewritten by their producers each forward, pad channels included, except the
@@ -187,6 +188,10 @@ struct bsr_handle {
   float* d_blob = nullptr;
   float* d_wino = nullptr;       // fp32 GSC / TSM handles: the Winograd weight streams of res0..5.conv2 (wino_conv2.h), derived from the blob's direct images at bsr_create
   float* d_keys = nullptr;       // fp32 GSC / TSM handles: the res0..5.c3q images with theta composed onto phi, N = [y3 | q' | g] (keys_compose), derived from the blob's at bsr_create
+  float* d_values = nullptr;     // fp32 GSC / TSM handles: per block the `w` image with g composed onto it, the c3q image of N = [y3 | q'] and the g image the att<i> probe
+                                 // applies (values_compose), derived from the blob's at bsr_create
+  float* att_scratch = nullptr;  // att<i> probes of a forward with conv2's output as the values: att = O Wg + bg is derived into this buffer
+  size_t att_scratch_floats = 0;
   std::unordered_map<std::string, LayerW> layers;
   Variant var = kGSC;
   int dtype = BSR_DTYPE_F32;     // BSR_DTYPE_F16 / BSR_DTYPE_F32X3: 16-bit matrix cores on the 3x3 / stride-2 / transposed 3x3 layers (igemm_h16.h), fp32 kernels elsewhere
@@ -215,6 +220,9 @@ struct bsr_handle {
   bool wino_conv2 = true;        // env BSR_WINO_CONV2=0: the fp32 res*.conv2 on the direct implicit-GEMM kernel instead of the Winograd F(2x2, 3x3) one (A/B measurements, the two-forms test)
   bool keys_conv2 = true;        // env BSR_KEYS_CONV2=0: the fp32 attention with phi projected by res*.c3q (N = 672, conv2's output in a buffer of its own) instead of conv2's
                                  // output as the keys (A/B measurements, the two-forms test)
+  bool values_conv2 = true;      // env BSR_VALUES_CONV2=0 (read only while keys_conv2 is on): g projected by res*.c3q (N = 544) and the attention on [q' | t2 | g] rows instead
+                                 // of conv2's output as the values too (A/B measurements, the two-forms test)
+  bool att_is_o = false;         // the last forward ran with conv2's output as the values: the att<i> slots hold O = softmax(f) t2 (probe attv<i>)
   bool timing = false;
   std::vector<hipEvent_t> ev;    // event pool, pairs
   std::vector<int> ev_class;
@@ -282,6 +290,49 @@ void keys_compose(const float* c3q_w, const float* c3q_b, float* out_w, float* o
     for (int c = 0; c < 128; ++c) acc += (double)c3q_b[288 + c] * (double)src(m, 416 + c);
     out_b[288 + m] = (float)acc;
   }
+}
+
+// conv2's output t2 as the attention VALUES as well.  g = t2 Wg + bg (Wg, bg = columns 544..671 of the c3q image) feeds the `w` conv with
+// no non-linearity in between (model.py:53-56), and softmax rows sum to 1, so
+//   softmax(f) g Ww + bw = (softmax(f) t2) (Wg Ww) + (bg Ww + bw):
+// the attention runs on [q' | t2] rows with ONE tile as keys and values, c3q computes N = [y3 288 | q' 128] (13 channel tiles instead
+// of 17), and the `w` GEMM keeps K = 128 with the composed image.  Sums over the g channel in channel order in float64 from the images'
+// float32 values (the products are exact), rounded once.  c3q / w = the blob's [4][1][768][36] and [4][1][384][36] images with their
+// biases (HOST pointers) -> out_w [4][1][384][36], out_b [384] in the layout of res<i>.w.  blindshadowremoval_amd/pack.py:
+// compose_values_w states the same in numpy.
+constexpr int kWNPad = 384;
+constexpr int kValuesN = 288 + 128, kValuesNPad = kValuesN + 64;      // the c3q image of this form: the keys image without its g columns
+constexpr int kGProbeNPad = 128 + 64;                                 // the g image of the att<i> probe: N = 128 + two zero tiles of slack (NI = 3)
+constexpr size_t kValuesWFloats = (size_t)4 * kWNPad * 36 + kWNPad, kValuesC3qFloats = (size_t)4 * kValuesNPad * 36 + kValuesNPad,
+                 kGProbeFloats = (size_t)4 * kGProbeNPad * 36 + kGProbeNPad;
+constexpr size_t kValuesFloats = kValuesWFloats + kValuesC3qFloats + kGProbeFloats;      // per block: w image, bias | c3q image, bias | g image, bias
+void values_compose(const float* c3q_w, const float* c3q_b, const float* w_w, const float* w_b, float* out_w, float* out_b) {
+  auto wg = [&](int k, int c) -> double { return (double)c3q_w[((size_t)(k / 32) * kC3qNPad + 544 + c) * 36 + k % 32]; };
+  auto ww = [&](int c, int n) -> double { return (double)w_w[((size_t)(c / 32) * kWNPad + n) * 36 + c % 32]; };
+  memset(out_w, 0, (size_t)4 * kWNPad * 36 * sizeof(float));
+  for (int n = 0; n < kWNPad; ++n) {
+    for (int k = 0; k < 128; ++k) {
+      double acc = 0.0;
+      for (int c = 0; c < 128; ++c) acc += wg(k, c) * ww(c, n);
+      out_w[((size_t)(k / 32) * kWNPad + n) * 36 + k % 32] = (float)acc;
+    }
+    double acc = (double)w_b[n];
+    for (int c = 0; c < 128; ++c) acc += (double)c3q_b[544 + c] * ww(c, n);
+    out_b[n] = (float)acc;
+  }
+}
+// The two images that are cut, not computed: the keys image (keys_compose) without its g columns, and the blob's g columns alone.
+void values_cut(const float* keys_w, const float* keys_b, const float* c3q_w, const float* c3q_b, float* v_w, float* v_b, float* g_w, float* g_b) {
+  memset(v_w, 0, (size_t)4 * kValuesNPad * 36 * sizeof(float));
+  memset(v_b, 0, kValuesNPad * sizeof(float));
+  memset(g_w, 0, (size_t)4 * kGProbeNPad * 36 * sizeof(float));
+  memset(g_b, 0, kGProbeNPad * sizeof(float));
+  for (int ch = 0; ch < 4; ++ch) {
+    memcpy(v_w + (size_t)ch * kValuesNPad * 36, keys_w + (size_t)ch * kKeysNPad * 36, (size_t)kValuesN * 36 * sizeof(float));
+    memcpy(g_w + (size_t)ch * kGProbeNPad * 36, c3q_w + ((size_t)ch * kC3qNPad + 544) * 36, (size_t)128 * 36 * sizeof(float));
+  }
+  memcpy(v_b, keys_b, kValuesN * sizeof(float));
+  memcpy(g_b, c3q_b + 544, 128 * sizeof(float));
 }
 
 int find_layer(bsr_handle* h, const char* name, int nchunk, int taps, int ldp, int n_min, LayerW* out) {
@@ -669,7 +720,7 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
                                                             {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2},
-                                                            {"BSR_KEYS_CONV2", &h->keys_conv2}};
+                                                            {"BSR_KEYS_CONV2", &h->keys_conv2}, {"BSR_VALUES_CONV2", &h->values_conv2}};
   for (const auto& sw : switches)
     if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_blob), nbytes);
@@ -765,6 +816,25 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     e = hipMalloc(reinterpret_cast<void**>(&h->d_keys), q.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_keys, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: composed c3q weights: ") + hipGetErrorString(e)); }
+    // the images for conv2's output as the attention values, once per handle (kept whatever BSR_VALUES_CONV2 says: 2.5 MB)
+    std::vector<float> v(6 * kValuesFloats);
+    for (int i = 0; i < 6; ++i) {
+      char nm[32];
+      LayerW l, lw;
+      snprintf(nm, sizeof nm, "res%d.c3q", i);
+      if (find_layer(h, nm, 4, 1, 36, kC3qNPad, &l) != BSR_OK) { bsr_destroy(h); return BSR_ERR_BLOB; }
+      snprintf(nm, sizeof nm, "res%d.w", i);
+      if (find_layer(h, nm, 4, 1, 36, kWNPad, &lw) != BSR_OK || lw.n_pad != kWNPad) { bsr_destroy(h); return fail(BSR_ERR_BLOB, std::string("bsr_create: layer '") + nm + "' is not a [4][1][384][36] image"); }
+      float* vw = v.data() + i * kValuesFloats;
+      float* vc = vw + kValuesWFloats;
+      float* vg = vc + kValuesC3qFloats;
+      const float* kq = q.data() + i * kKeysFloats;
+      values_compose(host(l.w), host(l.b), host(lw.w), host(lw.b), vw, vw + (size_t)4 * kWNPad * 36);
+      values_cut(kq, kq + (size_t)4 * kKeysNPad * 36, host(l.w), host(l.b), vc, vc + (size_t)4 * kValuesNPad * 36, vg, vg + (size_t)4 * kGProbeNPad * 36);
+    }
+    e = hipMalloc(reinterpret_cast<void**>(&h->d_values), v.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_values, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: composed w weights: ") + hipGetErrorString(e)); }
   }
   *out = h;
   return BSR_OK;
@@ -778,6 +848,8 @@ void bsr_destroy(bsr_handle* h) {
   if (h->d_blob) hipFree(h->d_blob);
   if (h->d_wino) hipFree(h->d_wino);
   if (h->d_keys) hipFree(h->d_keys);
+  if (h->d_values) hipFree(h->d_values);
+  if (h->att_scratch) hipFree(h->att_scratch);
   if (h->range_flag) hipHostFree(h->range_flag);
   delete h;
 }
@@ -953,15 +1025,26 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
     // instead of 21 — reads its A operand from there and writes q' and g around it: no workgroup of that launch writes the key
     // columns, so the in-place form has no read-after-write hazard.  The attention kernels see the layout they always had.
     // BSR_KEYS_CONV2=0 keeps phi projected (N = 672, t2 in a buffer of its own); the 16-bit modes have that form only.
+    // t2 is the attention's VALUE tensor as well (values_compose: g composed onto `w`): the rows are [q' | t2] at stride 256, c3q computes
+    // N = [y3 288 | q' 128] — 13 channel tiles — and writes q' in front of its own A operand (no gap to skip), the attention kernels run
+    // their one-tile form (KV1) and the `w` GEMM, fused or not, takes the composed image.  BSR_VALUES_CONV2=0 keeps g projected.
     const bool keys = h->dtype == BSR_DTYPE_F32 && h->keys_conv2;
+    const bool values = keys && h->values_conv2;
+    h->att_is_o = values;
     float* t2_row = keys ? ws + p.qkv : ws + p.t2;
-    const int t2_cs = keys ? 384 : 128, t2_coff = keys ? 128 : 0;
+    const int t2_cs = values ? 256 : keys ? 384 : 128, t2_coff = keys ? 128 : 0;
+    const float* vimg = h->d_values + (size_t)i * kValuesFloats;
+    const LayerW lvw{vimg, vimg + (size_t)4 * kWNPad * 36, 4, 1, kWNPad, 36};
     float* t2 = t2_row + t2_coff;
     snprintf(nm, sizeof nm, "res%d.conv2", i);
     if (h->dtype == BSR_DTYPE_F32 && h->wino_conv2) L.wino(nm, i, ws + p.t1, H8, W8, t2, t2_cs);
     else L.conv<3, 3, 1, false, 2, 32, 1>(K_CONV3, nm, ws + p.t1, 128, 0, 128, H8, W8, t2_row, t2_cs, t2_coff, 128, 1);
     snprintf(nm, sizeof nm, "res%d.c3q", i);
-    if (keys) {
+    if (values) {
+      const float* img = vimg + kValuesWFloats;
+      const LayerW lv{img, img + (size_t)4 * kValuesNPad * 36, 4, 1, kValuesNPad, 36};
+      L.gemm<3, 4>(K_CONV1, nm, t2, t2_cs, ncell, y3, CS_Y3X, kValuesN, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 256, 288, CS_Y3X, &lv);
+    } else if (keys) {
       const float* img = h->d_keys + (size_t)i * kKeysFloats;
       const LayerW lk{img, img + (size_t)4 * kKeysNPad * 36, 4, 1, kKeysNPad, 36};
       L.gemm<3, 4>(K_CONV1, nm, t2, t2_cs, ncell, y3, CS_Y3X, kKeysN, 0, x, x_cs, x_cs < 288 ? x_cs : 288, ws + p.qkv, 384, 288, CS_Y3X, &lk, 128, 128);
@@ -984,6 +1067,7 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
       // attention_h16.h — nine 16-KB tiles in the k order of the O^T accumulators, resident in LDS when the key loop ends
       snprintf(nm, sizeof nm, h16 ? "res%d.w4" : "res%d.w", i);
       L.rc = h16 ? find_layer(h, nm, 9, 1, 128, 32, &l) : find_layer(h, nm, 4, 1, 36, 12 * 32, &l);
+      if (values) l = lvw;
       if (L.rc == BSR_OK) {
         bsr::AttWArgs wa{};
         wa.w = l.w; wa.bias = l.b; wa.n_pad = h16 ? 288 : l.n_pad;
@@ -991,7 +1075,9 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
         wa.out = r_out; wa.out_cs = o_cs; wa.n_store = o_cs < 288 ? o_cs : 288; wa.n_store1 = wa.n_store; wa.act = 1; wa.stagger = 1;
         snprintf(nm, sizeof nm, "res%d.attw", i);
         L.begin(K_ATT, nm);
-        if (!h16)
+        if (values)
+          L.check(bsr::launch_nonlocal_attention_w<true>(ws + p.qkv, B, H8 * W8, wa, s), "attention+w");
+        else if (!h16)
           L.check(bsr::launch_nonlocal_attention_w(ws + p.qkv, B, H8 * W8, wa, s), "attention+w");
         else
           L.check(bsr::launch_nonlocal_attention_h16_w(ws + p.qkv, B, H8 * W8, wa, s, h->att_pv1), "attention_h16+w");
@@ -1001,14 +1087,16 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
       if (L.rc == BSR_OK) {
         snprintf(nm, sizeof nm, "res%d.attention", i);
         L.begin(K_ATT, nm);
-        if (!h16)
+        if (values)
+          L.check(bsr::launch_nonlocal_attention<true>(ws + p.qkv, ws + p.att[i], B, H8 * W8, s), "attention");
+        else if (!h16)
           L.check(bsr::launch_nonlocal_attention(ws + p.qkv, ws + p.att[i], B, H8 * W8, s), "attention");
         else
           L.check(bsr::launch_nonlocal_attention_h16(ws + p.qkv, ws + p.att[i], B, H8 * W8, s, h->att_pv1), "attention_h16");
         L.end();
       }
       snprintf(nm, sizeof nm, "res%d.w", i);
-      L.gemm<3, 4>(K_CONV1, nm, ws + p.att[i], 128, ncell, r_out, o_cs, o_cs < 288 ? o_cs : 288, 1, y3, CS_Y3X, CS_Y3X);
+      L.gemm<3, 4>(K_CONV1, nm, ws + p.att[i], 128, ncell, r_out, o_cs, o_cs < 288 ? o_cs : 288, 1, y3, CS_Y3X, CS_Y3X, nullptr, 0, 0, 0, values ? &lvw : nullptr);
     }
     if (x_c > 288 && L.rc == BSR_OK) {      // the block output keeps the wider of x / y (model.py:105-113): channels the GEMM does not cover
       glue_begin("lrelu_copy");
@@ -1420,6 +1508,14 @@ int bsr_debug_attention_qw(const float* qkv, float* y, int B, int tokens, int qw
   return BSR_OK;
 }
 
+int bsr_debug_attention_kv1(const float* qkv2, float* y, int B, int tokens, int qw, void* stream) {
+  if (qkv2 == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_attention_kv1: null argument");
+  if (B <= 0 || tokens <= 0 || tokens % 128 != 0) return fail(BSR_ERR_ARG, "bsr_debug_attention_kv1: tokens must be a positive multiple of 128");
+  if (qw != 0 && qw != 1 && qw != 2 && qw != 4) return fail(BSR_ERR_ARG, "bsr_debug_attention_kv1: qw must be 0 (automatic), 1, 2 or 4 query waves per workgroup");
+  HIP_TRY(bsr::launch_nonlocal_attention<true>(qkv2, y, B, tokens, static_cast<hipStream_t>(stream), qw));
+  return BSR_OK;
+}
+
 int bsr_debug_attention_rgb(const float* qkv, float* y, int B, int tokens, void* stream) {
   if (qkv == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: null argument");
   if (B <= 0 || tokens <= 0 || tokens % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_attention_rgb: tokens must be a positive multiple of 32");
@@ -1448,12 +1544,20 @@ int bsr_debug_keys_compose(const float* c3q_w, const float* c3q_b, float* out_w,
   return BSR_OK;
 }
 
+int bsr_debug_values_compose(const float* c3q_w, const float* c3q_b, const float* w_w, const float* w_b, float* out_w, float* out_b) {
+  if (c3q_w == nullptr || c3q_b == nullptr || w_w == nullptr || w_b == nullptr || out_w == nullptr || out_b == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_debug_values_compose: null argument");
+  values_compose(c3q_w, c3q_b, w_w, w_b, out_w, out_b);
+  return BSR_OK;
+}
+
 int bsr_debug_attention(const float* qkv, float* y, int B, int tokens, void* stream) {
   return bsr_debug_attention_dtype(qkv, y, B, tokens, BSR_DTYPE_F32, stream);
 }
 
 // bsr_probe's name tables: where a named intermediate of the last forward lies in the workspace.  half: an fp16 tensor (f16 mode).
-struct ProbeSrc { size_t off; int hh, ww, cs, coff, c; bool half; };
+// derive: an att<i> probe of a forward that kept O = softmax(f) t2 in the slot: bsr_probe computes att = O Wg + bg of block `derive` - 1 first.
+struct ProbeSrc { size_t off; int hh, ww, cs, coff, c; bool half; int derive; };
 
 // `prefix` followed by one digit below n: the digit, else -1
 static int probe_index(const std::string& nm, const char* prefix, int n) {
@@ -1499,7 +1603,19 @@ static int probe_src_gsc(const bsr_handle* h, const std::string& nm, ProbeSrc* s
     if (h->att_in_lds)
       return fail(BSR_ERR_STATE, "bsr_probe: att<i> does not exist for the last forward — attention and the `w` GEMM ran as one launch and the "
                                  "attention output never left LDS (create the handle with BSR_FUSE_ATTW=0 in the environment to probe it)");
+    *src = {p.att[i], H / 8, W / 8, 128, 0, 128, false, h->att_is_o ? i + 1 : 0};
+  }
+  else if ((i = probe_index(nm, "attv", 6)) >= 0) {      // the attention over conv2's output as the values, O = softmax(f) t2, as the kernel stored it
+    if (!h->att_is_o) return fail(BSR_ERR_STATE, "bsr_probe: attv<i> exists only for a forward with conv2's output as the attention values (fp32, BSR_KEYS_CONV2 and BSR_VALUES_CONV2 on)");
+    if (h->att_in_lds)
+      return fail(BSR_ERR_STATE, "bsr_probe: attv<i> does not exist for the last forward — attention and the `w` GEMM ran as one launch and the "
+                                 "attention output never left LDS (create the handle with BSR_FUSE_ATTW=0 in the environment to probe it)");
     *src = {p.att[i], H / 8, W / 8, 128, 0, 128};
+  }
+  else if (nm == "qkv") {      // the rows the LAST block's attention read (one buffer serves all six blocks): fp32 handles only
+    if (h->dtype != BSR_DTYPE_F32) return fail(BSR_ERR_STATE, "bsr_probe: qkv is an fp32 tensor of BSR_DTYPE_F32 handles only");
+    const int c = h->att_is_o ? 256 : 384;
+    *src = {p.qkv, H / 8, W / 8, c, 0, c};
   }
   else if ((i = probe_index(nm, "y3x", 6)) >= 0) *src = {p.y3[i], H / 8, W / 8, CS_Y3X, 0, CS_Y3X};
   else if (nm == "up1") *src = {p.c2, H / 4, W / 4, 160, 0, 96, p16};
@@ -1526,8 +1642,25 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
   const size_t npix = (size_t)h->B * src.hh * src.ww;
   shape4[0] = h->B; shape4[1] = src.hh; shape4[2] = src.ww; shape4[3] = src.c;
   if (npix * src.c > cap_floats) return fail(BSR_ERR_ARG, "bsr_probe: destination too small");
+  const float* from = h->ws + src.off;
+  if (src.derive) {
+    // att = O Wg + bg, the reference's softmax(f) g: one K = 128, N = 128 GEMM with the block's own g columns into a scratch of the handle's
+    if (h->att_scratch_floats < npix * 128) {
+      if (h->att_scratch) hipFree(h->att_scratch);
+      h->att_scratch = nullptr;
+      h->att_scratch_floats = 0;
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->att_scratch), npix * 128 * sizeof(float)));
+      h->att_scratch_floats = npix * 128;
+    }
+    const float* img = h->d_values + (size_t)(src.derive - 1) * kValuesFloats + kValuesWFloats + kValuesC3qFloats;
+    bsr::ConvArgs a{};
+    a.in = from; a.in_cs = 128; a.out = h->att_scratch; a.out_cs = 128;
+    a.w = img; a.bias = img + (size_t)4 * kGProbeNPad * 36; a.nchunk = 4; a.n_pad = kGProbeNPad; a.n_store = 128; a.act = 0;
+    HIP_TRY((bsr::launch_gemm_nloop<3, 4, 0, 2>(a, npix, 2, static_cast<hipStream_t>(stream))));
+    from = h->att_scratch;
+  }
   hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     h->ws + src.off, src.cs, src.coff, src.c, dst, npix, src.half ? 1 : 0);
+                     from, src.cs, src.coff, src.c, dst, npix, src.half ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
 }

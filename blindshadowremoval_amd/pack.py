@@ -260,6 +260,40 @@ def compose_keys_c3q(c3q_w: np.ndarray, c3q_b: np.ndarray):
     return out, b
 
 
+VALUES_N = 288 + 128         # [y3 288 | q' 128]
+VALUES_N_PAD = VALUES_N + 64  # + two zero tiles of slack (gemm_nloop group reads, NI = 3)
+W_N_PAD = 384                 # res<i>.w: 257 real of 288 + 3 zero tiles of slack (geometry())
+
+
+def compose_values(wg: np.ndarray, bg: np.ndarray, ww: np.ndarray, bw: np.ndarray):
+    """g composed onto the `w` conv.  With g = t Wg + bg and no non-linearity between g and w (model.py:53-56), and softmax rows that
+    sum to 1,  softmax(f) g Ww + bw = (softmax(f) t) (Wg Ww) + (bg Ww + bw): the values of the attention are t itself.
+    wg [K, D], bg [D], ww [D, N], bw [N] -> (Wg Ww [K, N], bw + bg Ww [N]) in float64, summed over the g channel in channel order
+    (float32 inputs have exact float64 products, so the library's loop in the same order gives the same bits)."""
+    wg, bg, ww, bw = (a.astype(np.float64) for a in (wg, bg, ww, bw))
+    w2, b2 = np.zeros((wg.shape[0], ww.shape[1])), bw.copy()
+    for c in range(wg.shape[1]):
+        w2 += wg[:, c:c + 1] * ww[c][None, :]
+        b2 += bg[c] * ww[c]
+    return w2, b2
+
+
+def compose_values_w(c3q_w: np.ndarray, c3q_b: np.ndarray, w_w: np.ndarray, w_b: np.ndarray):
+    """A res<i>.c3q blob entry ([4, 1, 768, 36], [768]: N = [y3 288 | theta | phi | g | slack]) and the block's res<i>.w entry
+    ([4, 1, 384, 36], [384]) -> the `w` image of the fp32 forward that takes conv2's output as the attention VALUES as well:
+    ([4, 1, 384, 36], [384]) in the layout of res<i>.w, rounded once to float32.
+
+    Like compose_keys_c3q this is the statement of what bsr_create derives per handle (bsr_api.hip: values_compose);
+    tests/test_values_conv2_cpu.py holds the library to it bit for bit."""
+    assert c3q_w.shape == (4, 1, 768, 36) and c3q_b.shape == (768,) and w_w.shape == (4, 1, W_N_PAD, 36) and w_b.shape == (W_N_PAD,)
+    wg = c3q_w[:, 0, 544:672, :32].transpose(0, 2, 1).reshape(128, 128)        # [K, D] float32
+    ww = w_w[:, 0, :, :32].transpose(0, 2, 1).reshape(128, W_N_PAD)            # [D, N]
+    w2, b2 = compose_values(wg, c3q_b[544:672], ww, w_b)
+    out = np.zeros((4, 1, W_N_PAD, 36), np.float32)
+    out[:, 0, :, :32] = w2.astype(np.float32).reshape(4, 32, W_N_PAD).transpose(0, 2, 1)
+    return out, b2.astype(np.float32)
+
+
 def layer_matrices(w: Dict[str, np.ndarray]) -> "Dict[str, Tuple[np.ndarray, np.ndarray]]":
     """Folded [taps, K, N] kernels + biases (float64) of every MFMA layer, in kernel K/N order."""
     out: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}

@@ -119,7 +119,7 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
 int bsr_set_timing(bsr_handle* h, int enable);
 int bsr_get_timing(bsr_handle* h, float ms_per_class[BSR_NUM_CLASSES], int launches_per_class[BSR_NUM_CLASSES]);
 /* The same events, launch by launch in issue order: bsr_timing_launches() entries; entry i = the layer name the launch computes
- * ("conv1", "down1", "res3.conv2", "res3.c3q" (conv3 + theta|phi|g), "res3.attention", "res3.w", "up2", "heads", "clr_conv1", glue
+ * ("conv1", "down1", "res3.conv2", "res3.c3q" (conv3 + theta|phi|g; fp32 GSC / TSM: conv3 + q', the keys and values of the attention being conv2's output), "res3.attention", "res3.w", "up2", "heads", "clr_conv1", glue
  * kernel names), its device time and its class.  bench.py derives the per-kernel roofline from these. */
 int bsr_timing_launches(bsr_handle* h);
 int bsr_timing_entry(bsr_handle* h, int i, char* name, size_t name_cap, float* ms, int* cls);
@@ -295,6 +295,18 @@ int bsr_debug_wino_filter(const float* direct, float* out);
  * q' = theta composed onto phi's weights in float64 (blindshadowremoval_amd.pack.compose_keys_c3q).  c3q_w = the layer's [4][1][768][36]
  * image, c3q_b = its [768] bias, out_w = [4][1][608][36] floats, out_b = [608] floats (all HOST pointers). */
 int bsr_debug_keys_compose(const float* c3q_w, const float* c3q_b, float* out_w, float* out_b);
+/* Test hook (additive, host only, no GPU call): the `w` image bsr_create derives per block of an fp32 GSC / TSM blob for the attention
+ * that takes conv2's output as its VALUES as well (env BSR_VALUES_CONV2, default on, read while BSR_KEYS_CONV2 is on): W' = Wg Ww,
+ * b' = bw + bg Ww in float64, rounded once (blindshadowremoval_amd.pack.compose_values_w).  With it res<i>.c3q computes
+ * N = [y3 288 | q' 128] (13 channel tiles; the qkv rows are [q' | t2] at stride 256) and the `w` GEMM keeps K = 128.  c3q_w / c3q_b = the
+ * layer's [4][1][768][36] image and [768] bias, w_w / w_b = res<i>.w's [4][1][384][36] image and [384] bias, out_w / out_b in the layout
+ * of the latter (all HOST pointers). */
+int bsr_debug_values_compose(const float* c3q_w, const float* c3q_b, const float* w_w, const float* w_b, float* out_w, float* out_b);
+/* Test hook (additive): the fp32 attention kernel in its shared-tile form alone — qkv2 [B,tokens,256] rows [q | kv], ONE tensor as keys
+ * and values -> y [B,tokens,128]; qw as bsr_debug_attention_qw.  Bit-identical to bsr_debug_attention_qw on [q | kv | kv] rows.
+ * bsr_probe on such a forward: "att<i>" stays the reference's softmax(f) g (derived from the stored O = softmax(f) t2 by one small
+ * GEMM with the block's g columns), "attv<i>" is O itself, "qkv" the rows the last block's attention read. */
+int bsr_debug_attention_kv1(const float* qkv2, float* y, int B, int tokens, int qw, void* stream);
 
 /* Measurement hook (ABI 7): one wave on `stream` writes (shader cycle counter, 100-MHz real-time counter) pairs to out[2 * samples] every
  * spin x ~3.4 us until *stop (device memory, written from another stream) is non-zero or `samples` pairs are taken; *taken receives the
