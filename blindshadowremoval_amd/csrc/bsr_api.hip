@@ -35,6 +35,7 @@
 #include "sfw_kernels.h"
 #include "wino_conv2.h"
 #include "wild_crop_kernels.h"
+#include "wild_paste_kernels.h"
 
 namespace {
 
@@ -1357,6 +1358,50 @@ int bsr_crop_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off
   }
   hipLaunchKernelGGL(bsr::crop_faces_kernel, dim3((unsigned)((S / 16) * (S / 16)), (unsigned)n), dim3(256), 0, s, blob,
                      reinterpret_cast<const bsr::CropItem*>(blob + items_off), S);
+  HIP_TRY(hipGetLastError());
+  return BSR_OK;
+}
+
+int bsr_paste_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, const float* im, int im_stride, const float* con,
+                    int con_stride, const float* face, int face_stride, int mode, void* stream) {
+  if (d_blob == nullptr || im == nullptr || con == nullptr || face == nullptr) return fail(BSR_ERR_ARG, "bsr_paste_faces: null argument");
+  if (n <= 0 || n > 65535 || items_off % 8 != 0) return fail(BSR_ERR_ARG, "bsr_paste_faces: n must be 1..65535 and items_off 8-byte aligned");
+  if (S != 32 && S != 64 && S != 128 && S != 256) return fail(BSR_ERR_ARG, "bsr_paste_faces: S must be 32, 64, 128 or 256");
+  if (mode != bsr::kPasteResidual && mode != bsr::kPasteReplace) return fail(BSR_ERR_ARG, "bsr_paste_faces: mode must be 0 (residual) or 1 (replace)");
+  if (im_stride < 3 || con_stride < 3 || face_stride < 1 || im_stride > 4096 || con_stride > 4096 || face_stride > 4096)
+    return fail(BSR_ERR_ARG, "bsr_paste_faces: pixel strides are floats between neighbouring pixels: 3..4096 for im and con, 1..4096 for face");
+  if (items_off > blob_bytes || (size_t)n * sizeof(bsr::PasteItem) > blob_bytes - items_off)
+    return fail(BSR_ERR_ARG, "bsr_paste_faces: the item table does not fit in blob_bytes");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  unsigned char* blob = static_cast<unsigned char*>(d_blob);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::vector<bsr::PasteItem> items;
+  if (int rc = read_records(blob, items_off, n, s, &items)) return rc;
+  const long long total = (long long)blob_bytes;
+  unsigned tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    const bsr::PasteItem& it = items[(size_t)i];
+    if (it.h < 1 || it.h > 65535 || it.w < 1 || it.w > 65535 || it.preset_x < 0 || it.preset_y < 0 || it.preset_x > (1 << 20) || it.preset_y > (1 << 20))
+      return fail(BSR_ERR_ARG, "bsr_paste_faces: a record needs 1 <= h, w <= 65535 and presets in 0..2^20");
+    if (it.photo_off < 0 || it.photo_off > total || 3ll * it.h * it.w > total - it.photo_off)
+      return fail(BSR_ERR_ARG, "bsr_paste_faces: a record points outside the blob");
+    // the photograph must not cover the record table the kernel is reading
+    if (it.photo_off < (long long)(items_off + (size_t)n * sizeof(bsr::PasteItem)) && it.photo_off + 3ll * it.h * it.w > (long long)items_off)
+      return fail(BSR_ERR_ARG, "bsr_paste_faces: a record's photograph overlaps the item table");
+    // the box against its canvas, as bsr_crop_faces; a side of at least 2 pixels
+    const bool padded = it.preset_x != 0 || it.preset_y != 0;
+    const long long cw = padded ? (long long)it.w + 2ll * it.preset_x + 2 : it.w, ch = padded ? (long long)it.h + 2ll * it.preset_y + 2 : it.h;
+    if (it.box[0] < 0 || it.box[1] < 0 || it.box[2] > cw || it.box[3] > ch || (long long)it.box[2] - it.box[0] < 2 || (long long)it.box[3] - it.box[1] < 2)
+      return fail(BSR_ERR_ARG, "bsr_paste_faces: a record's box has a side under 2 pixels or leaves its canvas");
+    if (it.row < 0 || it.row >= n) return fail(BSR_ERR_ARG, "bsr_paste_faces: a record's row is not one of the n rows of im / con / face");
+    const unsigned t = bsr::paste_tiles(it);
+    if (t > tiles) tiles = t;
+  }
+  if (tiles == 0) return BSR_OK;                    // no box meets its photograph: every photograph stays as it is
+  bsr::PastePlanes pl{im, con, face, im_stride, con_stride, face_stride};
+  hipLaunchKernelGGL(bsr::paste_faces_kernel, dim3(tiles, (unsigned)n), dim3(256), 0, s, blob, reinterpret_cast<const bsr::PasteItem*>(blob + items_off), S, pl,
+                     mode);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
 }

@@ -233,18 +233,25 @@ def _row_of(img: np.ndarray, gt: np.ndarray, lm0: np.ndarray, size: int) -> Tupl
     return np.concatenate([crop, uvm, reg_in, reg_out, face], axis=2).astype(np.float32), np.asarray(box, np.float32)
 
 
-def build_row_uncropped(img_path: str, size: int = 256):
+def build_row_uncropped(img_path: str, size: int = 256, keep_photo: bool = False):
     """One row from an UNCROPPED photograph `<name>.png` with `<name>.npy` beside it: the reference's two procedures back to back —
     dataprocess.py (wild_crop.crop_face: the 256 x 256 face and its landmarks, what the script writes to a folder) and then
-    parse_fn_test_FFHQ on that folder (build_row) — without the folder.  None where the script skips the photograph."""
+    parse_fn_test_FFHQ on that folder (build_row) — without the folder.  None where the script skips the photograph.  keep_photo: the
+    tuple gains a prep.WildPhoto — the photograph itself and the crop's geometry, for wild_paste.paste_face."""
     from .pngio import read_rgb_u8
-    from .wild_crop import crop_face
-    res = crop_face(read_rgb_u8(img_path), np.load(os.path.splitext(img_path)[0] + ".npy"))
-    if res is None:
+    from .wild_crop import crop_geometry, crop_pixels
+    photo = read_rgb_u8(img_path)
+    geo = crop_geometry(np.load(os.path.splitext(img_path)[0] + ".npy"), photo.shape[0], photo.shape[1])
+    if geo is None:
         return None
-    face, lm256, _ = res
+    box, preset_x, preset_y, lm256 = geo
+    face = crop_pixels(photo, box, preset_x, preset_y)                   # = wild_crop.crop_face
     img = face.astype(np.float64) / 255.0                                # imread_rgb of the file the script writes (PNG is lossless)
-    return _row_of(img, img, lm256, size)
+    row = _row_of(img, img, lm256, size)
+    if keep_photo:
+        from .prep import WildPhoto
+        return row + (WildPhoto(photo.shape[0], photo.shape[1], box, preset_x, preset_y, array=photo),)
+    return row
 
 
 def _maps(lm: np.ndarray, size: int):
@@ -398,11 +405,11 @@ def build_element(job) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         if part is None:
             raise ValueError("%s fails dataprocess.py's size rule: Dataset(uncropped=True) lists no such item" % lm_path)
         return part
-    if gt_path == "<uncropped>":
-        res = build_row_uncropped(lm_path, size)
+    if gt_path in ("<uncropped>", "<uncropped_keep>"):
+        res = build_row_uncropped(lm_path, size, keep_photo=gt_path == "<uncropped_keep>")
         if res is None:
             raise ValueError("%s fails dataprocess.py's size rule: Dataset(uncropped=True) lists no such item" % lm_path)
-        return res[0][None, None], res[1][None], np.array([lm_path.encode()])
+        return (res[0][None, None], res[1][None], np.array([lm_path.encode()])) + tuple(res[2:])
     if gt_path == "<sfw>":
         return build_sfw_pair(lm_path, size)
     if isinstance(gt_path, tuple) and gt_path[0] == "<ucb_tsm>":
@@ -432,7 +439,7 @@ class Dataset:
 
     def __init__(self, config, mode: str = "test", dset=None, ucb: bool = False, rows: int = 1, seed: int = 0,
                  workers: int = 0, prefetch: Optional[int] = None, device_prep: Optional[int] = None, device_batch: int = 16,
-                 device_groups: Optional[int] = None, uncropped: bool = False):
+                 device_groups: Optional[int] = None, uncropped: bool = False, keep_photo: bool = False):
         if mode != "test" or dset not in (None, "sfw", "sfw_video", "sfw_gsc", "ucb_tsm"):
             raise NotImplementedError("only the test loaders are provided (GSC: dset=None | 'sfw_gsc'; TSM: dset='sfw' | 'sfw_video' | 'ucb_tsm'); "
                                       "training loaders are out of scope")
@@ -483,6 +490,13 @@ class Dataset:
         self.uncropped = bool(uncropped)
         if self.uncropped and (ucb or rows != 1 or dset is not None or device_groups is not None):
             raise ValueError("uncropped=True is the FFHQ loader over uncropped photographs: ucb=False, rows=1, dset=None, no device_groups")
+        # keep_photo = True (uncropped only): every element additionally carries a prep.WildPhoto — the photograph it was cropped from and
+        # the crop's geometry — as its fourth entry, for FSRNet.testFFHQ(paste_back=...).  Host route: the decoded array.  Device route:
+        # the photograph's area of the batch blob, reconstructed in full (rows_needed = 0); the WildPhoto holds the blob.  The row is the
+        # same bits with and without it
+        self.keep_photo = bool(keep_photo)
+        if self.keep_photo and not self.uncropped:
+            raise ValueError("keep_photo=True keeps the photograph of uncropped=True elements: the other loaders' items come cropped")
         self.name_list: List[str] = []
         if self.uncropped:
             from .wild_crop import MIN_LENGTH, box_length
@@ -535,7 +549,7 @@ class Dataset:
             return
         if self.uncropped:                                                 # (no ring: a photograph's scanlines are ~3 MB, they take the pipe)
             for img_path in self.name_list[lo:hi]:
-                yield (img_path, "<uncropped_device>" if self.device_prep is not None else "<uncropped>", [], size)
+                yield (img_path, "<uncropped_device>" if self.device_prep is not None else ("<uncropped_keep>" if self.keep_photo else "<uncropped>"), [], size)
             return
         for i, lm_path in enumerate(self.name_list):
             if i >= hi:
@@ -655,7 +669,7 @@ class Dataset:
         self._emitted = 0
 
         def emit():
-            out, boxes, masks, names = dp.rows_uncropped(group) if self.uncropped else dp.rows_ex(group)
+            out, boxes, masks, names = dp.rows_uncropped(group, self.keep_photo) if self.uncropped else dp.rows_ex(group)
             self._emitted += len(group)
             if dp.ring is not None:
                 self._ring_copies.append([self._emitted, dp.last_copy, False])       # jobs < _emitted have left their slots once this event is done

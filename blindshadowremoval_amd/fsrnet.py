@@ -66,6 +66,7 @@ class Logging(object):
         self.losses: Dict[str, List[float]] = {}
         self.quiet = False
         self.saved: List[str] = []
+        self.pasted: List[str] = []              # the <stem>-pasted.png files of testFFHQ(paste_back=...)
         # PNG encoding (zlib) releases the GIL: with png_threads > 0 (the FSRNet loops use 4) strips are encoded by background
         # threads while the loop goes on and flush() — called by the loops before they return — waits for them; the default
         # (0) writes synchronously, as the reference's cv2.imwrite does
@@ -189,6 +190,32 @@ class Logging(object):
                 f.result()
             self._pending = [f for f in self._pending if not f.done()]
         return futs
+
+    def _pasted_path(self, fname: str) -> str:
+        return self._png_path(fname)[:-len('-result.png')] + '-pasted.png'
+
+    def save_pasted(self, fname: str, file_bytes=None, pixels=None):
+        """Write one item's photograph with the face pasted back (FSRNet.testFFHQ(paste_back=...)) as <stem>-pasted.png beside its strip:
+        `file_bytes` = the complete PNG file built on the device, or `pixels` = a uint8 [h,w,3] array, or a callable that returns one
+        (the host route's wild_paste.paste_face), for pngio's host writer.  -> the write's future (flush() waits for it too); the memory
+        behind the argument must stay untouched until it is done."""
+        if self._file_pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._file_pool = ThreadPoolExecutor(max_workers=max(1, self.file_threads), thread_name_prefix="bsr-file")
+        out = self._pasted_path(fname)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        self.pasted.append(out)
+
+        def put():
+            if file_bytes is not None:
+                with open(out, "wb") as f:
+                    f.write(memoryview(file_bytes).cast("B"))
+                return
+            from .pngio import write_png
+            write_png(out, pixels() if callable(pixels) else pixels)
+        fut = self._file_pool.submit(put)
+        self._pending.append(fut)
+        return fut
 
     def write_files_now(self, files: torch.Tensor, names: Sequence[str]) -> None:
         """save_files for PNG files built on the device ([B, file_bytes], e.g. files_on_device): copy them to the host, write them and
@@ -661,14 +688,14 @@ class FSRNet(object):
             out[k] = np.repeat(a[:, :, None], 3, axis=2)
         return out
 
-    def _loop(self, dataset, batch: int, ucb: bool, postprocess: bool = True, mask_files=None):
+    def _loop(self, dataset, batch: int, ucb: bool, postprocess: bool = True, mask_files=None, paste_back=None):
         try:
-            return self._loop_body(dataset, batch, ucb, postprocess, mask_files)
+            return self._loop_body(dataset, batch, ucb, postprocess, mask_files, paste_back)
         finally:
             # also on an exception mid-loop (loader failure, missing mask): no queued PNG writer is left unobserved
             self.log.flush()
 
-    def _loop_body(self, dataset, batch: int, ucb: bool, postprocess: bool, mask_files):
+    def _loop_body(self, dataset, batch: int, ucb: bool, postprocess: bool, mask_files, paste_back=None):
         """The reference's loops (train_test_GSC.py:360-408, 840-860), batched, data-parallel and pipelined:
 
         * rank r of a process group works on the contiguous shard r of ``dataset.name_list`` (no data-path collective: items are
@@ -726,6 +753,7 @@ class FSRNet(object):
         # PNG files there too, and what comes back per item is its file + two losses; post_workers / post_threads are the host forms
         post_dev = None
         pend_masks: Dict[int, object] = {}
+        pend_photo: Dict[int, object] = {}      # paste_back: the item's prep.WildPhoto (the device route's hold the batch blob until the batch is completed)
         if ucb and postprocess and on_gpu and self.post_device:
             post_dev = self._post_device(self.gen._device)
             if hasattr(dataset, "ucb_mask_files") and getattr(dataset, "device_prep", None) is not None and not getattr(dataset, "_started", False):
@@ -825,6 +853,79 @@ class FSRNet(object):
             view = pins[k][:nbytes].view(payload.dtype).reshape(payload.shape)
             return view.numpy(), copy_out(view), (-1 - k if pin_id else None)       # pin_id: the "slot" names the private pinned buffer (negative), for pin_busy
 
+        def paste_submit(items, im_d, con_rgb, face_d):
+            """paste_back for one batch, behind its forward: -> (uint8 device tensor to append to the batch's payload, per item what lies
+            where in it).  Device route (the photographs lie in the loader's blobs): bsr_paste_faces rewrites them in place — one launch
+            per blob, i.e. per batch when the loop's batch is the loader's — and each becomes a PNG file there (bsr_png_encode, B = 1) or,
+            past the encoder's width or without the device encoder, travels as pixels for pngio's writer.  Host route: im | con_rgb | face
+            travel as floats and wild_paste.paste_face runs when the batch is completed."""
+            from . import _lib
+            from .prep import PASTE_DTYPE
+            from .wild_paste import MODES
+            photos = [pend_photo.pop(it[0]) for it in items]
+            S = self.config.IMG_SIZE
+            chunks, layout, off = [], [], 0
+            if all(ph.array is not None for ph in photos):
+                src = torch.cat([im_d, con_rgb, face_d], dim=3).contiguous()
+                return src.view(torch.uint8).reshape(-1), [("host", j, ph) for j, ph in enumerate(photos)]
+            if any(ph.blob is None for ph in photos):
+                raise ValueError("paste_back: a batch mixes host and device photographs")
+            for t_ in (im_d, con_rgb, face_d):
+                if t_.stride(3) != 1 or t_.stride(1) != S * t_.stride(2) or t_.stride(0) != S * S * t_.stride(2):
+                    raise ValueError("paste_back: im / con_rgb / face must be dense in their pixel stride, got strides %s" % (t_.stride(),))
+            st = torch.cuda.current_stream().cuda_stream
+            lib = _lib.load()
+            j = 0
+            while j < len(items):
+                e = j + 1
+                while e < len(items) and photos[e].blob is photos[j].blob:
+                    e += 1
+                blob, at = photos[j].blob, photos[j].paste_off
+                if post_stream is not None:
+                    blob.record_stream(post_stream)
+                recs = np.zeros(e - j, PASTE_DTYPE)
+                for k in range(j, e):
+                    ph = photos[k]
+                    recs[k - j] = (ph.off, ph.h, ph.w, ph.box, ph.preset_x, ph.preset_y, k - j, 0)
+                blob[at:at + recs.nbytes].copy_(torch.from_numpy(recs.view(np.uint8).reshape(-1)))
+                _lib.check(lib.bsr_paste_faces(self.gen._device, blob.data_ptr(), blob.numel(), at, e - j, S, im_d[j:].data_ptr(), im_d.stride(2),
+                                               con_rgb[j:].data_ptr(), con_rgb.stride(2), face_d[j:].data_ptr(), face_d.stride(2), MODES.index(paste_back), st),
+                           "bsr_paste_faces")
+                j = e
+            for ph in photos:
+                if gpu_png and ph.w <= 5461 and ph.h <= 65535:               # the device encoder's geometry (bsr_png_file_bytes)
+                    # an encoder of its own: the strips' encoder (and its checksum scratch) may be at work on the compute stream for the next batch
+                    key = ("paste", self.gen._device)
+                    if key not in self.log._encoders:
+                        from .gpu_png import StripEncoder
+                        self.log._encoders[key] = StripEncoder(self.gen._device)
+                    c = self.log._encoders[key].encode(ph.view[None]).reshape(-1)
+                    layout.append(("png", off, int(c.numel()), ph))
+                else:
+                    c = ph.view.reshape(-1)
+                    layout.append(("raw", off, int(c.numel()), ph))
+                chunks.append(c)
+                off += int(c.numel())
+            return torch.cat(chunks), layout
+
+        def paste_complete(extra: np.ndarray, layout, items):
+            """the host half of paste_submit once the batch's copy has landed: -> the file writes' futures (they read `extra` in place)"""
+            from .wild_paste import paste_face
+            futs = []
+            S = self.config.IMG_SIZE
+            src = extra.view(np.float32).reshape(len(items), S, S, 7) if layout and layout[0][0] == "host" else None
+            for (step, name, _, _), lay in zip(items, layout):
+                if lay[0] == "host":
+                    _, j, ph = lay
+                    futs.append(self.log.save_pasted(name, pixels=lambda j=j, ph=ph: paste_face(ph.array, ph.box, ph.preset_x, ph.preset_y, src[j, ..., 0:3],
+                                                                                                   src[j, ..., 3:6], src[j, ..., 6:7], paste_back)))
+                elif lay[0] == "png":
+                    futs.append(self.log.save_pasted(name, file_bytes=extra[lay[1]:lay[1] + lay[2]]))
+                else:
+                    ph = lay[3]
+                    futs.append(self.log.save_pasted(name, pixels=extra[lay[1]:lay[1] + lay[2]].reshape(ph.h, ph.w, 3)))
+            return futs
+
         def submit():
             """one batch: rows -> device -> generator -> what the host needs, on its way to pinned memory; nothing here waits for the GPU"""
             if not pending:
@@ -838,6 +939,7 @@ class FSRNet(object):
             outs = self._generate(im_d, uv_d, ucb)
             items = list(pending)
             pending.clear()
+            paste = None
             if post_dev is not None:
                 # train_test_GSC.py:424-748 for the whole batch on the device; the seven figures leave as PNG files
                 from .prep import pack_masks, unpack_masks
@@ -880,11 +982,27 @@ class FSRNet(object):
                 else:
                     figs_b = [im_d, torch.clamp(con_rgb, 0, 1), mask_pred * face_d * 2]        # train_test_GSC.py:872-873,889
                     shown_b = figs_b
-                if gpu_png:                       # complete PNG files built on the device; the host only writes them
+                if paste_back is not None:
+                    # the strips as always, then — on the post stream behind this batch's forward, like the UCB post-processing — the
+                    # photographs with the face pasted back; both leave in ONE copy into this batch's pinned buffer
+                    main_t = self.log.files_on_device(shown_b) if gpu_png else self.log.strips_on_device(shown_b)
+                    side = post_stream is not None
+                    if side:
+                        fwd_done = torch.cuda.Event()
+                        fwd_done.record()
+                        for t_ in (rows_d, con_rgb, main_t):
+                            t_.record_stream(post_stream)
+                    with torch.cuda.stream(post_stream) if side else contextlib.nullcontext():
+                        if side:
+                            post_stream.wait_event(fwd_done)
+                        extra_t, layout = paste_submit(items, im_d, con_rgb, face_d)
+                        host, ev, slot = to_host_async(torch.cat([main_t.reshape(-1), extra_t]), to_pool=False, pin_id=True)
+                    paste = (tuple(main_t.shape), layout)
+                elif gpu_png:                     # complete PNG files built on the device; the host only writes them
                     host, ev, slot = to_host_async(self.log.files_on_device(shown_b), to_pool=False, pin_id=True)
                 else:
                     host, ev, slot = to_host_async(self.log.strips_on_device(shown_b), to_pool=self.log.png_workers > 0)
-            gpu_q.append((items, host, ev, figs_b, slot))
+            gpu_q.append((items, host, ev, figs_b, slot, paste))
             tm["forward_s"] += time.perf_counter() - t0
             tm["forwards"] += 1
             poll()
@@ -893,7 +1011,7 @@ class FSRNet(object):
 
         def complete(entry):
             """the batch's device work has to be done now: wait for its event, then hand its host half on"""
-            items, host, ev, figs_b, slot = entry
+            items, host, ev, figs_b, slot, paste = entry
             ring = ring_state[0]
             t0 = time.perf_counter()
             if ev is not None:
@@ -969,7 +1087,22 @@ class FSRNet(object):
                 tm["post_s"] += time.perf_counter() - t1
                 finish(items, post)
                 return
-            if gpu_png and slot is not None and slot < 0:
+            if paste is not None:
+                shape, layout = paste
+                nmain = int(np.prod(shape))
+                main_h = host[:nmain].reshape(shape)
+                if gpu_png:
+                    futs = self.log.save_files(main_h, [it[1] for it in items])
+                else:
+                    futs = []
+                    self.log.save_strips(np.array(main_h), [it[1] for it in items])
+                futs = futs + paste_complete(host[nmain:], layout, items)
+                if slot is not None and slot < 0:
+                    pin_busy[-1 - slot] = futs
+                else:
+                    for fu in futs:
+                        fu.result()
+            elif gpu_png and slot is not None and slot < 0:
                 pin_busy[-1 - slot] = self.log.save_files(host, [it[1] for it in items])
             elif slot is not None:                  # the strips already sit in a shared-memory slot: the PNG workers read them there
                 self.log.save_strips(host, [it[1] for it in items], parked=(ring.path(slot), lambda k=slot: ring.release(k)))
@@ -996,6 +1129,10 @@ class FSRNet(object):
                 pending.append((step, _name(img_name), img, element[1] if len(element) > 1 else None))
                 if post_dev is not None:
                     pend_masks[step] = element[3] if len(element) > 3 else None      # the item's packed masks when the loader decoded them
+                if paste_back is not None:
+                    if len(element) < 4 or not hasattr(element[3], "preset_x"):
+                        raise ValueError("testFFHQ(paste_back=...) needs the photographs: Dataset(config, 'test', uncropped=True, keep_photo=True)")
+                    pend_photo[step] = element[3]
                 if len(pending) >= batch:
                     submit()
             submit()
@@ -1076,10 +1213,21 @@ class FSRNet(object):
     def _split_row0(self, img) -> torch.Tensor:
         return _rows(img, self.config.IMG_SIZE)[:1]
 
-    def testFFHQ(self, dataset_val, batch: int = 16):
+    def testFFHQ(self, dataset_val, batch: int = 16, paste_back: Optional[str] = None):
         """train_test_GSC.py:840-860.  ``dataset_val`` needs ``.feed`` (iterator of (img[1,10,256,256,16], box, name))
-        and ``.name_list`` (dataset.py:29-30)."""
-        return self._loop(dataset_val, batch, ucb=False)
+        and ``.name_list`` (dataset.py:29-30).  ``paste_back`` = "residual" | "replace" (Dataset(uncropped=True, keep_photo=True) only):
+        besides the strips — written exactly as without it — every item's photograph with the de-shadowed face written back into it
+        (wild_paste.py; on the device route bsr_paste_faces and the device PNG encoder) goes to <CHECKPOINT_DIR>/test/<stem>-pasted.png
+        (``log.pasted``).  The return value is the same."""
+        if paste_back is not None:
+            from .wild_paste import MODES
+            if paste_back not in MODES:
+                raise ValueError("testFFHQ: paste_back is None or one of %s, got %r" % (MODES, paste_back))
+            if not getattr(dataset_val, "keep_photo", False):
+                raise ValueError("testFFHQ(paste_back=...) needs the photographs: Dataset(config, 'test', uncropped=True, keep_photo=True)")
+            if getattr(self.gen, "_device", None) is None or not torch.cuda.is_available():
+                raise RuntimeError("testFFHQ(paste_back=...) runs with the generator on a GPU")
+        return self._loop(dataset_val, batch, ucb=False, paste_back=paste_back)
 
     def test(self, dataset_val, batch: int = 16, postprocess: bool = True, mask_files=None):
         """train_test_GSC.py:360-408 + test_step :411-748.  Returns [(name, figs, {'ssim','psnr'})] with the reference's seven

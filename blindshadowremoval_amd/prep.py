@@ -54,6 +54,10 @@ assert UNFILTER_TALL_DTYPE.itemsize == 40     # UnfilterTallItem
 CROP_DTYPE = np.dtype([("src_off", "<i8"), ("out_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("box", "<i4", (4,)), ("preset_x", "<i4"),
                        ("preset_y", "<i4")], align=True)
 assert CROP_DTYPE.itemsize == 48              # CropItem
+# the way back (csrc/wild_paste_kernels.h): the photograph to rewrite in place, the crop's geometry, the item's row of im / con / face
+PASTE_DTYPE = np.dtype([("photo_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("box", "<i4", (4,)), ("preset_x", "<i4"), ("preset_y", "<i4"),
+                        ("row", "<i4"), ("pad", "<i4")], align=True)
+assert PASTE_DTYPE.itemsize == 48             # PasteItem
 UNFILTER_SLACK = 16                           # csrc/prep_kernels.h kUnfilterSlack: readable bytes around filtered scanlines
 
 
@@ -286,11 +290,30 @@ def host_part_uncropped(job, raw: bool = True):
     return (img, None, np.asarray(box, np.int32), meshes(lm), img_path.encode(), (np.asarray(cbox, np.int32), preset_x, preset_y))
 
 
-def _layout_uncropped(parts, size: int):
+class WildPhoto:
+    """The photograph an element of Dataset(uncropped=True, keep_photo=True) was cropped from, with the crop's geometry (wild_crop.
+    crop_geometry): what wild_paste / bsr_paste_faces need to write the network's change back.  Host route: `array` is the uint8
+    [h,w,3] photograph.  Device route: `blob` is the batch's uint8 device blob — every WildPhoto of a batch holds the same tensor, and
+    with it the blob's memory — the photograph's RGB8 area lies at `off`, and `paste_off` is the blob's area for the batch's
+    PASTE_DTYPE records."""
+    __slots__ = ("array", "blob", "off", "paste_off", "h", "w", "box", "preset_x", "preset_y")
+
+    def __init__(self, h, w, box, preset_x, preset_y, array=None, blob=None, off=0, paste_off=0):
+        self.h, self.w, self.box, self.preset_x, self.preset_y = int(h), int(w), [int(v) for v in box], int(preset_x), int(preset_y)
+        self.array, self.blob, self.off, self.paste_off = array, blob, int(off), int(paste_off)
+
+    @property
+    def view(self):
+        """The photograph as a uint8 [h,w,3] view of the device blob (device route)."""
+        return self.blob[self.off:self.off + self.h * self.w * 3].view(self.h, self.w, 3)
+
+
+def _layout_uncropped(parts, size: int, keep_photo: bool = False):
     """The blob of a batch of host_part_uncropped results: [row records | grid | crop records | tall records | per item: scanlines with
     their slack (or the decoded photograph) and the four tables] — the `head`, staged by the caller — then, device only, the
     reconstructed photographs and the S x S crops the row records point to.  -> (total, head, rows_off, grid_off, crop_off, tall_off,
-    number of tall records, pieces)."""
+    number of tall records, pieces).  keep_photo: every row of every photograph is reconstructed (rows_needed = 0) and the device part
+    ends with room for the batch's paste records; the tuple gains (paste_off, [photograph offset per item])."""
     B = len(parts)
     rows, crops = np.zeros(B, ROW_DTYPE), np.zeros(B, CROP_DTYPE)
     n_tall = sum(1 for p in parts if hasattr(p[0], "raw"))
@@ -320,7 +343,7 @@ def _layout_uncropped(parts, size: int):
             pieces.append((int(t["raw_off"]), img.raw))
             t["h"], t["w"], t["c"] = img.h, img.w, img.c
             # the lowest photograph row a tap of the crop can touch is the box's last one
-            t["rows_needed"] = min(max(int(cbox[3]) - int(preset_y), 1), img.h)
+            t["rows_needed"] = 0 if keep_photo else min(max(int(cbox[3]) - int(preset_y), 1), img.h)
         else:
             c["src_off"] = take(img.nbytes)
             pieces.append((int(c["src_off"]), img))
@@ -342,6 +365,9 @@ def _layout_uncropped(parts, size: int):
     for i in range(B):
         crops[i]["out_off"] = rows[i]["img_off"] = rows[i]["gt_off"] = take(size * size * 3)
     pieces += [(rows_off, rows), (crop_off, crops)] + ([(tall_off, talls)] if n_tall else [])
+    if keep_photo:
+        paste_off = take(B * PASTE_DTYPE.itemsize)
+        return off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces, paste_off, [int(c["src_off"]) for c in crops]
     return off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces
 
 
@@ -734,15 +760,17 @@ class DevicePrep:
                 masks[i] = ("dev_" + kind, v.view(7, -1) if kind == "bits" else v.view(7, ms, ms), ms)
         return out, boxes, masks, names
 
-    def rows_uncropped(self, parts):
+    def rows_uncropped(self, parts, keep_photo: bool = False):
         """rows_ex for host_part_uncropped results (they come through the workers' pipes: a 1024 x 1024 photograph is three ring slots):
         the scanlines go to the device as they were inflated, and bsr_png_unfilter_tall -> bsr_crop_faces -> bsr_prep_rows run behind the
-        copy in one stream; the crop's output is the row record's image.  -> (rows [B,S,S,16], boxes, [None] * B, names)."""
+        copy in one stream; the crop's output is the row record's image.  -> (rows [B,S,S,16], boxes, [None] * B, names).  keep_photo:
+        the third entry holds a WildPhoto per item instead — the whole photograph, reconstructed in the blob, and its geometry; the
+        rows are the same bits."""
         if self.planes is not None:
             raise ValueError("DevicePrep.rows_uncropped prepares rows (planes=None)")
         torch = self._torch
         B, S = len(parts), self.size
-        total, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces = _layout_uncropped(parts, S)
+        total, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces, *kept = _layout_uncropped(parts, S, keep_photo)
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
             k = self._turn = (getattr(self, "_turn", 0) + 1) & 1
@@ -775,4 +803,9 @@ class DevicePrep:
             d_blob.record_stream(main)
         self._check(rc, "bsr_prep_rows")
         boxes = np.stack([np.asarray(p[2], np.float32) for p in parts], axis=0)
-        return out, boxes, [None] * B, [p[4] for p in parts]
+        photos = [None] * B
+        if keep_photo:
+            paste_off, photo_offs = kept
+            photos = [WildPhoto(p[0].shape[0], p[0].shape[1], p[5][0], p[5][1], p[5][2], blob=d_blob, off=o, paste_off=paste_off)
+                      for p, o in zip(parts, photo_offs)]
+        return out, boxes, photos, [p[4] for p in parts]

@@ -13,6 +13,8 @@ with the loop's rate.  The process group is created by THIS process before it to
 Weights: the newest `ckpt-N` under --checkpoint-dir (tf_bundle.py), or `--random-weights SEED` (the reference ships no data shards).
 `--loop ffhq --uncropped`: --data globs uncropped photographs (`sample_uncropped_images/*.png`, landmarks in a .npy beside each); the
 reference's dataprocess.py crop runs inside the loader (Dataset(uncropped=True), wild_crop.py), on the device unless `--host-prep`.
+`--paste-back [residual|replace]` (with --uncropped): besides the strips, every photograph comes back with the de-shadowed face written
+into it, as <checkpoint-dir>/test/<stem>-pasted.png (wild_paste.py; on the device unless `--host-prep`).
 `--model rgb` runs the paper's single-stage RGB baseline instead (train_RGB_test.py's `main`: `FSRNetRGB.test`, `--loop ucb`, fp32 only).
 `--loop sfw` / `--loop sfw_video` run the GSC model's SFW evaluation (`FSRNet.testsfw` over Dataset(dset='sfw_gsc') /
 `FSRNet.testsfw_video` over Dataset(dset='sfw_video'): --data globs SFW video folders), in one process only.
@@ -49,6 +51,9 @@ def main(argv=None) -> int:
     ap.add_argument("--uncropped", action="store_true", help="--loop ffhq only: --data globs the .png files of uncropped photographs (each with its 68 "
                                                              "landmarks in a .npy beside it); dataprocess.py's crop runs in the loader (wild_crop.py; on the "
                                                              "device unless --host-prep)")
+    ap.add_argument("--paste-back", nargs="?", const="residual", default=None, choices=("residual", "replace"),
+                    help="--loop ffhq --uncropped only: also write each photograph with the de-shadowed face pasted back into it "
+                         "(<stem>-pasted.png): residual (default) adds the network's change under the face hull, replace blends the prediction in")
     ap.add_argument("--host-post", action="store_true", help="rounds 2-4 forms: UCB post-processing in worker processes and PNG encoding on the host "
                                                              "(default: both on the device — ucb_post_gpu.py, gpu_png.py)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl")
@@ -63,6 +68,10 @@ def main(argv=None) -> int:
     if args.uncropped and (args.loop != "ffhq" or args.model != "gsc"):
         sys.stderr.write("run_loop: --uncropped feeds uncropped photographs to FSRNet.testFFHQ: --model gsc --loop ffhq (the other loops read "
                          "data sets that come cropped)\n")
+        return 2
+    if args.paste_back is not None and (not args.uncropped or args.loop != "ffhq" or args.model != "gsc"):
+        sys.stderr.write("run_loop: --paste-back writes the face back into the photograph it was cropped from: --model gsc --loop ffhq --uncropped "
+                         "(the other loaders' items come cropped, there is no photograph to paste into)\n")
         return 2
     if tsm and args.loop == "ffhq":
         sys.stderr.write("run_loop: --model tsm runs train_with_TSM.py's loops: --loop ucb | sfw | sfw_video (it has no testFFHQ)\n")
@@ -125,7 +134,7 @@ def main(argv=None) -> int:
     else:
         if not args.host_prep:
             ds_kw.update(device_prep=local_rank, device_batch=args.batch)
-        ds = Dataset(cfg, "test", ucb=ucb, uncropped=args.uncropped, **ds_kw)
+        ds = Dataset(cfg, "test", ucb=ucb, uncropped=args.uncropped, keep_photo=args.paste_back is not None, **ds_kw)
     if tsm:
         return _run_tsm(args, cfg, ds)
     if args.model == "rgb":
@@ -149,7 +158,10 @@ def main(argv=None) -> int:
         if sfw:
             res = (fsr.testsfw if args.loop == "sfw" else fsr.testsfw_video)(ds, batch=args.batch)
         else:
-            res = fsr.test(ds, batch=args.batch) if ucb else fsr.testFFHQ(ds, batch=args.batch)
+            if ucb:
+                res = fsr.test(ds, batch=args.batch)
+            else:
+                res = fsr.testFFHQ(ds, batch=args.batch, **({"paste_back": args.paste_back} if args.paste_back is not None else {}))
         torch.cuda.synchronize()
         if grouped:
             dist.barrier()
@@ -160,7 +172,8 @@ def main(argv=None) -> int:
             loop = {"sfw": "FSRNet.testsfw", "sfw_video": "FSRNet.testsfw_video"}.get(args.loop, "FSRNet.testFFHQ")
             print("\n" + json.dumps({"loop": ("FSRNetRGB.test" if args.model == "rgb" else "FSRNet.test") if ucb else loop, "items": n, "ranks": world, "process_group": (args.backend if grouped else None), "items_this_rank": len(res),
                                      "images_per_sec": round(n / dt, 2), "seconds": round(dt, 3), "batch": args.batch, "dtype": args.dtype,
-                                     "cpus_per_rank": ncpu, "post_and_png": "host" if args.host_post else "device", "means": means}))
+                                     "cpus_per_rank": ncpu, "post_and_png": "host" if args.host_post else "device", "means": means,
+                                     **({"paste_back": args.paste_back, "pasted": len(fsr.log.pasted)} if args.paste_back is not None else {})}))
     finally:
         ds.close()
         fsr.close()

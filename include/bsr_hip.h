@@ -180,6 +180,22 @@ int bsr_png_unfilter_tall(int device, void* d_blob, size_t blob_bytes, size_t it
  * record can make the kernel read or write outside the blob: BSR_ERR_ARG and nothing launched otherwise.  Added under ABI 8. */
 int bsr_crop_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, void* stream);
 
+/* The way back for in-the-wild photographs: the network's change, resized to the crop box, written into the photograph the crop was cut
+ * from, IN PLACE in the blob.  The reference has no counterpart; every byte equals blindshadowremoval_amd/wild_paste.py's host statement
+ * (paste_face), which also writes the arithmetic out.  n records of 48 bytes at items_off (8-byte aligned)
+ * { int64 photo_off; int32 h, w, box[4], preset_x, preset_y, row, pad } — photo_off: the RGB8 photograph [h][w][3] in the blob; box and
+ * presets as bsr_crop_faces' record (canvas coordinates, the canvas never materialised: only pixels of the photograph are produced,
+ * pixels outside the box are not touched); row: the item's row of im / con / face, 0 <= row < n.  im, con [n][S][S][3] and face
+ * [n][S][S][1] are float32 device tensors addressed through their pixel strides (floats between neighbouring pixels; rows and items
+ * dense in that stride — a channel slice of the packed NHWC row is fine).  mode 0 = residual: out = sat_u8(rint(photo + interp((clip(con)
+ * - im) face) 255)); mode 1 = replace: out = sat_u8(rint((interp(clip(con)) a + photo / 255 (1 - a)) 255)), a = interp(face).  S = 32, 64,
+ * 128 or 256.  Like bsr_crop_faces the entry reads the records back (it synchronises `stream`) and validates each against blob_bytes
+ * before launching — offset and h w 3, the box against its canvas and a side of at least 2, the row, the photograph clear of the
+ * record table — and the mode and strides: BSR_ERR_ARG with a message and nothing launched otherwise.  An ADDITION under ABI 8: no
+ * existing signature changes, bsr_abi_version() stays 8. */
+int bsr_paste_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, const float* im, int im_stride, const float* con,
+                    int con_stride, const float* face, int face_stride, int mode, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
