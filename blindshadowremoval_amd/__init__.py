@@ -2,11 +2,14 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "generator_variable_shapes", "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
     if name in ("Generator", "GeneratorTSM", "GeneratorRGB"):
         from . import model
         return getattr(model, name)
+    if name == "ShadowSynth":
+        from .shadow_synth_gpu import ShadowSynth
+        return ShadowSynth
     raise AttributeError(name)

@@ -36,6 +36,7 @@
 #include "wino_conv2.h"
 #include "wild_crop_kernels.h"
 #include "wild_paste_kernels.h"
+#include "shadow_synth_kernels.h"
 
 namespace {
 
@@ -1404,6 +1405,21 @@ int bsr_paste_faces(int device, void* d_blob, size_t blob_bytes, size_t items_of
                      mode);
   HIP_TRY(hipGetLastError());
   return BSR_OK;
+}
+
+size_t bsr_shadow_synth_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= 65535 ? (size_t)B * bsr::shadow_item_scratch_bytes(S) : 0; }
+
+int bsr_shadow_synth(int device, const float* mask, const float* gt, const float* img_dark, const float* face, const void* draws, size_t draws_bytes,
+                     int B, int S, float* img, float* mask_sv, float* mask_edge, int* status, float* aux, void* scratch, void* stream) {
+  if (B > 65535) return fail(BSR_ERR_ARG, "bsr_shadow_synth: B must be 1..65535");
+  if (B > 0 && draws_bytes != (size_t)B * bsr::kShadowWords * sizeof(uint32_t))
+    return fail(BSR_ERR_ARG, "bsr_shadow_synth: draws_bytes must be B records of 16384 bytes (shadow_synth.pack_draws)");
+  if (reinterpret_cast<uintptr_t>(draws) % 4 != 0) return fail(BSR_ERR_ARG, "bsr_shadow_synth: draws must be 4-byte aligned");
+  return run_post("bsr_shadow_synth", {mask, gt, img_dark, face, draws, img, mask_sv, mask_edge, status, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_shadow_synth(mask, gt, img_dark, face, static_cast<const uint32_t*>(draws), B, S, img, mask_sv, mask_edge, status, aux, scratch,
+                                     static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
 }
 
 size_t bsr_png_file_bytes(int H, int W) {

@@ -196,6 +196,23 @@ int bsr_crop_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off
 int bsr_paste_faces(int device, void* d_blob, size_t blob_bytes, size_t items_off, int n, int S, const float* im, int im_stride, const float* con,
                     int con_stride, const float* face, int face_stride, int mode, void* stream);
 
+/* The reference's training-shadow synthesis, process_mask (train_test_GSC.py:81-105) with the utils.py functions it calls, for B items
+ * on the device; blindshadowremoval_amd/shadow_synth.py is the host statement and writes the arithmetic and the two rules of our own
+ * out.  mask, face [B][S][S][1] and gt, img_dark [B][S][S][3] are dense float32 NHWC device tensors.  Every random draw of the
+ * reference is an argument: draws holds B records of 16384 bytes (shadow_synth.pack_draws: branch uniforms, blur sizes, persistences,
+ * red gains, the Perlin gradients as (cos, sin) pairs and the Gaussian taps — the device evaluates no sin, cos or exp), draws_bytes
+ * their total.  Outputs: img, mask_sv, mask_edge [B][S][S][3] float32 and status [B] int32 — 0 ok; 1 the thresholded Perlin map blurs
+ * to a maximum of 0 (the reference divides 0 by 0): img = clip(gt, 0, 1), mask_sv = mask_edge = 0; 2 a record's integers are out of
+ * range (disc size 1..11, blur size 1..2, Gaussian radii 0..min(82, S - 1)): outputs as for 1, nothing indexed with them.  aux is
+ * optional (may be NULL): [B][3][S][S] float32 = the Perlin map, the brightness mask, the mask that is composited.  The Perlin map,
+ * its threshold, the blend guidance, the brightness mask and the disc blurs are bit-identical to the host statement; the Gaussians
+ * differ from it by float32 summation order at most.  scratch: bsr_shadow_synth_scratch_bytes(B, S) bytes, 256-byte aligned; its
+ * reduction words are reset by the chain itself on every call.  S = 32, 64, 128 or 256, B = 1..65535 (0 from the size query
+ * otherwise).  Four launches on `stream`, no host synchronisation.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_shadow_synth_scratch_bytes(int B, int S);
+int bsr_shadow_synth(int device, const float* mask, const float* gt, const float* img_dark, const float* face, const void* draws, size_t draws_bytes,
+                     int B, int S, float* img, float* mask_sv, float* mask_edge, int* status, float* aux, void* scratch, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
