@@ -2,7 +2,7 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "generator_variable_shapes", "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "ShadowSynth":
         from .shadow_synth_gpu import ShadowSynth
         return ShadowSynth
+    if name == "TrainLosses":
+        from .train_losses_gpu import TrainLosses
+        return TrainLosses
     raise AttributeError(name)

@@ -21,7 +21,8 @@ EXPORTS = ("bsr_create", "bsr_forward", "bsr_forward_tsm", "bsr_workspace_bytes"
            "bsr_forward_rgb", "bsr_debug_attention_rgb", "bsr_ucb_post_rgb_scratch_bytes", "bsr_ucb_post_rgb",
            "bsr_sfw_score_scratch_bytes", "bsr_sfw_score", "bsr_ucb_post_tsm_scratch_bytes", "bsr_ucb_post_tsm", "bsr_debug_wino_conv", "bsr_debug_wino_filter", "bsr_debug_keys_compose",
            "bsr_debug_values_compose",      # + bsr_debug_attention_kv1, which tests/test_cabi.py's header scan (names without digits) cannot see
-           "bsr_png_unfilter_tall", "bsr_crop_faces", "bsr_paste_faces", "bsr_shadow_synth_scratch_bytes", "bsr_shadow_synth")
+           "bsr_png_unfilter_tall", "bsr_crop_faces", "bsr_paste_faces", "bsr_shadow_synth_scratch_bytes", "bsr_shadow_synth",
+           "bsr_train_losses_scratch_bytes", "bsr_train_losses")
 
 
 def load() -> ctypes.CDLL:
@@ -124,6 +125,14 @@ def load() -> ctypes.CDLL:
                            "there is no fallback") from None
     lib.bsr_shadow_synth.restype = c_i
     lib.bsr_shadow_synth_scratch_bytes.restype = c_sz
+    try:
+        lib.bsr_train_losses.argtypes = [c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_v]
+        lib.bsr_train_losses_scratch_bytes.argtypes = [c_i, c_i]
+    except AttributeError:                  # added under ABI 8, like bsr_prep_groups
+        raise RuntimeError("libbsr_hip.so has no bsr_train_losses: rebuild (`python -c 'import __graft_entry__ as g; g.build()'`); "
+                           "there is no fallback") from None
+    lib.bsr_train_losses.restype = c_i
+    lib.bsr_train_losses_scratch_bytes.restype = c_sz
     lib.bsr_check_range.argtypes = [c_v, c_v]
     lib.bsr_check_range.restype = c_i
     lib.bsr_png_file_bytes.argtypes = [c_i, c_i]

@@ -37,6 +37,7 @@
 #include "wild_crop_kernels.h"
 #include "wild_paste_kernels.h"
 #include "shadow_synth_kernels.h"
+#include "train_losses_kernels.h"
 
 namespace {
 
@@ -1417,6 +1418,19 @@ int bsr_shadow_synth(int device, const float* mask, const float* gt, const float
   if (reinterpret_cast<uintptr_t>(draws) % 4 != 0) return fail(BSR_ERR_ARG, "bsr_shadow_synth: draws must be 4-byte aligned");
   return run_post("bsr_shadow_synth", {mask, gt, img_dark, face, draws, img, mask_sv, mask_edge, status, scratch}, B, S, scratch, device, [&] {
     HIP_TRY(bsr::launch_shadow_synth(mask, gt, img_dark, face, static_cast<const uint32_t*>(draws), B, S, img, mask_sv, mask_edge, status, aux, scratch,
+                                     static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+size_t bsr_train_losses_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= 65535 ? (size_t)B * bsr::loss_item_scratch_bytes(S) : 0; }
+
+int bsr_train_losses(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb, int B, int S, double* sums,
+                     float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, void* stream) {
+  if (B > 65535) return fail(BSR_ERR_ARG, "bsr_train_losses: B must be 1..65535");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, "bsr_train_losses: sums must be 8-byte aligned");
+  return run_post("bsr_train_losses", {img, gt, mask_sv, gs, con_rgb, sums, losses3, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_train_losses(img, gt, mask_sv, gs, con_rgb, B, S, sums, losses3, mask_edge, bmaskgt, dif_grad, scratch,
                                      static_cast<hipStream_t>(stream)));
     return BSR_OK;
   });

@@ -213,6 +213,20 @@ size_t bsr_shadow_synth_scratch_bytes(int B, int S);
 int bsr_shadow_synth(int device, const float* mask, const float* gt, const float* img_dark, const float* face, const void* draws, size_t draws_bytes,
                      int B, int S, float* img, float* mask_sv, float* mask_edge, int* status, float* aux, void* scratch, void* stream);
 
+/* The reconstruction and gradient losses of the reference's train_step (train_test_GSC.py:253-258, 287-301, 307-328; utils.py:22-52,
+ * 116-125) for a batch on the device: recon_gs, recon_c and grad; blindshadowremoval_amd/train_losses.py is the host statement and
+ * writes the arithmetic out.  img, gt, mask_sv, con_rgb [B][S][S][3] and gs [B][S][S][1] are dense float32 NHWC device tensors.
+ * Outputs: sums [B][18] float64, the per-item partial sums in train_losses.SUM_NAMES' order; losses3 [3] float32 = recon_gs, recon_c,
+ * grad over the whole batch; and, each optional (may be NULL), the figures mask_edge [B][S][S], bmaskgt [B][S][S] and dif_grad
+ * [B][S][S][3] (the sum of the five dif_grad planes / 1.2).  The three planes are bit-identical to the host statement; the sums are
+ * float64 sums in a fixed order (no floating-point atomics: a call repeats its bits).  scratch:
+ * bsr_train_losses_scratch_bytes(B, S) bytes, 256-byte aligned; every word a launch reads is written earlier in the same call.
+ * S = 32, 64, 128 or 256, B = 1..65535 (0 from the size query otherwise).  Three launches on `stream`, no host synchronisation.  A bad
+ * argument gives BSR_ERR_ARG with a message and nothing launched.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_train_losses_scratch_bytes(int B, int S);
+int bsr_train_losses(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb, int B, int S,
+                     double* sums, float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
