@@ -688,7 +688,7 @@ class Dataset:
             if group:
                 yield from emit()
         finally:
-            if dp.ring is not None and getattr(dp, "last_copy", None) is not None:
+            if dp.ring is not None and dp.last_copy is not None:
                 dp.last_copy.synchronize()          # the copy engine may still be reading the last slots
             dp.ring = None
             self.close()

@@ -14,11 +14,128 @@ functions — and the host `build_row` on the UCB items, 1e-6)."""
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Any, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import dataset as D
+
+
+# What the loaders' workers send to the loop's thread, one record per item.  Plain NamedTuples at module level: the workers import this
+# module without torch and pickle the records; the field order is the order the tuples always had.
+class HostPart(NamedTuple):
+    """The host half of one row (host_part) or of one TSM group (host_part_group: eight tables), the bytes travelling with it."""
+    img: Any                          # uint8 [h,w,3], or pngio.RawScanlines (inflated, still filtered)
+    gt: Any                           # like img | None (an SFW group: the cmap)
+    box: np.ndarray                   # int32 [4]
+    tabs: list                        # 4 | 8 triangle tables, float64 [ntri, TRI_DOUBLES]
+    name: bytes
+    masks: Optional[tuple] = None     # pack_masks' (kind, data, S)
+    label: Optional[np.ndarray] = None          # the SFW label plane, uint8 [h,w]
+
+
+class CropGeometry(NamedTuple):
+    """wild_crop.crop_geometry's crop of a photograph."""
+    box: np.ndarray                   # int32 [4]
+    preset_x: int
+    preset_y: int
+
+
+class UncroppedPart(NamedTuple):
+    """The host half of one uncropped photograph (host_part_uncropped)."""
+    img: Any
+    gt: None                          # kept for the field order HostPart has
+    box: np.ndarray                   # of the row, in the crop's coordinates
+    tabs: list
+    name: bytes
+    crop: CropGeometry
+
+
+class RingMasks(NamedTuple):
+    """Where the seven masks of a ring item lie in its slot."""
+    kind: str                         # "bits" | "u8" | "raw8"
+    S: int
+    off: int
+    nbytes: int
+
+
+class RingPart(NamedTuple):
+    """An item whose bytes lie in a slot of the loaders' ring (host_part_ring)."""
+    tag: str                          # "ring", kept for the field order
+    slot: int
+    hw: Tuple[int, int]
+    has_gt: bool
+    img_offs: Tuple[int, ...]         # the image's offset in the slot, then the ground truth's
+    tab_offs: Tuple[int, ...]
+    ntri: Tuple[int, ...]
+    box: np.ndarray
+    name: bytes
+    masks: Optional[RingMasks]
+    used: int                         # bytes of the slot
+    rawc: Tuple[int, ...]             # per image: channels per filtered pixel, 0 = decoded RGB
+
+    def __reduce_ex__(self, protocol):
+        # one record per item crosses the workers' pipes and is loaded on the loop's own thread.  Its own pickle would go through a
+        # NamedTuple's Python-level __new__ (once more for the nested RingMasks) and numpy's for the four ints of the box, which alone
+        # is half the time of the whole record: the fields travel as one list of plain values instead.  The box is int32 [4] by
+        # construction (host_part_ring) and comes back as that; _ring_part fills the list it is given, always pickle's own fresh one
+        f = list(self)
+        f[_RING_BOX], f[_RING_MASKS] = np.asarray(self.box).tolist(), self.masks and tuple(self.masks)
+        return _ring_part, (f,)
+
+
+_RING_BOX, _RING_MASKS = RingPart._fields.index("box"), RingPart._fields.index("masks")
+
+
+def _ring_part(f: list) -> RingPart:
+    """A RingPart back from its pickle."""
+    f[_RING_BOX], f[_RING_MASKS] = np.array(f[_RING_BOX], np.int32), f[_RING_MASKS] and tuple.__new__(RingMasks, f[_RING_MASKS])
+    return tuple.__new__(RingPart, f)
+
+
+class UnfilterTable(NamedTuple):
+    """The unfilter records of a blob: their offset, their number, and per item with "raw8" masks (output offset, S)."""
+    off: int
+    n: int
+    mask_out: dict
+
+
+class BlobLayout(NamedTuple):
+    """_layout_ex's result."""
+    total: int
+    rows_off: int
+    grid_off: int
+    pieces: list                      # [(offset, array)]: what pack_into copies
+    head: int                         # bytes staged on the host; behind them the ring cells and the device-only areas
+    cells: list                       # [(part index, slot, cell offset)]
+    unf: UnfilterTable
+
+
+class UncroppedLayout(NamedTuple):
+    """_layout_uncropped's result."""
+    total: int
+    head: int
+    rows_off: int
+    grid_off: int
+    crop_off: int
+    tall_off: int
+    n_tall: int
+    pieces: list
+    paste_off: Optional[int]          # keep_photo: the batch's PASTE_DTYPE records
+    photo_offs: Optional[List[int]]   # keep_photo: per item its reconstructed photograph
+
+
+class _Cursor:
+    """Hands out consecutive 8-byte aligned areas of a blob."""
+
+    def __init__(self):
+        self.off = 0
+
+    def take(self, nbytes: int) -> int:
+        o = self.off
+        self.off += (int(nbytes) + 7) & ~7
+        return o
+
 
 TRI_DOUBLES = 18          # csrc/prep_kernels.h kPrepTriDoubles
 MAX_TRI = 256
@@ -220,63 +337,61 @@ def unpack_masks(packed: Sequence[tuple], device):
     return torch.from_numpy(np.stack(full, axis=0)).to(device, non_blocking=True)
 
 
-def host_part(job, raw: bool = False):
-    """(lm_path, gt_path, size[, mask paths]) -> the host half of one row: (img u8, gt u8 | None, box, [4 triangle tables], name[, packed masks]).
-    raw = True (the ring path, round 6): img / gt may be pngio.RawScanlines — inflated, still filtered; the device reconstructs them."""
-    masks = None
-    if len(job) > 3:
-        masks = pack_masks(job[3], raw=raw)
-        job = job[:3]
-    lm_path, gt_path, size = job
+def _read_item(job, raw: bool):
+    """The head host_part and host_part_group share: (lm_path, gt_path, size[, mask paths]) -> (lm_path, img, gt | None, name, packed
+    masks | None), the mask paths split off the job, image and ground truth read by the raw or the decoding reader and of one size; the
+    name is the ground truth's path or, without one, the image's."""
+    masks = pack_masks(job[3], raw=raw) if len(job) > 3 else None
+    lm_path, gt_path, _ = job[:3]
     img_path = os.path.splitext(lm_path)[0] + ".png"
     read = _imread_raw if raw else _imread_u8
     img = read(img_path)
     gt = read(gt_path) if gt_path else None
     if gt is not None and gt.shape != img.shape:
         raise ValueError("ground truth %s and image %s differ in size" % (gt_path, img_path))
+    return lm_path, img, gt, (gt_path or img_path).encode(), masks
+
+
+def host_part(job, raw: bool = False) -> HostPart:
+    """(lm_path, gt_path, size[, mask paths]) -> the host half of one row: HostPart(img u8, gt u8 | None, box, [4 triangle tables], name,
+    packed masks | None).  raw = True (the ring path, round 6): img / gt may be pngio.RawScanlines — inflated, still filtered; the device
+    reconstructs them."""
+    lm_path, img, gt, name, masks = _read_item(job, raw)
     box, lm = crop_box(np.load(lm_path))
-    out = (img, gt, np.asarray(box, np.int32), meshes(lm), (gt_path or img_path).encode())
-    return out + (masks,) if masks is not None else out
+    return HostPart(img, gt, np.asarray(box, np.int32), meshes(lm), name, masks)
 
 
-def host_part_group(job, raw: bool = False):
+def host_part_group(job, raw: bool = False) -> HostPart:
     """The host half of one TSM group (an item and its mirror image, csrc/prep_group_kernels.h), in host_part's form with EIGHT triangle
     tables — meshes(lm) + meshes(lm_m) of face_crop_and_resize(with_mirror=True) — so that the ring and the blob code carry it like a row:
-    (lm_path, gt_path, size[, mask paths]) -> (img, gt, box, [8 tables], name[, packed masks]): dataset.build_ucb_tsm_pair's group;
-    (label_path, "<sfw>", size)            -> (img, cmap, box, [8 tables], name, None, label u8 [h,w]): dataset.build_sfw_pair's group
+    (lm_path, gt_path, size[, mask paths]) -> HostPart(img, gt, box, [8 tables], name, packed masks | None): dataset.build_ucb_tsm_pair's group;
+    (label_path, "<sfw>", size)            -> HostPart(img, cmap, box, [8 tables], name, None, label u8 [h,w]): dataset.build_sfw_pair's group
     (decoded in the worker: the label is a palette or grey file whose levels travel as they are).
     The reg_in mesh of the canonical landmarks is the one cached triangulation (_REF_TRI) for both rows and every item."""
-    masks = None
-    if len(job) > 3:
-        masks = pack_masks(job[3], raw=raw)
-        job = job[:3]
-    lm_path, gt_path, size = job
-    if gt_path == "<sfw>":
+    if job[1] == "<sfw>":
         from .pngio import read_grey_u8
+        lm_path = job[0]
         stem = lm_path.rsplit(".", 1)[0]
         frame = stem[:-6]                                                 # strips "_label"
         img, cmap, label = _imread_u8(frame + ".png"), _imread_u8(stem + "_cmap.png"), np.ascontiguousarray(read_grey_u8(lm_path))
         if cmap.shape != img.shape or label.shape != img.shape[:2]:
             raise ValueError("the planes of SFW frame %s differ in size" % frame)
         box, lm, lm_m = crop_box_pair(np.load(frame + ".npy"), img.shape[1])
-        return (img, cmap, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), (frame + ".png").encode(), None, label)
-    img_path = os.path.splitext(lm_path)[0] + ".png"
-    read = _imread_raw if raw else _imread_u8
-    img, gt = read(img_path), read(gt_path)
-    if gt.shape != img.shape:
-        raise ValueError("ground truth %s and image %s differ in size" % (gt_path, img_path))
+        return HostPart(img, cmap, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), (frame + ".png").encode(), None, label)
+    lm_path, img, gt, name, masks = _read_item(job, raw)
+    if gt is None:
+        raise ValueError("a TSM group needs the ground truth of %s" % lm_path)
     box, lm, lm_m = crop_box_pair(np.load(lm_path), img.shape[1])
-    out = (img, gt, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), gt_path.encode())
-    return out + (masks,) if masks is not None else out
+    return HostPart(img, gt, np.asarray(box, np.int32), meshes(lm) + meshes(lm_m), name, masks)
 
 
-def host_part_uncropped(job, raw: bool = True):
-    """The host half of one UNCROPPED photograph (dataset.Dataset(uncropped=True, device_prep=gpu)): (png_path, size) -> (img, None, box of
-    the row, [4 triangle tables], name, (crop box, preset_x, preset_y)) or None where dataprocess.py skips the photograph.  Everything
-    but `img` comes from the landmarks alone: wild_crop.crop_geometry (the script's box, presets and landmarks in the crop's
-    coordinates), then — as the FFHQ loader does with the folder the script wrote — crop_box and meshes of those landmarks.  img: the
-    file's inflated, still filtered scanlines (pngio.RawScanlines: the device reconstructs and crops them) or, for a file that is no
-    plain 8-bit PNG, the decoded photograph."""
+def host_part_uncropped(job, raw: bool = True) -> Optional[UncroppedPart]:
+    """The host half of one UNCROPPED photograph (dataset.Dataset(uncropped=True, device_prep=gpu)): (png_path, size) -> UncroppedPart(img,
+    None, box of the row, [4 triangle tables], name, CropGeometry(crop box, preset_x, preset_y)) or None where dataprocess.py skips the
+    photograph.  Everything but `img` comes from the landmarks alone: wild_crop.crop_geometry (the script's box, presets and landmarks in
+    the crop's coordinates), then — as the FFHQ loader does with the folder the script wrote — crop_box and meshes of those landmarks.
+    img: the file's inflated, still filtered scanlines (pngio.RawScanlines: the device reconstructs and crops them) or, for a file that
+    is no plain 8-bit PNG, the decoded photograph."""
     from . import wild_crop
     img_path, size = job
     img = (_imread_raw if raw else _imread_u8)(img_path)
@@ -287,7 +402,8 @@ def host_part_uncropped(job, raw: bool = True):
         return None
     cbox, preset_x, preset_y, lm256 = geo
     box, lm = crop_box(lm256)
-    return (img, None, np.asarray(box, np.int32), meshes(lm), img_path.encode(), (np.asarray(cbox, np.int32), preset_x, preset_y))
+    return UncroppedPart(img, None, np.asarray(box, np.int32), meshes(lm), img_path.encode(),
+                         CropGeometry(np.asarray(cbox, np.int32), preset_x, preset_y))
 
 
 class WildPhoto:
@@ -308,28 +424,24 @@ class WildPhoto:
         return self.blob[self.off:self.off + self.h * self.w * 3].view(self.h, self.w, 3)
 
 
-def _layout_uncropped(parts, size: int, keep_photo: bool = False):
+def _layout_uncropped(parts, size: int, keep_photo: bool = False) -> UncroppedLayout:
     """The blob of a batch of host_part_uncropped results: [row records | grid | crop records | tall records | per item: scanlines with
     their slack (or the decoded photograph) and the four tables] — the `head`, staged by the caller — then, device only, the
-    reconstructed photographs and the S x S crops the row records point to.  -> (total, head, rows_off, grid_off, crop_off, tall_off,
-    number of tall records, pieces).  keep_photo: every row of every photograph is reconstructed (rows_needed = 0) and the device part
-    ends with room for the batch's paste records; the tuple gains (paste_off, [photograph offset per item])."""
+    reconstructed photographs and the S x S crops the row records point to.  keep_photo: every row of every photograph is reconstructed
+    (rows_needed = 0) and the device part ends with room for the batch's paste records (paste_off; photo_offs: the photograph of each
+    item)."""
     B = len(parts)
     rows, crops = np.zeros(B, ROW_DTYPE), np.zeros(B, CROP_DTYPE)
-    n_tall = sum(1 for p in parts if hasattr(p[0], "raw"))
+    n_tall = sum(1 for p in parts if hasattr(p.img, "raw"))
     talls = np.zeros(n_tall, UNFILTER_TALL_DTYPE)
-    pieces, off = [], 0
-
-    def take(nbytes: int) -> int:
-        nonlocal off
-        o = off
-        off += (int(nbytes) + 7) & ~7
-        return o
+    pieces, cur = [], _Cursor()
+    take = cur.take
     rows_off, grid_off, crop_off, tall_off = take(rows.nbytes), take(size * 8), take(crops.nbytes), take(max(n_tall, 1) * UNFILTER_TALL_DTYPE.itemsize)
     pieces.append((grid_off, np.linspace(0, 1, size).astype("<f8")))
     k = 0
     for i, part in enumerate(parts):
-        img, _, box, tabs, _, (cbox, preset_x, preset_y) = part[:6]
+        img, box, tabs = part.img, part.box, part.tabs
+        cbox, preset_x, preset_y = part.crop
         if len(tabs) != 4:
             raise ValueError("prep blob: item %d carries %d triangle tables, the record takes 4" % (i, len(tabs)))
         c = crops[i]
@@ -356,19 +468,18 @@ def _layout_uncropped(parts, size: int, keep_photo: bool = False):
             r["tri_off"][m] = take(tab.nbytes)
             r["ntri"][m] = tab.shape[0]
             pieces.append((int(r["tri_off"][m]), tab))
-    head = off
+    head = cur.off
     k = 0
     for i, part in enumerate(parts):
-        if hasattr(part[0], "raw"):
-            talls[k]["out_off"] = crops[i]["src_off"] = take(part[0].h * part[0].w * 3 + UNFILTER_SLACK)
+        if hasattr(part.img, "raw"):
+            talls[k]["out_off"] = crops[i]["src_off"] = take(part.img.h * part.img.w * 3 + UNFILTER_SLACK)
             k += 1
     for i in range(B):
         crops[i]["out_off"] = rows[i]["img_off"] = rows[i]["gt_off"] = take(size * size * 3)
     pieces += [(rows_off, rows), (crop_off, crops)] + ([(tall_off, talls)] if n_tall else [])
-    if keep_photo:
-        paste_off = take(B * PASTE_DTYPE.itemsize)
-        return off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces, paste_off, [int(c["src_off"]) for c in crops]
-    return off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces
+    paste_off = take(B * PASTE_DTYPE.itemsize) if keep_photo else None
+    photo_offs = [int(c["src_off"]) for c in crops] if keep_photo else None
+    return UncroppedLayout(cur.off, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces, paste_off, photo_offs)
 
 
 RING_CAP = 1 << 20        # bytes of one slot of the loaders' shared-memory ring (a 256x256 UCB item with ground truth, tables and masks: ~0.55 MB)
@@ -376,23 +487,22 @@ _RING_VIEWS: dict = {}
 
 
 def _is_ring(part) -> bool:
-    return isinstance(part[0], str)
+    return isinstance(part, RingPart)
 
 
 def host_part_ring(job, ring, group: bool = False):
     """`host_part(job)` (group: `host_part_group(job)`, eight tables instead of four) written INTO slot `slot` of the shared-memory ring the parent page-locked (SlotRing) instead of pickled through
-    the worker's pipe: -> ("ring", slot, (h, w), has_gt, image offsets, table offsets, table lengths, box, name, mask record | None,
-    bytes used) — a few hundred bytes.  The loop's own thread then neither reads, unpickles nor repacks the ~0.5 MB of an item (0.1 ms
+    the worker's pipe: -> RingPart("ring", slot, (h, w), has_gt, image offsets, table offsets, table lengths, box, name, RingMasks | None,
+    bytes used, rawc) — a few hundred bytes.  The loop's own thread then neither reads, unpickles nor repacks the ~0.5 MB of an item (0.1 ms
     per item of the one thread every batch goes through): the slot goes to the device as it lies, by one copy per batch.  An item that
-    does not fit a slot comes back the old way.  Round 6: images that are plain 8-bit PNG files lie in the slot as their inflated,
-    still FILTERED scanlines (the last tuple element: channels per image, 0 = decoded RGB) and are reconstructed on the device
+    does not fit a slot comes back the old way, as a HostPart.  Round 6: images that are plain 8-bit PNG files lie in the slot as their
+    inflated, still FILTERED scanlines (rawc: channels per image, 0 = decoded RGB) and are reconstructed on the device
     (bsr_png_unfilter) when the job's ring tuple says so (its 4th element: dataset.Dataset.device_unfilter)."""
     path, slot, cap = ring[:3]
     use_raw = bool(ring[3]) if len(ring) > 3 else False       # dataset.Dataset.device_unfilter decides
     part = (host_part_group if group else host_part)(job, raw=use_raw)
-    img, gt, box, tabs, name = part[:5]
+    img, gt, tabs, masks = part.img, part.gt, part.tabs, part.masks
     nt = len(tabs)
-    masks = part[5] if len(part) > 5 else None
     # the device kernel takes images of at most UNFILTER_MAX_ROWS rows whose scanlines hold at least one dword; anything else is decoded
     # here.  "raw8" masks stay as they are: _masks_raw only made them for S x S grey files the kernel takes, whatever the images are
     fits = lambda a: not hasattr(a, "raw") or (a.h <= UNFILTER_MAX_ROWS and a.w * a.c >= 4)
@@ -406,8 +516,8 @@ def host_part_ring(job, ring, group: bool = False):
         off = (off + a.nbytes + 7) & ~7
     if off > cap:                                  # through the pipe after all: decoded here
         dec = lambda a: a.decode() if hasattr(a, "raw") else a
-        rest = tuple(part[2:5]) + ((masks_from_raw(masks) if masks[0] == "raw8" else masks,) if masks is not None else ())
-        return (dec(img), dec(gt) if gt is not None else None) + rest
+        return part._replace(img=dec(img), gt=dec(gt) if gt is not None else None,
+                             masks=masks_from_raw(masks) if masks is not None and masks[0] == "raw8" else masks)
     view = _RING_VIEWS.get(path)
     if view is None:
         view = _RING_VIEWS[path] = np.memmap(path, np.uint8, "r+")
@@ -416,9 +526,9 @@ def host_part_ring(job, ring, group: bool = False):
         raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         view[base + o:base + o + raw.size] = raw
     k = 2 if gt is not None else 1
-    mrec = None if masks is None else (masks[0], int(masks[2]), offs[k + nt], int(masks[1].nbytes))
-    return ("ring", int(slot), (int(img.shape[0]), int(img.shape[1])), gt is not None, tuple(offs[:k]), tuple(offs[k:k + nt]),
-            tuple(int(t.shape[0]) for t in tabs), np.asarray(box, np.int32), name, mrec, off, rawc)
+    mrec = None if masks is None else RingMasks(masks[0], int(masks[2]), offs[k + nt], int(masks[1].nbytes))
+    return RingPart("ring", int(slot), (int(img.shape[0]), int(img.shape[1])), gt is not None, tuple(offs[:k]), tuple(offs[k:k + nt]),
+                    tuple(int(t.shape[0]) for t in tabs), np.asarray(part.box, np.int32), part.name, mrec, off, rawc)
 
 
 class SlotRing:
@@ -478,15 +588,15 @@ class SlotRing:
 
 def _layout(parts, size: int):
     """The blob of a batch of `host_part` results that all came through the pipe: see _layout_ex."""
-    total, rows_off, grid_off, pieces, _, cells, _ = _layout_ex(parts, size, RING_CAP)
-    if cells:
+    lay = _layout_ex(parts, size, RING_CAP)
+    if lay.cells:
         raise ValueError("_layout: ring items need DevicePrep.rows_ex")
-    return total, rows_off, grid_off, pieces
+    return lay.total, lay.rows_off, lay.grid_off, lay.pieces
 
 
-def _layout_ex(parts, size: int, cap: int, group: bool = False):
-    """group = True: the parts are host_part_group's and the records GROUP_DTYPE (eight tables, the label plane).  Offsets of every section of the blob (all 8-byte aligned): -> (total bytes, rows_off, grid_off, [(offset, array)], head bytes,
-    ring cells, (unfilter table offset, records)).  Items that came through the pipe are packed behind the records (the `head`, staged
+def _layout_ex(parts, size: int, cap: int, group: bool = False) -> BlobLayout:
+    """group = True: the parts are host_part_group's and the records GROUP_DTYPE (eight tables, the label plane).  Offsets of every section
+    of the blob (all 8-byte aligned).  Items that came through the pipe are packed behind the records (the `head`, staged
     by the caller); every ring item gets one `cap`-byte cell behind the head, in batch order — cells = [(part index, slot, cell
     offset)] — which the caller fills with the slot's bytes.  Ring images that lie in their slot as filtered scanlines (round 6) get
     a record in the unfilter table (in the head) and an output area behind the cells, where the row records then point."""
@@ -494,20 +604,15 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
     dtype, nt = (GROUP_DTYPE, 8) if group else (ROW_DTYPE, 4)
     rows = np.zeros(B, dtype)
     pieces = []
-    off = 0
-
-    def take(nbytes: int) -> int:
-        nonlocal off
-        o = off
-        off += (nbytes + 7) & ~7
-        return o
+    cur = _Cursor()
+    take = cur.take
     rows_off = take(B * dtype.itemsize)
     grid_off = take(size * 8)
     pieces.append((grid_off, np.linspace(0, 1, size).astype("<f8")))
     for i, part in enumerate(parts):
         if _is_ring(part):
             continue
-        img, gt, box, tabs = part[:4]
+        img, gt, box, tabs = part.img, part.gt, part.box, part.tabs
         r = rows[i]
         r["h"], r["w"] = img.shape[0], img.shape[1]
         r["img_off"] = take(img.nbytes)
@@ -521,9 +626,9 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
         if len(tabs) != nt:
             raise ValueError("prep blob: item %d carries %d triangle tables, the record takes %d" % (i, len(tabs), nt))
         if group:
-            if len(part) > 6:                  # the SFW label plane
-                r["aux_off"] = take(part[6].nbytes)
-                pieces.append((int(r["aux_off"]), part[6]))
+            if part.label is not None:         # the SFW label plane
+                r["aux_off"] = take(part.label.nbytes)
+                pieces.append((int(r["aux_off"]), part.label))
             else:
                 r["aux_off"] = r["img_off"]
         for m, t in enumerate(tabs):
@@ -532,28 +637,29 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
             pieces.append((int(r["tri_off"][m]), t))
     pieces.append((rows_off, rows))
     ring_idx = [i for i, part in enumerate(parts) if _is_ring(part)]
-    n_unf = sum(sum(1 for c in (parts[i][11] if len(parts[i]) > 11 else ()) if c) + (7 if parts[i][9] is not None and parts[i][9][0] == "raw8" else 0)
-                for i in ring_idx)
+    rp = [parts[i] for i in ring_idx]
+    raw_masks = [j for j, p in enumerate(rp) if p.masks is not None and p.masks.kind == "raw8"]
+    n_unf = sum(sum(1 for c in p.rawc if c) for p in rp) + 7 * len(raw_masks)
     unf = np.zeros(n_unf, UNFILTER_DTYPE)
     unf_off = take(max(n_unf, 1) * UNFILTER_DTYPE.itemsize)
     if n_unf:
         pieces.append((unf_off, unf))
-    head, cells, mask_out = off, [], {}
+    head = off = cur.off
+    cells, mask_out = [], {}
     if ring_idx:
         # the records of the ring items in whole columns (per-field assignments on a structured array cost ~15 us each: 0.3 ms per batch
         # of the loop's own thread when done item by item)
-        rp = [parts[i] for i in ring_idx]
         n = len(rp)
         bases = off + cap * np.arange(n, dtype=np.int64)
         off += cap * n
-        hw = np.array([p[2] for p in rp], np.int64).reshape(n, 2)
-        has_gt = np.array([p[3] for p in rp], bool)
-        io0 = np.array([p[4][0] for p in rp], np.int64)
-        io1 = np.where(has_gt, np.array([p[4][-1] for p in rp], np.int64), io0)
-        toff = np.array([p[5] for p in rp], np.int64).reshape(n, nt)
-        ntri = np.array([p[6] for p in rp], np.int64).reshape(n, nt)
-        used = np.array([p[10] for p in rp], np.int64)
-        rawc = np.array([(tuple(p[11]) + (0, 0))[:2] if len(p) > 11 else (0, 0) for p in rp], np.int64).reshape(n, 2)
+        hw = np.array([p.hw for p in rp], np.int64).reshape(n, 2)
+        has_gt = np.array([p.has_gt for p in rp], bool)
+        io0 = np.array([p.img_offs[0] for p in rp], np.int64)
+        io1 = np.where(has_gt, np.array([p.img_offs[-1] for p in rp], np.int64), io0)
+        toff = np.array([p.tab_offs for p in rp], np.int64).reshape(n, nt)
+        ntri = np.array([p.ntri for p in rp], np.int64).reshape(n, nt)
+        used = np.array([p.used for p in rp], np.int64)
+        rawc = np.array([(tuple(p.rawc) + (0, 0))[:2] for p in rp], np.int64).reshape(n, 2)
         rawc[:, 1] = np.where(has_gt, rawc[:, 1], rawc[:, 0])
         if ((rawc != 0) & (rawc != 1) & (rawc != 3) & (rawc != 4)).any():
             raise ValueError("prep blob: a ring item names %s channels per filtered pixel" % sorted(set(rawc.reshape(-1).tolist())))
@@ -583,12 +689,11 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
             gt_at[jj[ww == 1]] = outs[ww == 1]
             gt_at = np.where(has_gt, gt_at, img_at)
             # the seven masks of an item that lie in its slot as filtered scanlines ("raw8"): seven records, grey output, one area
-            mj = [j for j in range(n) if rp[j][9] is not None and rp[j][9][0] == "raw8"]
-            if mj:
-                mj = np.array(mj)
-                mS = np.array([rp[j][9][1] for j in mj], np.int64)
-                moff = np.array([rp[j][9][2] for j in mj], np.int64)
-                mlen = np.array([rp[j][9][3] for j in mj], np.int64)
+            if raw_masks:
+                mj = np.array(raw_masks)
+                mS = np.array([rp[j].masks.S for j in mj], np.int64)
+                moff = np.array([rp[j].masks.off for j in mj], np.int64)
+                mlen = np.array([rp[j].masks.nbytes for j in mj], np.int64)
                 if ((mS < 4) | (mS > UNFILTER_MAX_ROWS) | (mlen != 7 * mS * (1 + mS)) | (moff < 0) | (moff + mlen > cap)).any():
                     raise ValueError("prep blob: a ring item's filtered masks do not fit its slot")
                 area = (7 * mS * mS + 7) & ~7
@@ -605,10 +710,10 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
         rows["gt_off"][sel] = gt_at
         if group:
             rows["aux_off"][sel] = img_at      # ring groups are UCB items: six planes, the label plane is not read
-        rows["box"][sel] = np.stack([np.asarray(p[7], np.int32).reshape(4) for p in rp])
+        rows["box"][sel] = np.stack([np.asarray(p.box, np.int32).reshape(4) for p in rp])
         rows["tri_off"][sel] = bases[:, None] + toff
         rows["ntri"][sel] = ntri
-        cells = [(i, int(p[1]), int(bs)) for i, p, bs in zip(ring_idx, rp, bases)]
+        cells = [(i, int(p.slot), int(bs)) for i, p, bs in zip(ring_idx, rp, bases)]
     # the kernel dereferences these offsets on the device without bounds information: every record is checked against the blob here
     h64, w64 = rows["h"].astype(np.int64), rows["w"].astype(np.int64)
     ends = np.maximum(np.maximum(rows["img_off"], rows["gt_off"]) + h64 * w64 * 3, (rows["tri_off"] + rows["ntri"].astype(np.int64) * (TRI_DOUBLES * 8)).max(axis=1))
@@ -618,7 +723,7 @@ def _layout_ex(parts, size: int, cap: int, group: bool = False):
     bad = (lows < 0) | (ends > off) | (rows["ntri"].max(axis=1) > MAX_TRI) | (rows["ntri"].min(axis=1) < 0) | (h64 < 0) | (w64 < 0)
     if bad.any():
         raise ValueError("prep blob: row %d points outside the %d-byte blob" % (int(np.argmax(bad)), off))
-    return off, rows_off, grid_off, pieces, head, cells, (unf_off, n_unf, mask_out)
+    return BlobLayout(off, rows_off, grid_off, pieces, head, cells, UnfilterTable(unf_off, n_unf, mask_out))
 
 
 def pack_into(buf: np.ndarray, pieces) -> None:
@@ -638,12 +743,12 @@ def pack_batch(parts, size: int):
 
 def pack_group_batch(parts, size: int):
     """One blob for bsr_prep_groups: [group records | grid | images | triangle tables], every section 8-byte aligned."""
-    total, rows_off, grid_off, pieces, _, cells, _ = _layout_ex(parts, size, RING_CAP, group=True)
-    if cells:
+    lay = _layout_ex(parts, size, RING_CAP, group=True)
+    if lay.cells:
         raise ValueError("pack_group_batch: ring items need DevicePrep.rows_ex")
-    buf = np.zeros(total, np.uint8)
-    pack_into(buf, pieces)
-    return buf.tobytes(), rows_off, grid_off
+    buf = np.zeros(lay.total, np.uint8)
+    pack_into(buf, lay.pieces)
+    return buf.tobytes(), lay.rows_off, lay.grid_off
 
 
 class DevicePrep:
@@ -660,13 +765,36 @@ class DevicePrep:
             raise RuntimeError("DevicePrep needs a ROCm GPU: the host path is blindshadowremoval_amd.dataset.build_row")
         self._torch, self._lib, self._check = torch, _lib.load(), _lib.check
         self.device, self.size = int(device), int(size)
-        self._stage, self._copied = [None, None], [None, None]
+        self._stage, self._copied, self._turn = [None, None], [None, None], 0
+        self.ring = None              # the loaders' SlotRing (set by the Dataset that owns it): where the bytes of RingPart records lie
+        self._h2d = None              # the side stream of the uploads, made by the first batch
+        self.last_copy = None         # the event behind the last batch's host-to-device copies
 
     def warm(self, nbytes: int = 8 << 20) -> None:
         """Page-lock the two staging buffers now (~60 ms each) instead of inside the first two batches of a timed loop."""
         for k in (0, 1):
             if self._stage[k] is None or self._stage[k].numel() < nbytes:
                 self._stage[k] = self._torch.empty(nbytes, dtype=self._torch.uint8).pin_memory()
+
+    def _staged(self, head: int, pieces):
+        """The host side of a batch's upload: `pieces` packed into the first `head` bytes of a pinned buffer, which is returned.  Two
+        buffers are used alternately (self._turn): the sections are copied straight into page-locked memory and go to the device in one
+        asynchronous copy; a buffer is reused only after the copy that read it (self._copied) has finished."""
+        k = self._turn = (self._turn + 1) & 1
+        stage = self._stage[k]
+        if stage is None or stage.numel() < head:
+            stage = self._stage[k] = self._torch.empty(max(head, 1 << 22) * 5 // 4, dtype=self._torch.uint8).pin_memory()
+        if self._copied[k] is not None:
+            self._copied[k].synchronize()
+        pack_into(stage.numpy(), pieces)
+        return stage
+
+    def _side_stream(self):
+        """The uploads' OWN stream: the copy engine moves batch k + 1 while the compute stream is still in batch k's forward (on one
+        stream the ~16 MB of a batch sat between two forwards: ~0.4 ms of a 4 ms step)."""
+        if self._h2d is None:
+            self._h2d = self._torch.cuda.Stream(device=self.device)
+        return self._h2d
 
     def rows(self, parts):
         out, boxes, _, _ = self.rows_ex(parts)
@@ -677,9 +805,10 @@ class DevicePrep:
         `parts`: `host_part` results (pickled through a worker's pipe) and / or `host_part_ring` records (the bytes lie in self.ring)."""
         torch = self._torch
         B, S = len(parts), self.size
-        ring = getattr(self, "ring", None)
+        ring = self.ring
         cap = ring.cap if ring is not None else RING_CAP
-        total, rows_off, grid_off, pieces, head, cells, (unf_off, n_unf, mask_out) = _layout_ex(parts, S, cap, group=self.planes is not None)
+        lay = _layout_ex(parts, S, cap, group=self.planes is not None)
+        total, rows_off, grid_off, head, cells, unf = lay.total, lay.rows_off, lay.grid_off, lay.head, lay.cells, lay.unf
 
         def launch(stream):
             """the preparation kernels on `stream`: -> (out, return code)"""
@@ -697,21 +826,10 @@ class DevicePrep:
             raise ValueError("DevicePrep.rows_ex: SFW groups (planes=7) do not travel through the ring")
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
-            # two pinned staging buffers used alternately: the sections are copied straight into page-locked memory and go to the
-            # device in one asynchronous copy; a buffer is reused only after the copy that read it has finished
-            k = self._turn = (getattr(self, "_turn", 0) + 1) & 1
-            stage = self._stage[k]
-            if stage is None or stage.numel() < head:
-                stage = self._stage[k] = torch.empty(max(head, 1 << 22) * 5 // 4, dtype=torch.uint8).pin_memory()
-            if self._copied[k] is not None:
-                self._copied[k].synchronize()
-            pack_into(stage.numpy(), pieces)
-            # the host-to-device copies run on their OWN stream: the copy engine moves batch k + 1 while the compute stream is still in
-            # batch k's forward (on one stream the ~16 MB of a batch sat between two forwards: ~0.4 ms of a 4 ms step)
+            stage = self._staged(head, lay.pieces)
             main = torch.cuda.current_stream()
-            if getattr(self, "_h2d", None) is None:
-                self._h2d = torch.cuda.Stream(device=self.device)
-            with torch.cuda.stream(self._h2d):
+            h2d = self._side_stream()
+            with torch.cuda.stream(h2d):
                 d_blob = torch.empty(total, dtype=torch.uint8, device=dev)
                 d_blob[:head].copy_(stage[:head], non_blocking=True)
                 # ring items: consecutive slots of consecutive cells go in ONE copy (the usual case: the whole batch), whole slots as they lie
@@ -723,15 +841,15 @@ class DevicePrep:
                     src = ring.tensor[cells[c][1] * cap:(cells[e - 1][1] + 1) * cap]
                     d_blob[cells[c][2]:cells[c][2] + (e - c) * cap].copy_(src, non_blocking=True)
                     c = e
-                ev = self._copied[k] = self.last_copy = torch.cuda.Event()
+                ev = self._copied[self._turn] = self.last_copy = torch.cuda.Event()
                 ev.record()
                 # the preparation kernel follows its input on the same side stream (BSR_PREP_SIDE=0: on the compute stream): a short
                 # bandwidth-bound kernel that shares the chip with the previous batch's forward instead of standing in line behind it
                 side = os.environ.get("BSR_PREP_SIDE", "1") != "0"
                 if side:
-                    if n_unf:                      # the filtered images of the ring items become RGB8 where their row records point
-                        self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf_off, n_unf, self._h2d.cuda_stream), "bsr_png_unfilter")
-                    out, rc = launch(self._h2d.cuda_stream)
+                    if unf.n:                      # the filtered images of the ring items become RGB8 where their row records point
+                        self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf.off, unf.n, h2d.cuda_stream), "bsr_png_unfilter")
+                    out, rc = launch(h2d.cuda_stream)
                     done = torch.cuda.Event()
                     done.record()
             if side:
@@ -741,23 +859,22 @@ class DevicePrep:
                 main.wait_event(ev)
             d_blob.record_stream(main)             # allocated on the side stream, read by the compute stream (the mask views; the kernel when it runs there)
             if not side:
-                if n_unf:
-                    self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf_off, n_unf, main.cuda_stream), "bsr_png_unfilter")
+                if unf.n:
+                    self._check(self._lib.bsr_png_unfilter(self.device, d_blob.data_ptr(), total, unf.off, unf.n, main.cuda_stream), "bsr_png_unfilter")
                 out, rc = launch(main.cuda_stream)
         self._check(rc, "bsr_prep_rows" if self.planes is None else "bsr_prep_groups")
-        boxes = np.stack([np.asarray(p[7] if _is_ring(p) else p[2], np.float32) for p in parts], axis=0)
-        names = [p[8] if _is_ring(p) else p[4] for p in parts]
-        masks = [(p[5] if len(p) > 5 else None) if not _is_ring(p) else None for p in parts]
+        boxes = np.stack([np.asarray(p.box, np.float32) for p in parts], axis=0)
+        names = [p.name for p in parts]
+        masks = [None if _is_ring(p) else p.masks for p in parts]
         for i, _, base in cells:
-            m = parts[i][9]
+            m = parts[i].masks
             if m is not None:
-                kind, ms, moff, nbytes = m
-                if kind == "raw8":                 # reconstructed by bsr_png_unfilter into their own area: grey levels [7,S,S]
-                    o = mask_out[i][0]
-                    masks[i] = ("dev_u8", d_blob[o:o + 7 * ms * ms].view(7, ms, ms), ms)
+                if m.kind == "raw8":               # reconstructed by bsr_png_unfilter into their own area: grey levels [7,S,S]
+                    o = unf.mask_out[i][0]
+                    masks[i] = ("dev_u8", d_blob[o:o + 7 * m.S * m.S].view(7, m.S, m.S), m.S)
                     continue
-                v = d_blob[base + moff:base + moff + nbytes]
-                masks[i] = ("dev_" + kind, v.view(7, -1) if kind == "bits" else v.view(7, ms, ms), ms)
+                v = d_blob[base + m.off:base + m.off + m.nbytes]
+                masks[i] = ("dev_" + m.kind, v.view(7, -1) if m.kind == "bits" else v.view(7, m.S, m.S), m.S)
         return out, boxes, masks, names
 
     def rows_uncropped(self, parts, keep_photo: bool = False):
@@ -770,31 +887,25 @@ class DevicePrep:
             raise ValueError("DevicePrep.rows_uncropped prepares rows (planes=None)")
         torch = self._torch
         B, S = len(parts), self.size
-        total, head, rows_off, grid_off, crop_off, tall_off, n_tall, pieces, *kept = _layout_uncropped(parts, S, keep_photo)
+        lay = _layout_uncropped(parts, S, keep_photo)
+        total, head = lay.total, lay.head
         dev = "cuda:%d" % self.device
         with torch.cuda.device(self.device):
-            k = self._turn = (getattr(self, "_turn", 0) + 1) & 1
-            stage = self._stage[k]
-            if stage is None or stage.numel() < head:
-                stage = self._stage[k] = torch.empty(max(head, 1 << 22) * 5 // 4, dtype=torch.uint8).pin_memory()
-            if self._copied[k] is not None:
-                self._copied[k].synchronize()
-            pack_into(stage.numpy(), pieces)
+            stage = self._staged(head, lay.pieces)
             main = torch.cuda.current_stream()
-            if getattr(self, "_h2d", None) is None:
-                self._h2d = torch.cuda.Stream(device=self.device)
-            with torch.cuda.stream(self._h2d):
-                st = self._h2d.cuda_stream
+            h2d = self._side_stream()
+            with torch.cuda.stream(h2d):
+                st = h2d.cuda_stream
                 d_blob = torch.empty(total, dtype=torch.uint8, device=dev)
                 d_blob[:head].copy_(stage[:head], non_blocking=True)
-                ev = self._copied[k] = self.last_copy = torch.cuda.Event()
+                ev = self._copied[self._turn] = self.last_copy = torch.cuda.Event()
                 ev.record()
-                if n_tall:
-                    self._check(self._lib.bsr_png_unfilter_tall(self.device, d_blob.data_ptr(), total, tall_off, n_tall, st), "bsr_png_unfilter_tall")
-                self._check(self._lib.bsr_crop_faces(self.device, d_blob.data_ptr(), total, crop_off, B, S, st), "bsr_crop_faces")
+                if lay.n_tall:
+                    self._check(self._lib.bsr_png_unfilter_tall(self.device, d_blob.data_ptr(), total, lay.tall_off, lay.n_tall, st), "bsr_png_unfilter_tall")
+                self._check(self._lib.bsr_crop_faces(self.device, d_blob.data_ptr(), total, lay.crop_off, B, S, st), "bsr_crop_faces")
                 out = torch.empty((B, S, S, 16), dtype=torch.float32, device=dev)
                 tmp = torch.empty((B, S, S), dtype=torch.float32, device=dev)
-                rc = self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, rows_off, grid_off, B, S, out.data_ptr(), tmp.data_ptr(), st)
+                rc = self._lib.bsr_prep_rows(self.device, d_blob.data_ptr(), total, lay.rows_off, lay.grid_off, B, S, out.data_ptr(), tmp.data_ptr(), st)
                 done = torch.cuda.Event()
                 done.record()
             main.wait_event(done)
@@ -802,10 +913,9 @@ class DevicePrep:
             tmp.record_stream(main)
             d_blob.record_stream(main)
         self._check(rc, "bsr_prep_rows")
-        boxes = np.stack([np.asarray(p[2], np.float32) for p in parts], axis=0)
+        boxes = np.stack([np.asarray(p.box, np.float32) for p in parts], axis=0)
         photos = [None] * B
         if keep_photo:
-            paste_off, photo_offs = kept
-            photos = [WildPhoto(p[0].shape[0], p[0].shape[1], p[5][0], p[5][1], p[5][2], blob=d_blob, off=o, paste_off=paste_off)
-                      for p, o in zip(parts, photo_offs)]
-        return out, boxes, photos, [p[4] for p in parts]
+            photos = [WildPhoto(p.img.shape[0], p.img.shape[1], p.crop.box, p.crop.preset_x, p.crop.preset_y, blob=d_blob, off=o,
+                                paste_off=lay.paste_off) for p, o in zip(parts, lay.photo_offs)]
+        return out, boxes, photos, [p.name for p in parts]

@@ -314,7 +314,7 @@ def test_ucb_masks_travel_bit_packed_with_the_loader_job(golden_dir):
     jobs = list(ds._jobs())[:3]
     assert all(len(j[1]) == 3 and j[1][0] == "<device>" and j[1][2] is mf[i] for i, j in enumerate(jobs))
     parts = [D.build_element(j) for j in jobs]
-    assert all(len(p) == 6 and p[5][0] == "bits" and p[5][1].shape == (7, 256 * 256 // 8) and p[5][2] == 256 for p in parts)
+    assert all(isinstance(p, prep.HostPart) and p.label is None and p[5][0] == "bits" and p[5][1].shape == (7, 256 * 256 // 8) and p[5][2] == 256 for p in parts)
     un = prep.unpack_masks([p[5] for p in parts], torch.device("cpu")).numpy()
     assert un.shape == (3, 7, 256, 256) and un.dtype == np.uint8
     for i in range(3):
@@ -379,9 +379,8 @@ def test_loader_ring_slot_holds_what_the_pipe_would_carry(tmp_path, golden_dir):
         assert np.array_equal(np.packbits(lv != 0), pipe[i][5][1][m]) and set(np.unique(lv)) <= {0, 255}
     assert len(set(int(u["out_off"]) for u in unf)) == n_unf
     assert prep.masks_from_raw(("raw8", blob[unf[6]["raw_off"]:unf[6]["raw_off"] + 7 * 256 * 257], 256))[0] == "bits"
-    bad = list(recs[0]); bad[11] = (2, 3)
     with pytest.raises(ValueError, match="channels per filtered pixel"):
-        prep._layout_ex([tuple(bad)], 256, cap)
+        prep._layout_ex([recs[0]._replace(rawc=(2, 3))], 256, cap)
     # without the flag (round 5's form, the FFHQ loop's): decoded images in the slot, byte for byte what the pipe carries
     recs = [D.build_element(j + ((path, s, cap),)) for j, s in zip(jobs, slots)]
     assert all(r[0] == "ring" and r[1] == s and r[10] <= cap and r[11] == (0, 0) for r, s in zip(recs, slots))
@@ -419,9 +418,8 @@ def test_loader_ring_slot_holds_what_the_pipe_would_carry(tmp_path, golden_dir):
     # an item that does not fit a slot comes back through the pipe; a record that lies about its slot is refused before any kernel sees it
     small = D.build_element(jobs[0] + ((path, 0, 1 << 16),))
     assert not prep._is_ring(small) and np.array_equal(small[0], pipe[0][0])
-    bad = list(recs[0]); bad[5] = (cap - 8,) + tuple(bad[5][1:])
     with pytest.raises(ValueError, match="outside its slot"):
-        prep._layout_ex([tuple(bad)], 256, cap)
+        prep._layout_ex([recs[0]._replace(tab_offs=(cap - 8,) + recs[0].tab_offs[1:])], 256, cap)
     with pytest.raises(ValueError, match="ring items"):
         prep._layout(recs, 256)
 

@@ -100,7 +100,7 @@ def test_group_blob_layout_round_trips():
         assert (h, w) == part[0].shape[:2] and np.array_equal(r["box"], part[2])
         for off, a in ((r["img_off"], part[0]), (r["gt_off"], part[1])):
             assert int(off) % 8 == 0 and np.array_equal(np.frombuffer(blob, np.uint8, count=h * w * 3, offset=int(off)).reshape(h, w, 3), a)
-        if len(part) > 6:
+        if part[6] is not None:
             assert np.array_equal(np.frombuffer(blob, np.uint8, count=h * w, offset=int(r["aux_off"])).reshape(h, w), part[6])
         for m in range(8):
             t = np.frombuffer(blob, "<f8", count=int(r["ntri"][m]) * prep.TRI_DOUBLES, offset=int(r["tri_off"][m])).reshape(-1, prep.TRI_DOUBLES)
@@ -115,7 +115,7 @@ def _emulate_group(part, size):
     r0 = emulate((img, gt, box, tabs[:4], b""), size)
     r1 = emulate((img, gt, box, tabs[4:], b""), size)
     planes = [r0[..., :6]]
-    if len(part) > 6:                                            # the label plane: the zero-extended crop of its grey levels (not / 255), resized
+    if part[6] is not None:                                      # the label plane: the zero-extended crop of its grey levels (not / 255), resized
         n = int(box[2] - box[0])
         c = np.zeros((n, n, 1), np.float64)
         ys, xs = np.arange(n) + box[1], np.arange(n) + box[0]

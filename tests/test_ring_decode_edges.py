@@ -99,7 +99,7 @@ def _rebuild(parts, ring_path: str):
                 v = blob[base + m[2]:base + m[2] + m[3]]
                 lv = _levels((m[0], v.reshape(7, -1) if m[0] == "bits" else v.reshape(7, m[1], m[1]), m[1]))
         else:
-            name, lv = p[4], (_levels(p[5]) if len(p) > 5 else None)
+            name, lv = p[4], (_levels(p[5]) if p[5] is not None else None)
         out.append((img, gt, r["box"].copy(), tabs, name, lv))
     return out
 
@@ -126,7 +126,7 @@ def test_ring_record_carries_what_the_pipe_carries(corpus, name, host, tmp_path,
     rec = prep.host_part_ring(job, (path, 1, CAP, True))
     want = RC.BRANCH[name]
     if want == "pipe":                                          # overflows its slot: host_part's tuple, every raw piece decoded
-        assert isinstance(rec, tuple) and not prep._is_ring(rec) and len(rec) == 6
+        assert isinstance(rec, prep.HostPart) and rec.masks is not None and rec.label is None
         assert not np.fromfile(path, np.uint8).any()
         assert rec[5][0] == pipe[5][0] and np.array_equal(rec[5][1], pipe[5][1]) and rec[5][2] == pipe[5][2]
     else:
@@ -184,16 +184,12 @@ def test_layout_refuses_what_the_kernel_cannot_take(corpus, tmp_path):
     assert rec[11] == (3, 3) and rec[9][0] == "raw8"
     prep._layout_ex([rec], 256, CAP)
 
-    def edit(**kw):
-        r = list(rec)
-        for k, v in kw.items():
-            r[int(k[1:])] = v
-        return tuple(r)
-    for bad in (edit(f2=(257, 256)), edit(f2=(256, 1)), edit(f2=(256, 3), f11=(1, 1)), edit(f2=(256, 3), f11=(3, 1))):
+    edit = rec._replace
+    for bad in (edit(hw=(257, 256)), edit(hw=(256, 1)), edit(hw=(256, 3), rawc=(1, 1)), edit(hw=(256, 3), rawc=(3, 1))):
         with pytest.raises(ValueError, match="more than 256 rows or scanlines under 4 bytes"):
             prep._layout_ex([bad], 256, CAP)
     m = rec[9]
     with pytest.raises(ValueError, match="filtered masks do not fit"):
-        prep._layout_ex([edit(f9=("raw8", 257, m[2], 7 * 257 * 258))], 256, CAP)
+        prep._layout_ex([edit(masks=m._replace(S=257, nbytes=7 * 257 * 258))], 256, CAP)
     with pytest.raises(ValueError, match="filtered masks do not fit"):
-        prep._layout_ex([edit(f9=("raw8", 3, m[2], 7 * 3 * 4))], 256, CAP)
+        prep._layout_ex([edit(masks=m._replace(S=3, nbytes=7 * 3 * 4))], 256, CAP)
