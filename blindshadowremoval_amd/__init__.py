@@ -2,7 +2,7 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "generator_variable_shapes", "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "TrainLosses":
         from .train_losses_gpu import TrainLosses
         return TrainLosses
+    if name == "Discriminators":
+        from .discriminator_gpu import Discriminators
+        return Discriminators
     raise AttributeError(name)

@@ -38,6 +38,7 @@
 #include "wild_paste_kernels.h"
 #include "shadow_synth_kernels.h"
 #include "train_losses_kernels.h"
+#include "disc_kernels.h"
 
 namespace {
 
@@ -1432,6 +1433,28 @@ int bsr_train_losses(int device, const float* img, const float* gt, const float*
   return run_post("bsr_train_losses", {img, gt, mask_sv, gs, con_rgb, sums, losses3, scratch}, B, S, scratch, device, [&] {
     HIP_TRY(bsr::launch_train_losses(img, gt, mask_sv, gs, con_rgb, B, S, sums, losses3, mask_edge, bmaskgt, dif_grad, scratch,
                                      static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+size_t bsr_disc_blob_bytes(void) { return 3 * bsr::disc_record_floats() * sizeof(float); }
+
+size_t bsr_disc_losses_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kDiscMaxB ? bsr::disc_map_offset(B, S, 3, 0) : 0; }
+
+size_t bsr_disc_act_offset(int B, int S, int k, int layer) {
+  if (!post_size_ok(B, S) || B > bsr::kDiscMaxB || k < 1 || k > 3 || layer < 0 || layer > bsr::kDiscLayers + 1) return SIZE_MAX;
+  return bsr::disc_map_offset(B, S, k - 1, layer);
+}
+
+int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums,
+                    float* losses3, float* logits, void* scratch, void* stream) {
+  if (B > bsr::kDiscMaxB) return fail(BSR_ERR_ARG, "bsr_disc_losses: B must be 1..32767");
+  if (blob_bytes != bsr_disc_blob_bytes()) return fail(BSR_ERR_ARG, "bsr_disc_losses: blob_bytes must be bsr_disc_blob_bytes() (pack.pack_discriminators)");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0) return fail(BSR_ERR_ARG, "bsr_disc_losses: d_blob must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, "bsr_disc_losses: sums must be 8-byte aligned");
+  return run_post("bsr_disc_losses", {d_blob, gt, con_rgb, mask_sv, sums, losses3, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_disc_losses(static_cast<const float*>(d_blob), gt, con_rgb, mask_sv, B, S, sums, losses3, logits, scratch,
+                                    static_cast<hipStream_t>(stream)));
     return BSR_OK;
   });
 }

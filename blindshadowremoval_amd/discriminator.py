@@ -1,0 +1,261 @@
+"""The three multi-scale patch discriminators of the reference's `train_step` and its three GAN losses as a host statement: `gen`,
+`disc_real` and `disc_fake` (train_test_GSC.py:121-123, 264-268, 302, 334-336, 353-355; model.py:115-147, 292-312; utils.py:100-102),
+restated in numpy for training=False.  It plays the role for csrc/disc_kernels.h (bsr_disc_losses, discriminator_gpu.Discriminators)
+that train_losses.py plays for its chain.  The VGG perceptual term, g_total_loss, training=True (batch statistics, dropout), every
+backward pass and the optimisers are not here.
+
+INPUTS.  gt, con_rgb (deshadow_img_c), mask_sv [B,S,S,3] float32; S in SIZES, B in 1..32767.  The variables are float32
+(weights.discriminator_variable_shapes).
+
+THE INPUT.  x = concat([concat([gt, con_rgb], axis 0), concat([mask_sv, mask_sv], axis 0)], axis 3): [2B,S,S,6], rows [0, B) real,
+rows [B, 2B) fake, channels [image 3 | mask_sv 3].  Discriminator k = 1, 2, 3 (downsize 1, 2, 4) first resizes x to S // downsize:
+tf.image.resize, bilinear, half-pixel centres, no antialiasing, in ucb_post.resize_bilinear's float32 arithmetic.  At these ratios an
+output pixel is one lerp of 0.5 per axis: top = tl + (tr - tl) * .5, bottom = bl + (br - bl) * .5, out = top + (bottom - top) * .5 of
+the pixels (2y, 2x) .. (2y + 1, 2x + 1) for downsize 2 and (4y + 1, 4x + 1) .. (4y + 2, 4x + 2) for downsize 4.
+
+THE LAYERS (float64 arithmetic from the float32 input and variables).  Four Conv(n_ch[i], ksize 4, stride 2, norm 'batch'), n_ch = 32,
+32, 64, 64, then conv2 = Conv(1, ksize 4, stride 1, no norm, no activation):
+  Conv2D SAME    out = ceil(in / s) per axis; total = max((out - 1) s + 4 - in, 0), before = total // 2, the rest after (same_pad):
+                 stride 2 on an even size pads 1, 1; on a 1 x 1 map 1, 2; the stride-1 head always 1, 2.  Cross-correlation with the HWIO
+                 kernel, y[n, oy, ox, o] = sum_{a, b, c} x[n, s oy + a - before, s ox + b - before, c] k[a, b, c, o] + bias[o], positions
+                 outside the map reading 0.
+  BatchNormalization (moving statistics, eps 1e-3)    inv = gamma / sqrt(moving_variance + eps);  y * inv + (beta - moving_mean * inv)
+  LeakyReLU(0.3)                                        y if y >= 0 else 0.3 y
+At S = 32 the third discriminator's maps are 8, 4, 2, 1, 1 on a side; the final map of discriminator k has side h_k = max(S / (16
+downsize), 1).  `forward` returns every activation: `d{k}/in` float32 [2B,s,s,6], `d{k}/conv{i}` float64 [2B,.,.,n_ch[i]], `d{k}/out`
+float64 [2B,h_k,h_k,1].
+
+THE LOSSES.  The output is split in two along the batch: real = out[:B], fake = out[B:].  With y the float32 logits:
+  hinge(y, +1) terms   max(0, 1 - y), `1 - y` rounded once to float32;   hinge(y, -1) terms   max(0, 1 + y), likewise
+Every sum is a float64 sum of float32 terms, kept per item as a row of DISC_SUM_NAMES: per discriminator hinge_real (over the real
+row of the item), hinge_fake and fake (the plain sum of the fake logits): [B, 9].  The losses are formed from the batch totals t (the
+items' rows added in order) in float64 and rounded once to float32; the divisor of discriminator k is n_k = B h_k^2:
+  m_k = t[fake_k] / n_k;  gen = (-m_1 - m_2) - m_3
+  disc_real = (t[hinge_real_1] / n_1 + t[hinge_real_2] / n_2) + t[hinge_real_3] / n_3;  disc_fake the same over hinge_fake.
+
+WHAT IS NOT PINNED.  TensorFlow convolves and reduces in float32 in orders of its own; tests/golden/discriminator_*.npz holds the
+reference's Discriminator, Conv and hinge_loss and train_step's statements executed over a numpy stand-in
+(tools/make_discriminator_fixture.py), and tests/test_discriminator_fixture.py holds this statement to it.
+
+`python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host]` scores the three terms on a folder written
+by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling (train_losses.folder_steps): the
+generator runs on row 0 of each element and its con_rgb is the fake image.  The weights of the generator and of the discriminators
+come from the latest checkpoint under --ckpt, from init_weights / init_discriminator_weights without it.  The step-weighted means
+are printed as Logging.display prints them.  --host computes the three terms with this statement from the same generator outputs.
+"""
+from __future__ import annotations
+
+import contextlib
+import sys
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .shadow_synth import SIZES
+from .ucb_post import resize_bilinear
+from .weights import BN_EPS, DISC_CH, LRELU_ALPHA, N_LAYER_D  # noqa: F401 (DISC_CH: the binding reads it here)
+
+f32 = np.float32
+DOWNSIZE = (1, 2, 4)
+MAX_B = 32767
+LOSS_NAMES = ("gen", "disc_real", "disc_fake")
+DISC_SUM_NAMES = tuple("%s_%d" % (n, k) for k in (1, 2, 3) for n in ("hinge_real", "hinge_fake", "fake"))
+K = len(DISC_SUM_NAMES)
+IDX = {n: i for i, n in enumerate(DISC_SUM_NAMES)}
+SIZE_TEXT = "discriminators take 1..32767 items of side 32, 64, 128 or 256, got B=%d S=%d"
+
+
+def same_pad(size: int, k: int, s: int) -> Tuple[int, int]:
+    """TF 'SAME' padding of one axis (oracle.gsc_oracle.same_pad): (before, after)."""
+    out = -(-size // s)
+    total = max((out - 1) * s + k - size, 0)
+    return total // 2, total - total // 2
+
+
+def map_sides(S: int, k: int) -> List[int]:
+    """The sides of discriminator k's maps: its input, the four stride-2 outputs, the head's output."""
+    sides = [S // DOWNSIZE[k - 1]]
+    for _ in range(N_LAYER_D):
+        sides.append(-(-sides[-1] // 2))
+    return sides + [sides[-1]]
+
+
+def final_side(S: int, k: int) -> int:
+    return map_sides(S, k)[-1]
+
+
+def conv2d_same(x: np.ndarray, kernel: np.ndarray, bias: np.ndarray, stride: int) -> np.ndarray:
+    """[N,H,W,C] x HWIO kernel -> float64 [N,ceil(H/s),ceil(W/s),O]: Conv2D(padding='same') + bias."""
+    x, kernel = np.asarray(x, np.float64), np.asarray(kernel, np.float64)
+    n, h, w, c = x.shape
+    kh, kw = kernel.shape[:2]
+    (pt, pb), (pl, pr) = same_pad(h, kh, stride), same_pad(w, kw, stride)
+    ho, wo = -(-h // stride), -(-w // stride)
+    xp = np.zeros((n, h + pt + pb, w + pl + pr, c), np.float64)
+    xp[:, pt:pt + h, pl:pl + w] = x
+    out = np.zeros((n, ho, wo, kernel.shape[3]), np.float64)
+    for a in range(kh):
+        for b in range(kw):
+            out += xp[:, a:a + (ho - 1) * stride + 1:stride, b:b + (wo - 1) * stride + 1:stride] @ kernel[a, b]
+    return out + np.asarray(bias, np.float64)
+
+
+def layer(weights: Dict[str, np.ndarray], k: int, i: int, x: np.ndarray) -> np.ndarray:
+    """conv_stack[i] of discriminator k on [N,H,W,C]: Conv2D stride 2 + bias, BatchNormalization (moving statistics), LeakyReLU."""
+    st = "discriminator_%d/conv_stack/%d/" % (k, i)
+    y = conv2d_same(x, weights[st + "conv/kernel"], weights[st + "conv/bias"], 2)
+    g, beta, mean, var = (np.asarray(weights[st + "bnorm/" + p], np.float64) for p in ("gamma", "beta", "moving_mean", "moving_variance"))
+    inv = g / np.sqrt(var + BN_EPS)
+    y = y * inv + (beta - mean * inv)
+    return np.where(y >= 0, y, LRELU_ALPHA * y)
+
+
+def head(weights: Dict[str, np.ndarray], k: int, x: np.ndarray) -> np.ndarray:
+    """conv2 of discriminator k on [N,h,h,64] -> float64 [N,h,h,1]."""
+    st = "discriminator_%d/conv2/conv/" % k
+    return conv2d_same(x, weights[st + "kernel"], weights[st + "bias"], 1)
+
+
+def check_inputs(gt, con_rgb, mask_sv) -> Tuple[int, int]:
+    arrays = [np.asarray(a) for a in (gt, con_rgb, mask_sv)]
+    if arrays[0].ndim != 4:
+        raise ValueError("discriminators: gt must be [B,S,S,3], got %s" % (arrays[0].shape,))
+    B, S = arrays[0].shape[:2]
+    if S not in SIZES or not 1 <= B <= MAX_B:
+        raise ValueError(SIZE_TEXT % (B, S))
+    for name, a in zip(("gt", "con_rgb", "mask_sv"), arrays):
+        if a.shape != (B, S, S, 3):
+            raise ValueError("discriminators: %s must be [%d,%d,%d,3] like gt, got %s" % (name, B, S, S, a.shape))
+    return B, S
+
+
+def disc_input(gt, con_rgb, mask_sv, k: int) -> np.ndarray:
+    """The input of discriminator k: float32 [2B, S // downsize, S // downsize, 6]."""
+    gt, con_rgb, mask_sv = (np.asarray(a, f32) for a in (gt, con_rgb, mask_sv))
+    x = np.concatenate([np.concatenate([gt, con_rgb], axis=0), np.concatenate([mask_sv, mask_sv], axis=0)], axis=3)
+    ds = DOWNSIZE[k - 1]
+    return x if ds == 1 else np.stack([resize_bilinear(item, x.shape[1] // ds) for item in x])
+
+
+def forward(weights: Dict[str, np.ndarray], gt, con_rgb, mask_sv) -> Dict[str, np.ndarray]:
+    """Every activation of the three discriminators: `d{k}/in`, `d{k}/conv{i}`, `d{k}/out`."""
+    check_inputs(gt, con_rgb, mask_sv)
+    acts: Dict[str, np.ndarray] = {}
+    for k in (1, 2, 3):
+        x = disc_input(gt, con_rgb, mask_sv, k)
+        acts["d%d/in" % k] = x
+        h = x.astype(np.float64)
+        for i in range(N_LAYER_D):
+            h = layer(weights, k, i, h)
+            acts["d%d/conv%d" % (k, i)] = h
+        acts["d%d/out" % k] = head(weights, k, h)
+    return acts
+
+
+def logits_of(acts: Dict[str, np.ndarray]) -> List[np.ndarray]:
+    """The three logit maps [2B,h_k,h_k] of `forward`'s result."""
+    return [np.asarray(acts["d%d/out" % k])[..., 0] for k in (1, 2, 3)]
+
+
+def losses_from_logits(logits: Sequence[np.ndarray]) -> Dict[str, np.ndarray]:
+    """Three logit maps [2B,h_k,h_k] -> dict(losses float32 [3] (LOSS_NAMES), sums float64 [B,9] (DISC_SUM_NAMES))."""
+    maps = [np.asarray(y).astype(f32) for y in logits]
+    B = maps[0].shape[0] // 2
+    sums = np.zeros((B, K), np.float64)
+    for j, y in enumerate(maps):
+        assert y.ndim == 3 and y.shape[0] == 2 * B and y.shape[1] == y.shape[2]
+        real, fake = y[:B].reshape(B, -1), y[B:].reshape(B, -1)
+        sums[:, 3 * j + 0] = np.maximum(f32(0), f32(1) - real).sum(axis=1, dtype=np.float64)
+        sums[:, 3 * j + 1] = np.maximum(f32(0), f32(1) + fake).sum(axis=1, dtype=np.float64)
+        sums[:, 3 * j + 2] = fake.sum(axis=1, dtype=np.float64)
+    return {"losses": losses_from_sums(sums, [y.shape[1] for y in maps]), "sums": sums}
+
+
+def losses_from_sums(sums: np.ndarray, sides: Sequence[int]) -> np.ndarray:
+    """float64 [B,9] and the three final sides h_k -> float32 [3]: gen, disc_real, disc_fake over the whole batch."""
+    sums = np.asarray(sums, np.float64)
+    t = np.zeros(K, np.float64)
+    for row in sums:
+        t = t + row
+    n = [float(sums.shape[0] * h * h) for h in sides]
+    m = [t[3 * j + 2] / n[j] for j in range(3)]
+    gen = (-m[0] - m[1]) - m[2]
+    real = (t[0] / n[0] + t[3] / n[1]) + t[6] / n[2]
+    fake = (t[1] / n[0] + t[4] / n[1]) + t[7] / n[2]
+    return np.array([gen, real, fake], np.float64).astype(f32)
+
+
+def gan_losses(weights: Dict[str, np.ndarray], gt, con_rgb, mask_sv) -> Dict[str, np.ndarray]:
+    """Batches -> dict(losses float32 [3], sums float64 [B,9], logits: three float64 maps [2B,h_k,h_k], acts: `forward`'s dict)."""
+    acts = forward(weights, gt, con_rgb, mask_sv)
+    logits = logits_of(acts)
+    out = losses_from_logits(logits)
+    out.update(logits=logits, acts=acts)
+    return out
+
+
+def example_inputs(S: int, B: int, seed: int = 0):
+    """gt, con_rgb, mask_sv of train_losses.example_inputs(S, B, seed)."""
+    from .train_losses import example_inputs as ex
+    _, gt, mask_sv, _, con = ex(S, B, seed)
+    return gt, con, mask_sv
+
+
+# ---- the command-line entry
+def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False,
+                 stats: Optional[Dict[str, float]] = None) -> Dict[str, float]:
+    """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of gen, disc_real and disc_fake.
+    With `host`, a `stats` dict receives `max_abs_logit`, the largest magnitude of the statement's logits over all steps."""
+    import torch
+    from .fsrnet import Logging
+    from .train_losses import folder_steps
+    from .weights import init_discriminator_weights
+    if ckpt is not None:
+        from .tf_bundle import latest_checkpoint, load_discriminator_weights
+        prefix = latest_checkpoint(ckpt)
+        if prefix is None:
+            raise FileNotFoundError("discriminator: no checkpoint under %s" % ckpt)
+        weights = load_discriminator_weights(prefix)
+    else:
+        weights = init_discriminator_weights(1)
+    runner = None
+    acc: Dict[str, List[float]] = {}
+    dev = torch.device("cuda", device)
+    with contextlib.closing(folder_steps(folder, ckpt, batch, device, "discriminator")) as batches:
+        for step, steps, _, gt_a, mask_a, _, con_rgb in batches:
+            if host:
+                torch.cuda.synchronize(dev)
+                r = gan_losses(weights, gt_a, con_rgb.cpu().numpy(), mask_a)
+                loss = r["losses"]
+                if stats is not None:
+                    stats["max_abs_logit"] = max([stats.get("max_abs_logit", 0.0)] + [float(np.abs(y).max()) for y in r["logits"]])
+            else:
+                if runner is None:
+                    from .discriminator_gpu import Discriminators
+                    runner = Discriminators(device)
+                    runner.load_weights(weights)
+                loss = runner.gan_losses(torch.from_numpy(gt_a).to(dev), con_rgb, torch.from_numpy(mask_a).to(dev))[0].cpu().numpy()
+            Logging.accumulate(acc, {k: float(v) for k, v in zip(LOSS_NAMES, loss)})
+            if not quiet:
+                print(Logging.format_line(acc, step, steps), end="", flush=True)
+    if not quiet:
+        print("")
+    return {k: s / max(c, 1) for k, (s, c) in acc.items()}
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m blindshadowremoval_amd.discriminator",
+                                 description="Score a generator on synthesised pairs with train_step's three GAN terms.")
+    ap.add_argument("folder")
+    ap.add_argument("--ckpt", default=None, help="checkpoint directory; without it the weights come from init_weights / init_discriminator_weights")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--host", action="store_true", help="compute the three terms with the host statement instead of the device chain")
+    a = ap.parse_args(argv)
+    means = score_folder(a.folder, ckpt=a.ckpt, batch=a.batch, host=a.host)
+    print(", ".join("%s:%.9g" % (k, means[k]) for k in LOSS_NAMES))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -459,3 +459,90 @@ def _write_blob(entries, dtype: str) -> bytes:
     for o, raw in chunks:
         blob[o:o + len(raw)] = raw
     return bytes(blob)
+
+
+# ---- the three patch discriminators (csrc/disc_kernels.h): a blob of its own, no header, float32 ----
+DISC_CC = 8                  # channels per K chunk of disc_conv_kernel; the first layer's 6 input channels are padded to 8
+DISC_TAPS = 16
+
+
+def disc_layout():
+    """([(name, offset in floats, shape)] of ONE discriminator, floats per discriminator).  A stride-2 layer `conv<i>` is stored as the
+    kernel stages it, a chunk of 8 input channels at a time: w [C_in / 8][16 taps (a * 4 + b)][8][N], then bias [N], BatchNormalization
+    folded; the head as w [16 taps][64], then [bias, 0, 0, 0].  Every offset is a multiple of 4 floats.  The blob is the three
+    discriminators' records in order."""
+    from .weights import DISC_CH, DISC_IN_CH
+    out, off, cin = [], 0, -(-DISC_IN_CH // DISC_CC) * DISC_CC
+    for i, n in enumerate(DISC_CH):
+        out.append(("conv%d/w" % i, off, (cin // DISC_CC, DISC_TAPS, DISC_CC, n)))
+        off += DISC_TAPS * cin * n
+        out.append(("conv%d/b" % i, off, (n,)))
+        off += n
+        cin = n
+    out.append(("head/w", off, (DISC_TAPS, cin)))
+    off += DISC_TAPS * cin
+    out.append(("head/b", off, (4,)))
+    return out, off + 4
+
+
+def disc_folded(weights: Dict[str, np.ndarray], k: int):
+    """{`conv<i>`: (kernel [16, C_in padded to 8, N], bias [N]), `head`: (kernel [16, 64, 1], bias [1])} of discriminator k, float32,
+    BatchNormalization folded with fold_bn."""
+    from .weights import DISC_CH
+    out = {}
+    for i in range(len(DISC_CH)):
+        st = "discriminator_%d/conv_stack/%d" % (k, i)
+        kern = np.asarray(weights[st + "/conv/kernel"])
+        kt, b = fold_bn(kern.reshape(DISC_TAPS, kern.shape[2], kern.shape[3]), np.asarray(weights[st + "/conv/bias"]), _bn(weights, st + "/bnorm"))
+        cin = -(-kt.shape[1] // DISC_CC) * DISC_CC
+        full = np.zeros((DISC_TAPS, cin, kt.shape[2]), np.float32)
+        full[:, :kt.shape[1]] = kt
+        out["conv%d" % i] = (full, b.astype(np.float32))
+    st = "discriminator_%d/conv2/conv/" % k
+    kern = np.asarray(weights[st + "kernel"])
+    out["head"] = (kern.reshape(DISC_TAPS, kern.shape[2], 1).astype(np.float32), np.asarray(weights[st + "bias"]).astype(np.float32))
+    return out
+
+
+def pack_discriminators(weights: Dict[str, np.ndarray]) -> bytes:
+    """The three discriminators' variables (weights.discriminator_variable_shapes) -> the blob bsr_disc_losses takes (disc_layout)."""
+    from .weights import check_discriminator_weights
+    check_discriminator_weights(weights)
+    layout, per = disc_layout()
+    blob = np.zeros((3, per), np.float32)
+    for k in (1, 2, 3):
+        folded = disc_folded(weights, k)
+        for name, off, shape in layout:
+            kern, bias = folded[name.split("/")[0]]
+            if name == "head/w":
+                a = kern[:, :, 0]
+            elif name == "head/b":
+                a = np.array([bias[0], 0, 0, 0], np.float32)
+            elif name.endswith("/w"):
+                a = kern.reshape(DISC_TAPS, shape[0], DISC_CC, shape[3]).transpose(1, 0, 2, 3)
+            else:
+                a = bias
+            assert a.shape == tuple(shape)
+            blob[k - 1, off:off + a.size] = a.reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_discriminators(blob: bytes):
+    """The inverse of pack_discriminators: [disc_folded(w, 1), disc_folded(w, 2), disc_folded(w, 3)]."""
+    layout, per = disc_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != 3 * per:
+        raise ValueError("a discriminator blob holds %d bytes, got %d" % (3 * per * 4, len(blob)))
+    out = []
+    for k in range(3):
+        rec = {name: arr[k * per + off:k * per + off + int(np.prod(shape))].reshape(shape) for name, off, shape in layout}
+        d = {}
+        for name in rec:
+            stem = name.split("/")[0]
+            if stem == "head" or stem in d:
+                continue
+            w = rec[stem + "/w"]
+            d[stem] = (w.transpose(1, 0, 2, 3).reshape(DISC_TAPS, w.shape[0] * DISC_CC, w.shape[3]).copy(), rec[stem + "/b"].copy())
+        d["head"] = (rec["head/w"][:, :, None].copy(), rec["head/b"][:1].copy())
+        out.append(d)
+    return out

@@ -155,11 +155,9 @@ def latest_checkpoint(ckpt_dir: str) -> Optional[str]:
     return prefix if os.path.isfile(prefix + ".index") else None
 
 
-def load_generator_weights(prefix: str) -> Dict[str, np.ndarray]:
-    """Load every ``generator/*`` float32 variable of checkpoint ``prefix`` (path without suffix).
-
-    Raises FileNotFoundError when the data shard is absent (the reference repo ships only the
-    ``.index`` files: /root/reference/.MISSING_LARGE_BLOBS)."""
+def _load_variables(prefix: str, wanted, strip: int) -> Dict[str, np.ndarray]:
+    """The float32 variables of checkpoint ``prefix`` whose key ``wanted`` accepts, named by the key without its first ``strip``
+    characters and without the variable suffix."""
     entries = read_index(prefix + ".index")
     data_path = prefix + ".data-00000-of-00001"
     if not os.path.isfile(data_path):
@@ -167,23 +165,50 @@ def load_generator_weights(prefix: str) -> Dict[str, np.ndarray]:
     out = {}
     with open(data_path, "rb") as f:
         for key, e in entries.items():
-            if not _is_generator_var(key) or e.dtype != _DT_FLOAT:
+            if not wanted(key) or e.dtype != _DT_FLOAT:
                 continue
             if e.shard != 0:
                 raise ValueError("multi-shard bundles are not supported")
             f.seek(e.offset)
             raw = f.read(e.size)
             arr = np.frombuffer(raw, dtype="<f4").reshape(e.shape).copy()
-            out[key[len(GEN_PREFIX):-len(VAR_SUFFIX)]] = arr
+            out[key[strip:-len(VAR_SUFFIX)]] = arr
     return out
 
 
-def write_bundle(prefix: str, tensors: Dict[str, np.ndarray]) -> None:
+def load_generator_weights(prefix: str) -> Dict[str, np.ndarray]:
+    """Load every ``generator/*`` float32 variable of checkpoint ``prefix`` (path without suffix).
+
+    Raises FileNotFoundError when the data shard is absent (the reference repo ships only the
+    ``.index`` files: /root/reference/.MISSING_LARGE_BLOBS)."""
+    return _load_variables(prefix, _is_generator_var, len(GEN_PREFIX))
+
+
+DISC_PREFIXES = ("discriminator_1/", "discriminator_2/", "discriminator_3/")
+
+
+def _is_discriminator_var(key: str) -> bool:
+    return key.startswith(DISC_PREFIXES) and key.endswith(VAR_SUFFIX) and ".OPTIMIZER_SLOT" not in key
+
+
+def discriminator_inventory(index_path: str) -> Dict[str, Tuple[int, ...]]:
+    """{variable name with its ``discriminator_<k>/`` prefix (e.g. ``discriminator_1/conv2/conv/kernel``): shape}."""
+    return {key[:-len(VAR_SUFFIX)]: e.shape for key, e in read_index(index_path).items() if _is_discriminator_var(key) and e.dtype == _DT_FLOAT}
+
+
+def load_discriminator_weights(prefix: str) -> Dict[str, np.ndarray]:
+    """Load every ``discriminator_{1,2,3}/*`` float32 variable of checkpoint ``prefix`` (path without suffix), named as
+    ``weights.discriminator_variable_shapes`` names them.  FileNotFoundError when the data shard is absent."""
+    return _load_variables(prefix, _is_discriminator_var, 0)
+
+
+def write_bundle(prefix: str, tensors: Dict[str, np.ndarray], key_prefix: str = GEN_PREFIX) -> None:
     """Write a single-block-per-entry tensor bundle (used by tests to round-trip the reader and to
-    let users stage real weights).  Keys get the ``generator/`` prefix and variable suffix."""
+    let users stage real weights).  Keys get the ``generator/`` prefix and variable suffix; ``key_prefix`` puts another
+    prefix in its place ("" for names that carry their own, as the discriminators' do)."""
     items: List[Tuple[bytes, np.ndarray]] = []
     for name in sorted(tensors):
-        items.append(((GEN_PREFIX + name + VAR_SUFFIX).encode(), np.ascontiguousarray(tensors[name], dtype="<f4")))
+        items.append(((key_prefix + name + VAR_SUFFIX).encode(), np.ascontiguousarray(tensors[name], dtype="<f4")))
     items.sort(key=lambda kv: kv[0])
 
     def enc_varint(v: int) -> bytes:

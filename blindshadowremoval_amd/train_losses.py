@@ -53,6 +53,7 @@ computes the losses with this statement from the same generator outputs.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import sys
 from typing import Dict, List, Optional, Tuple
@@ -227,19 +228,21 @@ def example_inputs(S: int, B: int, seed: int = 0):
 
 
 # ---- the command-line entry
-def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False) -> Dict[str, float]:
-    """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of recon_gs, recon_c and grad, a
-    step being `batch` items (the last one may hold fewer)."""
+def folder_steps(folder: str, ckpt: Optional[str] = None, batch: int = 8, device: int = 0, who: str = "train_losses"):
+    """The folder handling of the commands that score a generator on synthesised pairs: for every step of `batch` item folders
+    `<folder>/<name>/` (the last one may hold fewer) yields (step, steps, img on the device, gt [b,S,S,3], mask_sv [b,S,S,3] (numpy), gs,
+    con_rgb (the generator's outputs on the device)).  The generator's weights come from the latest checkpoint under `ckpt`, from
+    init_weights without it."""
     import torch
     from . import Generator, init_weights
     from .dataset import Dataset
-    from .fsrnet import SPLIT_FFHQ, Config, Logging
+    from .fsrnet import SPLIT_FFHQ, Config
     from .pngio import read_rgb_u8
     cfg = Config(device)
     cfg.DATA_DIR_TEST = [os.path.join(folder, "*")]
     ds = Dataset(cfg, "test")
     if not ds.name_list:
-        raise ValueError("train_losses: no item folder with a .npy under %s" % folder)
+        raise ValueError("%s: no item folder with a .npy under %s" % (who, folder))
     S = cfg.IMG_SIZE
     dev = torch.device("cuda", device)
     gen = Generator(device=device)
@@ -248,37 +251,49 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
         gen._require_weights()
     else:
         gen.load_weights(init_weights(1))
-    runner = None
-    acc: Dict[str, List[float]] = {}
     batch = max(1, int(batch))
     steps = (len(ds.name_list) + batch - 1) // batch
-    for step in range(steps):
-        names = ds.name_list[step * batch:(step + 1) * batch]
-        rows, gts, masks = [], [], []
-        for lm_path in names:
-            element = next(ds.feed)[0]
-            rows.append(torch.as_tensor(np.asarray(element)).reshape(-1, S, S, sum(SPLIT_FFHQ))[:1])
-            stem = os.path.splitext(lm_path)[0]
-            for path, dst in ((stem + "-gt.png", gts), (stem + "-mask.png", masks)):
-                a = read_rgb_u8(path)
-                if a.shape != (S, S, 3):
-                    raise ValueError("train_losses: %s is %s, not %d x %d x 3" % (path, a.shape, S, S))
-                dst.append(a.astype(f32) / f32(255))
-        im, _, uv, _, _ = torch.split(torch.cat(rows, 0).float(), list(SPLIT_FFHQ), dim=3)
-        im_d = im.contiguous().to(dev)
-        gs, con_rgb, _, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
-        gt_a, mask_a = np.stack(gts), np.stack(masks)
-        if host:
-            torch.cuda.synchronize(dev)
-            loss = step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy())["losses"]
-        else:
-            from .train_losses_gpu import TrainLosses
-            runner = runner or TrainLosses(device)
-            loss = runner.step_losses(im_d, torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev), gs, con_rgb)[0].cpu().numpy()
-        Logging.accumulate(acc, {k: float(v) for k, v in zip(LOSS_NAMES, loss)})
-        if not quiet:
-            print(Logging.format_line(acc, step, steps), end="", flush=True)
-    gen.close()
+    try:
+        for step in range(steps):
+            names = ds.name_list[step * batch:(step + 1) * batch]
+            rows, gts, masks = [], [], []
+            for lm_path in names:
+                element = next(ds.feed)[0]
+                rows.append(torch.as_tensor(np.asarray(element)).reshape(-1, S, S, sum(SPLIT_FFHQ))[:1])
+                stem = os.path.splitext(lm_path)[0]
+                for path, dst in ((stem + "-gt.png", gts), (stem + "-mask.png", masks)):
+                    a = read_rgb_u8(path)
+                    if a.shape != (S, S, 3):
+                        raise ValueError("%s: %s is %s, not %d x %d x 3" % (who, path, a.shape, S, S))
+                    dst.append(a.astype(f32) / f32(255))
+            im, _, uv, _, _ = torch.split(torch.cat(rows, 0).float(), list(SPLIT_FFHQ), dim=3)
+            im_d = im.contiguous().to(dev)
+            gs, con_rgb, _, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
+            yield step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb
+    finally:                    # also when the consumer stops early or raises: the handle is closed with the generator
+        gen.close()
+
+
+def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False) -> Dict[str, float]:
+    """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of recon_gs, recon_c and grad, a
+    step being `batch` items (the last one may hold fewer)."""
+    import torch
+    from .fsrnet import Logging
+    dev = torch.device("cuda", device)
+    runner = None
+    acc: Dict[str, List[float]] = {}
+    with contextlib.closing(folder_steps(folder, ckpt, batch, device)) as batches:          # closes the generator handle on any way out
+        for step, steps, im_d, gt_a, mask_a, gs, con_rgb in batches:
+            if host:
+                torch.cuda.synchronize(dev)
+                loss = step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy())["losses"]
+            else:
+                from .train_losses_gpu import TrainLosses
+                runner = runner or TrainLosses(device)
+                loss = runner.step_losses(im_d, torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev), gs, con_rgb)[0].cpu().numpy()
+            Logging.accumulate(acc, {k: float(v) for k, v in zip(LOSS_NAMES, loss)})
+            if not quiet:
+                print(Logging.format_line(acc, step, steps), end="", flush=True)
     if not quiet:
         print("")
     return {k: s / max(c, 1) for k, (s, c) in acc.items()}

@@ -118,6 +118,62 @@ def generator_variable_shapes(variant: str = "gsc") -> "OrderedDict[str, Tuple[i
     return s
 
 
+N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
+DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
+DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)
+
+
+def discriminator_variable_shapes(n_layer: int = N_LAYER_D) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape for the float32 variables of the three patch discriminators (/root/reference/model.py:292-312), named as
+    ``tf.train.Checkpoint(discriminator_1=..., discriminator_2=..., discriminator_3=...)`` names them minus the variable suffix:
+    ``discriminator_<k>/conv_stack/<i>/{conv/kernel, conv/bias, bnorm/*}`` and ``discriminator_<k>/conv2/conv/{kernel, bias}``.
+    tests/golden/disc_ckpt_inventory.json holds the same table parsed from the reference's index files."""
+    n_ch = [32, 32, 64, 64, 128, 256]
+    if not 1 <= n_layer <= len(n_ch):
+        raise ValueError("n_layer must be 1..%d" % len(n_ch))
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    for k in (1, 2, 3):
+        cin = DISC_IN_CH
+        for i in range(n_layer):
+            _conv(s, "discriminator_%d/conv_stack/%d" % (k, i), 4, cin, n_ch[i], True)      # Conv(n_ch[i], ksize=4, stride=2, norm='batch')
+            cin = n_ch[i]
+        _conv(s, "discriminator_%d/conv2" % k, 4, cin, 1, False)                            # Conv(1, ksize=4, norm=False, nl=False)
+    return s
+
+
+def _draw(rng, name: str, shp, fan_in: float, gain: float) -> np.ndarray:
+    """One variable of the SURVEY.md §8d recipe, by the leaf of its name."""
+    leaf = name.rsplit("/", 1)[1]
+    if leaf == "kernel":
+        w = rng.standard_normal(shp) * np.sqrt(gain / fan_in)
+    elif leaf == "gamma":
+        w = rng.uniform(0.8, 1.2, shp)
+    elif leaf == "moving_variance":
+        w = rng.uniform(0.75, 1.25, shp)
+    else:                               # bias, beta, moving_mean
+        w = rng.standard_normal(shp) * 0.05
+    return w.astype(np.float32)
+
+
+def init_discriminator_weights(seed: int = 1, n_layer: int = N_LAYER_D) -> Dict[str, np.ndarray]:
+    """Seeded synthetic weights of the three discriminators in ``init_weights``' recipe: kernels N(0, 1.6/fan_in), biases / beta /
+    moving_mean N(0, 0.05^2), gamma U[0.8,1.2], moving_variance U[0.75,1.25]."""
+    rng = np.random.default_rng(seed)
+    return {name: _draw(rng, name, shp, shp[0] * shp[1] * shp[2] if len(shp) == 4 else 1, 1.6)
+            for name, shp in discriminator_variable_shapes(n_layer).items()}
+
+
+def check_discriminator_weights(weights: Dict[str, np.ndarray], n_layer: int = N_LAYER_D) -> None:
+    """Raise ValueError if ``weights`` is not exactly the three discriminators' variable set."""
+    spec = discriminator_variable_shapes(n_layer)
+    missing = [k for k in spec if k not in weights]
+    if missing:
+        raise ValueError("missing discriminator variables: %s%s" % (missing[:4], " ..." if len(missing) > 4 else ""))
+    for k, shp in spec.items():
+        if tuple(np.shape(weights[k])) != tuple(shp):
+            raise ValueError("variable %s has shape %s, expected %s" % (k, tuple(np.shape(weights[k])), shp))
+
+
 # Kernel variance gains (x 1/fan_in).  1.6 roughly preserves variance through LeakyReLU(0.3); the
 # residual branches (``conv3``, ``non_local/w``) and the attention projections are damped so the six
 # bottleneck blocks neither blow activations up nor saturate the 1024-wide softmax — a trained
@@ -143,21 +199,13 @@ def init_weights(seed: int = 1, con_bias_shift: float = 0.25, variant: str = "gs
     rng = np.random.default_rng(seed)
     out: Dict[str, np.ndarray] = {}
     for name, shp in generator_variable_shapes(variant).items():
-        leaf = name.rsplit("/", 1)[1]
-        if leaf == "kernel":
+        fan_in = 1.0
+        if name.endswith("/kernel"):
             transpose = name.split("/")[0] in ("up1", "up2", "up3", "clr_up1", "clr_up2", "clr_up3")
-            cin = shp[3] if transpose else shp[2]
-            fan_in = shp[0] * shp[1] * cin
+            fan_in = shp[0] * shp[1] * (shp[3] if transpose else shp[2])
             if transpose:
                 fan_in = fan_in / 4.0       # stride-2 transposed conv: 9/4 taps reach one output on average
-            w = rng.standard_normal(shp) * np.sqrt(_gain(name) / fan_in)
-        elif leaf == "gamma":
-            w = rng.uniform(0.8, 1.2, shp)
-        elif leaf == "moving_variance":
-            w = rng.uniform(0.75, 1.25, shp)
-        else:                               # bias, beta, moving_mean
-            w = rng.standard_normal(shp) * 0.05
-        out[name] = w.astype(np.float32)
+        out[name] = _draw(rng, name, shp, fan_in, _gain(name))
     if con_bias_shift and variant != "rgb":          # the RGB baseline has no threshold: its conv3 is the output layer
         out["conv3/conv/bias"] = (out["conv3/conv/bias"] + np.float32(con_bias_shift)).astype(np.float32)
     return out

@@ -227,6 +227,26 @@ size_t bsr_train_losses_scratch_bytes(int B, int S);
 int bsr_train_losses(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb, int B, int S,
                      double* sums, float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, void* stream);
 
+/* The three multi-scale patch discriminators of the reference's train_step and its three GAN losses (train_test_GSC.py:264-268, 302,
+ * 334-336; model.py:115-147, 292-312; utils.py:100-102; training=False) for a batch on the device: gen, disc_real and disc_fake;
+ * blindshadowremoval_amd/discriminator.py is the host statement and writes the arithmetic out.  d_blob: the device copy of
+ * pack.pack_discriminators' blob, blob_bytes = bsr_disc_blob_bytes(), 16-byte aligned.  gt, con_rgb, mask_sv [B][S][S][3] are dense
+ * float32 NHWC device tensors; the discriminators see rows [0, B) = [gt | mask_sv] (real) and [B, 2B) = [con_rgb | mask_sv] (fake).
+ * Outputs: sums [B][9] float64, the per-item partial sums in discriminator.DISC_SUM_NAMES' order; losses3 [3] float32 = gen, disc_real,
+ * disc_fake over the whole batch; and, optional (may be NULL), logits = the three maps [2B][h_k][h_k] one after the other, h_k = max(S /
+ * (16 downsize), 1).  The sums are float64 sums in a fixed order (no floating-point atomics: a call repeats its bits).  scratch:
+ * bsr_disc_losses_scratch_bytes(B, S) bytes, 256-byte aligned; every word a launch reads is written earlier in the same call.  It
+ * holds every activation afterwards: bsr_disc_act_offset(B, S, k, layer) is the byte offset of discriminator k's (1..3) map `layer` —
+ * 0 its input [2B][s][s][8] (channels 6, 7 zero), 1..4 the stride-2 layers' outputs [2B][.][.][32, 32, 64, 64], 5 the logits — and
+ * SIZE_MAX for arguments out of range.  S = 32, 64, 128 or 256, B = 1..32767 (0 from the size query otherwise).  Seven launches on
+ * `stream`, one after the other, no host synchronisation.  A bad argument gives BSR_ERR_ARG with a message and nothing launched.
+ * ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_disc_blob_bytes(void);
+size_t bsr_disc_losses_scratch_bytes(int B, int S);
+size_t bsr_disc_act_offset(int B, int S, int k, int layer);
+int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S,
+                    double* sums, float* losses3, float* logits, void* scratch, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
