@@ -2,7 +2,7 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "generator_variable_shapes", "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name == "Discriminators":
         from .discriminator_gpu import Discriminators
         return Discriminators
+    if name == "Perceptual":
+        from .perceptual_gpu import Perceptual
+        return Perceptual
     raise AttributeError(name)

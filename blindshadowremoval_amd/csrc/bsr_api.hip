@@ -39,6 +39,7 @@
 #include "shadow_synth_kernels.h"
 #include "train_losses_kernels.h"
 #include "disc_kernels.h"
+#include "vgg_kernels.h"
 
 namespace {
 
@@ -1455,6 +1456,27 @@ int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const flo
   return run_post("bsr_disc_losses", {d_blob, gt, con_rgb, mask_sv, sums, losses3, scratch}, B, S, scratch, device, [&] {
     HIP_TRY(bsr::launch_disc_losses(static_cast<const float*>(d_blob), gt, con_rgb, mask_sv, B, S, sums, losses3, logits, scratch,
                                     static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
+
+size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
+
+size_t bsr_vgg_act_offset(int B, int S, int layer) {
+  if (!post_size_ok(B, S) || B > bsr::kVggMaxB || layer < 0 || layer >= bsr::kVggMaps) return SIZE_MAX;
+  return bsr::vgg_act_offset(B, S, layer);
+}
+
+int bsr_vgg_per_loss(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, int B, int S, double* sums, float* loss1,
+                     void* scratch, void* stream) {
+  if (B > bsr::kVggMaxB) return fail(BSR_ERR_ARG, "bsr_vgg_per_loss: B must be 1..4096");
+  if (blob_bytes != bsr_vgg_blob_bytes()) return fail(BSR_ERR_ARG, "bsr_vgg_per_loss: blob_bytes must be bsr_vgg_blob_bytes() (pack.pack_vgg)");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0) return fail(BSR_ERR_ARG, "bsr_vgg_per_loss: d_blob must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, "bsr_vgg_per_loss: sums must be 8-byte aligned");
+  return run_post("bsr_vgg_per_loss", {d_blob, gt, con_rgb, sums, loss1, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_vgg_per_loss(static_cast<const float*>(d_blob), gt, con_rgb, B, S, sums, loss1, scratch, static_cast<hipStream_t>(stream)));
     return BSR_OK;
   });
 }

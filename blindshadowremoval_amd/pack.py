@@ -546,3 +546,73 @@ def unpack_discriminators(blob: bytes):
         d["head"] = (rec["head/w"][:, :, None].copy(), rec["head/b"][:1].copy())
         out.append(d)
     return out
+
+
+# ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
+VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
+VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8
+
+
+def vgg_chunk(layer: int) -> int:
+    """Input channels per K chunk of vgg_conv_kernel: 8 for the first layer, 16 after it."""
+    return 8 if layer == 0 else 16
+
+
+def vgg_layout():
+    """([(name, offset in floats, shape)], floats in all).  Layer `block<b>_conv<i>` is stored as the kernel stages it, a block of 64
+    output channels and a chunk of CC input channels at a time: w [N / 64][C_in / CC][9 taps (a * 3 + b)][CC][64], then bias [N]; CC =
+    vgg_chunk(layer), the first layer's C_in padded with zeros to 8.  Every offset is a multiple of 4 floats."""
+    from .weights import VGG_LAYERS, vgg_variable_shapes
+    shapes = vgg_variable_shapes()
+    out, off = [], 0
+    for i, st in enumerate(VGG_LAYERS):
+        _, _, cin, n = shapes[st + "/kernel"]
+        cin = VGG_IN_C if i == 0 else cin
+        cc = vgg_chunk(i)
+        out.append((st + "/w", off, (n // VGG_NB, cin // cc, 9, cc, VGG_NB)))
+        off += 9 * cin * n
+        out.append((st + "/b", off, (n,)))
+        off += n
+    return out, off
+
+
+def pack_vgg(weights: Dict[str, np.ndarray]) -> bytes:
+    """The 26 VGG19 variables (weights.vgg_variable_shapes) -> the blob bsr_vgg_per_loss takes (vgg_layout)."""
+    from .weights import check_vgg_weights
+    check_vgg_weights(weights)
+    layout, total = vgg_layout()
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        st = name[:-2]
+        if name.endswith("/b"):
+            a = np.asarray(weights[st + "/bias"], np.float32)
+        else:
+            kern = np.asarray(weights[st + "/kernel"], np.float32)
+            nblk, nchunk, _, cc, _ = shape
+            full = np.zeros((9, nchunk * cc, kern.shape[3]), np.float32)
+            full[:, :kern.shape[2]] = kern.reshape(9, kern.shape[2], kern.shape[3])
+            a = full.reshape(9, nchunk, cc, nblk, VGG_NB).transpose(3, 1, 0, 2, 4)
+        assert a.shape == tuple(shape)
+        blob[off:off + a.size] = a.reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_vgg(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_vgg: the 26 variables (the first layer's kernel cut back to its 3 input channels)."""
+    from .weights import vgg_variable_shapes
+    layout, total = vgg_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a VGG19 blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    shapes = vgg_variable_shapes()
+    out = {}
+    for name, off, shape in layout:
+        a = arr[off:off + int(np.prod(shape))].reshape(shape)
+        st = name[:-2]
+        if name.endswith("/b"):
+            out[st + "/bias"] = a.copy()
+        else:
+            nblk, nchunk, _, cc, _ = shape
+            k = a.transpose(2, 1, 3, 0, 4).reshape(3, 3, nchunk * cc, nblk * VGG_NB)
+            out[st + "/kernel"] = k[:, :, :shapes[st + "/kernel"][2]].copy()
+    return out

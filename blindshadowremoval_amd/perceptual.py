@@ -1,0 +1,245 @@
+"""The VGG19 perceptual term of the reference's `train_step` and its two totals as a host statement: `per_loss =
+style_content_loss(self.feat_extractor, d_img)`, `g_total_loss` and `d_total_loss` (train_test_GSC.py:128-139, 153-160, 264, 301-310,
+336; utils.py:104-114), restated in numpy.  It plays the role for csrc/vgg_kernels.h (bsr_vgg_per_loss, perceptual_gpu.Perceptual) that
+discriminator.py plays for its chain.  training=True, every backward pass, the optimisers and a training loader are not here.
+
+INPUTS.  gt, con_rgb (deshadow_img_c) [B,S,S,3] float32; S in SIZES, B in 1..MAX_B.  The 26 variables are float32
+(weights.vgg_variable_shapes).
+
+THE INPUT ROWS.  d_img = concat([gt, con_rgb], axis 0): [2B,S,S,3], rows [0, B) real, rows [B, 2B) fake.
+
+PREPROCESSING.  tf.keras.applications.vgg19.preprocess_input(d_img * 255), which is "caffe" mode, in float32 with one rounding per
+operation and no fused multiply-add:  x = d_img * 255;  the channels reversed, RGB -> BGR;  the means [103.939, 116.779, 123.68]
+subtracted from B, G, R.  No scaling.  `preprocess` returns float32 [2B,S,S,3].
+
+THE ARCHITECTURE.  Keras' VGG19(include_top=False) up to block5_conv1 (weights.VGG_BLOCKS): blocks of 2, 2, 4, 4 and 1 layers with
+64, 128, 256, 512 and 512 channels, and a 2 x 2 stride-2 max pool ('valid'; every size here is even) after each of blocks 1 to 4.
+A layer is Conv2D(3 x 3, stride 1, padding 'same' = one row and column of zeros on every side) + bias + ReLU:
+  y[n, oy, ox, o] = max(0, sum_{a, b, c} x[n, oy + a - 1, ox + b - 1, c] k[a, b, c, o] + bias[o]),    positions outside the map reading 0,
+a cross-correlation with the HWIO kernel, in float64 arithmetic from the float32 input and variables.  At S = 32 the maps of the five
+blocks are 32, 16, 8, 4 and 2 on a side.  The five tapped features are the post-ReLU outputs of block{1..5}_conv1 (weights.VGG_TAPS);
+block5's other layers and pool are never computed.  `forward` returns every activation by name: `input` float32 [2B,S,S,3],
+`block<b>_conv<i>` and `block<b>_pool` float64.
+
+THE LOSS.  Each feature is split in two along the batch: real = feat[:B], fake = feat[B:].  With the features rounded to float32,
+every term |real - fake| is a float32; every sum is a float64 sum of those terms, kept per item as a row of PER_SUM_NAMES: [B, 5].  With
+t_k the batch total of tap k (the items' rows added in order), h_k = S / 2^(k-1) and C_k the tap's channels, in float64:
+  m_k = t_k / (B h_k^2 C_k)        (tf.reduce_mean(tf.abs(real - fake)), style_weight 1)
+  per = (((m_1 + m_2) + m_3) + m_4) + m_5,  rounded once to float32.
+
+THE TOTALS, float32 in the reference's order:
+  g_total_loss(recon_gs, recon_c, grad, gen, per) = ((recon * 400 + gen) + per * .005) + grad * 2,   recon = (recon_gs + recon_c) / 2
+  d_total_loss(disc_real, disc_fake)              = disc_real + disc_fake
+
+WHAT IS NOT PINNED.  The ImageNet weights are in no checkpoint of the reference and are not shipped: `weights.load_vgg_weights(path)`
+reads an `.npz` keyed `block<b>_conv<i>/kernel` (HWIO) and `block<b>_conv<i>/bias` (INTEGRATION.md shows how Keras' own weight file
+becomes one on a machine that has Keras), and `weights.init_vgg_weights(seed)` draws He-normal kernels for tests and benchmarks.  The
+architecture and the preprocessing are pinned to this restatement of Keras, not to Keras itself: tests/golden/perceptual_*.npz holds the
+reference's style_content_loss, vgg_feat_extractor and train_step's statements executed over a numpy stand-in whose VGG19 and
+preprocess_input are written from Keras' documentation (tools/make_perceptual_fixture.py).  TensorFlow convolves and reduces in float32
+in orders of its own.
+
+`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host]` evaluates the whole objective on
+a folder written by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling
+(train_losses.folder_steps): the six logged losses (recon_gs, recon_c, grad, gen, disc_real, disc_fake), per, g_total and d_total per
+batch and as step-weighted means.  The device route uses TrainLosses, Discriminators and Perceptual; --host the three host statements.
+"""
+from __future__ import annotations
+
+import contextlib
+import sys
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from .discriminator import conv2d_same
+from .shadow_synth import SIZES
+from .weights import VGG_BLOCKS, VGG_LAYERS, VGG_TAPS, init_vgg_weights, load_vgg_weights, vgg_variable_shapes  # noqa: F401
+
+f32 = np.float32
+MAX_B = 4096
+MEANS_BGR = (f32(103.939), f32(116.779), f32(123.68))
+PER_SUM_NAMES = tuple("l1_block%d" % b for b in range(1, 6))
+K = len(PER_SUM_NAMES)
+TAP_CH = tuple(ch for ch, _ in VGG_BLOCKS)
+LOGGED = ("recon_gs", "recon_c", "grad", "gen", "disc_real", "disc_fake")
+ALL_NAMES = LOGGED + ("per", "g_total", "d_total")
+SIZE_TEXT = "the perceptual term takes 1..4096 items of side 32, 64, 128 or 256, got B=%d S=%d"
+
+
+def tap_sides(S: int) -> List[int]:
+    """The sides h_k of the five tapped features."""
+    return [S >> k for k in range(K)]
+
+
+def check_inputs(gt, con_rgb) -> Tuple[int, int]:
+    g, c = np.asarray(gt), np.asarray(con_rgb)
+    if g.ndim != 4:
+        raise ValueError("perceptual: gt must be [B,S,S,3], got %s" % (g.shape,))
+    B, S = g.shape[:2]
+    if S not in SIZES or not 1 <= B <= MAX_B:
+        raise ValueError(SIZE_TEXT % (B, S))
+    for name, a in (("gt", g), ("con_rgb", c)):
+        if a.shape != (B, S, S, 3):
+            raise ValueError("perceptual: %s must be [%d,%d,%d,3] like gt, got %s" % (name, B, S, S, a.shape))
+    return B, S
+
+
+def preprocess(gt, con_rgb) -> np.ndarray:
+    """vgg19.preprocess_input(concat([gt, con_rgb]) * 255): float32 [2B,S,S,3], BGR, the means subtracted."""
+    x = np.concatenate([np.asarray(gt, f32), np.asarray(con_rgb, f32)], axis=0) * f32(255)
+    x = x[..., ::-1]
+    out = np.empty(x.shape, f32)
+    for c in range(3):
+        out[..., c] = x[..., c] - MEANS_BGR[c]
+    return out
+
+
+def conv_relu(weights: Dict[str, np.ndarray], name: str, x: np.ndarray) -> np.ndarray:
+    """Layer `name` (`block<b>_conv<i>`) on [N,H,W,C] -> float64 [N,H,W,O]."""
+    return np.maximum(conv2d_same(x, weights[name + "/kernel"], weights[name + "/bias"], 1), 0.0)
+
+
+def max_pool(x: np.ndarray) -> np.ndarray:
+    """2 x 2 stride-2 max pool of [N,H,W,C], H and W even."""
+    n, h, w, c = x.shape
+    return x.reshape(n, h // 2, 2, w // 2, 2, c).max(axis=(2, 4))
+
+
+def forward(weights: Dict[str, np.ndarray], gt, con_rgb) -> Dict[str, np.ndarray]:
+    """Every activation up to block5_conv1: `input`, `block<b>_conv<i>`, `block<b>_pool` (b = 1..4)."""
+    check_inputs(gt, con_rgb)
+    acts: Dict[str, np.ndarray] = {"input": preprocess(gt, con_rgb)}
+    h = acts["input"].astype(np.float64)
+    for b, (_, n) in enumerate(VGG_BLOCKS):
+        for i in range(n):
+            name = "block%d_conv%d" % (b + 1, i + 1)
+            h = conv_relu(weights, name, h)
+            acts[name] = h
+        if b < len(VGG_BLOCKS) - 1:
+            h = max_pool(h)
+            acts["block%d_pool" % (b + 1)] = h
+    return acts
+
+
+def features_of(acts: Dict[str, np.ndarray]) -> List[np.ndarray]:
+    """The five tapped features of `forward`'s result."""
+    return [np.asarray(acts[n]) for n in VGG_TAPS]
+
+
+def sums_from_features(feats) -> np.ndarray:
+    """Five features [2B,h_k,h_k,C_k] -> float64 [B,5] (PER_SUM_NAMES): per item the float64 sums of the float32 terms |real - fake|."""
+    B = np.asarray(feats[0]).shape[0] // 2
+    sums = np.zeros((B, K), np.float64)
+    for k, feat in enumerate(feats):
+        y = np.asarray(feat).astype(f32)
+        assert y.ndim == 4 and y.shape[0] == 2 * B
+        sums[:, k] = np.abs(y[:B] - y[B:]).reshape(B, -1).sum(axis=1, dtype=np.float64)
+    return sums
+
+
+def loss_from_sums(sums: np.ndarray, S: int) -> np.ndarray:
+    """float64 [B,5] and the input side -> float32 [1]: per over the whole batch."""
+    sums = np.asarray(sums, np.float64)
+    t = np.zeros(K, np.float64)
+    for row in sums:
+        t = t + row
+    m = [t[k] / (float(sums.shape[0]) * float(h * h * TAP_CH[k])) for k, h in enumerate(tap_sides(S))]
+    return np.array([(((m[0] + m[1]) + m[2]) + m[3]) + m[4]], np.float64).astype(f32)
+
+
+def per_loss(weights: Dict[str, np.ndarray], gt, con_rgb) -> Dict[str, np.ndarray]:
+    """Batches -> dict(loss float32 [1], sums float64 [B,5], acts: `forward`'s dict)."""
+    _, S = check_inputs(gt, con_rgb)
+    acts = forward(weights, gt, con_rgb)
+    sums = sums_from_features(features_of(acts))
+    return {"loss": loss_from_sums(sums, S), "sums": sums, "acts": acts}
+
+
+def g_total_loss(recon_gs, recon_c, grad, gen, per) -> np.float32:
+    """train_step's g_total_loss from its five float32 terms, in the reference's order."""
+    recon_gs, recon_c, grad, gen, per = (f32(v) for v in (recon_gs, recon_c, grad, gen, per))
+    recon = (recon_gs + recon_c) / f32(2)
+    return f32(f32(f32(recon * f32(400)) + gen) + f32(per * f32(.005))) + f32(grad * f32(2))
+
+
+def d_total_loss(disc_real, disc_fake) -> np.float32:
+    return f32(disc_real) + f32(disc_fake)
+
+
+def example_inputs(S: int, B: int, seed: int = 0):
+    """gt, con_rgb of train_losses.example_inputs(S, B, seed)."""
+    from .train_losses import example_inputs as ex
+    _, gt, _, _, con = ex(S, B, seed)
+    return gt, con
+
+
+# ---- the command-line entry
+def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
+                 quiet: bool = False) -> Dict[str, float]:
+    """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
+    of weights.load_vgg_weights; the discriminators' weights come from the latest checkpoint under `ckpt`, from
+    init_discriminator_weights without it."""
+    import torch
+    from . import discriminator as disc
+    from . import train_losses as tl
+    from .fsrnet import Logging
+    from .weights import init_discriminator_weights
+    vgg_w = load_vgg_weights(vgg)
+    if ckpt is not None:
+        from .tf_bundle import latest_checkpoint, load_discriminator_weights
+        prefix = latest_checkpoint(ckpt)
+        if prefix is None:
+            raise FileNotFoundError("perceptual: no checkpoint under %s" % ckpt)
+        disc_w = load_discriminator_weights(prefix)
+    else:
+        disc_w = init_discriminator_weights(1)
+    runners = None
+    acc: Dict[str, List[float]] = {}
+    dev = torch.device("cuda", device)
+    with contextlib.closing(tl.folder_steps(folder, ckpt, batch, device, "perceptual")) as batches:
+        for step, steps, im_d, gt_a, mask_a, gs, con_rgb in batches:
+            if host:
+                torch.cuda.synchronize(dev)
+                con_a = con_rgb.cpu().numpy()
+                three = tl.step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a)["losses"]
+                gan = disc.gan_losses(disc_w, gt_a, con_a, mask_a)["losses"]
+                per = per_loss(vgg_w, gt_a, con_a)["loss"]
+            else:
+                if runners is None:
+                    from .discriminator_gpu import Discriminators
+                    from .perceptual_gpu import Perceptual
+                    from .train_losses_gpu import TrainLosses
+                    runners = (TrainLosses(device), Discriminators(device), Perceptual(device))
+                    runners[1].load_weights(disc_w)
+                    runners[2].load_weights(vgg_w)
+                gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
+                three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
+                gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
+                per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
+            vals = [float(v) for v in three] + [float(v) for v in gan] + [float(per[0])]
+            vals.append(float(g_total_loss(three[0], three[1], three[2], gan[0], per[0])))
+            vals.append(float(d_total_loss(gan[1], gan[2])))
+            Logging.accumulate(acc, dict(zip(ALL_NAMES, vals)))
+            if not quiet:
+                print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in zip(ALL_NAMES, vals)), flush=True)
+    return {k: s / max(c, 1) for k, (s, c) in acc.items()}
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m blindshadowremoval_amd.perceptual",
+                                 description="Evaluate train_step's whole objective (six logged losses, per, g_total, d_total) on synthesised pairs.")
+    ap.add_argument("folder")
+    ap.add_argument("--vgg", required=True, help="the VGG19 variables as an .npz (weights.load_vgg_weights)")
+    ap.add_argument("--ckpt", default=None, help="checkpoint directory; without it the weights come from init_weights / init_discriminator_weights")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
+    a = ap.parse_args(argv)
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host)
+    print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -174,6 +174,68 @@ def check_discriminator_weights(weights: Dict[str, np.ndarray], n_layer: int = N
             raise ValueError("variable %s has shape %s, expected %s" % (k, tuple(np.shape(weights[k])), shp))
 
 
+# ---- VGG19 up to block5_conv1: the perceptual term's feature extractor (train_test_GSC.py:128-139) ----
+VGG_BLOCKS = ((64, 2), (128, 2), (256, 4), (512, 4), (512, 1))        # (channels, conv layers used) of block 1..5
+VGG_LAYERS = tuple("block%d_conv%d" % (b + 1, i + 1) for b, (_, n) in enumerate(VGG_BLOCKS) for i in range(n))
+VGG_TAPS = tuple("block%d_conv1" % b for b in range(1, 6))
+
+
+def vgg_variable_shapes() -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape for the 26 float32 variables of Keras' VGG19(include_top=False) up to block5_conv1, by Keras' layer names:
+    `block<b>_conv<i>/kernel` (HWIO, 3 x 3) and `block<b>_conv<i>/bias`."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    cin = 3
+    for b, (ch, n) in enumerate(VGG_BLOCKS):
+        for i in range(n):
+            st = "block%d_conv%d" % (b + 1, i + 1)
+            s[st + "/kernel"] = (3, 3, cin, ch)
+            s[st + "/bias"] = (ch,)
+            cin = ch
+    return s
+
+
+def init_vgg_weights(seed: int = 1) -> Dict[str, np.ndarray]:
+    """Seeded synthetic VGG19 variables for tests and benchmarks (the ImageNet weights are in no checkpoint): He-normal kernels
+    N(0, 2 / fan_in), biases N(0, 0.05^2)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, shp in vgg_variable_shapes().items():
+        if name.endswith("/kernel"):
+            out[name] = (rng.standard_normal(shp, dtype=np.float32) * np.float32(np.sqrt(2.0 / (shp[0] * shp[1] * shp[2])))).astype(np.float32)
+        else:
+            out[name] = (rng.standard_normal(shp) * 0.05).astype(np.float32)
+    return out
+
+
+def check_vgg_weights(weights: Dict[str, np.ndarray]) -> None:
+    """Raise ValueError if ``weights`` is not exactly vgg_variable_shapes()' variable set."""
+    spec = vgg_variable_shapes()
+    missing = [k for k in spec if k not in weights]
+    if missing:
+        raise ValueError("missing VGG19 variables: %s%s" % (missing[:4], " ..." if len(missing) > 4 else ""))
+    for k, shp in spec.items():
+        if tuple(np.shape(weights[k])) != tuple(shp):
+            raise ValueError("variable %s has shape %s, expected %s" % (k, tuple(np.shape(weights[k])), shp))
+
+
+def load_vgg_weights(path: str) -> Dict[str, np.ndarray]:
+    """An `.npz` with the keys of vgg_variable_shapes() (INTEGRATION.md shows how Keras' own weight file becomes one) -> the float32
+    variables.  ValueError unless it holds exactly those shapes; further keys are ignored."""
+    with np.load(path) as z:
+        missing = [k for k in vgg_variable_shapes() if k not in z.files]
+        if missing:
+            raise ValueError("%s: missing VGG19 variables: %s%s" % (path, missing[:4], " ..." if len(missing) > 4 else ""))
+        weights = {k: np.asarray(z[k], np.float32) for k in vgg_variable_shapes()}
+    check_vgg_weights(weights)
+    return weights
+
+
+def save_vgg_weights(path: str, weights: Dict[str, np.ndarray]) -> None:
+    """The inverse of load_vgg_weights."""
+    check_vgg_weights(weights)
+    np.savez(path, **{k: np.asarray(weights[k], np.float32) for k in vgg_variable_shapes()})
+
+
 # Kernel variance gains (x 1/fan_in).  1.6 roughly preserves variance through LeakyReLU(0.3); the
 # residual branches (``conv3``, ``non_local/w``) and the attention projections are damped so the six
 # bottleneck blocks neither blow activations up nor saturate the 1024-wide softmax — a trained

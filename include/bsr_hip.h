@@ -247,6 +247,25 @@ size_t bsr_disc_act_offset(int B, int S, int k, int layer);
 int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S,
                     double* sums, float* losses3, float* logits, void* scratch, void* stream);
 
+/* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
+ * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
+ * statement and writes the arithmetic out.  d_blob: the device copy of pack.pack_vgg's blob, blob_bytes = bsr_vgg_blob_bytes() (about
+ * 52 MB), 16-byte aligned.  gt, con_rgb [B][S][S][3] are dense float32 NHWC device tensors; the network sees rows [0, B) = gt (real) and
+ * [B, 2B) = con_rgb (fake).  Outputs: sums [B][5] float64, per item the float64 sums of the float32 terms |real - fake| over the
+ * post-ReLU outputs of block{1..5}_conv1 (perceptual.PER_SUM_NAMES); loss1 [1] float32 = the five means added in order over the whole
+ * batch.  The sums are taken in a fixed order (no floating-point atomics: a call repeats its bits).  scratch: bsr_vgg_scratch_bytes(B,
+ * S) bytes, 256-byte aligned; every word a launch reads is written earlier in the same call.  It holds every activation afterwards
+ * (5.5 GB at 32 items of 256 x 256): bsr_vgg_act_offset(B, S, layer) is the byte offset of map `layer` — 0 the preprocessed input
+ * [2B][S][S][8] (BGR, channels 3..7 zero), 1..13 the conv layers' post-ReLU outputs in the network's order, 14..17 the four pooled maps
+ * — and SIZE_MAX for arguments out of range.  S = 32, 64, 128 or 256, B = 1..4096 (0 from the size query otherwise).  Twenty launches on
+ * `stream`, one after the other, no host synchronisation.  A bad argument gives BSR_ERR_ARG with a message and nothing launched.
+ * ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_vgg_blob_bytes(void);
+size_t bsr_vgg_scratch_bytes(int B, int S);
+size_t bsr_vgg_act_offset(int B, int S, int layer);
+int bsr_vgg_per_loss(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, int B, int S, double* sums,
+                     float* loss1, void* scratch, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
