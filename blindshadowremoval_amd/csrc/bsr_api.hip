@@ -40,6 +40,7 @@
 #include "train_losses_kernels.h"
 #include "disc_kernels.h"
 #include "vgg_kernels.h"
+#include "vgg_grad_kernels.h"
 
 namespace {
 
@@ -1479,6 +1480,50 @@ int bsr_vgg_per_loss(int device, const void* d_blob, size_t blob_bytes, const fl
     HIP_TRY(bsr::launch_vgg_per_loss(static_cast<const float*>(d_blob), gt, con_rgb, B, S, sums, loss1, scratch, static_cast<hipStream_t>(stream)));
     return BSR_OK;
   });
+}
+
+size_t bsr_vgg_dgrad_blob_bytes(void) { return bsr::vgg_dgrad_w_off(bsr::kVggLayers) * sizeof(float); }
+
+size_t bsr_vgg_grad_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_grad_offset(B, S, 2) : 0; }
+
+size_t bsr_vgg_grad_offset(int B, int S, int which) {
+  if (!post_size_ok(B, S) || B > bsr::kVggMaxB || which < 0 || which > 1) return SIZE_MAX;
+  return bsr::vgg_grad_offset(B, S, which);
+}
+
+namespace {
+
+int vgg_per_loss_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                      const float* con_rgb, const float* upstream, int B, int S, double* sums, float* loss1, float* grad, void* scratch, int stop_after,
+                      void* stream) {
+  const std::string n(name);
+  if (B > bsr::kVggMaxB) return fail(BSR_ERR_ARG, n + ": B must be 1..4096");
+  if (blob_bytes != bsr_vgg_blob_bytes()) return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_vgg_blob_bytes() (pack.pack_vgg)");
+  if (dgrad_bytes != bsr_vgg_dgrad_blob_bytes()) return fail(BSR_ERR_ARG, n + ": dgrad_bytes must be bsr_vgg_dgrad_blob_bytes() (pack.pack_vgg_dgrad)");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(d_dgrad_blob) % 16 != 0)
+    return fail(BSR_ERR_ARG, n + ": d_blob and d_dgrad_blob must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, n + ": sums must be 8-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kVggGradLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..18");
+  return run_post(name, {d_blob, d_dgrad_blob, gt, con_rgb, sums, loss1, grad, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_vgg_per_loss_grad(static_cast<const float*>(d_blob), static_cast<const float*>(d_dgrad_blob), gt, con_rgb, upstream, B, S, sums, loss1,
+                                          grad, scratch, stop_after, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+}  // namespace
+
+int bsr_vgg_per_loss_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt, const float* con_rgb,
+                          const float* upstream, int B, int S, double* sums, float* loss1, float* grad, void* scratch, void* stream) {
+  return vgg_per_loss_grad("bsr_vgg_per_loss_grad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, gt, con_rgb, upstream, B, S, sums, loss1, grad, scratch,
+                           bsr::kVggGradLaunches, stream);
+}
+
+int bsr_debug_vgg_per_loss_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                                const float* con_rgb, const float* upstream, int B, int S, double* sums, float* loss1, float* grad, void* scratch, int stop_after,
+                                void* stream) {
+  return vgg_per_loss_grad("bsr_debug_vgg_per_loss_grad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, gt, con_rgb, upstream, B, S, sums, loss1, grad,
+                           scratch, stop_after, stream);
 }
 
 size_t bsr_png_file_bytes(int H, int W) {

@@ -14,8 +14,9 @@
 //                        channels are padded to 8): the 18 x 18 input patch of the chunk (halo included; padding and pixels outside the map
 //                        are stored as 0) and the chunk's [9][CC][64] weights go to LDS, and each tap reads the patch at a shifted address.
 //                        The NEXT chunk's global loads are issued into registers before the current chunk's 288 matrix instructions
-//                        and land behind them.  Epilogue: bias (bias_tile) + ReLU (leaky_relu_tile(acc, 0): negative values leave as
-//                        -0).  Output pixels outside the map are computed and not stored, so maps smaller than a tile, down to 2 x 2, take
+//                        and land behind them.  Epilogue (the template parameter Epi, here VggBiasRelu; vgg_grad_kernels.h runs the
+//                        same main loop with the data gradient's): bias (bias_tile) + ReLU (leaky_relu_tile(acc, 0): negative values
+//                        leave as -0).  Output pixels outside the map are computed and not stored, so maps smaller than a tile, down to 2 x 2, take
 //                        the same path.  The workgroup index runs over the 64-channel blocks fastest: the blocks of one tile run
 //                        together and share its patch through L2.  LDS: 22 KB + 36 KB.
 //   vgg_pool_kernel      x 4: 2 x 2 stride-2 max pool, a thread per four channels of an output pixel; exact.
@@ -91,15 +92,44 @@ __global__ __launch_bounds__(256) void vgg_input_kernel(const float* __restrict_
 }
 
 struct VggConvArgs {
-  const float* in;        // [2B][H][H][CIN]
-  float* out;             // [2B][H][H][N]
+  const float* in;        // [rows][H][H][CIN]
   const float* w;         // [N / 64][CIN / CC][9][CC][64]
-  const float* bias;      // [N]
   int H, CIN, N, tiles_x, tiles, nblk;      // tiles per row = tiles_x^2; nblk = N / 64
 };
 
-template <int CC>
-__global__ __launch_bounds__(256) void vgg_conv_kernel(const VggConvArgs a) {
+// What a wave of vgg_conv_kernel knows about its four accumulator tiles: acc[t][nt][i] is pixel (oy0 + wave * 4 + t * 2 + (mr >> 4),
+// ox0 + (mr & 15)), mr = (i & 3) + 8 * (i >> 2) + 4 * kh, of network row `row`, channel nb * 64 + nt * 32 + m.
+struct VggTilePos {
+  int row, oy0, ox0, wave, kh, m, nb, H, N;
+};
+
+// The forward layer's epilogue: the accumulators start as the bias (bias_tile) and leave through ReLU (leaky_relu_tile(acc, 0):
+// negative values leave as -0).
+struct VggBiasRelu {
+  float* out;             // [rows][H][H][N]
+  const float* bias;      // [N]
+  __device__ __forceinline__ f32x16 init(int kh, int ch) const { return bias_tile(kh, bias[ch]); }
+  __device__ __forceinline__ void finish(f32x16 (&acc)[2][2], const VggTilePos& p) const {
+    const int H = p.H, N = p.N, kh = p.kh, m = p.m, wave = p.wave, oy0 = p.oy0, ox0 = p.ox0;
+    float* out = this->out + (size_t)p.row * H * H * N + p.nb * kVggNB;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        leaky_relu_tile(acc[t][nt], 0.f);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int mr = (i & 3) + 8 * (i >> 2) + 4 * kh;                  // the accumulator's row: pixel mr of the M tile
+          const int oy = oy0 + wave * 4 + t * 2 + (mr >> 4), ox = ox0 + (mr & 15);
+          if (oy < H && ox < H) out[((size_t)oy * H + ox) * N + nt * 32 + m] = acc[t][nt][i];
+        }
+      }
+  }
+};
+
+// Epi: how the accumulators start and leave (VggBiasRelu here; the data gradient's, VggGradEpilogue, in vgg_grad_kernels.h).
+template <int CC, class Epi>
+__global__ __launch_bounds__(256) void vgg_conv_kernel(const VggConvArgs a, const Epi epi) {
   static_assert(CC == 8 || CC == 16, "chunk");
   constexpr int Ld = CC + 1, Q = CC / 4;
   constexpr int PN = kVggPH * kVggPW * Q, PIT = (PN + 255) / 256;          // f32x4 of the patch, per thread
@@ -123,8 +153,8 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(const VggConvArgs a) {
   f32x16 acc[2][2];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
-    acc[0][nt] = bias_tile(kh, a.bias[nb * kVggNB + nt * 32 + m]);
-    acc[1][nt] = bias_tile(kh, a.bias[nb * kVggNB + nt * 32 + m]);
+    acc[0][nt] = epi.init(kh, nb * kVggNB + nt * 32 + m);
+    acc[1][nt] = epi.init(kh, nb * kVggNB + nt * 32 + m);
   }
 
   // where this thread's patch words come from (-1: padding or outside the map) — the same for every chunk but for + c0
@@ -182,19 +212,7 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(const VggConvArgs a) {
       }
     }
   }
-  float* out = a.out + (size_t)row * H * H * N + nb * kVggNB;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      leaky_relu_tile(acc[t][nt], 0.f);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int mr = (i & 3) + 8 * (i >> 2) + 4 * kh;                    // the accumulator's row: pixel mr of the M tile
-        const int oy = oy0 + wave * 4 + t * 2 + (mr >> 4), ox = ox0 + (mr & 15);
-        if (oy < H && ox < H) out[((size_t)oy * H + ox) * N + nt * 32 + m] = acc[t][nt][i];
-      }
-    }
+  epi.finish(acc, VggTilePos{row, oy0, ox0, wave, kh, m, nb, H, N});
 }
 
 // in [rows][2h][2h][C] -> out [rows][h][h][C]; a thread per four channels of an output pixel
@@ -267,6 +285,19 @@ __global__ __launch_bounds__(256) void vgg_finish_kernel(const VggL1Args a, int 
   if (tid == 0) loss1[0] = (float)((((s_t[0] + s_t[1]) + s_t[2]) + s_t[3]) + s_t[4]);
 }
 
+inline VggConvArgs vgg_conv_args(const float* in, const float* w, int H, int CIN, int N) {
+  VggConvArgs a;
+  a.in = in;
+  a.w = w;
+  a.H = H;
+  a.CIN = CIN;
+  a.N = N;
+  a.tiles_x = (H + kVggTW - 1) / kVggTW;
+  a.tiles = a.tiles_x * a.tiles_x;
+  a.nblk = N / kVggNB;
+  return a;
+}
+
 inline hipError_t launch_vgg_per_loss(const float* blob, const float* gt, const float* con, int B, int S, double* sums, float* loss1, void* scratch,
                                       hipStream_t stream) {
   const size_t pixels = (size_t)2 * B * S * S;
@@ -283,20 +314,11 @@ inline hipError_t launch_vgg_per_loss(const float* blob, const float* gt, const 
       if ((e = hipGetLastError()) != hipSuccess) return e;
       src = dst;
     }
-    VggConvArgs a;
-    a.in = vgg_map(scratch, B, S, src);
-    a.out = vgg_map(scratch, B, S, i + 1);
-    a.w = blob + vgg_w_off(i);
-    a.bias = a.w + (size_t)9 * vgg_cin(i) * vgg_ch(i);
-    a.H = vgg_side(S, i);
-    a.CIN = vgg_cin(i);
-    a.N = vgg_ch(i);
-    a.tiles_x = (a.H + kVggTW - 1) / kVggTW;
-    a.tiles = a.tiles_x * a.tiles_x;
-    a.nblk = a.N / kVggNB;
+    const VggConvArgs a = vgg_conv_args(vgg_map(scratch, B, S, src), blob + vgg_w_off(i), vgg_side(S, i), vgg_cin(i), vgg_ch(i));
+    const VggBiasRelu epi{vgg_map(scratch, B, S, i + 1), a.w + (size_t)9 * vgg_cin(i) * vgg_ch(i)};
     const dim3 grid((unsigned)(2 * B) * (unsigned)a.tiles * (unsigned)a.nblk);
-    if (i == 0) hipLaunchKernelGGL((vgg_conv_kernel<8>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((vgg_conv_kernel<16>), grid, dim3(256), 0, stream, a);
+    if (i == 0) hipLaunchKernelGGL((vgg_conv_kernel<8, VggBiasRelu>), grid, dim3(256), 0, stream, a, epi);
+    else hipLaunchKernelGGL((vgg_conv_kernel<16, VggBiasRelu>), grid, dim3(256), 0, stream, a, epi);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     src = i + 1;
   }

@@ -576,6 +576,40 @@ def vgg_layout():
     return out, off
 
 
+def vgg_dgrad_layout():
+    """([(name, offset in floats, shape)], floats in all) of the gradient layers' blob (csrc/vgg_grad_kernels.h).  The data gradient of
+    layer `block<b>_conv<i>` is a 3 x 3 SAME convolution from its C' = C_out to its N' = C_in channels, stored like vgg_layout's w in
+    chunks of 16: [N' / 64][C' / 16][9 taps (a * 3 + b)][16][64]; the first layer's N' = 3 is padded with zeros to one 64-block.  No
+    bias."""
+    from .weights import VGG_LAYERS, vgg_variable_shapes
+    shapes = vgg_variable_shapes()
+    out, off = [], 0
+    for st in VGG_LAYERS:
+        _, _, cin, n = shapes[st + "/kernel"]
+        npad = -(-cin // VGG_NB) * VGG_NB
+        out.append((st + "/dgrad", off, (npad // VGG_NB, n // 16, 9, 16, VGG_NB)))
+        off += 9 * n * npad
+    return out, off
+
+
+def pack_vgg_dgrad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The VGG19 kernels -> the blob bsr_vgg_per_loss_grad takes beside pack_vgg's (vgg_dgrad_layout): per layer
+    k'[a, b, o, c] = k[2 - a, 2 - b, c, o], the taps turned by 180 degrees and the channel roles swapped."""
+    from .weights import check_vgg_weights
+    check_vgg_weights(weights)
+    layout, total = vgg_dgrad_layout()
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        kern = np.asarray(weights[name[:-len("/dgrad")] + "/kernel"], np.float32)
+        nblk, nchunk, _, cc, _ = shape
+        full = np.zeros((9, kern.shape[3], nblk * VGG_NB), np.float32)
+        full[:, :, :kern.shape[2]] = kern[::-1, ::-1].transpose(0, 1, 3, 2).reshape(9, kern.shape[3], kern.shape[2])
+        a = full.reshape(9, nchunk, cc, nblk, VGG_NB).transpose(3, 1, 0, 2, 4)
+        assert a.shape == tuple(shape)
+        blob[off:off + a.size] = a.reshape(-1)
+    return blob.tobytes()
+
+
 def pack_vgg(weights: Dict[str, np.ndarray]) -> bytes:
     """The 26 VGG19 variables (weights.vgg_variable_shapes) -> the blob bsr_vgg_per_loss takes (vgg_layout)."""
     from .weights import check_vgg_weights

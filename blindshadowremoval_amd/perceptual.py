@@ -1,7 +1,8 @@
 """The VGG19 perceptual term of the reference's `train_step` and its two totals as a host statement: `per_loss =
 style_content_loss(self.feat_extractor, d_img)`, `g_total_loss` and `d_total_loss` (train_test_GSC.py:128-139, 153-160, 264, 301-310,
 336; utils.py:104-114), restated in numpy.  It plays the role for csrc/vgg_kernels.h (bsr_vgg_per_loss, perceptual_gpu.Perceptual) that
-discriminator.py plays for its chain.  training=True, every backward pass, the optimisers and a training loader are not here.
+discriminator.py plays for its chain, and the term's data gradient d per / d con_rgb (THE BACKWARD below; bsr_vgg_per_loss_grad,
+csrc/vgg_grad_kernels.h).  training=True, every other backward pass, weight gradients, the optimisers and a training loader are not here.
 
 INPUTS.  gt, con_rgb (deshadow_img_c) [B,S,S,3] float32; S in SIZES, B in 1..MAX_B.  The 26 variables are float32
 (weights.vgg_variable_shapes).
@@ -39,10 +40,31 @@ reference's style_content_loss, vgg_feat_extractor and train_step's statements e
 preprocess_input are written from Keras' documentation (tools/make_perceptual_fixture.py).  TensorFlow convolves and reduces in float32
 in orders of its own.
 
-`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host]` evaluates the whole objective on
+THE BACKWARD: d per / d con_rgb (`per_loss_grad`).  VGG19 is frozen (`vgg.trainable = False`, train_test_GSC.py:156) and gt is a constant, so
+the data gradient with respect to con_rgb is the whole backward of the term; only the network's rows [B, 2B) are differentiated.  It is
+pinned to this restatement of TensorFlow's gradient definitions, as the forward is pinned to a restatement of Keras: there is no
+GradientTape stand-in to execute the reference's text over.  In float64 from the float32 variables, from the top down:
+  seeds            d per / d fake_k = sign(fake_k - real_k) w_k,  w_k = float32(1 / (B h_k^2 C_k)),  sign(0) = 0 (TensorFlow's gradient of
+                   tf.abs), the sign taken from the float32 features as the forward's |real - fake| terms are.
+  relu_mask        g [y > 0] (ReluGrad): nothing passes at y == 0, so the device's -0 counts as 0.
+  conv_dgrad       the data gradient of the layer's cross-correlation:
+                     gx[n, iy, ix, c] = sum_{a, b, o} gy[n, iy - a + 1, ix - b + 1, o] k[a, b, c, o],    positions outside the map reading 0,
+                   itself a 3 x 3 stride-1 SAME cross-correlation with the taps turned by 180 degrees and the channel roles swapped.
+  max_pool_grad    each window's gradient goes to its first maximum in row-major order of the window (TensorFlow's kernels and torch
+                   agree), zeros elsewhere.
+At each block{k}_conv1 output the seed is added to the gradient arriving from deeper layers before the mask; block5_conv1 gets the seed
+alone.  Through the preprocessing, with g_bgr the gradient at the network's input rounded to float32:
+  grad[..., c] = (float32(255) g_bgr[..., 2 - c]) upstream,    float32 multiplies in that order, upstream 1 by default.
+With `acts` given (a dict like `forward`'s, for example the device's kept activations) the masks, the pooling winners and the signs are
+read from it instead of from the statement's own float64 forward, so that a comparison with the device is free of mask flips at values
+that round across 0.  `per_loss_f64` is the same objective with no float32 rounding anywhere, for finite differences.
+
+`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad]` evaluates the whole objective on
 a folder written by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling
 (train_losses.folder_steps): the six logged losses (recon_gs, recon_c, grad, gen, disc_real, disc_fake), per, g_total and d_total per
 batch and as step-weighted means.  The device route uses TrainLosses, Discriminators and Perceptual; --host the three host statements.
+With --grad each batch's line also carries per_grad_l1 and per_grad_linf, the L1 and L-infinity norms of 0.005 d per / d con_rgb: the
+share of g_total_loss' gradient that this term contributes (Perceptual.per_loss_grad with upstream 0.005; --host: per_loss_grad).
 """
 from __future__ import annotations
 
@@ -156,6 +178,107 @@ def per_loss(weights: Dict[str, np.ndarray], gt, con_rgb) -> Dict[str, np.ndarra
     return {"loss": loss_from_sums(sums, S), "sums": sums, "acts": acts}
 
 
+# ---- the backward: d per / d con_rgb
+GRAD_NAMES = ("per_grad_l1", "per_grad_linf")
+PER_WEIGHT = f32(.005)                # per_loss' weight in g_total_loss
+
+
+def tap_weights(B: int, S: int) -> List[np.float32]:
+    """w_k = float32(1 / (B h_k^2 C_k)), k = 1..5."""
+    return [f32(1.0 / (float(B) * float(h * h * TAP_CH[k]))) for k, h in enumerate(tap_sides(S))]
+
+
+def seeds(feats, B: int) -> List[np.ndarray]:
+    """Five features [2B,h_k,h_k,C_k] -> five float32 [B,h_k,h_k,C_k]: d per / d fake_k = sign(fake_k - real_k) w_k, sign(0) = 0."""
+    S = np.asarray(feats[0]).shape[1]
+    out = []
+    for k, (feat, w) in enumerate(zip(feats, tap_weights(B, S))):
+        y = np.asarray(feat).astype(f32)
+        assert y.ndim == 4 and y.shape[0] == 2 * B
+        out.append(np.sign(y[B:] - y[:B]).astype(f32) * w)
+    return out
+
+
+def conv_dgrad(weights: Dict[str, np.ndarray], name: str, g: np.ndarray) -> np.ndarray:
+    """The gradient [N,H,W,O] at layer `name`'s convolution output -> float64 [N,H,W,C] at its input."""
+    kernel = np.asarray(weights[name + "/kernel"], np.float64)
+    g = np.asarray(g, np.float64)
+    n, h, w, _ = g.shape
+    gp = np.zeros((n, h + 2, w + 2, g.shape[3]), np.float64)
+    gp[:, 1:1 + h, 1:1 + w] = g
+    out = np.zeros((n, h, w, kernel.shape[2]), np.float64)
+    for a in range(3):
+        for b in range(3):
+            out += gp[:, 2 - a:2 - a + h, 2 - b:2 - b + w] @ kernel[a, b].T
+    return out
+
+
+def relu_mask(g: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """g [y > 0]: ReluGrad on the layer's post-ReLU output y."""
+    return np.where(np.asarray(y) > 0, g, np.zeros((), np.asarray(g).dtype))
+
+
+def max_pool_grad(g: np.ndarray, x: np.ndarray) -> np.ndarray:
+    """The gradient [N,h,w,C] at max_pool(x)'s output -> [N,2h,2w,C] at x: each window's value at its first maximum in row-major order."""
+    g, x = np.asarray(g), np.asarray(x)
+    n, h, w, c = g.shape
+    assert x.shape == (n, 2 * h, 2 * w, c)
+    win = x.reshape(n, h, 2, w, 2, c).transpose(0, 1, 3, 5, 2, 4).reshape(n, h, w, c, 4)
+    first = np.argmax(win, axis=-1)                      # numpy's argmax is the first maximum; -0 and 0 compare equal
+    out = np.zeros((n, h, w, c, 4), g.dtype)
+    np.put_along_axis(out, first[..., None], g[..., None], axis=-1)
+    return out.reshape(n, h, w, c, 2, 2).transpose(0, 1, 4, 2, 5, 3).reshape(n, 2 * h, 2 * w, c)
+
+
+def input_grad(g_bgr: np.ndarray, upstream=None) -> np.ndarray:
+    """The gradient at the network's input [B,S,S,3] (BGR) -> float32 d / d con_rgb: (255 g_bgr[2 - c]) upstream in float32."""
+    up = f32(1) if upstream is None else f32(np.asarray(upstream).reshape(-1)[0])
+    return (f32(255) * np.asarray(g_bgr).astype(f32)[..., ::-1]) * up
+
+
+def per_loss_grad(weights: Dict[str, np.ndarray], gt, con_rgb, upstream=None, acts=None) -> Dict[str, np.ndarray]:
+    """`per_loss`'s dict plus `grad`: float32 [B,S,S,3] = d per / d con_rgb * upstream (a float32, 1 without it), and `grad_input`:
+    float64 [B,S,S,3], the gradient at the network's input (BGR) before any float32 rounding.  Without `acts` the
+    masks, pooling winners and signs come from the statement's own float64 forward; with `acts` from it, and `loss` and `sums` are
+    then those of its features."""
+    B, S = check_inputs(gt, con_rgb)
+    if acts is None:
+        res = per_loss(weights, gt, con_rgb)
+    else:
+        sums = sums_from_features(features_of(acts))
+        res = {"loss": loss_from_sums(sums, S), "sums": sums, "acts": acts}
+    A = res["acts"]
+    seed = dict(zip(VGG_TAPS, seeds(features_of(A), B)))
+    g = None
+    for i in reversed(range(len(VGG_LAYERS))):
+        name = VGG_LAYERS[i]
+        if name in seed:
+            g = seed[name].astype(np.float64) if g is None else g + seed[name]
+        g = conv_dgrad(weights, name, relu_mask(g, np.asarray(A[name])[B:]))
+        if i > 0 and name.endswith("conv1"):
+            g = max_pool_grad(g, np.asarray(A[VGG_LAYERS[i - 1]])[B:])
+    res = dict(res)
+    res["grad_input"] = g
+    res["grad"] = input_grad(g, upstream)
+    return res
+
+
+def per_loss_f64(weights: Dict[str, np.ndarray], gt, con_rgb) -> float:
+    """per as a function of float64 images with no float32 rounding anywhere (the variables are still the float32 ones): what
+    per_loss_grad differentiates, for finite differences."""
+    x = np.concatenate([np.asarray(gt, np.float64), np.asarray(con_rgb, np.float64)], axis=0) * 255.0
+    h = x[..., ::-1] - np.array([float(m) for m in MEANS_BGR])
+    B, per = x.shape[0] // 2, 0.0
+    for b, (_, n) in enumerate(VGG_BLOCKS):
+        for i in range(n):
+            h = conv_relu(weights, "block%d_conv%d" % (b + 1, i + 1), h)
+            if i == 0:
+                per = per + float(np.abs(h[:B] - h[B:]).mean())
+        if b < len(VGG_BLOCKS) - 1:
+            h = max_pool(h)
+    return per
+
+
 def g_total_loss(recon_gs, recon_c, grad, gen, per) -> np.float32:
     """train_step's g_total_loss from its five float32 terms, in the reference's order."""
     recon_gs, recon_c, grad, gen, per = (f32(v) for v in (recon_gs, recon_c, grad, gen, per))
@@ -175,11 +298,18 @@ def example_inputs(S: int, B: int, seed: int = 0):
 
 
 # ---- the command-line entry
+def grad_norms(grad) -> List[float]:
+    """GRAD_NAMES of a gradient that already carries PER_WEIGHT: the sum and the largest of its magnitudes, in float64."""
+    g = np.abs(np.asarray(grad, np.float64))
+    return [float(g.sum()), float(g.max())]
+
+
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False) -> Dict[str, float]:
+                 quiet: bool = False, grad: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the discriminators' weights come from the latest checkpoint under `ckpt`, from
-    init_discriminator_weights without it."""
+    init_discriminator_weights without it.  With `grad` each batch's line also carries GRAD_NAMES, the norms of PER_WEIGHT d per / d con_rgb
+    (they are per batch, not part of the means)."""
     import torch
     from . import discriminator as disc
     from . import train_losses as tl
@@ -194,7 +324,7 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         disc_w = load_discriminator_weights(prefix)
     else:
         disc_w = init_discriminator_weights(1)
-    runners = None
+    runners = weight_d = None
     acc: Dict[str, List[float]] = {}
     dev = torch.device("cuda", device)
     with contextlib.closing(tl.folder_steps(folder, ckpt, batch, device, "perceptual")) as batches:
@@ -204,7 +334,11 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                 con_a = con_rgb.cpu().numpy()
                 three = tl.step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a)["losses"]
                 gan = disc.gan_losses(disc_w, gt_a, con_a, mask_a)["losses"]
-                per = per_loss(vgg_w, gt_a, con_a)["loss"]
+                if grad:
+                    res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
+                    per, norms = res["loss"], grad_norms(res["grad"])
+                else:
+                    per = per_loss(vgg_w, gt_a, con_a)["loss"]
             else:
                 if runners is None:
                     from .discriminator_gpu import Discriminators
@@ -216,13 +350,20 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                 gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
                 three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
                 gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
-                per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
+                if grad:
+                    if weight_d is None:
+                        weight_d = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=dev)
+                    res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
+                    per, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
+                else:
+                    per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
             vals = [float(v) for v in three] + [float(v) for v in gan] + [float(per[0])]
             vals.append(float(g_total_loss(three[0], three[1], three[2], gan[0], per[0])))
             vals.append(float(d_total_loss(gan[1], gan[2])))
             Logging.accumulate(acc, dict(zip(ALL_NAMES, vals)))
             if not quiet:
-                print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in zip(ALL_NAMES, vals)), flush=True)
+                shown = list(zip(ALL_NAMES, vals)) + (list(zip(GRAD_NAMES, norms)) if grad else [])
+                print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in shown), flush=True)
     return {k: s / max(c, 1) for k, (s, c) in acc.items()}
 
 
@@ -235,8 +376,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ckpt", default=None, help="checkpoint directory; without it the weights come from init_weights / init_discriminator_weights")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
+    ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
     a = ap.parse_args(argv)
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host)
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

@@ -43,13 +43,15 @@ class PostDevice:
     def empty(self, shape, dtype) -> torch.Tensor:
         return torch.empty(shape, dtype=dtype, device=self._dev)
 
-    def call(self, *args) -> None:
-        """`SYMBOL`(device, *args, current stream): tensors go as their device addresses, None as a null pointer.  Asynchronous."""
+    def call(self, *args, symbol: Optional[str] = None) -> None:
+        """`SYMBOL` (or `symbol`)(device, *args, current stream): tensors go as their device addresses, None as a null pointer.
+        Asynchronous."""
         lib = _lib.load()
+        symbol = symbol or self.SYMBOL
         ptrs = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
         with torch.cuda.device(self.device):
-            rc = getattr(lib, self.SYMBOL)(self.device, *ptrs, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, self.SYMBOL)
+            rc = getattr(lib, symbol)(self.device, *ptrs, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, symbol)
 
 
 def raise_for_status(status, names: Optional[Sequence[str]], texts: Dict[int, str], prefix: str, other: str = "status %d",

@@ -266,6 +266,30 @@ size_t bsr_vgg_act_offset(int B, int S, int layer);
 int bsr_vgg_per_loss(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, int B, int S, double* sums,
                      float* loss1, void* scratch, void* stream);
 
+/* bsr_vgg_per_loss and its data gradient d per_loss / d con_rgb in one call (blindshadowremoval_amd/perceptual.py: per_loss_grad is the
+ * host statement).  VGG19 is frozen and gt is a constant, so this is the whole backward of the term: no weight gradient, no state.
+ * d_dgrad_blob: the device copy of pack.pack_vgg_dgrad's blob, dgrad_bytes = bsr_vgg_dgrad_blob_bytes() (per layer the taps turned by
+ * 180 degrees and the channel roles swapped, no bias), 16-byte aligned.  upstream: a device float32[1] the gradient is multiplied by, or
+ * NULL for 1.  Outputs: sums and loss1 exactly as bsr_vgg_per_loss writes them (the same launches), and grad [B][S][S][3] float32 =
+ * (255 * d per / d bgr[2 - c]) * upstream.  The forward's 20 launches, then 18 more on `stream`, one after the other: the seed at
+ * block5_conv1, thirteen data-gradient convolutions (the forward kernel's main loop on B rows) and four un-pools; no host
+ * synchronisation, no second stream, no floating-point atomics: a call repeats its bits.  scratch: bsr_vgg_grad_scratch_bytes(B, S)
+ * bytes, 256-byte aligned = the forward's scratch, unchanged (bsr_vgg_act_offset keeps its values), followed by two gradient buffers
+ * at bsr_vgg_grad_offset(B, S, 0 / 1) of B * S * S * 64 floats each (SIZE_MAX for arguments out of range); every word read is written
+ * earlier in the same call.  Sizes and errors as bsr_vgg_per_loss.  bsr_debug_vgg_per_loss_grad stops after `stop_after` (0..18) of
+ * the backward launches, whose order is: seed, then for layer 13 down to 1 its gradient convolution, followed by the un-pool where the
+ * layer is the first of its block; launch j = 1..17 writes buffer (j - 1) & 1, launch 18 writes grad.  For the tests' stage-by-stage
+ * comparison.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_vgg_dgrad_blob_bytes(void);
+size_t bsr_vgg_grad_scratch_bytes(int B, int S);
+size_t bsr_vgg_grad_offset(int B, int S, int which);
+int bsr_vgg_per_loss_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                          const float* con_rgb, const float* upstream, int B, int S, double* sums, float* loss1, float* grad, void* scratch,
+                          void* stream);
+int bsr_debug_vgg_per_loss_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes,
+                                const float* gt, const float* con_rgb, const float* upstream, int B, int S, double* sums, float* loss1,
+                                float* grad, void* scratch, int stop_after, void* stream);
+
 /* The output sink of the reference's loops on the device: replaces `cv2.imwrite(fname, strip)` of Logging.save_img
  * (/root/reference/utils.py:196-204; called per item from train_test_GSC.py:744-746 and :889-890) up to the write() itself.
  * pixels: [B,H,W,3] uint8 RGB strips (device).  out: B complete PNG FILE images, out_stride bytes apart (device or device-mapped
