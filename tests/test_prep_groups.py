@@ -9,7 +9,7 @@ import pytest
 
 from blindshadowremoval_amd import dataset as D
 from blindshadowremoval_amd import prep
-from test_prep_gpu import emulate
+from prep_cases import emulate
 from tsm_group_cases import make_edges, sfw_labels, ucb_items
 
 
@@ -110,7 +110,7 @@ def test_group_blob_layout_round_trips():
 
 
 def _emulate_group(part, size):
-    """numpy statement of csrc/prep_group_kernels.h for one group, on test_prep_gpu.emulate (the row kernel's statement)."""
+    """numpy statement of csrc/prep_group_kernels.h for one group, on prep_cases.emulate (the row kernel's statement)."""
     img, gt, box, tabs = part[:4]
     r0 = emulate((img, gt, box, tabs[:4], b""), size)
     r1 = emulate((img, gt, box, tabs[4:], b""), size)
