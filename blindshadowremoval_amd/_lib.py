@@ -24,7 +24,8 @@ EXPORTS = ("bsr_create", "bsr_forward", "bsr_forward_tsm", "bsr_workspace_bytes"
            "bsr_png_unfilter_tall", "bsr_crop_faces", "bsr_paste_faces", "bsr_shadow_synth_scratch_bytes", "bsr_shadow_synth",
            "bsr_train_losses_scratch_bytes", "bsr_train_losses", "bsr_disc_blob_bytes", "bsr_disc_losses_scratch_bytes", "bsr_disc_act_offset",
            "bsr_disc_losses", "bsr_vgg_blob_bytes", "bsr_vgg_scratch_bytes", "bsr_vgg_act_offset", "bsr_vgg_per_loss",
-           "bsr_vgg_dgrad_blob_bytes", "bsr_vgg_grad_scratch_bytes", "bsr_vgg_grad_offset", "bsr_vgg_per_loss_grad", "bsr_debug_vgg_per_loss_grad")
+           "bsr_vgg_dgrad_blob_bytes", "bsr_vgg_grad_scratch_bytes", "bsr_vgg_grad_offset", "bsr_vgg_per_loss_grad", "bsr_debug_vgg_per_loss_grad",
+           "bsr_disc_dgrad_blob_bytes", "bsr_disc_grad_scratch_bytes", "bsr_disc_grad_offset", "bsr_disc_gen_grad", "bsr_debug_disc_gen_grad")
 
 
 def load() -> ctypes.CDLL:
@@ -173,6 +174,20 @@ def load() -> ctypes.CDLL:
     lib.bsr_vgg_grad_scratch_bytes.restype = c_sz
     lib.bsr_vgg_grad_offset.restype = c_sz
     lib.bsr_vgg_dgrad_blob_bytes.restype = c_sz
+    try:
+        lib.bsr_disc_gen_grad.argtypes = [c_i, c_v, c_sz, c_v, c_sz, c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v]
+        lib.bsr_debug_disc_gen_grad.argtypes = [c_i, c_v, c_sz, c_v, c_sz, c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_v]
+        lib.bsr_disc_grad_scratch_bytes.argtypes = [c_i, c_i]
+        lib.bsr_disc_grad_offset.argtypes = [c_i, c_i, c_i, c_i]
+        lib.bsr_disc_dgrad_blob_bytes.argtypes = []
+    except AttributeError:                  # added under ABI 8 after bsr_vgg_per_loss_grad
+        raise RuntimeError("libbsr_hip.so has no bsr_disc_gen_grad: rebuild (`python -c 'import __graft_entry__ as g; g.build()'`); "
+                           "there is no fallback") from None
+    lib.bsr_disc_gen_grad.restype = c_i
+    lib.bsr_debug_disc_gen_grad.restype = c_i
+    lib.bsr_disc_grad_scratch_bytes.restype = c_sz
+    lib.bsr_disc_grad_offset.restype = c_sz
+    lib.bsr_disc_dgrad_blob_bytes.restype = c_sz
     lib.bsr_check_range.argtypes = [c_v, c_v]
     lib.bsr_check_range.restype = c_i
     lib.bsr_png_file_bytes.argtypes = [c_i, c_i]

@@ -39,6 +39,7 @@
 #include "shadow_synth_kernels.h"
 #include "train_losses_kernels.h"
 #include "disc_kernels.h"
+#include "disc_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1459,6 +1460,52 @@ int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const flo
                                     static_cast<hipStream_t>(stream)));
     return BSR_OK;
   });
+}
+
+size_t bsr_disc_dgrad_blob_bytes(void) { return 3 * bsr::disc_dgrad_w_off(bsr::kDiscLayers) * sizeof(float); }
+
+size_t bsr_disc_grad_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kDiscMaxB ? bsr::disc_grad_offset(B, S, 3, 0) : 0; }
+
+size_t bsr_disc_grad_offset(int B, int S, int k, int layer) {
+  if (!post_size_ok(B, S) || B > bsr::kDiscMaxB || k < 1 || k > 3 || layer < 0 || layer > bsr::kDiscLayers) return SIZE_MAX;
+  return bsr::disc_grad_offset(B, S, k - 1, layer);
+}
+
+namespace {
+
+int disc_gen_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                  const float* con_rgb, const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3, float* logits, float* grad,
+                  void* scratch, int stop_after, void* stream) {
+  const std::string n(name);
+  if (B > bsr::kDiscMaxB) return fail(BSR_ERR_ARG, n + ": B must be 1..32767");
+  if (blob_bytes != bsr_disc_blob_bytes()) return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_disc_blob_bytes() (pack.pack_discriminators)");
+  if (dgrad_bytes != bsr_disc_dgrad_blob_bytes())
+    return fail(BSR_ERR_ARG, n + ": dgrad_bytes must be bsr_disc_dgrad_blob_bytes() (pack.pack_discriminators_dgrad)");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(d_dgrad_blob) % 16 != 0)
+    return fail(BSR_ERR_ARG, n + ": d_blob and d_dgrad_blob must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, n + ": sums must be 8-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kDiscGradLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..6");
+  return run_post(name, {d_blob, d_dgrad_blob, gt, con_rgb, mask_sv, sums, losses3, grad, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_disc_gen_grad(static_cast<const float*>(d_blob), static_cast<const float*>(d_dgrad_blob), gt, con_rgb, mask_sv, upstream, B, S, sums,
+                                      losses3, logits, grad, scratch, stop_after, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+}  // namespace
+
+int bsr_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt, const float* con_rgb,
+                      const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3, float* logits, float* grad, void* scratch,
+                      void* stream) {
+  return disc_gen_grad("bsr_disc_gen_grad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, gt, con_rgb, mask_sv, upstream, B, S, sums, losses3, logits,
+                       grad, scratch, bsr::kDiscGradLaunches, stream);
+}
+
+int bsr_debug_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                            const float* con_rgb, const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3, float* logits,
+                            float* grad, void* scratch, int stop_after, void* stream) {
+  return disc_gen_grad("bsr_debug_disc_gen_grad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, gt, con_rgb, mask_sv, upstream, B, S, sums, losses3,
+                       logits, grad, scratch, stop_after, stream);
 }
 
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }

@@ -37,11 +37,20 @@ WHAT IS NOT PINNED.  TensorFlow convolves and reduces in float32 in orders of it
 reference's Discriminator, Conv and hinge_loss and train_step's statements executed over a numpy stand-in
 (tools/make_discriminator_fixture.py), and tests/test_discriminator_fixture.py holds this statement to it.
 
-`python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host]` scores the three terms on a folder written
+THE BACKWARD: d gen / d con_rgb (`gen_grad`, csrc/disc_grad_kernels.h, Discriminators.gen_grad).  For the generator's update the
+discriminators are constants and gt and mask_sv are data, so the data gradient with respect to con_rgb is the whole backward of the
+term; only the rows [B, 2B) are differentiated.  `gen_grad`'s docstring writes every operation out; it is pinned to this restatement
+of TensorFlow's gradient definitions (Conv2DBackpropInput, the moving-statistics BatchNormalization, LeakyReluGrad, the transpose of
+the bilinear resize) and tests/golden/discriminator_grad_*.npz holds torch autograd's float64 gradient of the same objective
+(tools/make_discriminator_grad_fixture.py).
+
+`python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host] [--grad]` scores the three terms on a folder written
 by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling (train_losses.folder_steps): the
 generator runs on row 0 of each element and its con_rgb is the fake image.  The weights of the generator and of the discriminators
 come from the latest checkpoint under --ckpt, from init_weights / init_discriminator_weights without it.  The step-weighted means
 are printed as Logging.display prints them.  --host computes the three terms with this statement from the same generator outputs.
+With --grad each batch's line also carries gen_grad_l1 and gen_grad_linf, the L1 and L-infinity norms of d gen / d con_rgb
+(Discriminators.gen_grad; --host: gen_grad).
 """
 from __future__ import annotations
 
@@ -201,11 +210,131 @@ def example_inputs(S: int, B: int, seed: int = 0):
     return gt, con, mask_sv
 
 
+# ---- the backward: d gen / d con_rgb
+GRAD_NAMES = ("gen_grad_l1", "gen_grad_linf")
+
+
+def seed_weights(B: int, S: int) -> List[np.float32]:
+    """w_k = float32(1 / (B h_k^2)), k = 1, 2, 3."""
+    return [f32(1.0 / (float(B) * float(final_side(S, k) ** 2))) for k in (1, 2, 3)]
+
+
+def conv2d_same_dgrad(gy: np.ndarray, kernel: np.ndarray, stride: int, side: int) -> np.ndarray:
+    """The gradient [N,Ho,Wo,O] at a Conv2D(padding='same') output -> float64 [N,side,side,C] at its input of side `side`:
+    gx[n, s oy + a - before, s ox + b - before, c] += sum_o gy[n, oy, ox, o] k[a, b, c, o], positions outside the map dropped."""
+    gy, kernel = np.asarray(gy, np.float64), np.asarray(kernel, np.float64)
+    n, ho, wo, _ = gy.shape
+    kh, kw = kernel.shape[:2]
+    (pt, pb), (pl, pr) = same_pad(side, kh, stride), same_pad(side, kw, stride)
+    assert ho == -(-side // stride) and wo == ho
+    gp = np.zeros((n, side + pt + pb, side + pl + pr, kernel.shape[2]), np.float64)
+    for a in range(kh):
+        for b in range(kw):
+            gp[:, a:a + (ho - 1) * stride + 1:stride, b:b + (wo - 1) * stride + 1:stride] += gy @ kernel[a, b].T
+    return gp[:, pt:pt + side, pl:pl + side].copy()
+
+
+def leaky_grad(g: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """TensorFlow's LeakyReluGrad on the layer's kept output y: g where y > 0, 0.3 g otherwise (0 takes 0.3)."""
+    g = np.asarray(g)
+    return np.where(np.asarray(y) > 0, g, g.dtype.type(LRELU_ALPHA) * g)
+
+
+def resize_grad(g: np.ndarray, ds: int) -> np.ndarray:
+    """The gradient [N,s,s,C] at disc_input's resize output -> [N,s ds,s ds,C] at its input: the identity for 1; 0.25 g[y // 2, x // 2]
+    on all four pixels of the 2 x 2 block for 2; 0.25 g[y // 4, x // 4] on the middle 2 x 2 of each 4 x 4 block and 0 on the other
+    twelve for 4."""
+    g = np.asarray(g)
+    if ds == 1:
+        return g.copy()
+    n, s, _, c = g.shape
+    q = g.dtype.type(0.25) * g
+    out = np.zeros((n, s, ds, s, ds, c), g.dtype)
+    lo = 0 if ds == 2 else 1
+    out[:, :, lo:lo + 2, :, lo:lo + 2, :] = q[:, :, None, :, None, :]
+    return out.reshape(n, s * ds, s * ds, c)
+
+
+def bn_inv(weights: Dict[str, np.ndarray], k: int, i: int) -> np.ndarray:
+    """inv = gamma / sqrt(moving_variance + eps) of conv_stack[i] of discriminator k, float64 [n_ch[i]]."""
+    st = "discriminator_%d/conv_stack/%d/bnorm/" % (k, i)
+    return np.asarray(weights[st + "gamma"], np.float64) / np.sqrt(np.asarray(weights[st + "moving_variance"], np.float64) + BN_EPS)
+
+
+def gen_grad(weights: Dict[str, np.ndarray], gt, con_rgb, mask_sv, upstream=None, acts=None) -> Dict[str, np.ndarray]:
+    """d gen / d con_rgb for a batch, training=False -> dict(`grad` float64 [B,S,S,3], and each stage's gradient under `forward`'s
+    names: `d{k}/out` [B,h_k,h_k,1] the seed, `d{k}/conv{i}` [B,.,.,n_ch[i]] the gradient at conv_stack[i]'s BatchNormalization output
+    (LeakyReLU's input), `d{k}/in` [B,s,s,3] the gradient at the image channels of discriminator k's input).  float64 arithmetic from the
+    float32 variables, for discriminator k = 1, 2, 3 from the top down:
+      seed             gen = (-m_1 - m_2) - m_3 is linear in the fake logits, with no hinge: d gen / d out_k[B + b, y, x] = -w_k, w_k =
+                       float32(1 / (B h_k^2)).  The real rows [0, B) get nothing and are never computed.
+      conv dgrad       the input gradient of the cross-correlation, with `before` of same_pad:
+                         gx[n, s oy + a - before, s ox + b - before, c] += sum_o gy[n, oy, ox, o] k[a, b, c, o]
+                       for the head conv2 (s = 1, pad 1 before and 2 after) and the four stride-2 layers, the 1 x 1 -> 1 x 1 map (pad 1, 2)
+                       of discriminator 3 at S = 32 included.  The bias has no part.
+      BatchNormalization (moving statistics)   gy * inv per output channel, inv = gamma / sqrt(moving_variance + eps), before the
+                       convolution's gradient.
+      LeakyReLU(0.3)   TensorFlow's LeakyReluGrad on the layer's kept post-activation output y, whose sign is the pre-activation's:
+                       g where y > 0, 0.3 g otherwise, so 0 takes 0.3.
+      resize           the gradient is read on channels 0..2 of the discriminator's input (the mask channels are dropped) and goes back
+                       through the resize (`resize_grad`): downsize 1 the identity; 2 sends 0.25 g[y // 2, x // 2] to all four pixels of
+                       the 2 x 2 block; 4 sends 0.25 g[y // 4, x // 4] to the middle 2 x 2 of each 4 x 4 block and 0 to the other twelve.
+    The three contributions are added in the order 1, 2, 3: t = (r_1 + r_2) + r_3.  Without `upstream`, grad = t; with it (a float32),
+    grad = float32(t) * float32(upstream) as one float32 product, as the device forms it.  With `acts` given (a dict like `forward`'s,
+    for example the device's kept activations) the LeakyReLU masks are read from it instead of from the statement's own float64
+    forward: pre-activations within 3e-7 of 0 occur on the example inputs, so masks flip between float32 and float64."""
+    B, S = check_inputs(gt, con_rgb, mask_sv)
+    A = forward(weights, gt, con_rgb, mask_sv) if acts is None else acts
+    out: Dict[str, np.ndarray] = {}
+    total = None
+    for k, w_k in zip((1, 2, 3), seed_weights(B, S)):
+        sides = map_sides(S, k)
+        g = np.full((B, sides[-1], sides[-1], 1), -float(w_k), np.float64)
+        out["d%d/out" % k] = g
+        g = conv2d_same_dgrad(g, weights["discriminator_%d/conv2/conv/kernel" % k], 1, sides[N_LAYER_D])
+        for i in reversed(range(N_LAYER_D)):
+            g = leaky_grad(g, np.asarray(A["d%d/conv%d" % (k, i)])[B:])
+            out["d%d/conv%d" % (k, i)] = g
+            g = conv2d_same_dgrad(g * bn_inv(weights, k, i), weights["discriminator_%d/conv_stack/%d/conv/kernel" % (k, i)], 2, sides[i])
+        g = np.ascontiguousarray(g[..., :3])
+        out["d%d/in" % k] = g
+        r = resize_grad(g, DOWNSIZE[k - 1])
+        total = r if total is None else total + r
+    out["grad"] = total if upstream is None else (total.astype(f32) * f32(np.asarray(upstream).reshape(-1)[0])).astype(np.float64)
+    return out
+
+
+def gen_f64(weights: Dict[str, np.ndarray], con_rgb, mask_sv, masks: Optional[List[np.ndarray]] = None) -> float:
+    """gen as a function of a float64 con_rgb with no float32 rounding anywhere (the variables are still the float32 ones, the
+    resizes the exact means of their four pixels): the objective gen_grad differentiates.  A list given as `masks` receives every
+    LeakyReLU mask (y > 0) in order.  tests/test_discriminator_grad_cpu.py takes its finite differences of the same operations in
+    extended precision, where the rounding of a loss value can be bounded usefully."""
+    x = np.concatenate([np.asarray(con_rgb, np.float64), np.asarray(mask_sv, np.float64)], axis=3)
+    n, S = x.shape[:2]
+    gen = 0.0
+    for k in (1, 2, 3):
+        ds = DOWNSIZE[k - 1]
+        lo = 0 if ds < 4 else 1
+        h = x if ds == 1 else x.reshape(n, S // ds, ds, S // ds, ds, 6)[:, :, lo:lo + 2, :, lo:lo + 2].mean(axis=(2, 4))
+        for i in range(N_LAYER_D):
+            h = layer(weights, k, i, h)
+            if masks is not None:
+                masks.append(h > 0)
+        gen = gen - float(head(weights, k, h).mean())
+    return gen
+
+
+def grad_norms(grad) -> Tuple[float, float]:
+    g = np.abs(np.asarray(grad, np.float64))
+    return float(g.sum()), float(g.max())
+
+
 # ---- the command-line entry
 def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False,
-                 stats: Optional[Dict[str, float]] = None) -> Dict[str, float]:
+                 stats: Optional[Dict[str, float]] = None, grad: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of gen, disc_real and disc_fake.
-    With `host`, a `stats` dict receives `max_abs_logit`, the largest magnitude of the statement's logits over all steps."""
+    With `host`, a `stats` dict receives `max_abs_logit`, the largest magnitude of the statement's logits over all steps.  With `grad`
+    each batch's line and the means also carry GRAD_NAMES, the norms of d gen / d con_rgb."""
     import torch
     from .fsrnet import Logging
     from .train_losses import folder_steps
@@ -225,8 +354,11 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
         for step, steps, _, gt_a, mask_a, _, con_rgb in batches:
             if host:
                 torch.cuda.synchronize(dev)
-                r = gan_losses(weights, gt_a, con_rgb.cpu().numpy(), mask_a)
+                con_a = con_rgb.cpu().numpy()
+                r = gan_losses(weights, gt_a, con_a, mask_a)
                 loss = r["losses"]
+                if grad:
+                    norms = grad_norms(gen_grad(weights, gt_a, con_a, mask_a, acts=r["acts"])["grad"])
                 if stats is not None:
                     stats["max_abs_logit"] = max([stats.get("max_abs_logit", 0.0)] + [float(np.abs(y).max()) for y in r["logits"]])
             else:
@@ -234,8 +366,16 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
                     from .discriminator_gpu import Discriminators
                     runner = Discriminators(device)
                     runner.load_weights(weights)
-                loss = runner.gan_losses(torch.from_numpy(gt_a).to(dev), con_rgb, torch.from_numpy(mask_a).to(dev))[0].cpu().numpy()
-            Logging.accumulate(acc, {k: float(v) for k, v in zip(LOSS_NAMES, loss)})
+                gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
+                if grad:
+                    res = runner.gen_grad(gt_d, con_rgb.contiguous(), mask_d)
+                    loss, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
+                else:
+                    loss = runner.gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
+            line = {k: float(v) for k, v in zip(LOSS_NAMES, loss)}
+            if grad:
+                line.update(zip(GRAD_NAMES, norms))
+            Logging.accumulate(acc, line)
             if not quiet:
                 print(Logging.format_line(acc, step, steps), end="", flush=True)
     if not quiet:
@@ -251,9 +391,10 @@ def main(argv=None) -> int:
     ap.add_argument("--ckpt", default=None, help="checkpoint directory; without it the weights come from init_weights / init_discriminator_weights")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--host", action="store_true", help="compute the three terms with the host statement instead of the device chain")
+    ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of d gen / d con_rgb")
     a = ap.parse_args(argv)
-    means = score_folder(a.folder, ckpt=a.ckpt, batch=a.batch, host=a.host)
-    print(", ".join("%s:%.9g" % (k, means[k]) for k in LOSS_NAMES))
+    means = score_folder(a.folder, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad)
+    print(", ".join("%s:%.9g" % (k, means[k]) for k in LOSS_NAMES + (GRAD_NAMES if a.grad else ())))
     return 0
 
 

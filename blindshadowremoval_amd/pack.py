@@ -548,6 +548,64 @@ def unpack_discriminators(blob: bytes):
     return out
 
 
+DISC_GRAD_IN_C = 3           # the image channels of a discriminator's input: the only ones whose gradient is wanted
+
+
+def disc_dgrad_layout():
+    """([(name, offset in floats, shape)] of ONE discriminator, floats per discriminator) of the gradient layers' blob
+    (csrc/disc_grad_kernels.h).  The input gradient of `conv<i>`, i = 1, 2, 3, runs from its C' = C_out to its N' = C_in channels and is
+    stored as disc_dgrad_kernel stages it, a chunk of 8 output channels at a time: [C_out / 8][16 taps (a * 4 + b)][8][C_in], the folded
+    kernel of disc_folded with the channel roles swapped (k'[t, o, c] = k[t, c, o]); the taps keep their places, the kernel picks the
+    four of each sub-pixel phase.  `conv0`, whose gradient is wanted on the 3 image channels only, as [16 taps][3][32].  No bias.  The
+    blob is the three discriminators' records in order."""
+    from .weights import DISC_CH
+    out, off, cin = [("conv0/dgrad", 0, (DISC_TAPS, DISC_GRAD_IN_C, DISC_CH[0]))], DISC_TAPS * DISC_GRAD_IN_C * DISC_CH[0], DISC_CH[0]
+    for i, n in list(enumerate(DISC_CH))[1:]:
+        out.append(("conv%d/dgrad" % i, off, (n // DISC_CC, DISC_TAPS, DISC_CC, cin)))
+        off += DISC_TAPS * cin * n
+        cin = n
+    return out, off
+
+
+def pack_discriminators_dgrad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The three discriminators' variables -> the blob bsr_disc_gen_grad takes beside pack_discriminators' (disc_dgrad_layout)."""
+    from .weights import check_discriminator_weights
+    check_discriminator_weights(weights)
+    layout, per = disc_dgrad_layout()
+    blob = np.zeros((3, per), np.float32)
+    for k in (1, 2, 3):
+        folded = disc_folded(weights, k)
+        for name, off, shape in layout:
+            swapped = folded[name.split("/")[0]][0].transpose(0, 2, 1)             # [16][N][C_in padded]
+            if name == "conv0/dgrad":
+                a = swapped[:, :, :DISC_GRAD_IN_C].transpose(0, 2, 1)
+            else:
+                a = swapped.reshape(DISC_TAPS, shape[0], DISC_CC, shape[3]).transpose(1, 0, 2, 3)
+            assert a.shape == tuple(shape)
+            blob[k - 1, off:off + a.size] = a.reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_discriminators_dgrad(blob: bytes):
+    """The inverse of pack_discriminators_dgrad: per discriminator {`conv<i>`: the folded kernel [16, C_in, N] of disc_folded}, conv0's
+    cut to its 3 image channels."""
+    layout, per = disc_dgrad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != 3 * per:
+        raise ValueError("a discriminator gradient blob holds %d bytes, got %d" % (3 * per * 4, len(blob)))
+    out = []
+    for k in range(3):
+        d = {}
+        for name, off, shape in layout:
+            a = arr[k * per + off:k * per + off + int(np.prod(shape))].reshape(shape)
+            if name == "conv0/dgrad":
+                d["conv0"] = a.copy()
+            else:
+                d[name.split("/")[0]] = a.transpose(1, 0, 2, 3).reshape(DISC_TAPS, shape[0] * DISC_CC, shape[3]).transpose(0, 2, 1).copy()
+        out.append(d)
+    return out
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

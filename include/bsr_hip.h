@@ -247,6 +247,31 @@ size_t bsr_disc_act_offset(int B, int S, int k, int layer);
 int bsr_disc_losses(int device, const void* d_blob, size_t blob_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S,
                     double* sums, float* losses3, float* logits, void* scratch, void* stream);
 
+/* bsr_disc_losses and the data gradient d gen / d con_rgb in one call (blindshadowremoval_amd/discriminator.py: gen_grad is the host
+ * statement).  For the generator's update the discriminators are constants and gt and mask_sv are data, so this is the whole backward
+ * of the term: no weight gradient, no state.  d_dgrad_blob: the device copy of pack.pack_discriminators_dgrad's blob, dgrad_bytes =
+ * bsr_disc_dgrad_blob_bytes() (the folded kernels with the channel roles swapped, no bias), 16-byte aligned.  upstream: a device
+ * float32[1] the gradient is multiplied by, or NULL for 1.  Outputs: sums, losses3 and logits exactly as bsr_disc_losses writes them
+ * (the same launches), and grad [B][S][S][3] float32.  The forward's seven launches, then six more on `stream`, one after the other:
+ * the head's gradient with conv3's slope, the gradient convolutions of conv3, conv2, conv1 (matrix instructions, sub-pixel form) and
+ * conv0 (narrow), and the gather through the three resizes; each covers all three discriminators and works on the B fake rows only.
+ * No host synchronisation, no second stream, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_disc_grad_scratch_bytes(B, S) bytes, 256-byte aligned = the forward's scratch, unchanged (bsr_disc_act_offset keeps its values),
+ * followed by the gradient maps: bsr_disc_grad_offset(B, S, k, layer) is the byte offset of discriminator k's (1..3) gradient at its
+ * image channels [B][s][s][4] (channel 3 zero) for layer 0 and at conv0..conv3's pre-activation [B][.][.][32, 32, 64, 64] for layer
+ * 1..4; SIZE_MAX for arguments out of range.  Every word read is written earlier in the same call.  Sizes and errors as
+ * bsr_disc_losses.  bsr_debug_disc_gen_grad stops after `stop_after` (0..6) of the backward launches, for the tests' stage-by-stage
+ * comparison.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_disc_dgrad_blob_bytes(void);
+size_t bsr_disc_grad_scratch_bytes(int B, int S);
+size_t bsr_disc_grad_offset(int B, int S, int k, int layer);
+int bsr_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                      const float* con_rgb, const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3, float* logits,
+                      float* grad, void* scratch, void* stream);
+int bsr_debug_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const float* gt,
+                            const float* con_rgb, const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3,
+                            float* logits, float* grad, void* scratch, int stop_after, void* stream);
+
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
  * statement and writes the arithmetic out.  d_blob: the device copy of pack.pack_vgg's blob, blob_bytes = bsr_vgg_blob_bytes() (about

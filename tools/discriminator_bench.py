@@ -17,6 +17,20 @@ through Discriminators.gan_losses.
   generator_ms_per_call  the fp32 generator forward at the same batch, by the same events; ratio_to_generator = device_ms_per_call / it.
 
     python tools/discriminator_bench.py [--batch 32] [--size 256] [--iters 3000] [--stats CSV] [--calls-only]
+
+With --grad the call is Discriminators.gen_grad (bsr_disc_gen_grad, csrc/disc_grad_kernels.h: the forward's seven launches and the six of
+d gen / d con_rgb) and the line, also written to --out (profiles/discriminator_grad_bench.json), holds
+  device_ms_per_call       forward plus backward by device events, and forward_ms_per_call, the forward alone (gan_losses) in the same run,
+                           beside forward_ms_parent, the figure of profiles/discriminator_bench.json, and its run-to-run spread there.
+  kernel_ms                with --stats, all thirteen launches; conv_rate holds, per stride-2 layer, the forward launch's and the gradient
+                           launch's TFLOP/s from the shapes (the gradient works on the B fake rows: half the forward's work; conv0's
+                           gradient is wanted on 3 of its input channels only and is counted so).
+  parity                   with --parity, per (S, B) of the device tests' sizes the scaled error max |grad - ref| / max |ref| against
+                           discriminator.gen_grad on the device's own masks, and against the statement's own float64 forward; e2e_measured
+                           is the largest of the former, the figure the device test's bound is 4 x of.
+  build                    with --build FILE, the compiler's register and LDS figures of the new kernels (a JSON object, merged in as is).
+
+    python tools/discriminator_bench.py --grad [--parity] [--stats CSV] [--build FILE] [--out FILE] [--calls-only]
 """
 import argparse
 import csv
@@ -31,6 +45,9 @@ MATRIX_FLOPS = 157.3e12
 HBM_BYTES_PER_S = 8.0e12
 KERNELS = ("disc_input_kernel", "disc_conv_kernel<8, 32>", "disc_conv_kernel<32, 32>", "disc_conv_kernel<32, 64>", "disc_conv_kernel<64, 64>",
            "disc_head_kernel", "disc_finish_kernel")
+GRAD_KERNELS = ("disc_head_grad_kernel", "disc_dgrad_kernel<64, 64>", "disc_dgrad_kernel<64, 32>", "disc_dgrad_kernel<32, 32>", "disc_dgrad_in_kernel",
+                "disc_gather_kernel")
+PARITY_SIZES = ((32, 1), (32, 3), (64, 2), (128, 1))
 
 
 def work(S):
@@ -50,14 +67,84 @@ def work(S):
     return flop, 4 * floats
 
 
-def kernel_stats(path):
+def kernel_stats(path, kernels=KERNELS):
     found = {}
     with open(path) as f:
         for row in csv.DictReader(f):
-            for name in KERNELS:
+            for name in kernels:
                 if name in row["Name"]:
                     found[name] = found.get(name, 0.0) + float(row["AverageNs"]) / 1e6
-    return {k: round(found[k], 5) for k in KERNELS} if len(found) == len(KERNELS) else None
+    return {k: round(found[k], 5) for k in kernels} if len(found) == len(kernels) else None
+
+
+def conv_flop(S, i, cin=None):
+    """FLOP of stride-2 layer i per discriminator row over the three scales, from the shapes."""
+    from blindshadowremoval_amd import discriminator as host
+    from blindshadowremoval_amd.weights import DISC_CH
+    cin = cin if cin is not None else (6 if i == 0 else DISC_CH[i - 1])
+    return sum(2 * 16 * cin * DISC_CH[i] * host.map_sides(S, k)[i + 1] ** 2 for k in (1, 2, 3))
+
+
+def parity():
+    """The device tests' cases: init_discriminator_weights(3), discriminator.example_inputs(S, B, 1)."""
+    import numpy as np
+    import torch
+    from blindshadowremoval_amd import Discriminators, discriminator as host
+    from blindshadowremoval_amd.weights import init_discriminator_weights
+    out, dev, weights = [], torch.device("cuda", 0), init_discriminator_weights(3)
+    runner = Discriminators(0)
+    runner.load_weights(weights)
+    for S, B in PARITY_SIZES:
+        arrays = host.example_inputs(S, B, 1)
+        res = runner.gen_grad(*[torch.from_numpy(a).to(dev) for a in arrays], keep=True)
+        torch.cuda.synchronize()
+        grad, acts = res[2].cpu().numpy().astype(np.float64), {k: v.cpu().numpy() for k, v in res[3].items()}
+        err = []
+        for ref in (host.gen_grad(weights, *arrays, acts=acts)["grad"], host.gen_grad(weights, *arrays)["grad"]):
+            err.append(float(np.abs(grad - ref).max() / np.abs(ref).max()))
+        out.append({"size": S, "batch": B, "scaled_error_device_masks": float("%.3g" % err[0]), "scaled_error_own_forward": float("%.3g" % err[1])})
+    return out
+
+
+def main_grad(args, runner, weights, t, timed):
+    import torch
+    B, S = args.batch, args.size
+    if args.calls_only:
+        timed(lambda: runner.gen_grad(*t), min(args.iters, 20))
+        return
+    ms, res = timed(lambda: runner.gen_grad(*t), args.iters)
+    fwd = [timed(lambda: runner.gan_losses(*t), args.iters)[0] for _ in range(2)]
+    spread = [timed(lambda: runner.gen_grad(*t), args.iters)[0] for _ in range(2)]
+    g = res[2]
+    with open(os.path.join(ROOT, "profiles", "discriminator_bench.json")) as f:
+        parent = json.loads(f.readline())
+    kernel_ms = kernel_stats(args.stats, KERNELS + GRAD_KERNELS) if args.stats else None
+    rate = None
+    if kernel_ms:
+        rate = {}
+        fwd_names, grad_names = KERNELS[1:5], (GRAD_KERNELS[4], GRAD_KERNELS[3], GRAD_KERNELS[2], GRAD_KERNELS[1])
+        for i in range(4):
+            f_flop, g_flop = 2 * B * conv_flop(S, i), B * conv_flop(S, i, 3 if i == 0 else None)
+            rate["conv%d" % i] = {"forward_kernel": fwd_names[i], "forward_gflop": round(f_flop / 1e9, 3),
+                                  "forward_tflops": round(f_flop / kernel_ms[fwd_names[i]] / 1e9, 1), "grad_kernel": grad_names[i],
+                                  "grad_gflop": round(g_flop / 1e9, 3), "grad_tflops": round(g_flop / kernel_ms[grad_names[i]] / 1e9, 1),
+                                  "grad_ms_over_half_forward_ms": round(kernel_ms[grad_names[i]] / (0.5 * kernel_ms[fwd_names[i]]), 2)}
+    line = {"batch": B, "size": S, "losses": [float(v) for v in res[0].cpu()], "grad_l1": float(g.abs().sum().cpu()), "grad_linf": float(g.abs().max().cpu()),
+            "device_ms_per_call": round(ms, 4), "device_ms_per_call_repeats": [round(v, 4) for v in spread],
+            "forward_ms_per_call": round(min(fwd), 4), "forward_ms_per_call_repeats": [round(v, 4) for v in fwd],
+            "forward_ms_parent": parent["device_ms_per_call"], "forward_ms_parent_repeats": parent["device_ms_per_call_repeats"],
+            "backward_ms_per_call": round(ms - min(fwd), 4), "kernel_ms": kernel_ms, "kernel_ms_unmeasured": kernel_ms is None, "conv_rate": rate,
+            "backward_kernel_ms": round(sum(kernel_ms[k] for k in GRAD_KERNELS), 5) if kernel_ms else None}
+    if args.parity:
+        line["parity"] = parity()
+        line["e2e_measured"] = max(p["scaled_error_device_masks"] for p in line["parity"])
+    if args.build:
+        with open(args.build) as f:
+            line["build"] = json.load(f)
+    text = json.dumps(line)
+    print(text)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
 
 
 def main():
@@ -68,6 +155,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--stats", default=None, help="the kernel statistics CSV of a profiled --calls-only run")
     ap.add_argument("--calls-only", action="store_true", help="the warm-up and the calls, nothing else: the program to profile")
+    ap.add_argument("--grad", action="store_true", help="time gen_grad (forward + d gen / d con_rgb) and the forward alone in the same run")
+    ap.add_argument("--parity", action="store_true", help="with --grad: the end-to-end scaled errors over the device tests' sizes")
+    ap.add_argument("--build", default=None, help="with --grad: a JSON file of the compiler's register and LDS figures, merged in under `build`")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "discriminator_grad_bench.json"), help="with --grad: where the line is written")
     args = ap.parse_args()
     import torch
     from blindshadowremoval_amd import Discriminators, discriminator as host
@@ -78,7 +169,8 @@ def main():
     dev = torch.device("cuda", 0)
     t = [torch.from_numpy(a).to(dev) for a in host.example_inputs(S, B, seed=0)]
     runner = Discriminators(0)
-    runner.load_weights(init_discriminator_weights(1))
+    weights = init_discriminator_weights(1)
+    runner.load_weights(weights)
 
     def timed(fn, iters):
         for _ in range(args.warmup):
@@ -91,6 +183,8 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / iters, res
+    if args.grad:
+        return main_grad(args, runner, weights, t, timed)
     if args.calls_only:
         timed(lambda: runner.gan_losses(*t), min(args.iters, 20))
         return
