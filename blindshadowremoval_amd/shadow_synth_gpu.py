@@ -16,26 +16,12 @@ class ShadowSynth(PostDevice):
     SYMBOL = "bsr_shadow_synth"
     SIZE_TEXT = "process_mask takes 1..65535 items of side 32, 64, 128 or 256, got B=%(b)d S=%(s)d"
 
-    def _check_input(self, mask, gt, img_dark, face):
-        for name, t, c in (("mask", mask, 1), ("gt", gt, 3), ("img_dark", img_dark, 3), ("face", face, 1)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.device != self._dev:
-                raise TypeError("%s must be a float32 tensor [B,S,S,%d] on %s" % (name, c, self._dev))
-            if not t.is_contiguous():
-                raise ValueError("%s must be contiguous (NHWC, dense)" % name)
-        b, s = int(gt.shape[0]), int(gt.shape[1])
-        if s not in host.SIZES or not 1 <= b <= 65535:
-            raise ValueError(self.SIZE_TEXT % {"b": b, "s": s})
-        for name, t, c in (("mask", mask, 1), ("gt", gt, 3), ("img_dark", img_dark, 3), ("face", face, 1)):
-            if tuple(t.shape) != (b, s, s, c):
-                raise ValueError("%s must be [%d,%d,%d,%d] like gt, got %s" % (name, b, s, s, c, tuple(t.shape)))
-        return b, s
-
     def process_mask(self, mask: torch.Tensor, gt: torch.Tensor, img_dark: torch.Tensor, face: torch.Tensor, draws: Sequence[host.ShadowDraws],
                      out: Optional[Tuple[torch.Tensor, ...]] = None, aux: Optional[torch.Tensor] = None):
         """-> (img, mask_sv, mask_edge [B,S,S,3] float32, status [B] int32) on the device, asynchronously on the current stream.  `out`:
         four such tensors to write into.  `aux`: an optional float32 [B,3,S,S] that receives the Perlin map, the brightness mask and
         the composited mask.  Everything is checked here, before any launch: TypeError / ValueError."""
-        b, s = self._check_input(mask, gt, img_dark, face)
+        b, s = self.images((("mask", mask, 1), ("gt", gt, 3), ("img_dark", img_dark, 3), ("face", face, 1)), 65535)
         if len(draws) != b:
             raise ValueError("process_mask: %d draws records for %d items" % (len(draws), b))
         blob = torch.from_numpy(host.pack_draws(draws, s).view(np.int32)).to(self._dev)          # ValueError: r too large for S, bad integers

@@ -16,26 +16,11 @@ class TrainLosses(PostDevice):
     SYMBOL = "bsr_train_losses"
     SIZE_TEXT = "train_losses takes 1..65535 items of side 32, 64, 128 or 256, got B=%(b)d S=%(s)d"
 
-    def _check_input(self, img, gt, mask_sv, gs, con_rgb):
-        spec = (("img", img, 3), ("gt", gt, 3), ("mask_sv", mask_sv, 3), ("gs", gs, 1), ("con_rgb", con_rgb, 3))
-        for name, t, c in spec:
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.device != self._dev:
-                raise TypeError("%s must be a float32 tensor [B,S,S,%d] on %s" % (name, c, self._dev))
-            if not t.is_contiguous():
-                raise ValueError("%s must be contiguous (NHWC, dense)" % name)
-        b, s = int(gt.shape[0]), int(gt.shape[1])
-        if s not in host.SIZES or not 1 <= b <= 65535:
-            raise ValueError(self.SIZE_TEXT % {"b": b, "s": s})
-        for name, t, c in spec:
-            if tuple(t.shape) != (b, s, s, c):
-                raise ValueError("%s must be [%d,%d,%d,%d] like gt, got %s" % (name, b, s, s, c, tuple(t.shape)))
-        return b, s
-
     def step_losses(self, img: torch.Tensor, gt: torch.Tensor, mask_sv: torch.Tensor, gs: torch.Tensor, con_rgb: torch.Tensor, figs: bool = False):
         """-> (losses float32 [3] = recon_gs, recon_c, grad (train_losses.LOSS_NAMES), sums float64 [B,K] (train_losses.SUM_NAMES)) on the
         device, asynchronously on the current stream; with `figs` also (mask_edge [B,S,S,1], bmaskgt [B,S,S,1], dif_grad [B,S,S,3]), the
         reference's figures 5, 6 and 8.  Everything is checked here, before any launch: TypeError / ValueError."""
-        b, s = self._check_input(img, gt, mask_sv, gs, con_rgb)
+        b, s = self.images((("img", img, 3), ("gt", gt, 3), ("mask_sv", mask_sv, 3), ("gs", gs, 1), ("con_rgb", con_rgb, 3)), 65535)
         losses = self.empty((3,), torch.float32)
         sums = self.empty((b, host.K), torch.float64)
         planes = (self.empty((b, s, s, 1), torch.float32), self.empty((b, s, s, 1), torch.float32), self.empty((b, s, s, 3), torch.float32)) if figs \

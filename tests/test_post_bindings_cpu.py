@@ -8,25 +8,10 @@ import torch
 from blindshadowremoval_amd import _lib
 from blindshadowremoval_amd import sfw_post_gpu, ucb_post_gpu, ucb_post_rgb_gpu, ucb_post_tsm_gpu
 from blindshadowremoval_amd.build import build_library
+from on_dev0 import BSR_ERR_ARG, DEV, P, d0
 
-BSR_ERR_ARG = 1
 S_TEXT = "supports S in {32, 64, 128, 256} (reference: 256)"
-
-
-class OnDev0(torch.Tensor):
-    """A host tensor that reports cuda:0: reaches the runners' shape and size checks, which come before any device work."""
-
-    @property
-    def device(self):
-        return torch.device("cuda", 0)
-
-
-def d0(*shape, dtype=torch.float32):
-    return torch.zeros(shape, dtype=dtype).as_subclass(OnDev0)
-
-
 U8 = torch.uint8
-DEV = torch.device("cuda", 0)
 
 # runner, good inputs (B = 2, S = 32) by name, the shape message's head, then the message of a good shape at S = 16
 RUNNERS = [
@@ -101,9 +86,6 @@ def test_scratch_bytes(lib, fn):
     for b in (0, 1, 16):
         for s in (16, 32, 256, 512):
             assert getattr(lib, fn)(b, s) == SCRATCH[fn].get((b, s), 0), (fn, b, s)
-
-
-P = 0x10000            # a 256-byte aligned stand-in address: never dereferenced by the checks
 
 
 def _ucb_args(B, S, scratch, n_out):
