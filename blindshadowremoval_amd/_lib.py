@@ -74,6 +74,9 @@ SIGNATURES = {
     "bsr_shadow_synth": (c_i, [c_i, c_v, c_v, c_v, c_v, c_v, c_sz, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_v]),
     "bsr_train_losses_scratch_bytes": (c_sz, _BS),
     "bsr_train_losses": (c_i, [c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_v]),
+    "bsr_train_losses_grad_scratch_bytes": (c_sz, _BS),
+    "bsr_train_losses_grad_offset": (c_sz, [c_i, c_i, c_i]),
+    "bsr_train_losses_grad": (c_i, [c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_v, c_v]),
     "bsr_disc_blob_bytes": (c_sz, []),
     "bsr_disc_losses_scratch_bytes": (c_sz, _BS),
     "bsr_disc_act_offset": (c_sz, [c_i, c_i, c_i, c_i]),

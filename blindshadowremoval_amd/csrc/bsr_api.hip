@@ -1440,6 +1440,25 @@ int bsr_train_losses(int device, const float* img, const float* gt, const float*
   });
 }
 
+size_t bsr_train_losses_grad_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= 65535 ? bsr::loss_grad_scratch_bytes(B, S) : 0; }
+
+size_t bsr_train_losses_grad_offset(int B, int S, int level) {
+  if (!post_size_ok(B, S) || B > 65535 || level < 0 || level >= bsr::kLossLevels) return SIZE_MAX;
+  return bsr::loss_grad_map_offset(B, S, level);
+}
+
+int bsr_train_losses_grad(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb, const float* upstream,
+                          int B, int S, double* sums, float* losses3, float* grad_gs, float* grad_con, float* d_recon_c, float* d_grad, void* scratch,
+                          void* stream) {
+  if (B > 65535) return fail(BSR_ERR_ARG, "bsr_train_losses_grad: B must be 1..65535");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, "bsr_train_losses_grad: sums must be 8-byte aligned");
+  return run_post("bsr_train_losses_grad", {img, gt, mask_sv, gs, con_rgb, sums, losses3, grad_gs, grad_con, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_train_losses_grad(img, gt, mask_sv, gs, con_rgb, upstream, B, S, sums, losses3, grad_gs, grad_con, d_recon_c, d_grad, scratch,
+                                          static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
 size_t bsr_disc_blob_bytes(void) { return 3 * bsr::disc_record_floats() * sizeof(float); }
 
 size_t bsr_disc_losses_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kDiscMaxB ? bsr::disc_map_offset(B, S, 3, 0) : 0; }

@@ -81,6 +81,23 @@ __global__ __launch_bounds__(256) void losses_coarse_kernel(const float* __restr
   }
 }
 
+// the six coarse planes of level l (gt's three channels, then con_rgb's) back at S, at fine pixel (y, x): level 0 is read as it stands,
+// the others are bilinear samples of the coarse planes
+__device__ inline void loss_level_samples(const float* __restrict__ coarse, int S, int l, int y, int x, float* v) {
+  const int s = loss_level_side(S, l);
+  const float* pl = coarse + (size_t)loss_level_offset(S, l) * 6;
+  if (l == 0) {
+    for (int j = 0; j < 6; ++j) v[j] = pl[((size_t)y * S + x) * 6 + j];
+  } else {
+    const BilinearTap t(y, x, S, s);
+    const float* a = pl + ((size_t)t.y0 * s + t.x0) * 6;
+    const float* b = pl + ((size_t)t.y0 * s + t.x1) * 6;
+    const float* c = pl + ((size_t)t.y1 * s + t.x0) * 6;
+    const float* d = pl + ((size_t)t.y1 * s + t.x1) * 6;
+    for (int j = 0; j < 6; ++j) v[j] = t.lerp(a[j], b[j], c[j], d[j]);
+  }
+}
+
 __global__ __launch_bounds__(256) void losses_pixel_kernel(const float* __restrict__ img, const float* __restrict__ gt, const float* __restrict__ mask_sv,
                                                            const float* __restrict__ gs, const float* __restrict__ con, int S, void* scratch,
                                                            float* __restrict__ mask_edge, float* __restrict__ bmaskgt, float* __restrict__ dif_grad) {
@@ -143,19 +160,8 @@ __global__ __launch_bounds__(256) void losses_pixel_kernel(const float* __restri
   // the five gradient planes back at S: level 0 is read as it stands, the others are bilinear samples of the coarse planes
   float total[3] = {0.f, 0.f, 0.f};
   for (int l = 0; l < kLossLevels; ++l) {
-    const int s = loss_level_side(S, l);
-    const float* pl = sc.coarse + (size_t)loss_level_offset(S, l) * 6;
     float v[6];
-    if (l == 0) {
-      for (int j = 0; j < 6; ++j) v[j] = pl[p1 * 6 + j];
-    } else {
-      const BilinearTap t(y, x, S, s);
-      const float* a = pl + ((size_t)t.y0 * s + t.x0) * 6;
-      const float* b = pl + ((size_t)t.y0 * s + t.x1) * 6;
-      const float* c = pl + ((size_t)t.y1 * s + t.x0) * 6;
-      const float* d = pl + ((size_t)t.y1 * s + t.x1) * 6;
-      for (int j = 0; j < 6; ++j) v[j] = t.lerp(a[j], b[j], c[j], d[j]);
-    }
+    loss_level_samples(sc.coarse, S, l, y, x, v);
     for (int c = 0; c < 3; ++c) {
       const float a = fabsf(v[3 + c] - v[c]);
       const float d = ((a + (30.0f * a) * (bi[c] ? 1.0f : 0.f)) + (10.0f * a) * (edge ? 1.0f : 0.f)) / 41.0f;
@@ -192,7 +198,7 @@ __device__ inline void loss_formulas(const double* t, double n, float* losses3) 
   losses3[2] = (float)(t[LS_DG] / d_edge);
 }
 
-__global__ __launch_bounds__(256) void losses_finish_kernel(int B, int S, void* scratch, double* sums, float* losses3) {      // grid (1)
+__global__ __launch_bounds__(256) void losses_finish_kernel(int B, int S, void* scratch, double* sums, float* losses3, double* totals) {      // grid (1)
 #pragma clang fp contract(off)
   __shared__ double s_tot[kLossK];
   const int tid = threadIdx.x, tiles = loss_tiles(S);
@@ -211,10 +217,12 @@ __global__ __launch_bounds__(256) void losses_finish_kernel(int B, int S, void* 
   }
   __syncthreads();
   if (tid == 0) loss_formulas(s_tot, (double)B * (double)S * (double)S, losses3);
+  if (totals != nullptr && tid < kLossK) totals[tid] = s_tot[tid];          // the backward reads n_bi and n_edge here
 }
 
 inline hipError_t launch_train_losses(const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con, int B, int S, double* sums,
-                                      float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, hipStream_t stream) {
+                                      float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, hipStream_t stream,
+                                      double* totals = nullptr) {
   hipLaunchKernelGGL(losses_coarse_kernel, dim3((unsigned)((loss_coarse_pixels(S) + 255) / 256), (unsigned)B), dim3(256), 0, stream, gt, con, S, scratch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -222,7 +230,207 @@ inline hipError_t launch_train_losses(const float* img, const float* gt, const f
                      bmaskgt, dif_grad);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(losses_finish_kernel, dim3(1), dim3(256), 0, stream, B, S, scratch, sums, losses3);
+  hipLaunchKernelGGL(losses_finish_kernel, dim3(1), dim3(256), 0, stream, B, S, scratch, sums, losses3, totals);
+  return hipGetLastError();
+}
+
+// ---- THE BACKWARD: d (u_gs recon_gs + u_c recon_c + u_g grad) / d (gs, con_rgb), train_losses.step_losses_grad.  The forward's three
+// launches run first, with mask_edge and the batch totals left in the gradient part of the scratch; then three more on the same stream:
+//   losses_sign_kernel     grid (S^2 / 256, B), a thread per pixel: the forward's float32 samples of the ten planes once more (the same
+//                          device function, so the same bits) and the sign of each of the 15 differences.  Level 0 needs no resize:
+//                          g_0 = D_0 is written as it stands.  The 12 signs of levels 1..4, the pixel's three mask_bi bits and its
+//                          mask_edge bit go into ONE 32-bit word (two bits per sign): D_l is never stored.
+//   losses_upT_kernel      grid (S/2 + S/4 + S/8 + S/16, B), a workgroup per coarse row of a level: U_l^T as a separable GATHER.  The row
+//                          pass sums, for every fine row the coarse row receives from and every coarse column, the fine pixels of that
+//                          column's footprint (2 scale of them, 1.5 scale at a clamped edge; the weights tabulated once per workgroup
+//                          from BilinearTap) in index order into LDS; the column pass
+//                          sums the rows in index order.  float64 throughout, the map g_l is stored as float32.
+//   losses_grad_kernel     grid (S^2 / 256, B), a thread per pixel: grad_gs and d_recon_c in float64 in the statement's order (bit-identical
+//                          to it); the transpose of (dy + dx) * 5 read off g_l at the one coarse pixel per level whose 2 x 2 quarter
+//                          taps hold this pixel (R_l^T as a gather); grad_con = d_recon_c + d_grad added in float64, rounded once.
+// No atomics, every sum in a fixed order, every scratch word read was written earlier in the same call.
+struct LossGradScratch {                 // per batch, behind the forward's B items
+  double* totals;                        // [K]: the batch totals the forward's finish kernel formed
+  float* mask_edge;                      // [B][S][S]
+  uint32_t* words;                       // [B][S][S]: bits 0..23 the signs of levels 1..4 (0: zero, 1: plus, 2: minus), 24..26 mask_bi, 27 mask_edge
+  float* g[kLossLevels];                 // [B][s][s][3]
+  __host__ __device__ static LossGradScratch carve(ScratchCarver& c, int B, int S) {
+    LossGradScratch s;
+    s.totals = c.take<double>(32);                     // K of them, the block padded to 256 bytes
+    s.mask_edge = c.take<float>((size_t)B * S * S);
+    s.words = c.take<uint32_t>((size_t)B * S * S);
+    for (int l = 0; l < kLossLevels; ++l) s.g[l] = c.take<float>((size_t)B * loss_level_side(S, l) * loss_level_side(S, l) * 3);
+    return s;
+  }
+};
+__host__ __device__ inline LossGradScratch loss_grad_scratch(void* base, int B, int S) {
+  ScratchCarver c{static_cast<unsigned char*>(base) + (size_t)B * loss_item_scratch_bytes(S)};
+  return LossGradScratch::carve(c, B, S);
+}
+__host__ __device__ inline size_t loss_grad_scratch_bytes(int B, int S) {
+  ScratchCarver c{nullptr};
+  LossGradScratch::carve(c, B, S);
+  return (size_t)B * loss_item_scratch_bytes(S) + c.end();
+}
+__host__ __device__ inline size_t loss_grad_map_offset(int B, int S, int l) {
+  return (size_t)reinterpret_cast<uintptr_t>(loss_grad_scratch(nullptr, B, S).g[l]);          // carved from a null base: the pointer is the offset
+}
+__host__ __device__ inline int loss_up_rows(int S) { return (S >> 1) + (S >> 2) + (S >> 3) + (S >> 4); }
+
+__device__ inline int loss_sign(float d) { return (d > 0.f ? 1 : 0) - (d < 0.f ? 1 : 0); }
+// ((1 + 30 bi_c) + 10 e) / 41: a difference's weight in dif_grad
+__device__ inline double loss_grad_weight(int bi, int e) {
+#pragma clang fp contract(off)
+  return ((1.0 + 30.0 * (double)bi) + 10.0 * (double)e) / 41.0;
+}
+// what coarse index `coarse` receives from fine index `fine` along one axis of the resize s -> S
+__device__ inline double loss_up_weight(int fine, int coarse, int S, int s) {
+  const BilinearTap t(fine, fine, S, s);
+  return (t.y0 == coarse ? 1.0 - (double)t.yl : 0.0) + (t.y1 == coarse ? (double)t.yl : 0.0);
+}
+// the fine indices [lo, hi) whose taps can hold coarse index c
+__device__ inline void loss_up_range(int c, int scale, int S, int& lo, int& hi) {
+  lo = max(scale * c - scale / 2, 0);
+  hi = min(scale * c + 3 * scale / 2, S);
+}
+
+__global__ __launch_bounds__(256) void losses_sign_kernel(const float* __restrict__ mask_sv, int B, int S, void* scratch) {
+#pragma clang fp contract(off)
+  const int item = blockIdx.y, p1 = blockIdx.x * 256 + threadIdx.x;
+  const int y = p1 / S, x = p1 % S;
+  const size_t px = (size_t)item * S * S + p1;
+  const LossScratch sc = item_scratch<LossScratch>(scratch, item, S);
+  const LossGradScratch gsc = loss_grad_scratch(scratch, B, S);
+  const double d_edge = gsc.totals[LS_NEDGE] + 1e-6;
+  const int e = gsc.mask_edge[px] != 0.f ? 1 : 0;
+  int bi[3];
+  uint32_t word = (uint32_t)e << 27;
+  for (int c = 0; c < 3; ++c) { bi[c] = mask_sv[px * 3 + c] > 0.01f ? 1 : 0; word |= (uint32_t)bi[c] << (24 + c); }
+  for (int l = 0; l < kLossLevels; ++l) {
+    float v[6];
+    loss_level_samples(sc.coarse, S, l, y, x, v);
+    for (int c = 0; c < 3; ++c) {
+      const int sg = loss_sign(v[3 + c] - v[c]);
+      if (l == 0) gsc.g[0][px * 3 + c] = (float)(((double)sg * loss_grad_weight(bi[c], e)) / d_edge);
+      else word |= (uint32_t)(sg > 0 ? 1 : (sg < 0 ? 2 : 0)) << (2 * ((l - 1) * 3 + c));
+    }
+  }
+  gsc.words[px] = word;
+}
+
+__global__ __launch_bounds__(256) void losses_upT_kernel(int B, int S, void* scratch) {
+#pragma clang fp contract(off)
+  __shared__ double s_t[6 * 256];              // [rows <= 2 scale][s][3]: 6 S doubles at most
+  __shared__ double s_w[4];                    // weight / d_edge by (bi, e)
+  __shared__ double s_wx[2 * 256];             // [s][2 scale]: what coarse column cx receives from fine column scale cx - scale / 2 + j
+  const int item = blockIdx.y, tid = threadIdx.x;
+  int l = 1, cy = blockIdx.x;
+  while (cy >= (S >> l)) { cy -= S >> l; ++l; }
+  const int s = S >> l, scale = 1 << l;
+  const LossGradScratch gsc = loss_grad_scratch(scratch, B, S);
+  if (tid < 4) s_w[tid] = loss_grad_weight(tid >> 1, tid & 1) / (gsc.totals[LS_NEDGE] + 1e-6);
+  for (int i = tid; i < 2 * S; i += 256) {
+    const int cx = i / (2 * scale), x = scale * cx - scale / 2 + i % (2 * scale);
+    s_wx[i] = x >= 0 && x < S ? loss_up_weight(x, cx, S, s) : 0.0;
+  }
+  __syncthreads();
+  int ylo, yhi;
+  loss_up_range(cy, scale, S, ylo, yhi);
+  const int rows = yhi - ylo;
+  const uint32_t* words = gsc.words + (size_t)item * S * S;
+  for (int i = tid; i < rows * s; i += 256) {              // the row pass: a thread per (fine row, coarse column), its three channels
+    const int cx = i % s, y = ylo + i / s;
+    const int shift = 6 * (l - 1);
+    int xlo, xhi;
+    loss_up_range(cx, scale, S, xlo, xhi);
+    const double* wx = s_wx + (scale * cx + scale / 2);          // cx's row of the table, indexed by the fine column: 2 scale cx - (scale cx - scale / 2)
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int x = xlo; x < xhi; ++x) {
+      const uint32_t w = words[(size_t)y * S + x];
+      const uint32_t e = (w >> 27) & 1u;
+      const double wgt = wx[x];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint32_t code = (w >> (shift + 2 * c)) & 3u;
+        const double d = s_w[(((w >> (24 + c)) & 1u) << 1) | e];
+        acc[c] += wgt * (code == 1u ? d : (code == 2u ? -d : 0.0));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s_t[(size_t)i * 3 + c] = acc[c];
+  }
+  __syncthreads();
+  for (int i = tid; i < s * 3; i += 256) {                 // the column pass
+    const int c = i % 3, cx = i / 3;
+    double acc = 0.0;
+    for (int r = 0; r < rows; ++r) acc += loss_up_weight(ylo + r, cy, S, s) * s_t[((size_t)r * s + cx) * 3 + c];
+    gsc.g[l][(((size_t)item * s + cy) * s + cx) * 3 + c] = (float)acc;
+  }
+}
+
+// rbar[i, j] of channel c of one item's map g [s][s][3]: the transpose of (dy + dx) * 5 with its zero last row and last column
+__device__ inline double loss_diff_t(const float* __restrict__ g, int s, int i, int j, int c) {
+#pragma clang fp contract(off)
+  const double own = (double)g[((size_t)i * s + j) * 3 + c];
+  const double up = i >= 1 ? (double)g[((size_t)(i - 1) * s + j) * 3 + c] : 0.0;
+  const double left = j >= 1 ? (double)g[((size_t)i * s + j - 1) * 3 + c] : 0.0;
+  return 5.0 * (((up - (i + 1 < s ? own : 0.0)) + left) - (j + 1 < s ? own : 0.0));
+}
+
+__global__ __launch_bounds__(256) void losses_grad_kernel(const float* __restrict__ gt, const float* __restrict__ mask_sv, const float* __restrict__ gs,
+                                                          const float* __restrict__ con, const float* __restrict__ upstream, int B, int S, void* scratch,
+                                                          float* __restrict__ grad_gs, float* __restrict__ grad_con, float* __restrict__ d_recon_c,
+                                                          float* __restrict__ d_grad) {
+#pragma clang fp contract(off)
+  const int item = blockIdx.y, p1 = blockIdx.x * 256 + threadIdx.x;
+  const int y = p1 / S, x = p1 % S;
+  const size_t px = (size_t)item * S * S + p1, q = px * 3;
+  const LossGradScratch gsc = loss_grad_scratch(scratch, B, S);
+  const double u_gs = upstream != nullptr ? (double)upstream[0] : 1.0, u_c = upstream != nullptr ? (double)upstream[1] : 1.0,
+               u_g = upstream != nullptr ? (double)upstream[2] : 1.0;
+  const double n = (double)B * (double)S * (double)S, d_bi = gsc.totals[LS_NBI] + 1e-6, d_edge = gsc.totals[LS_NEDGE] + 1e-6;
+  const double e = gsc.mask_edge[px] != 0.f ? 1.0 : 0.0;
+  float g3[3], c3[3];
+  double bi[3], nb = 0.0;
+  for (int c = 0; c < 3; ++c) { g3[c] = gt[q + c]; c3[c] = con[q + c]; bi[c] = mask_sv[q + c] > 0.01f ? 1.0 : 0.0; }
+  nb = (bi[0] + bi[1]) + bi[2];
+  const double w1 = (1.0 / n + (30.0 * nb) / d_bi) + (10.0 * e) / d_edge;
+  grad_gs[px] = (float)(((u_gs * (double)loss_sign(gs[px] - loss_gray(g3))) * w1) / 41.0);
+  const float yuv_w[3][3] = {{.299f, .587f, .114f}, {-.168736f, -.331264f, .5f}, {.5f, -.418688f, -.081312f}};
+  double sk[3];
+  for (int k = 0; k < 3; ++k)
+    sk[k] = (double)loss_sign(loss_weighted(c3, yuv_w[k][0], yuv_w[k][1], yuv_w[k][2]) - loss_weighted(g3, yuv_w[k][0], yuv_w[k][1], yuv_w[k][2]));
+  for (int c = 0; c < 3; ++c) {
+    const double a_c = (1.0 / (3.0 * n) + (30.0 * bi[c]) / (3.0 * d_bi)) + (10.0 * e) / (3.0 * d_edge);
+    const double yuv_c = (sk[0] * (double)yuv_w[0][c] + sk[1] * (double)yuv_w[1][c]) + sk[2] * (double)yuv_w[2][c];
+    const double rc = (u_c * ((double)loss_sign(c3[c] - g3[c]) * a_c + (yuv_c * w1) / 2.0)) / 82.0;
+    double acc = loss_diff_t(gsc.g[0] + (size_t)item * S * S * 3, S, y, x, c);
+    for (int l = 1; l < kLossLevels; ++l) {
+      const int scale = 1 << l, s = S >> l, ry = y & (scale - 1), rx = x & (scale - 1);
+      const bool hit = (ry == scale / 2 - 1 || ry == scale / 2) && (rx == scale / 2 - 1 || rx == scale / 2);
+      acc = acc + (hit ? 0.25 * loss_diff_t(gsc.g[l] + (size_t)item * s * s * 3, s, y >> l, x >> l, c) : 0.0);
+    }
+    const double dg = u_g * acc;
+    grad_con[q + c] = (float)(rc + dg);
+    if (d_recon_c != nullptr) d_recon_c[q + c] = (float)rc;
+    if (d_grad != nullptr) d_grad[q + c] = (float)dg;
+  }
+}
+
+inline hipError_t launch_train_losses_grad(const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con, const float* upstream,
+                                           int B, int S, double* sums, float* losses3, float* grad_gs, float* grad_con, float* d_recon_c, float* d_grad,
+                                           void* scratch, hipStream_t stream) {
+  const LossGradScratch gsc = loss_grad_scratch(scratch, B, S);
+  hipError_t e = launch_train_losses(img, gt, mask_sv, gs, con, B, S, sums, losses3, gsc.mask_edge, nullptr, nullptr, scratch, stream, gsc.totals);
+  if (e != hipSuccess) return e;
+  const dim3 pixels((unsigned)(S * S / 256), (unsigned)B);
+  hipLaunchKernelGGL(losses_sign_kernel, pixels, dim3(256), 0, stream, mask_sv, B, S, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(losses_upT_kernel, dim3((unsigned)loss_up_rows(S), (unsigned)B), dim3(256), 0, stream, B, S, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(losses_grad_kernel, pixels, dim3(256), 0, stream, gt, mask_sv, gs, con, upstream, B, S, scratch, grad_gs, grad_con, d_recon_c, d_grad);
   return hipGetLastError();
 }
 

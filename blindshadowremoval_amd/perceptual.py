@@ -59,12 +59,15 @@ With `acts` given (a dict like `forward`'s, for example the device's kept activa
 read from it instead of from the statement's own float64 forward, so that a comparison with the device is free of mask flips at values
 that round across 0.  `per_loss_f64` is the same objective with no float32 rounding anywhere, for finite differences.
 
-`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad]` evaluates the whole objective on
+`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total]` evaluates the whole objective on
 a folder written by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling
 (train_losses.folder_steps): the six logged losses (recon_gs, recon_c, grad, gen, disc_real, disc_fake), per, g_total and d_total per
 batch and as step-weighted means.  The device route uses TrainLosses, Discriminators and Perceptual; --host the three host statements.
 With --grad each batch's line also carries per_grad_l1 and per_grad_linf, the L1 and L-infinity norms of 0.005 d per / d con_rgb: the
 share of g_total_loss' gradient that this term contributes (Perceptual.per_loss_grad with upstream 0.005; --host: per_loss_grad).
+With --grad-total each batch's line carries instead TOTAL_GRAD_NAMES, the norms of the whole d g_total_loss / d con_rgb and
+d g_total_loss / d gs: TrainLosses.step_losses_grad under train_losses.G_TOTAL_WEIGHTS, plus Discriminators.gen_grad, plus
+Perceptual.per_loss_grad with 0.005, added as float32 tensors in that order (--host: the three statements' gradients likewise).
 """
 from __future__ import annotations
 
@@ -181,6 +184,7 @@ def per_loss(weights: Dict[str, np.ndarray], gt, con_rgb) -> Dict[str, np.ndarra
 # ---- the backward: d per / d con_rgb
 GRAD_NAMES = ("per_grad_l1", "per_grad_linf")
 PER_WEIGHT = f32(.005)                # per_loss' weight in g_total_loss
+TOTAL_GRAD_NAMES = ("g_total_grad_con_l1", "g_total_grad_con_linf", "g_total_grad_gs_l1", "g_total_grad_gs_linf")
 
 
 def tap_weights(B: int, S: int) -> List[np.float32]:
@@ -305,11 +309,12 @@ def grad_norms(grad) -> List[float]:
 
 
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False, grad: bool = False) -> Dict[str, float]:
+                 quiet: bool = False, grad: bool = False, grad_total: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the discriminators' weights come from the latest checkpoint under `ckpt`, from
     init_discriminator_weights without it.  With `grad` each batch's line also carries GRAD_NAMES, the norms of PER_WEIGHT d per / d con_rgb
-    (they are per batch, not part of the means)."""
+    (they are per batch, not part of the means); with `grad_total` TOTAL_GRAD_NAMES instead, the norms of the whole
+    d g_total_loss / d con_rgb and d g_total_loss / d gs."""
     import torch
     from . import discriminator as disc
     from . import train_losses as tl
@@ -332,9 +337,18 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
             if host:
                 torch.cuda.synchronize(dev)
                 con_a = con_rgb.cpu().numpy()
-                three = tl.step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a)["losses"]
+                if grad_total:
+                    three_g = tl.step_losses_grad(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a, upstream=np.array(tl.G_TOTAL_WEIGHTS, f32))
+                    three = three_g["losses"]
+                    gan_g = disc.gen_grad(disc_w, gt_a, con_a, mask_a)["grad"].astype(f32)
+                else:
+                    three = tl.step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a)["losses"]
                 gan = disc.gan_losses(disc_w, gt_a, con_a, mask_a)["losses"]
-                if grad:
+                if grad_total:
+                    res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
+                    per = res["loss"]
+                    norms = grad_norms((three_g["grad_con"] + gan_g) + np.asarray(res["grad"], f32)) + grad_norms(three_g["grad_gs"])
+                elif grad:
                     res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
                     per, norms = res["loss"], grad_norms(res["grad"])
                 else:
@@ -348,21 +362,28 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                     runners[1].load_weights(disc_w)
                     runners[2].load_weights(vgg_w)
                 gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
-                three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
-                gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
-                if grad:
-                    if weight_d is None:
-                        weight_d = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=dev)
+                if (grad or grad_total) and weight_d is None:
+                    weight_d = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=dev)
+                if grad_total:
+                    three_g = runners[0].step_losses_grad(im_d, gt_d, mask_d, gs, con_rgb, upstream=torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(dev))
+                    gan_g = runners[1].gen_grad(gt_d, con_rgb, mask_d)
                     res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
-                    per, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
+                    three, gan, per = three_g[0].cpu().numpy(), gan_g[0].cpu().numpy(), res[0].cpu().numpy()
+                    norms = grad_norms(((three_g[3] + gan_g[2]) + res[2]).cpu().numpy()) + grad_norms(three_g[2].cpu().numpy())
                 else:
-                    per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
+                    three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
+                    gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
+                    if grad:
+                        res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
+                        per, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
+                    else:
+                        per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
             vals = [float(v) for v in three] + [float(v) for v in gan] + [float(per[0])]
             vals.append(float(g_total_loss(three[0], three[1], three[2], gan[0], per[0])))
             vals.append(float(d_total_loss(gan[1], gan[2])))
             Logging.accumulate(acc, dict(zip(ALL_NAMES, vals)))
             if not quiet:
-                shown = list(zip(ALL_NAMES, vals)) + (list(zip(GRAD_NAMES, norms)) if grad else [])
+                shown = list(zip(ALL_NAMES, vals)) + (list(zip(TOTAL_GRAD_NAMES, norms)) if grad_total else list(zip(GRAD_NAMES, norms)) if grad else [])
                 print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in shown), flush=True)
     return {k: s / max(c, 1) for k, (s, c) in acc.items()}
 
@@ -377,8 +398,9 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
     ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
+    ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
     a = ap.parse_args(argv)
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad)
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

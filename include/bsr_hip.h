@@ -227,6 +227,23 @@ size_t bsr_train_losses_scratch_bytes(int B, int S);
 int bsr_train_losses(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb, int B, int S,
                      double* sums, float* losses3, float* mask_edge, float* bmaskgt, float* dif_grad, void* scratch, void* stream);
 
+/* The same three losses and the gradient of upstream[0] recon_gs + upstream[1] recon_c + upstream[2] grad with respect to gs and
+ * con_rgb; train_losses.step_losses_grad is the host statement and writes the arithmetic out.  Inputs as bsr_train_losses; upstream: three
+ * float32 on the device, or NULL for ones.  sums and losses3 are bsr_train_losses' bytes.  Outputs: grad_gs [B][S][S][1], grad_con
+ * [B][S][S][3] = d_recon_c + d_grad (added in float64, rounded once) and, each optional (may be NULL), the two parts d_recon_c and d_grad
+ * [B][S][S][3].  grad_gs and d_recon_c are formed in float64 in the statement's order and are bit-identical to it; d_grad goes through
+ * the five maps g_l (the transposed resize back to S of the signed weights, level l = 0..4, [B][S >> l][S >> l][3] float32), which stay
+ * in the scratch: scratch is bsr_train_losses_grad_scratch_bytes(B, S) bytes, 256-byte aligned = the forward's scratch, unchanged,
+ * followed by the gradient's; bsr_train_losses_grad_offset(B, S, level) is the byte offset of g_level, SIZE_MAX for arguments out of
+ * range.  The forward's three launches and three more on `stream`: no host synchronisation, no second stream, no floating-point
+ * atomics, every sum in a fixed order: a call repeats its bits.  Every word read is written earlier in the same call.  Sizes and errors
+ * as bsr_train_losses.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_train_losses_grad_scratch_bytes(int B, int S);
+size_t bsr_train_losses_grad_offset(int B, int S, int level);
+int bsr_train_losses_grad(int device, const float* img, const float* gt, const float* mask_sv, const float* gs, const float* con_rgb,
+                          const float* upstream, int B, int S, double* sums, float* losses3, float* grad_gs, float* grad_con, float* d_recon_c,
+                          float* d_grad, void* scratch, void* stream);
+
 /* The three multi-scale patch discriminators of the reference's train_step and its three GAN losses (train_test_GSC.py:264-268, 302,
  * 334-336; model.py:115-147, 292-312; utils.py:100-102; training=False) for a batch on the device: gen, disc_real and disc_fake;
  * blindshadowremoval_amd/discriminator.py is the host statement and writes the arithmetic out.  d_blob: the device copy of
