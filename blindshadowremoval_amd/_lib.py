@@ -86,6 +86,13 @@ SIGNATURES = {
     "bsr_disc_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
     "bsr_disc_gen_grad": (c_i, [c_i] + _BLOBS + [c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v]),
     "bsr_debug_disc_gen_grad": (c_i, [c_i] + _BLOBS + [c_v, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_v]),
+    "bsr_disc_wgrad_blob_bytes": (c_sz, []),
+    "bsr_disc_wgrad_scratch_bytes": (c_sz, _BS),
+    "bsr_disc_wgrad_floats": (c_sz, []),
+    "bsr_disc_wgrad_var_offset": (c_sz, [c_i]),
+    "bsr_disc_wgrad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_disc_wgrad": (c_i, [c_i] + _BLOBS + [c_v, c_sz, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v]),
+    "bsr_debug_disc_wgrad": (c_i, [c_i] + _BLOBS + [c_v, c_sz, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_v]),
     "bsr_vgg_blob_bytes": (c_sz, []),
     "bsr_vgg_scratch_bytes": (c_sz, _BS),
     "bsr_vgg_act_offset": (c_sz, [c_i, c_i, c_i]),

@@ -40,6 +40,7 @@
 #include "train_losses_kernels.h"
 #include "disc_kernels.h"
 #include "disc_grad_kernels.h"
+#include "disc_wgrad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1525,6 +1526,59 @@ int bsr_debug_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, c
                             float* grad, void* scratch, int stop_after, void* stream) {
   return disc_gen_grad("bsr_debug_disc_gen_grad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, gt, con_rgb, mask_sv, upstream, B, S, sums, losses3,
                        logits, grad, scratch, stop_after, stream);
+}
+
+size_t bsr_disc_wgrad_blob_bytes(void) { return 3 * bsr::disc_wgrad_w_off(bsr::kDiscLayers) * sizeof(float); }
+
+size_t bsr_disc_wgrad_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kDiscMaxB ? bsr::disc_wgrad_plan(B, S).total : 0; }
+
+size_t bsr_disc_wgrad_floats(void) { return bsr::disc_wgrad_var_offset(bsr::kDiscVars); }
+
+size_t bsr_disc_wgrad_var_offset(int index) { return index < 0 || index >= bsr::kDiscVars ? SIZE_MAX : bsr::disc_wgrad_var_offset(index); }
+
+size_t bsr_disc_wgrad_offset(int B, int S, int k, int layer) {
+  if (!post_size_ok(B, S) || B > bsr::kDiscMaxB || k < 1 || k > 3 || layer < 1 || layer > bsr::kDiscLayers + 1) return SIZE_MAX;
+  return bsr::disc_wgrad_map_offset(B, S, k - 1, layer);
+}
+
+namespace {
+
+int disc_wgrad(const char* name, int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const void* d_wgrad_blob,
+               size_t wgrad_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums, float* losses3, float* logits,
+               float* grads, void* scratch, int stop_after, void* stream) {
+  const std::string n(name);
+  if (B > bsr::kDiscMaxB) return fail(BSR_ERR_ARG, n + ": B must be 1..32767");
+  if (blob_bytes != bsr_disc_blob_bytes()) return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_disc_blob_bytes() (pack.pack_discriminators)");
+  if (dgrad_bytes != bsr_disc_dgrad_blob_bytes())
+    return fail(BSR_ERR_ARG, n + ": dgrad_bytes must be bsr_disc_dgrad_blob_bytes() (pack.pack_discriminators_dgrad)");
+  if (wgrad_bytes != bsr_disc_wgrad_blob_bytes())
+    return fail(BSR_ERR_ARG, n + ": wgrad_bytes must be bsr_disc_wgrad_blob_bytes() (pack.pack_discriminators_wgrad)");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(d_dgrad_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(d_wgrad_blob) % 16 != 0)
+    return fail(BSR_ERR_ARG, n + ": d_blob, d_dgrad_blob and d_wgrad_blob must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sums) % 8 != 0) return fail(BSR_ERR_ARG, n + ": sums must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(grads) % 4 != 0) return fail(BSR_ERR_ARG, n + ": grads must be 4-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kDiscWgradLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..11");
+  return run_post(name, {d_blob, d_dgrad_blob, d_wgrad_blob, gt, con_rgb, mask_sv, sums, losses3, grads, scratch}, B, S, scratch, device, [&] {
+    HIP_TRY(bsr::launch_disc_wgrad(static_cast<const float*>(d_blob), static_cast<const float*>(d_dgrad_blob), static_cast<const float*>(d_wgrad_blob), gt,
+                                   con_rgb, mask_sv, B, S, sums, losses3, logits, grads, scratch, stop_after, static_cast<hipStream_t>(stream)));
+    return BSR_OK;
+  });
+}
+
+}  // namespace
+
+int bsr_disc_wgrad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const void* d_wgrad_blob, size_t wgrad_bytes,
+                   const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums, float* losses3, float* logits, float* grads,
+                   void* scratch, void* stream) {
+  return disc_wgrad("bsr_disc_wgrad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, d_wgrad_blob, wgrad_bytes, gt, con_rgb, mask_sv, B, S, sums, losses3,
+                    logits, grads, scratch, bsr::kDiscWgradLaunches, stream);
+}
+
+int bsr_debug_disc_wgrad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const void* d_wgrad_blob,
+                         size_t wgrad_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums, float* losses3,
+                         float* logits, float* grads, void* scratch, int stop_after, void* stream) {
+  return disc_wgrad("bsr_debug_disc_wgrad", device, d_blob, blob_bytes, d_dgrad_blob, dgrad_bytes, d_wgrad_blob, wgrad_bytes, gt, con_rgb, mask_sv, B, S, sums,
+                    losses3, logits, grads, scratch, stop_after, stream);
 }
 
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }

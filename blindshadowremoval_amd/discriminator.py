@@ -1,8 +1,8 @@
 """The three multi-scale patch discriminators of the reference's `train_step` and its three GAN losses as a host statement: `gen`,
 `disc_real` and `disc_fake` (train_test_GSC.py:121-123, 264-268, 302, 334-336, 353-355; model.py:115-147, 292-312; utils.py:100-102),
 restated in numpy for training=False.  It plays the role for csrc/disc_kernels.h (bsr_disc_losses, discriminator_gpu.Discriminators)
-that train_losses.py plays for its chain.  The VGG perceptual term, g_total_loss, training=True (batch statistics, dropout), every
-backward pass and the optimisers are not here.
+that train_losses.py plays for its chain.  The VGG perceptual term, g_total_loss, training=True (batch statistics, dropout), the
+generator's backward and the optimisers are not here.
 
 INPUTS.  gt, con_rgb (deshadow_img_c), mask_sv [B,S,S,3] float32; S in SIZES, B in 1..32767.  The variables are float32
 (weights.discriminator_variable_shapes).
@@ -44,13 +44,21 @@ of TensorFlow's gradient definitions (Conv2DBackpropInput, the moving-statistics
 the bilinear resize) and tests/golden/discriminator_grad_*.npz holds torch autograd's float64 gradient of the same objective
 (tools/make_discriminator_grad_fixture.py).
 
-`python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host] [--grad]` scores the three terms on a folder written
+`python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host] [--grad] [--wgrad]` scores the three terms on a folder written
 by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling (train_losses.folder_steps): the
 generator runs on row 0 of each element and its con_rgb is the fake image.  The weights of the generator and of the discriminators
 come from the latest checkpoint under --ckpt, from init_weights / init_discriminator_weights without it.  The step-weighted means
 are printed as Logging.display prints them.  --host computes the three terms with this statement from the same generator outputs.
 With --grad each batch's line also carries gen_grad_l1 and gen_grad_linf, the L1 and L-infinity norms of d gen / d con_rgb
-(Discriminators.gen_grad; --host: gen_grad).
+(Discriminators.gen_grad; --host: gen_grad).  With --wgrad it carries d_grad_l1 and d_grad_linf, the norms over all 54 gradients of
+d_total_loss with respect to the discriminators' variables (Discriminators.disc_grad; --host: disc_grad).
+
+THE BACKWARD: d d_total_loss / d the discriminators' variables (`disc_grad`, csrc/disc_wgrad_kernels.h, Discriminators.disc_grad).  For
+the discriminators' update the images are data and d_total_loss = disc_real + disc_fake is differentiated with respect to the 54
+trainable variables (weights.discriminator_trainable_names) over all 2B rows, in the mode everything here runs in (training=False,
+moving statistics).  `disc_grad`'s docstring writes every operation out; tests/golden/discriminator_wgrad_32.npz holds torch autograd's
+float64 gradients as float32 (tools/make_discriminator_wgrad_fixture.py), and `d_total_f64` is the objective without float32 rounding
+for the finite-difference test.
 """
 from __future__ import annotations
 
@@ -329,12 +337,159 @@ def grad_norms(grad) -> Tuple[float, float]:
     return float(g.sum()), float(g.max())
 
 
+# ---- the backward: d d_total_loss / d the discriminators' variables
+WGRAD_NAMES = ("d_grad_l1", "d_grad_linf")
+
+
+def hinge_seed(logits: np.ndarray, B: int, w_k) -> np.ndarray:
+    """The float32 logits [2B,h,h] of one discriminator -> float64 [2B,h,h,1], d d_total_loss / d out: -w_k on a real row where the
+    float32 term 1 - y is > 0, +w_k on a fake row where the float32 term 1 + y is > 0, 0 elsewhere (a term of exactly 0 passes
+    nothing: TensorFlow's Maximum hands a tie to its first argument, the constant 0.)."""
+    y = np.asarray(logits).astype(f32)
+    seed = np.zeros(y.shape, np.float64)
+    seed[:B] = np.where(f32(1) - y[:B] > 0, -float(w_k), 0.0)
+    seed[B:] = np.where(f32(1) + y[B:] > 0, float(w_k), 0.0)
+    return seed[..., None]
+
+
+def conv2d_same_wgrad(x: np.ndarray, gy: np.ndarray, stride: int, ksize: int = 4) -> np.ndarray:
+    """The input [N,H,H,C] of a Conv2D(padding='same') and the gradient [N,Ho,Ho,O] at its output -> float64 [ksize,ksize,C,O], the
+    gradient at its HWIO kernel: gk[a, b, c, o] = sum_{n, oy, ox} x[n, s oy + a - before, s ox + b - before, c] gy[n, oy, ox, o],
+    positions outside the map reading 0."""
+    x, gy = np.asarray(x, np.float64), np.asarray(gy, np.float64)
+    n, h, _, c = x.shape
+    ho = gy.shape[1]
+    pt, pb = same_pad(h, ksize, stride)
+    assert ho == -(-h // stride) and gy.shape[2] == ho
+    xp = np.zeros((n, h + pt + pb, h + pt + pb, c), np.float64)
+    xp[:, pt:pt + h, pt:pt + h] = x
+    out = np.zeros((ksize, ksize, c, gy.shape[3]), np.float64)
+    span = (ho - 1) * stride + 1
+    for a in range(ksize):
+        for b in range(ksize):
+            out[a, b] = np.tensordot(xp[:, a:a + span:stride, b:b + span:stride], gy, axes=([0, 1, 2], [0, 1, 2]))
+    return out
+
+
+def disc_grad(weights: Dict[str, np.ndarray], gt, con_rgb, mask_sv, acts=None, logits=None) -> Dict[str, np.ndarray]:
+    """d d_total_loss / d v for each of the 54 trainable variables v of the three discriminators
+    (weights.discriminator_trainable_names), training=False, with d_total_loss = disc_real + disc_fake -> dict(name -> float64 array in
+    the variable's own shape (HWIO kernels), and each stage's gradient for all 2B rows under `forward`'s names: `d{k}/out` [2B,h_k,h_k,1]
+    the seed, `d{k}/conv{i}` [2B,.,.,n_ch[i]] the gradient at conv_stack[i]'s BatchNormalization output).  float64 arithmetic from the
+    float32 variables, for discriminator k = 1, 2, 3 from the top down:
+      seed             with w_k = float32(1 / (B h_k^2)) and y the float32 logit (`hinge_seed`): a real row gets -w_k where the float32
+                       term 1 - y is > 0, a fake row +w_k where the float32 term 1 + y is > 0, everything else 0.  This is TensorFlow's
+                       Maximum gradient with the constant 0. as first argument: a tie goes to the constant, so a term of exactly 0
+                       passes nothing.
+      head             d kernel[a, b, c, 0] = sum_{n, oy, ox} seed[n, oy, ox] x[n, oy + a - 1, ox + b - 1, c] over conv3's kept output x,
+                       positions outside the map reading 0 (`conv2d_same_wgrad`, stride 1); d bias = sum seed; the gradient handed
+                       down is conv2d_same_dgrad(seed, kernel, 1, side).
+      each stride-2 layer i, from 3 down to 0, with gz the incoming gradient after LeakyReluGrad on the layer's kept output
+      (`leaky_grad`: g where y > 0, 0.3 g otherwise), inv = gamma / sqrt(moving_variance + eps) (`bn_inv`), x the layer's input
+      (`d{k}/in`, 6 channels, for layer 0 and `d{k}/conv{i-1}` otherwise) and c = conv2d_same(x, kernel, bias, 2):
+                       d beta[o] = sum gz[..., o]
+                       d gamma[o] = sum gz[..., o] (c[..., o] - moving_mean[o]) / sqrt(moving_variance[o] + eps)
+                       d bias[o] = inv[o] sum gz[..., o]
+                       d kernel[a, b, c, o] = inv[o] sum_{n, oy, ox} x[n, 2 oy + a - before, 2 ox + b - before, c] gz[n, oy, ox, o],
+                       `before` of same_pad and positions outside the map reading 0, the 1 x 1 -> 1 x 1 layer (pad 1, 2) of
+                       discriminator 3 at S = 32 included.
+                       The gradient handed down is conv2d_same_dgrad(gz inv, kernel, 2, side); it is not formed below conv0.
+    With `logits` given (three maps [2B,h_k,h_k], for example the device's) the hinge masks are read from them instead of from the
+    statement's own float64 forward rounded to float32; with `acts` given (a dict like `forward`'s) the LeakyReLU masks, the layers'
+    inputs x and the convolution outputs c are read or formed from it, as gen_grad reads its masks."""
+    B, S = check_inputs(gt, con_rgb, mask_sv)
+    A = forward(weights, gt, con_rgb, mask_sv) if acts is None else acts
+    Y = logits_of(A) if logits is None else logits
+    out: Dict[str, np.ndarray] = {}
+    for k, w_k in zip((1, 2, 3), seed_weights(B, S)):
+        sides = map_sides(S, k)
+        head_st = "discriminator_%d/conv2/conv/" % k
+        g = hinge_seed(np.asarray(Y[k - 1]).reshape(2 * B, sides[-1], sides[-1]), B, w_k)
+        out["d%d/out" % k] = g
+        out[head_st + "kernel"] = conv2d_same_wgrad(A["d%d/conv%d" % (k, N_LAYER_D - 1)], g, 1)
+        out[head_st + "bias"] = g.sum(axis=(0, 1, 2))
+        g = conv2d_same_dgrad(g, weights[head_st + "kernel"], 1, sides[N_LAYER_D])
+        for i in reversed(range(N_LAYER_D)):
+            st = "discriminator_%d/conv_stack/%d/" % (k, i)
+            gz = leaky_grad(g, np.asarray(A["d%d/conv%d" % (k, i)]))
+            out["d%d/conv%d" % (k, i)] = gz
+            inv = bn_inv(weights, k, i)
+            x = np.asarray(A["d%d/in" % k] if i == 0 else A["d%d/conv%d" % (k, i - 1)], np.float64)
+            c = conv2d_same(x, weights[st + "conv/kernel"], weights[st + "conv/bias"], 2)
+            mean, var = (np.asarray(weights[st + "bnorm/" + p], np.float64) for p in ("moving_mean", "moving_variance"))
+            total = gz.sum(axis=(0, 1, 2))
+            out[st + "bnorm/beta"] = total
+            out[st + "bnorm/gamma"] = (gz * ((c - mean) / np.sqrt(var + BN_EPS))).sum(axis=(0, 1, 2))
+            out[st + "conv/bias"] = inv * total
+            out[st + "conv/kernel"] = conv2d_same_wgrad(x, gz, 2) * inv
+            if i > 0:
+                g = conv2d_same_dgrad(gz * inv, weights[st + "conv/kernel"], 2, sides[i])
+    return out
+
+
+def d_total_f64(weights: Dict[str, np.ndarray], gt, con_rgb, mask_sv, masks: Optional[List[np.ndarray]] = None, dtype=np.float64):
+    """d_total_loss = disc_real + disc_fake as a function of the variables with no float32 rounding anywhere (the resizes are the
+    exact means of their four pixels, the hinge terms and the divisors B h_k^2 are formed in `dtype`): the objective disc_grad
+    differentiates, up to w_k's rounding to float32.  `weights` may hold arrays of any float type; they are used in `dtype`
+    (float64, or numpy's extended precision for tests/test_discriminator_wgrad_cpu.py's finite differences).  A list given as `masks`
+    receives every LeakyReLU mask (y > 0) and then the two hinge masks of each discriminator, in order."""
+    T = dtype
+    gt, con_rgb, mask_sv = (np.asarray(a, T) for a in (gt, con_rgb, mask_sv))
+    x = np.concatenate([np.concatenate([gt, con_rgb], axis=0), np.concatenate([mask_sv, mask_sv], axis=0)], axis=3)
+    n, S = x.shape[:2]
+    B = n // 2
+    total = T(0)
+    for k in (1, 2, 3):
+        ds = DOWNSIZE[k - 1]
+        lo = 0 if ds < 4 else 1
+        h = x if ds == 1 else x.reshape(n, S // ds, ds, S // ds, ds, 6)[:, :, lo:lo + 2, :, lo:lo + 2].mean(axis=(2, 4))
+        for i in range(N_LAYER_D):
+            st = "discriminator_%d/conv_stack/%d/" % (k, i)
+            g, beta, mean, var = (np.asarray(weights[st + "bnorm/" + p], T) for p in ("gamma", "beta", "moving_mean", "moving_variance"))
+            inv = g / np.sqrt(var + T(BN_EPS))
+            y = _conv_same_any(h, weights[st + "conv/kernel"], weights[st + "conv/bias"], 2, T) * inv + (beta - mean * inv)
+            if masks is not None:
+                masks.append(np.asarray(y > 0))
+            h = np.where(y >= 0, y, T(LRELU_ALPHA) * y)
+        st = "discriminator_%d/conv2/conv/" % k
+        out = _conv_same_any(h, weights[st + "kernel"], weights[st + "bias"], 1, T)[..., 0]
+        real, fake = T(1) - out[:B], T(1) + out[B:]
+        if masks is not None:
+            masks += [np.asarray(real > 0), np.asarray(fake > 0)]
+        total = total + (np.maximum(T(0), real).sum() + np.maximum(T(0), fake).sum()) / T(B * out.shape[1] * out.shape[2])
+    return total
+
+
+def _conv_same_any(x, kernel, bias, stride: int, T) -> np.ndarray:
+    """conv2d_same in the float type T."""
+    x, kernel = np.asarray(x, T), np.asarray(kernel, T)
+    n, h, _, c = x.shape
+    pt, pb = same_pad(h, kernel.shape[0], stride)
+    ho = -(-h // stride)
+    xp = np.zeros((n, h + pt + pb, h + pt + pb, c), T)
+    xp[:, pt:pt + h, pt:pt + h] = x
+    out = np.zeros((n, ho, ho, kernel.shape[3]), T)
+    span = (ho - 1) * stride + 1
+    for a in range(kernel.shape[0]):
+        for b in range(kernel.shape[1]):
+            out += xp[:, a:a + span:stride, b:b + span:stride] @ kernel[a, b]
+    return out + np.asarray(bias, T)
+
+
+def wgrad_norms(grads: Dict[str, np.ndarray]) -> Tuple[float, float]:
+    """The L1 and L-infinity norms over all 54 gradients of a dict that holds them under the trainable variables' names."""
+    from .weights import discriminator_trainable_names
+    mags = [np.abs(np.asarray(grads[n], np.float64)) for n in discriminator_trainable_names()]
+    return float(sum(m.sum() for m in mags)), float(max(m.max() for m in mags))
+
+
 # ---- the command-line entry
 def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False,
-                 stats: Optional[Dict[str, float]] = None, grad: bool = False) -> Dict[str, float]:
+                 stats: Optional[Dict[str, float]] = None, grad: bool = False, wgrad: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of gen, disc_real and disc_fake.
     With `host`, a `stats` dict receives `max_abs_logit`, the largest magnitude of the statement's logits over all steps.  With `grad`
-    each batch's line and the means also carry GRAD_NAMES, the norms of d gen / d con_rgb."""
+    each batch's line and the means also carry GRAD_NAMES, the norms of d gen / d con_rgb; with `wgrad`, WGRAD_NAMES, the norms over the
+    54 gradients of d_total_loss with respect to the discriminators' variables."""
     import torch
     from .fsrnet import Logging
     from .train_losses import folder_steps
@@ -359,6 +514,8 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
                 loss = r["losses"]
                 if grad:
                     norms = grad_norms(gen_grad(weights, gt_a, con_a, mask_a, acts=r["acts"])["grad"])
+                if wgrad:
+                    wnorms = wgrad_norms(disc_grad(weights, gt_a, con_a, mask_a, acts=r["acts"], logits=r["logits"]))
                 if stats is not None:
                     stats["max_abs_logit"] = max([stats.get("max_abs_logit", 0.0)] + [float(np.abs(y).max()) for y in r["logits"]])
             else:
@@ -372,9 +529,13 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
                     loss, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
                 else:
                     loss = runner.gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
+                if wgrad:
+                    wnorms = wgrad_norms({k: v.cpu().numpy() for k, v in runner.disc_grad(gt_d, con_rgb.contiguous(), mask_d)[2].items()})
             line = {k: float(v) for k, v in zip(LOSS_NAMES, loss)}
             if grad:
                 line.update(zip(GRAD_NAMES, norms))
+            if wgrad:
+                line.update(zip(WGRAD_NAMES, wnorms))
             Logging.accumulate(acc, line)
             if not quiet:
                 print(Logging.format_line(acc, step, steps), end="", flush=True)
@@ -392,9 +553,10 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--host", action="store_true", help="compute the three terms with the host statement instead of the device chain")
     ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of d gen / d con_rgb")
+    ap.add_argument("--wgrad", action="store_true", help="per batch also the L1 and L-infinity norms over the 54 gradients of d_total_loss")
     a = ap.parse_args(argv)
-    means = score_folder(a.folder, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad)
-    print(", ".join("%s:%.9g" % (k, means[k]) for k in LOSS_NAMES + (GRAD_NAMES if a.grad else ())))
+    means = score_folder(a.folder, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, wgrad=a.wgrad)
+    print(", ".join("%s:%.9g" % (k, means[k]) for k in LOSS_NAMES + (GRAD_NAMES if a.grad else ()) + (WGRAD_NAMES if a.wgrad else ())))
     return 0
 
 

@@ -606,6 +606,67 @@ def unpack_discriminators_dgrad(blob: bytes):
     return out
 
 
+DISC_WGRAD_VECS = ("bias", "inv", "moving_mean", "rstd")
+
+
+def disc_wgrad_layout():
+    """([(name, offset in floats, shape)] of ONE discriminator, floats per discriminator) of the weight-gradient chain's blob
+    (csrc/disc_wgrad_kernels.h): per stride-2 layer `conv<i>` the UNFOLDED kernel [16 taps (a * 4 + b)][C_in padded to 8][N] (d gamma
+    is formed from it), then four vectors [4][N]: the convolution's bias, inv = gamma / sqrt(moving_variance + eps), moving_mean and
+    rstd = 1 / sqrt(moving_variance + eps), inv and rstd formed in float64 and rounded once.  The head needs nothing here.  The blob is
+    the three discriminators' records in order."""
+    from .weights import DISC_CH, DISC_IN_CH
+    out, off, cin = [], 0, -(-DISC_IN_CH // DISC_CC) * DISC_CC
+    for i, n in enumerate(DISC_CH):
+        out.append(("conv%d/kernel" % i, off, (DISC_TAPS, cin, n)))
+        off += DISC_TAPS * cin * n
+        out.append(("conv%d/vecs" % i, off, (len(DISC_WGRAD_VECS), n)))
+        off += len(DISC_WGRAD_VECS) * n
+        cin = n
+    return out, off
+
+
+def disc_wgrad_record(weights: Dict[str, np.ndarray], k: int):
+    """{`conv<i>/kernel`: [16, C_in padded to 8, N], `conv<i>/vecs`: [4, N] (DISC_WGRAD_VECS)} of discriminator k, float32."""
+    from .weights import BN_EPS, DISC_CH
+    out = {}
+    for i in range(len(DISC_CH)):
+        st = "discriminator_%d/conv_stack/%d" % (k, i)
+        kern = np.asarray(weights[st + "/conv/kernel"], np.float32)
+        cin = -(-kern.shape[2] // DISC_CC) * DISC_CC
+        full = np.zeros((DISC_TAPS, cin, kern.shape[3]), np.float32)
+        full[:, :kern.shape[2]] = kern.reshape(DISC_TAPS, kern.shape[2], kern.shape[3])
+        rstd = 1.0 / np.sqrt(np.asarray(weights[st + "/bnorm/moving_variance"], np.float64) + BN_EPS)
+        inv = np.asarray(weights[st + "/bnorm/gamma"], np.float64) * rstd
+        out["conv%d/kernel" % i] = full
+        out["conv%d/vecs" % i] = np.stack([np.asarray(weights[st + "/conv/bias"], np.float64), inv,
+                                          np.asarray(weights[st + "/bnorm/moving_mean"], np.float64), rstd]).astype(np.float32)
+    return out
+
+
+def pack_discriminators_wgrad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The three discriminators' variables -> the blob bsr_disc_wgrad takes beside the other two (disc_wgrad_layout)."""
+    from .weights import check_discriminator_weights
+    check_discriminator_weights(weights)
+    layout, per = disc_wgrad_layout()
+    blob = np.zeros((3, per), np.float32)
+    for k in (1, 2, 3):
+        rec = disc_wgrad_record(weights, k)
+        for name, off, shape in layout:
+            assert rec[name].shape == tuple(shape)
+            blob[k - 1, off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_discriminators_wgrad(blob: bytes):
+    """The inverse of pack_discriminators_wgrad: [disc_wgrad_record(w, 1), disc_wgrad_record(w, 2), disc_wgrad_record(w, 3)]."""
+    layout, per = disc_wgrad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != 3 * per:
+        raise ValueError("a discriminator weight-gradient blob holds %d bytes, got %d" % (3 * per * 4, len(blob)))
+    return [{name: arr[k * per + off:k * per + off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout} for k in range(3)]
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

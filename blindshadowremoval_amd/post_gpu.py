@@ -57,9 +57,9 @@ class PostDevice:
 
     def scratch(self, b: int, s: int, grad: bool = False) -> int:
         """The 256-byte aligned device address of at least `SCRATCH_QUERY`(b, s) bytes of scratch; with `grad`, of
-        `GRAD_SCRATCH_QUERY`(b, s): the same bytes followed by the gradient maps.  A buffer that is too small is released before the
-        larger one is allocated."""
-        query = self.GRAD_SCRATCH_QUERY if grad else self.SCRATCH_QUERY or self.SYMBOL + "_scratch_bytes"
+        `GRAD_SCRATCH_QUERY`(b, s): the same bytes followed by the gradient maps; `grad` may also name a size query of a further chain
+        itself.  A buffer that is too small is released before the larger one is allocated."""
+        query = grad if isinstance(grad, str) else self.GRAD_SCRATCH_QUERY if grad else self.SCRATCH_QUERY or self.SYMBOL + "_scratch_bytes"
         need = int(getattr(_lib.load(), query)(b, s))
         if need == 0:
             raise ValueError(self.SIZE_TEXT % {"b": b, "s": s})

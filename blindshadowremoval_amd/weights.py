@@ -12,7 +12,7 @@ benchmarks and parity tests use ``init_weights(seed)``.
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, Tuple  # noqa: F401 (Tuple: string annotations)
+from typing import Dict, List, Tuple  # noqa: F401 (Tuple: string annotations)
 
 import numpy as np
 
@@ -139,6 +139,12 @@ def discriminator_variable_shapes(n_layer: int = N_LAYER_D) -> "OrderedDict[str,
             cin = n_ch[i]
         _conv(s, "discriminator_%d/conv2" % k, 4, cin, 1, False)                            # Conv(1, ksize=4, norm=False, nl=False)
     return s
+
+
+def discriminator_trainable_names(n_layer: int = N_LAYER_D) -> List[str]:
+    """The trainable variables of the three discriminators in discriminator_variable_shapes' order: every kernel, bias, gamma and beta;
+    moving_mean and moving_variance are BatchNormalization's statistics and take no gradient."""
+    return [n for n in discriminator_variable_shapes(n_layer) if not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
 def _draw(rng, name: str, shp, fan_in: float, gain: float) -> np.ndarray:

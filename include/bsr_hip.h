@@ -289,6 +289,35 @@ int bsr_debug_disc_gen_grad(int device, const void* d_blob, size_t blob_bytes, c
                             const float* con_rgb, const float* mask_sv, const float* upstream, int B, int S, double* sums, float* losses3,
                             float* logits, float* grad, void* scratch, int stop_after, void* stream);
 
+/* bsr_disc_losses and d d_total_loss / d the discriminators' 54 trainable variables in one call, d_total_loss = disc_real + disc_fake,
+ * training=False (blindshadowremoval_amd/discriminator.py: disc_grad is the host statement).  d_wgrad_blob: the device copy of
+ * pack.pack_discriminators_wgrad's blob, wgrad_bytes = bsr_disc_wgrad_blob_bytes() (the unfolded kernels and the per-channel vectors
+ * bias, inv, moving_mean, rstd), 16-byte aligned; d_blob and d_dgrad_blob as bsr_disc_gen_grad takes them.  Outputs: sums, losses3 and
+ * logits exactly as bsr_disc_losses writes them (the same launches), and grads, bsr_disc_wgrad_floats() float32: the variables of
+ * weights.discriminator_trainable_names() in that order, each dense in its own shape (HWIO kernels), variable `index` (0..53) at float
+ * offset bsr_disc_wgrad_var_offset(index); SIZE_MAX for an index out of range.  The forward's seven launches, then eleven more on
+ * `stream`, one after the other (csrc/disc_wgrad_kernels.h): the per-pixel hinge seed and the head's input gradient, the head's kernel
+ * gradient, per stride-2 layer the kernel gradient (matrix instructions, the reduction over the output pixels split over workgroups
+ * into partials) and, down to conv1, the data gradient over all 2B rows, then the fold of the partials in a fixed order in float64 and
+ * the per-channel gradients.  No host synchronisation, no second stream, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_disc_wgrad_scratch_bytes(B, S) bytes, 256-byte aligned = the forward's scratch, unchanged, followed by the gradient maps and the
+ * partials: bsr_disc_wgrad_offset(B, S, k, layer) is the byte offset of discriminator k's (1..3) gradient at conv0..conv3's
+ * BatchNormalization output [2B][.][.][32, 32, 64, 64] for layer 1..4 and of its seed [2B][h][h] for layer 5; SIZE_MAX for arguments out
+ * of range.  Every word read is written earlier in the same call.  Sizes and errors as bsr_disc_losses.  bsr_debug_disc_wgrad stops
+ * after `stop_after` (0..11) of the backward launches, for the tests' stage-by-stage comparison.  ADDITIONS under ABI 8:
+ * bsr_abi_version() stays 8. */
+size_t bsr_disc_wgrad_blob_bytes(void);
+size_t bsr_disc_wgrad_scratch_bytes(int B, int S);
+size_t bsr_disc_wgrad_floats(void);
+size_t bsr_disc_wgrad_var_offset(int index);
+size_t bsr_disc_wgrad_offset(int B, int S, int k, int layer);
+int bsr_disc_wgrad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const void* d_wgrad_blob,
+                   size_t wgrad_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums, float* losses3,
+                   float* logits, float* grads, void* scratch, void* stream);
+int bsr_debug_disc_wgrad(int device, const void* d_blob, size_t blob_bytes, const void* d_dgrad_blob, size_t dgrad_bytes, const void* d_wgrad_blob,
+                         size_t wgrad_bytes, const float* gt, const float* con_rgb, const float* mask_sv, int B, int S, double* sums, float* losses3,
+                         float* logits, float* grads, void* scratch, int stop_after, void* stream);
+
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
  * statement and writes the arithmetic out.  d_blob: the device copy of pack.pack_vgg's blob, blob_bytes = bsr_vgg_blob_bytes() (about

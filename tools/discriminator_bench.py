@@ -31,6 +31,19 @@ d gen / d con_rgb) and the line, also written to --out (profiles/discriminator_g
   build                    with --build FILE, the compiler's register and LDS figures of the new kernels (a JSON object, merged in as is).
 
     python tools/discriminator_bench.py --grad [--parity] [--stats CSV] [--build FILE] [--out FILE] [--calls-only]
+
+With --wgrad the call is Discriminators.disc_grad (bsr_disc_wgrad, csrc/disc_wgrad_kernels.h: the forward's seven launches and the eleven of
+d d_total_loss / d the discriminators' variables) and the line, written to --out (profiles/discriminator_wgrad_bench.json), holds
+  device_ms_per_call       disc_grad by device events, beside gan_losses_ms_per_call and gen_grad_ms_per_call in the same run.
+  kernel_ms                with --stats, all eighteen launches; wgrad_rate holds, per stride-2 layer, the forward launch's and the
+                           kernel-gradient launch's TFLOP/s from the shapes (both work on all 2B rows and the 6 real input channels of
+                           conv0: the same FLOP) and the latter's share of the 157.3 TFLOP/s fp32 matrix bound.
+  parity                   with --parity, per (S, B) of the device tests' sizes and the hinge case the worst scaled error of a variable's
+                           gradient against discriminator.disc_grad on the device's own masks and logits, and against the statement's
+                           own float64 forward; e2e_measured is the largest of the former, the figure the device test's bound is 4 x of.
+  build                    with --build FILE, the compiler's register and LDS figures of the new kernels.
+
+    python tools/discriminator_bench.py --wgrad [--parity] [--stats CSV] [--build FILE] [--out FILE] [--calls-only]
 """
 import argparse
 import csv
@@ -48,6 +61,9 @@ KERNELS = ("disc_input_kernel", "disc_conv_kernel<8, 32>", "disc_conv_kernel<32,
 GRAD_KERNELS = ("disc_head_grad_kernel", "disc_dgrad_kernel<64, 64>", "disc_dgrad_kernel<64, 32>", "disc_dgrad_kernel<32, 32>", "disc_dgrad_in_kernel",
                 "disc_gather_kernel")
 PARITY_SIZES = ((32, 1), (32, 3), (64, 2), (128, 1))
+WGRAD_KERNELS = ("disc_wgrad_seed_kernel", "disc_head_wgrad_kernel", "disc_wgrad_kernel<64, 64>", "disc_dgrad_kernel<64, 64>", "disc_wgrad_kernel<32, 64>",
+                 "disc_dgrad_kernel<64, 32>", "disc_wgrad_kernel<32, 32>", "disc_dgrad_kernel<32, 32>", "disc_wgrad_kernel<8, 32>", "disc_wgrad_fold_kernel",
+                 "disc_wgrad_finish_kernel")
 
 
 def work(S):
@@ -147,6 +163,71 @@ def main_grad(args, runner, weights, t, timed):
         f.write(text + "\n")
 
 
+def wgrad_parity():
+    """The device tests' cases: init_discriminator_weights(3), discriminator.example_inputs(S, B, 1), and the hinge case."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import discriminator_cases as dcases
+    from blindshadowremoval_amd import Discriminators, discriminator as host
+    from blindshadowremoval_amd.weights import discriminator_trainable_names, init_discriminator_weights
+    out, dev, names = [], torch.device("cuda", 0), discriminator_trainable_names()
+    runner = Discriminators(0)
+
+    def worst(got, ref):
+        return max(float(np.abs(got[n].astype(np.float64) - ref[n]).max() / np.abs(ref[n]).max()) for n in names if np.abs(ref[n]).max() > 0)
+    for S, B in PARITY_SIZES + ((128, 2),):
+        weights, arrays = (init_discriminator_weights(3), host.example_inputs(S, B, 1)) if (S, B) != (128, 2) else (lambda c: (c[0], c[1:]))(dcases.hinge_case())
+        runner.load_weights(weights)
+        res = runner.disc_grad(*[torch.from_numpy(a).to(dev) for a in arrays], keep=True, logits=True)
+        torch.cuda.synchronize()
+        grads = {k: v.cpu().numpy() for k, v in res[2].items()}
+        logits, acts = [y.cpu().numpy() for y in res[3]], {k: v.cpu().numpy() for k, v in res[4].items()}
+        err = [worst(grads, host.disc_grad(weights, *arrays, acts=acts, logits=logits)), worst(grads, host.disc_grad(weights, *arrays))]
+        out.append({"size": S, "batch": B, "scaled_error_device_masks": float("%.3g" % err[0]), "scaled_error_own_forward": float("%.3g" % err[1])})
+    return out
+
+
+def main_wgrad(args, runner, t, timed):
+    B, S = args.batch, args.size
+    if args.calls_only:
+        timed(lambda: runner.disc_grad(*t), min(args.iters, 20))
+        return
+    ms, res = timed(lambda: runner.disc_grad(*t), args.iters)
+    fwd = [timed(lambda: runner.gan_losses(*t), args.iters)[0] for _ in range(2)]
+    gen = [timed(lambda: runner.gen_grad(*t), args.iters)[0] for _ in range(2)]
+    spread = [timed(lambda: runner.disc_grad(*t), args.iters)[0] for _ in range(2)]
+    flat = res[2][""]
+    kernel_ms = kernel_stats(args.stats, KERNELS + WGRAD_KERNELS) if args.stats else None
+    rate = None
+    if kernel_ms:
+        rate = {}
+        fwd_names, grad_names = KERNELS[1:5], (WGRAD_KERNELS[8], WGRAD_KERNELS[6], WGRAD_KERNELS[4], WGRAD_KERNELS[2])
+        for i in range(4):
+            flop = 2 * B * conv_flop(S, i)
+            tflops = flop / kernel_ms[grad_names[i]] / 1e9
+            rate["conv%d" % i] = {"forward_kernel": fwd_names[i], "gflop": round(flop / 1e9, 3), "forward_tflops": round(flop / kernel_ms[fwd_names[i]] / 1e9, 1),
+                                  "wgrad_kernel": grad_names[i], "wgrad_tflops": round(tflops, 1), "wgrad_share_of_matrix_bound": round(tflops * 1e12 / MATRIX_FLOPS, 3),
+                                  "wgrad_ms_over_forward_ms": round(kernel_ms[grad_names[i]] / kernel_ms[fwd_names[i]], 2)}
+    line = {"batch": B, "size": S, "losses": [float(v) for v in res[0].cpu()], "d_grad_l1": float(flat.abs().sum().cpu()), "d_grad_linf": float(flat.abs().max().cpu()),
+            "device_ms_per_call": round(ms, 4), "device_ms_per_call_repeats": [round(v, 4) for v in spread],
+            "gan_losses_ms_per_call": round(min(fwd), 4), "gan_losses_ms_per_call_repeats": [round(v, 4) for v in fwd],
+            "gen_grad_ms_per_call": round(min(gen), 4), "gen_grad_ms_per_call_repeats": [round(v, 4) for v in gen],
+            "backward_ms_per_call": round(ms - min(fwd), 4), "kernel_ms": kernel_ms, "kernel_ms_unmeasured": kernel_ms is None, "wgrad_rate": rate,
+            "backward_kernel_ms": round(sum(kernel_ms[k] for k in WGRAD_KERNELS), 5) if kernel_ms else None, "stage_budget": 1e-5,
+            "stage_budget_note": "every stage figure measured on the device tests' sizes is below the fp32-class budget 1e-5; no stage budget is widened"}
+    if args.parity:
+        line["parity"] = wgrad_parity()
+        line["e2e_measured"] = max(p["scaled_error_device_masks"] for p in line["parity"])
+    if args.build:
+        with open(args.build) as f:
+            line["build"] = json.load(f)
+    text = json.dumps(line)
+    print(text)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -156,10 +237,12 @@ def main():
     ap.add_argument("--stats", default=None, help="the kernel statistics CSV of a profiled --calls-only run")
     ap.add_argument("--calls-only", action="store_true", help="the warm-up and the calls, nothing else: the program to profile")
     ap.add_argument("--grad", action="store_true", help="time gen_grad (forward + d gen / d con_rgb) and the forward alone in the same run")
-    ap.add_argument("--parity", action="store_true", help="with --grad: the end-to-end scaled errors over the device tests' sizes")
+    ap.add_argument("--wgrad", action="store_true", help="time disc_grad (forward + d d_total_loss / d the variables) beside gan_losses and gen_grad")
+    ap.add_argument("--parity", action="store_true", help="with --grad or --wgrad: the end-to-end scaled errors over the device tests' sizes")
     ap.add_argument("--build", default=None, help="with --grad: a JSON file of the compiler's register and LDS figures, merged in under `build`")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "discriminator_grad_bench.json"), help="with --grad: where the line is written")
+    ap.add_argument("--out", default=None, help="with --grad or --wgrad: where the line is written (profiles/discriminator_[w]grad_bench.json)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "discriminator_%s_bench.json" % ("wgrad" if args.wgrad else "grad"))
     import torch
     from blindshadowremoval_amd import Discriminators, discriminator as host
     from blindshadowremoval_amd.weights import init_discriminator_weights
@@ -183,6 +266,8 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / iters, res
+    if args.wgrad:
+        return main_wgrad(args, runner, t, timed)
     if args.grad:
         return main_grad(args, runner, weights, t, timed)
     if args.calls_only:
