@@ -2,7 +2,8 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "generator_variable_shapes", "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "generator_variable_shapes",
+           "init_weights"]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name == "Perceptual":
         from .perceptual_gpu import Perceptual
         return Perceptual
+    if name == "ColourTail":
+        from .clr_tail_gpu import ColourTail
+        return ColourTail
     raise AttributeError(name)

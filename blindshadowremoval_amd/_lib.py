@@ -93,6 +93,15 @@ SIGNATURES = {
     "bsr_disc_wgrad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
     "bsr_disc_wgrad": (c_i, [c_i] + _BLOBS + [c_v, c_sz, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_v]),
     "bsr_debug_disc_wgrad": (c_i, [c_i] + _BLOBS + [c_v, c_sz, c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_v, c_i, c_v]),
+    "bsr_clr_tail_grad_blob_bytes": (c_sz, []),
+    "bsr_clr_tail_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "bsr_clr_tail_grad_floats": (c_sz, []),
+    "bsr_clr_tail_grad_var_offset": (c_sz, [c_i]),
+    "bsr_clr_tail_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_clr_tail_grad_partials": (c_i, [c_i, c_i, c_i]),
+    "bsr_clr_tail_grad": (c_i, [c_i, c_v, c_sz, c_v, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v, c_v]),
+    "bsr_debug_clr_tail_grad": (c_i, [c_i, c_v, c_sz, c_v, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v, c_i, c_v]),
+    "bsr_last_f": (c_i, [c_v, ctypes.POINTER(c_v), ctypes.POINTER(c_i), ctypes.POINTER(c_i * 4)]),
     "bsr_vgg_blob_bytes": (c_sz, []),
     "bsr_vgg_scratch_bytes": (c_sz, _BS),
     "bsr_vgg_act_offset": (c_sz, [c_i, c_i, c_i]),

@@ -41,6 +41,7 @@
 #include "disc_kernels.h"
 #include "disc_grad_kernels.h"
 #include "disc_wgrad_kernels.h"
+#include "clr_tail_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1581,6 +1582,60 @@ int bsr_debug_disc_wgrad(int device, const void* d_blob, size_t blob_bytes, cons
                     losses3, logits, grads, scratch, stop_after, stream);
 }
 
+size_t bsr_clr_tail_grad_blob_bytes(void) { return bsr::kClrBlobFloats * sizeof(float); }
+
+size_t bsr_clr_tail_grad_scratch_bytes(int B, int H, int W) { return bsr::clr_tail_size_ok(B, H, W) ? bsr::clr_tail_plan(B, H, W).total : 0; }
+
+size_t bsr_clr_tail_grad_floats(void) { return bsr::clr_tail_var_offset(bsr::kClrVars); }
+
+size_t bsr_clr_tail_grad_var_offset(int index) { return index < 0 || index >= bsr::kClrVars ? SIZE_MAX : bsr::clr_tail_var_offset(index); }
+
+size_t bsr_clr_tail_grad_offset(int B, int H, int W, int map) {
+  if (!bsr::clr_tail_size_ok(B, H, W) || map < 0 || map > 6) return SIZE_MAX;
+  return bsr::clr_tail_plan(B, H, W).map[map];
+}
+
+int bsr_clr_tail_grad_partials(int B, int H, int W) { return bsr::clr_tail_size_ok(B, H, W) ? bsr::clr_tail_plan(B, H, W).P : 0; }
+
+namespace {
+
+int clr_tail_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* gs, const float* f, int f_cs, const float* g_con,
+                  const float* g_gs, int B, int H, int W, float* d_f, float* d_gs, float* grads, int keep, void* scratch, int stop_after, void* stream) {
+  const std::string n(name);
+  for (const void* p : {d_blob, (const void*)gs, (const void*)f, (const void*)g_con, (const void*)d_f, (const void*)d_gs, (const void*)grads, (const void*)scratch})
+    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
+  if (!bsr::clr_tail_size_ok(B, H, W))
+    return fail(BSR_ERR_ARG, n + ": B must be positive, H a multiple of 8 and W a multiple of 32 (conv_n16_kernel's tile), at most 2^26 pixels in all");
+  if (blob_bytes != bsr_clr_tail_grad_blob_bytes()) return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_clr_tail_grad_blob_bytes() (pack.pack_clr_tail_grad)");
+  if (f_cs < 64 || f_cs % 4 != 0) return fail(BSR_ERR_ARG, n + ": f_cs must be a multiple of 4 and at least 64");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(f) % 16 != 0 || reinterpret_cast<uintptr_t>(d_f) % 16 != 0)
+    return fail(BSR_ERR_ARG, n + ": d_blob, f and d_f must be 16-byte aligned");
+  for (const void* p : {(const void*)gs, (const void*)g_con, (const void*)g_gs, (const void*)d_gs, (const void*)grads})
+    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": gs, g_con, g_gs, d_gs and grads must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kClrTailLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..6");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_clr_tail_grad(static_cast<const float*>(d_blob), gs, f, f_cs, g_con, g_gs, B, H, W, d_f, d_gs, grads, keep != 0, scratch, stop_after,
+                                    static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+}  // namespace
+
+int bsr_clr_tail_grad(int device, const void* d_blob, size_t blob_bytes, const float* gs, const float* f, int f_cs, const float* g_con, const float* g_gs,
+                      int B, int H, int W, float* d_f, float* d_gs, float* grads, int keep, void* scratch, void* stream) {
+  return clr_tail_grad("bsr_clr_tail_grad", device, d_blob, blob_bytes, gs, f, f_cs, g_con, g_gs, B, H, W, d_f, d_gs, grads, keep, scratch,
+                       bsr::kClrTailLaunches, stream);
+}
+
+int bsr_debug_clr_tail_grad(int device, const void* d_blob, size_t blob_bytes, const float* gs, const float* f, int f_cs, const float* g_con,
+                            const float* g_gs, int B, int H, int W, float* d_f, float* d_gs, float* grads, int keep, void* scratch, int stop_after,
+                            void* stream) {
+  return clr_tail_grad("bsr_debug_clr_tail_grad", device, d_blob, blob_bytes, gs, f, f_cs, g_con, g_gs, B, H, W, d_f, d_gs, grads, keep, scratch, stop_after,
+                       stream);
+}
+
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
 
 size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
@@ -1947,6 +2002,17 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
   hipLaunchKernelGGL(bsr::slice_copy_kernel, dim3((unsigned)((npix * src.c + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      from, src.cs, src.coff, src.c, dst, npix, src.half ? 1 : 0);
   HIP_TRY(hipGetLastError());
+  return BSR_OK;
+}
+
+int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]) {
+  if (h == nullptr || f == nullptr || f_cs == nullptr || shape4 == nullptr) return fail(BSR_ERR_ARG, "bsr_last_f: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_f: an RGB handle has no colour tail");
+  if (h->dtype != BSR_DTYPE_F32) return fail(BSR_ERR_STATE, "bsr_last_f: f is an fp32 tensor of BSR_DTYPE_F32 handles only (the 16-bit modes keep it as fp16)");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_f: no forward has run on this handle");
+  *f = h->ws + h->plan.cf;
+  *f_cs = CS_CF;
+  shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
   return BSR_OK;
 }
 

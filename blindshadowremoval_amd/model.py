@@ -215,6 +215,15 @@ class Generator:
             _lib.check(self._lib.bsr_probe(self._handle, name.encode(), dst.data_ptr(), dst.numel(), ctypes.byref(shape), stream), "bsr_probe")
         return dst.reshape(shape[0], shape[1], shape[2], shape[3])
 
+    def last_f(self) -> Tuple[int, int, Tuple[int, int, int, int]]:
+        """(device address, floats between pixels, (B, H, W, 64)) of the last forward's f — clr_up3's output, the colour tail's input —
+        in the handle's workspace (bsr_last_f): no copy; valid until the next forward on this generator.  fp32 generators only:
+        RuntimeError before any forward and for the 16-bit modes."""
+        self._require_weights()
+        ptr, cs, shape = ctypes.c_void_p(), ctypes.c_int(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_f(self._handle, ctypes.byref(ptr), ctypes.byref(cs), ctypes.byref(shape)), "bsr_last_f")
+        return int(ptr.value), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

@@ -667,6 +667,75 @@ def unpack_discriminators_wgrad(blob: bytes):
     return [{name: arr[k * per + off:k * per + off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout} for k in range(3)]
 
 
+# ---- the generator's colour tail backward (csrc/clr_tail_grad_kernels.h): a blob of its own, no header, float32 ----
+CLR_TAIL_VECS = ("bias", "inv", "moving_mean", "rstd")
+
+
+def clr_tail_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the colour tail's gradient blob:
+      fwd/w, fwd/bias, fwd/gs  the forward images conv_n16_kernel<3,3,GS> recomputes a1 from: pack_taps of the BN-folded clr_conv1
+                               kernel's 64 f channels, its folded bias, clr_gs_weights
+      tail/k2f, tail/b2f       clr_conv2 BN-folded, [16 k][16 n] and [16]: z2 = a1 k2f + b2f, and (gz2 inv2) K2^T = gz2 k2f^T
+      tail/k3                  clr_conv3's kernel [16 k][4], column 3 zero
+      dgrad/w, dgrad/gs        the BN-folded clr_conv1 kernel FLIPPED for the data gradient: [9 taps (ta, tb)][64 c][16 o] =
+                               k1f[2 - ta, 2 - tb, 1 + c, o] and [9][16 o] = k1f[2 - ta, 2 - tb, 0, o] (gz1 inv1 through K1 = gz1
+                               through k1f)
+      k1, k2                   the UNFOLDED kernels [9][65][16] and [16][16] (d gamma is formed from them)
+      vecs1, vecs2             [4][16] per layer: the convolution's bias, inv, moving_mean, rstd (CLR_TAIL_VECS)
+    inv, rstd and every folded product are formed in float64 and rounded once."""
+    out, off = [], 0
+    for name, shape in (("fwd/w", (2, 9, 16, 36)), ("fwd/bias", (16,)), ("fwd/gs", (16, 16)), ("tail/k2f", (16, 16)), ("tail/b2f", (16,)),
+                        ("tail/k3", (16, 4)), ("dgrad/w", (9, 64, 16)), ("dgrad/gs", (9, 16)), ("k1", (9, 65, 16)), ("k2", (16, 16)),
+                        ("vecs1", (4, 16)), ("vecs2", (4, 16))):
+        out.append((name, off, shape))
+        off += int(np.prod(shape))
+    return out, off
+
+
+def clr_tail_grad_record(weights: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """name -> float32 array of clr_tail_grad_layout's shapes."""
+    from .weights import BN_EPS
+    k1 = np.asarray(weights["clr_conv1/conv/kernel"], np.float64).reshape(9, 65, 16)
+    k2 = np.asarray(weights["clr_conv2/conv/kernel"], np.float64).reshape(1, 16, 16)
+    k1f, b1f = fold_bn(k1, weights["clr_conv1/conv/bias"], _bn(weights, "clr_conv1/bnorm"))
+    k2f, b2f = fold_bn(k2, weights["clr_conv2/conv/bias"], _bn(weights, "clr_conv2/bnorm"))
+    rec = {}
+    rec["fwd/w"], rec["fwd/bias"] = pack_taps(k1f[:, 1:, :], b1f, 32, 64, 16)
+    rec["fwd/gs"] = clr_gs_weights(weights)
+    rec["tail/k2f"], rec["tail/b2f"] = k2f[0], b2f
+    k3 = np.zeros((16, 4), np.float64)
+    k3[:, :3] = np.asarray(weights["clr_conv3/conv/kernel"], np.float64).reshape(16, 3)
+    rec["tail/k3"] = k3
+    flipped = k1f.reshape(3, 3, 65, 16)[::-1, ::-1].reshape(9, 65, 16)
+    rec["dgrad/w"], rec["dgrad/gs"] = flipped[:, 1:, :], flipped[:, 0, :]
+    rec["k1"], rec["k2"] = k1, k2[0]
+    for i, stem in ((1, "clr_conv1"), (2, "clr_conv2")):
+        rstd = 1.0 / np.sqrt(np.asarray(weights[stem + "/bnorm/moving_variance"], np.float64) + BN_EPS)
+        rec["vecs%d" % i] = np.stack([np.asarray(weights[stem + "/conv/bias"], np.float64), np.asarray(weights[stem + "/bnorm/gamma"], np.float64) * rstd,
+                                      np.asarray(weights[stem + "/bnorm/moving_mean"], np.float64), rstd])
+    return {name: np.ascontiguousarray(a, np.float32) for name, a in rec.items()}
+
+
+def pack_clr_tail_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (the colour tail's 16 are read) -> the blob bsr_clr_tail_grad takes (clr_tail_grad_layout)."""
+    layout, total = clr_tail_grad_layout()
+    rec = clr_tail_grad_record(weights)
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        assert rec[name].shape == tuple(shape), name
+        blob[off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_clr_tail_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_clr_tail_grad: clr_tail_grad_record's dict."""
+    layout, total = clr_tail_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a colour tail gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

@@ -68,6 +68,9 @@ share of g_total_loss' gradient that this term contributes (Perceptual.per_loss_
 With --grad-total each batch's line carries instead TOTAL_GRAD_NAMES, the norms of the whole d g_total_loss / d con_rgb and
 d g_total_loss / d gs: TrainLosses.step_losses_grad under train_losses.G_TOTAL_WEIGHTS, plus Discriminators.gen_grad, plus
 Perceptual.per_loss_grad with 0.005, added as float32 tensors in that order (--host: the three statements' gradients likewise).
+With --tail beside --grad-total the line also carries tail_grad_names(): the L1 and L-infinity norms of d g_total_loss / d f at clr_up3's
+output, of the complete d g_total_loss / d gs and of the gradient of each of the colour tail's ten variables, from those two gradients
+through ColourTail.backward, which reads f in the generator's workspace (--host: generator_grad.tail_grad on a copy of f).
 """
 from __future__ import annotations
 
@@ -308,19 +311,37 @@ def grad_norms(grad) -> List[float]:
     return [float(g.sum()), float(g.max())]
 
 
+def tail_grad_names() -> List[str]:
+    """`<name>_l1`, `<name>_linf` for generator_grad.TAIL_NORM_NAMES: d_f, d_gs and the colour tail's ten variables."""
+    from .generator_grad import TAIL_NORM_NAMES
+    return [n + s for n in TAIL_NORM_NAMES for s in ("_l1", "_linf")]
+
+
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False, grad: bool = False, grad_total: bool = False) -> Dict[str, float]:
+                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the discriminators' weights come from the latest checkpoint under `ckpt`, from
     init_discriminator_weights without it.  With `grad` each batch's line also carries GRAD_NAMES, the norms of PER_WEIGHT d per / d con_rgb
     (they are per batch, not part of the means); with `grad_total` TOTAL_GRAD_NAMES instead, the norms of the whole
-    d g_total_loss / d con_rgb and d g_total_loss / d gs."""
+    d g_total_loss / d con_rgb and d g_total_loss / d gs; with `tail` beside it also tail_grad_names(), those two gradients taken through
+    the generator's colour tail."""
     import torch
     from . import discriminator as disc
     from . import train_losses as tl
     from .fsrnet import Logging
     from .weights import init_discriminator_weights
+    if tail and not grad_total:
+        raise ValueError("perceptual: --tail goes with --grad-total")
     vgg_w = load_vgg_weights(vgg)
+    gen_w = tail_runner = None
+    if tail:
+        from . import generator_grad
+        if ckpt is not None:
+            from .tf_bundle import latest_checkpoint, load_generator_weights
+            gen_w = load_generator_weights(latest_checkpoint(ckpt))
+        else:
+            from .weights import init_weights
+            gen_w = init_weights(1)
     if ckpt is not None:
         from .tf_bundle import latest_checkpoint, load_discriminator_weights
         prefix = latest_checkpoint(ckpt)
@@ -332,8 +353,9 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
     runners = weight_d = None
     acc: Dict[str, List[float]] = {}
     dev = torch.device("cuda", device)
-    with contextlib.closing(tl.folder_steps(folder, ckpt, batch, device, "perceptual")) as batches:
-        for step, steps, im_d, gt_a, mask_a, gs, con_rgb in batches:
+    with contextlib.closing(tl.folder_steps(folder, ckpt, batch, device, "perceptual", with_generator=tail)) as batches:
+        for step, steps, im_d, gt_a, mask_a, gs, con_rgb, *gen in batches:
+            tail_norms: List[float] = []
             if host:
                 torch.cuda.synchronize(dev)
                 con_a = con_rgb.cpu().numpy()
@@ -347,7 +369,11 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                 if grad_total:
                     res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
                     per = res["loss"]
-                    norms = grad_norms((three_g["grad_con"] + gan_g) + np.asarray(res["grad"], f32)) + grad_norms(three_g["grad_gs"])
+                    g_con = (three_g["grad_con"] + gan_g) + np.asarray(res["grad"], f32)
+                    norms = grad_norms(g_con) + grad_norms(three_g["grad_gs"])
+                    if tail:
+                        tg = generator_grad.tail_grad(gen_w, gs.cpu().numpy(), gen[0].probe("f").cpu().numpy(), g_con, three_g["grad_gs"])
+                        tail_norms = [v for pair in generator_grad.tail_norms(tg).values() for v in pair]
                 elif grad:
                     res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
                     per, norms = res["loss"], grad_norms(res["grad"])
@@ -369,7 +395,15 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                     gan_g = runners[1].gen_grad(gt_d, con_rgb, mask_d)
                     res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
                     three, gan, per = three_g[0].cpu().numpy(), gan_g[0].cpu().numpy(), res[0].cpu().numpy()
-                    norms = grad_norms(((three_g[3] + gan_g[2]) + res[2]).cpu().numpy()) + grad_norms(three_g[2].cpu().numpy())
+                    g_con = (three_g[3] + gan_g[2]) + res[2]
+                    norms = grad_norms(g_con.cpu().numpy()) + grad_norms(three_g[2].cpu().numpy())
+                    if tail:
+                        if tail_runner is None:
+                            from .clr_tail_gpu import ColourTail
+                            tail_runner = ColourTail(device)
+                            tail_runner.load_weights(gen_w)
+                        tg = tail_runner.backward(gen[0], gs, g_con, three_g[2])
+                        tail_norms = [v for pair in generator_grad.tail_norms({k: t.cpu().numpy() for k, t in tg.items()}).values() for v in pair]
                 else:
                     three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
                     gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
@@ -384,6 +418,7 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
             Logging.accumulate(acc, dict(zip(ALL_NAMES, vals)))
             if not quiet:
                 shown = list(zip(ALL_NAMES, vals)) + (list(zip(TOTAL_GRAD_NAMES, norms)) if grad_total else list(zip(GRAD_NAMES, norms)) if grad else [])
+                shown += list(zip(tail_grad_names(), tail_norms))
                 print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in shown), flush=True)
     return {k: s / max(c, 1) for k, (s, c) in acc.items()}
 
@@ -399,8 +434,11 @@ def main(argv=None) -> int:
     ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
     ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
     ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
+    ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
     a = ap.parse_args(argv)
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total)
+    if a.tail and not a.grad_total:
+        ap.error("--tail goes with --grad-total")
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

@@ -400,11 +400,12 @@ def example_inputs(S: int, B: int, seed: int = 0):
 
 
 # ---- the command-line entry
-def folder_steps(folder: str, ckpt: Optional[str] = None, batch: int = 8, device: int = 0, who: str = "train_losses"):
+def folder_steps(folder: str, ckpt: Optional[str] = None, batch: int = 8, device: int = 0, who: str = "train_losses", with_generator: bool = False):
     """The folder handling of the commands that score a generator on synthesised pairs: for every step of `batch` item folders
     `<folder>/<name>/` (the last one may hold fewer) yields (step, steps, img on the device, gt [b,S,S,3], mask_sv [b,S,S,3] (numpy), gs,
-    con_rgb (the generator's outputs on the device)).  The generator's weights come from the latest checkpoint under `ckpt`, from
-    init_weights without it."""
+    con_rgb (the generator's outputs on the device)), with `with_generator` also the generator itself, whose last forward is the
+    step's (Generator.last_f, Generator.probe).  The generator's weights come from the latest checkpoint under `ckpt`, from init_weights
+    without it."""
     import torch
     from . import Generator, init_weights
     from .dataset import Dataset
@@ -441,7 +442,7 @@ def folder_steps(folder: str, ckpt: Optional[str] = None, batch: int = 8, device
             im, _, uv, _, _ = torch.split(torch.cat(rows, 0).float(), list(SPLIT_FFHQ), dim=3)
             im_d = im.contiguous().to(dev)
             gs, con_rgb, _, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
-            yield step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb
+            yield (step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb) + ((gen,) if with_generator else ())
     finally:                    # also when the consumer stops early or raises: the handle is closed with the generator
         gen.close()
 

@@ -118,6 +118,13 @@ def generator_variable_shapes(variant: str = "gsc") -> "OrderedDict[str, Tuple[i
     return s
 
 
+def generator_tail_trainable_names() -> List[str]:
+    """The ten trainable variables of the generator's colour tail (clr_conv1, clr_conv2, clr_conv3) in generator_variable_shapes' order,
+    9 763 floats in all: every kernel, bias, gamma and beta; moving_mean and moving_variance take no gradient."""
+    return [n for n in generator_variable_shapes() if n.split("/", 1)[0] in ("clr_conv1", "clr_conv2", "clr_conv3")
+            and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
 DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
 DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)
