@@ -1,7 +1,7 @@
 """The three multi-scale patch discriminators of the reference's `train_step` and its three GAN losses as a host statement: `gen`,
 `disc_real` and `disc_fake` (train_test_GSC.py:121-123, 264-268, 302, 334-336, 353-355; model.py:115-147, 292-312; utils.py:100-102),
 restated in numpy for training=False.  It plays the role for csrc/disc_kernels.h (bsr_disc_losses, discriminator_gpu.Discriminators)
-that train_losses.py plays for its chain.  The VGG perceptual term, g_total_loss, training=True (batch statistics, dropout), the
+that train_losses.py plays for its chain.  The VGG perceptual term, g_total_loss (objective.py), training=True (batch statistics, dropout), the
 generator's backward and the optimisers are not here.
 
 INPUTS.  gt, con_rgb (deshadow_img_c), mask_sv [B,S,S,3] float32; S in SIZES, B in 1..32767.  The variables are float32
@@ -45,7 +45,7 @@ the bilinear resize) and tests/golden/discriminator_grad_*.npz holds torch autog
 (tools/make_discriminator_grad_fixture.py).
 
 `python -m blindshadowremoval_amd.discriminator FOLDER [--ckpt DIR] [--batch N] [--host] [--grad] [--wgrad]` scores the three terms on a folder written
-by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling (train_losses.folder_steps): the
+by `python -m blindshadowremoval_amd.shadow_synth`, with the folder handling and the loop all three commands share (objective.folder_steps, objective.score_steps): the
 generator runs on row 0 of each element and its con_rgb is the fake image.  The weights of the generator and of the discriminators
 come from the latest checkpoint under --ckpt, from init_weights / init_discriminator_weights without it.  The step-weighted means
 are printed as Logging.display prints them.  --host computes the three terms with this statement from the same generator outputs.
@@ -62,7 +62,6 @@ for the finite-difference test.
 """
 from __future__ import annotations
 
-import contextlib
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -491,57 +490,39 @@ def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: 
     each batch's line and the means also carry GRAD_NAMES, the norms of d gen / d con_rgb; with `wgrad`, WGRAD_NAMES, the norms over the
     54 gradients of d_total_loss with respect to the discriminators' variables."""
     import torch
-    from .fsrnet import Logging
-    from .train_losses import folder_steps
-    from .weights import init_discriminator_weights
-    if ckpt is not None:
-        from .tf_bundle import latest_checkpoint, load_discriminator_weights
-        prefix = latest_checkpoint(ckpt)
-        if prefix is None:
-            raise FileNotFoundError("discriminator: no checkpoint under %s" % ckpt)
-        weights = load_discriminator_weights(prefix)
-    else:
-        weights = init_discriminator_weights(1)
-    runner = None
-    acc: Dict[str, List[float]] = {}
+    from .objective import discriminator_weights, score_steps
+    weights = discriminator_weights(ckpt, "discriminator")
     dev = torch.device("cuda", device)
-    with contextlib.closing(folder_steps(folder, ckpt, batch, device, "discriminator")) as batches:
-        for step, steps, _, gt_a, mask_a, _, con_rgb in batches:
-            if host:
-                torch.cuda.synchronize(dev)
-                con_a = con_rgb.cpu().numpy()
-                r = gan_losses(weights, gt_a, con_a, mask_a)
-                loss = r["losses"]
-                if grad:
-                    norms = grad_norms(gen_grad(weights, gt_a, con_a, mask_a, acts=r["acts"])["grad"])
-                if wgrad:
-                    wnorms = wgrad_norms(disc_grad(weights, gt_a, con_a, mask_a, acts=r["acts"], logits=r["logits"]))
-                if stats is not None:
-                    stats["max_abs_logit"] = max([stats.get("max_abs_logit", 0.0)] + [float(np.abs(y).max()) for y in r["logits"]])
-            else:
-                if runner is None:
-                    from .discriminator_gpu import Discriminators
-                    runner = Discriminators(device)
-                    runner.load_weights(weights)
-                gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
-                if grad:
-                    res = runner.gen_grad(gt_d, con_rgb.contiguous(), mask_d)
-                    loss, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
-                else:
-                    loss = runner.gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
-                if wgrad:
-                    wnorms = wgrad_norms({k: v.cpu().numpy() for k, v in runner.disc_grad(gt_d, con_rgb.contiguous(), mask_d)[2].items()})
-            line = {k: float(v) for k, v in zip(LOSS_NAMES, loss)}
+    if host:
+        def step(gt_a, mask_a, con_rgb):
+            torch.cuda.synchronize(dev)
+            con_a = con_rgb.cpu().numpy()
+            r = gan_losses(weights, gt_a, con_a, mask_a)
+            if stats is not None:
+                stats["max_abs_logit"] = max([stats.get("max_abs_logit", 0.0)] + [float(np.abs(y).max()) for y in r["logits"]])
+            return (r["losses"], grad_norms(gen_grad(weights, gt_a, con_a, mask_a, acts=r["acts"])["grad"]) if grad else (),
+                    wgrad_norms(disc_grad(weights, gt_a, con_a, mask_a, acts=r["acts"], logits=r["logits"])) if wgrad else ())
+    else:
+        from .discriminator_gpu import Discriminators
+        runner = Discriminators(device)
+        runner.load_weights(weights)
+
+        def step(gt_a, mask_a, con_rgb):
+            gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
             if grad:
-                line.update(zip(GRAD_NAMES, norms))
-            if wgrad:
-                line.update(zip(WGRAD_NAMES, wnorms))
-            Logging.accumulate(acc, line)
-            if not quiet:
-                print(Logging.format_line(acc, step, steps), end="", flush=True)
-    if not quiet:
-        print("")
-    return {k: s / max(c, 1) for k, (s, c) in acc.items()}
+                res = runner.gen_grad(gt_d, con_rgb.contiguous(), mask_d)
+                loss, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
+            else:
+                loss, norms = runner.gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy(), ()
+            if not wgrad:
+                return loss, norms, ()
+            return loss, norms, wgrad_norms({k: v.cpu().numpy() for k, v in runner.disc_grad(gt_d, con_rgb.contiguous(), mask_d)[2].items()})
+
+    def record(_, gt_a, mask_a, __, con_rgb):
+        loss, norms, wnorms = step(gt_a, mask_a, con_rgb)
+        return dict(list(zip(LOSS_NAMES, (float(v) for v in loss))) + list(zip(GRAD_NAMES, norms)) + list(zip(WGRAD_NAMES, wnorms))), ()
+
+    return score_steps(folder, ckpt, batch, device, "discriminator", record, quiet)
 
 
 def main(argv=None) -> int:

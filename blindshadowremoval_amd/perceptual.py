@@ -1,7 +1,6 @@
-"""The VGG19 perceptual term of the reference's `train_step` and its two totals as a host statement: `per_loss =
-style_content_loss(self.feat_extractor, d_img)`, `g_total_loss` and `d_total_loss` (train_test_GSC.py:128-139, 153-160, 264, 301-310,
-336; utils.py:104-114), restated in numpy.  It plays the role for csrc/vgg_kernels.h (bsr_vgg_per_loss, perceptual_gpu.Perceptual) that
-discriminator.py plays for its chain, and the term's data gradient d per / d con_rgb (THE BACKWARD below; bsr_vgg_per_loss_grad,
+"""The VGG19 perceptual term of the reference's `train_step` as a host statement: `per_loss = style_content_loss(self.feat_extractor,
+d_img)` (train_test_GSC.py:128-139, 153-160, 264, 303; utils.py:104-114), restated in numpy.  It plays the role for
+csrc/vgg_kernels.h (bsr_vgg_per_loss, perceptual_gpu.Perceptual) that discriminator.py plays for its chain, and the term's data gradient d per / d con_rgb (THE BACKWARD below; bsr_vgg_per_loss_grad,
 csrc/vgg_grad_kernels.h).  training=True, every other backward pass, weight gradients, the optimisers and a training loader are not here.
 
 INPUTS.  gt, con_rgb (deshadow_img_c) [B,S,S,3] float32; S in SIZES, B in 1..MAX_B.  The 26 variables are float32
@@ -27,10 +26,6 @@ every term |real - fake| is a float32; every sum is a float64 sum of those terms
 t_k the batch total of tap k (the items' rows added in order), h_k = S / 2^(k-1) and C_k the tap's channels, in float64:
   m_k = t_k / (B h_k^2 C_k)        (tf.reduce_mean(tf.abs(real - fake)), style_weight 1)
   per = (((m_1 + m_2) + m_3) + m_4) + m_5,  rounded once to float32.
-
-THE TOTALS, float32 in the reference's order:
-  g_total_loss(recon_gs, recon_c, grad, gen, per) = ((recon * 400 + gen) + per * .005) + grad * 2,   recon = (recon_gs + recon_c) / 2
-  d_total_loss(disc_real, disc_fake)              = disc_real + disc_fake
 
 WHAT IS NOT PINNED.  The ImageNet weights are in no checkpoint of the reference and are not shipped: `weights.load_vgg_weights(path)`
 reads an `.npz` keyed `block<b>_conv<i>/kernel` (HWIO) and `block<b>_conv<i>/bias` (INTEGRATION.md shows how Keras' own weight file
@@ -59,24 +54,13 @@ With `acts` given (a dict like `forward`'s, for example the device's kept activa
 read from it instead of from the statement's own float64 forward, so that a comparison with the device is free of mask flips at values
 that round across 0.  `per_loss_f64` is the same objective with no float32 rounding anywhere, for finite differences.
 
-`python -m blindshadowremoval_amd.perceptual FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total]` evaluates the whole objective on
-a folder written by `python -m blindshadowremoval_amd.shadow_synth`, with the train_losses command's folder handling
-(train_losses.folder_steps): the six logged losses (recon_gs, recon_c, grad, gen, disc_real, disc_fake), per, g_total and d_total per
-batch and as step-weighted means.  The device route uses TrainLosses, Discriminators and Perceptual; --host the three host statements.
-With --grad each batch's line also carries per_grad_l1 and per_grad_linf, the L1 and L-infinity norms of 0.005 d per / d con_rgb: the
-share of g_total_loss' gradient that this term contributes (Perceptual.per_loss_grad with upstream 0.005; --host: per_loss_grad).
-With --grad-total each batch's line carries instead TOTAL_GRAD_NAMES, the norms of the whole d g_total_loss / d con_rgb and
-d g_total_loss / d gs: TrainLosses.step_losses_grad under train_losses.G_TOTAL_WEIGHTS, plus Discriminators.gen_grad, plus
-Perceptual.per_loss_grad with 0.005, added as float32 tensors in that order (--host: the three statements' gradients likewise).
-With --tail beside --grad-total the line also carries tail_grad_names(): the L1 and L-infinity norms of d g_total_loss / d f at clr_up3's
-output, of the complete d g_total_loss / d gs and of the gradient of each of the colour tail's ten variables, from those two gradients
-through ColourTail.backward, which reads f in the generator's workspace (--host: generator_grad.tail_grad on a copy of f).
+The objective this term is one of (g_total_loss, d_total_loss, PER_WEIGHT, the total gradient) and the command that evaluates it on a folder
+are in objective.py: `python -m blindshadowremoval_amd.objective`; `python -m blindshadowremoval_amd.perceptual` delegates to it.
 """
 from __future__ import annotations
 
-import contextlib
 import sys
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Tuple
 
 import numpy as np
 
@@ -90,8 +74,6 @@ MEANS_BGR = (f32(103.939), f32(116.779), f32(123.68))
 PER_SUM_NAMES = tuple("l1_block%d" % b for b in range(1, 6))
 K = len(PER_SUM_NAMES)
 TAP_CH = tuple(ch for ch, _ in VGG_BLOCKS)
-LOGGED = ("recon_gs", "recon_c", "grad", "gen", "disc_real", "disc_fake")
-ALL_NAMES = LOGGED + ("per", "g_total", "d_total")
 SIZE_TEXT = "the perceptual term takes 1..4096 items of side 32, 64, 128 or 256, got B=%d S=%d"
 
 
@@ -186,8 +168,6 @@ def per_loss(weights: Dict[str, np.ndarray], gt, con_rgb) -> Dict[str, np.ndarra
 
 # ---- the backward: d per / d con_rgb
 GRAD_NAMES = ("per_grad_l1", "per_grad_linf")
-PER_WEIGHT = f32(.005)                # per_loss' weight in g_total_loss
-TOTAL_GRAD_NAMES = ("g_total_grad_con_l1", "g_total_grad_con_linf", "g_total_grad_gs_l1", "g_total_grad_gs_linf")
 
 
 def tap_weights(B: int, S: int) -> List[np.float32]:
@@ -286,17 +266,6 @@ def per_loss_f64(weights: Dict[str, np.ndarray], gt, con_rgb) -> float:
     return per
 
 
-def g_total_loss(recon_gs, recon_c, grad, gen, per) -> np.float32:
-    """train_step's g_total_loss from its five float32 terms, in the reference's order."""
-    recon_gs, recon_c, grad, gen, per = (f32(v) for v in (recon_gs, recon_c, grad, gen, per))
-    recon = (recon_gs + recon_c) / f32(2)
-    return f32(f32(f32(recon * f32(400)) + gen) + f32(per * f32(.005))) + f32(grad * f32(2))
-
-
-def d_total_loss(disc_real, disc_fake) -> np.float32:
-    return f32(disc_real) + f32(disc_fake)
-
-
 def example_inputs(S: int, B: int, seed: int = 0):
     """gt, con_rgb of train_losses.example_inputs(S, B, seed)."""
     from .train_losses import example_inputs as ex
@@ -304,143 +273,10 @@ def example_inputs(S: int, B: int, seed: int = 0):
     return gt, con
 
 
-# ---- the command-line entry
-def grad_norms(grad) -> List[float]:
-    """GRAD_NAMES of a gradient that already carries PER_WEIGHT: the sum and the largest of its magnitudes, in float64."""
-    g = np.abs(np.asarray(grad, np.float64))
-    return [float(g.sum()), float(g.max())]
-
-
-def tail_grad_names() -> List[str]:
-    """`<name>_l1`, `<name>_linf` for generator_grad.TAIL_NORM_NAMES: d_f, d_gs and the colour tail's ten variables."""
-    from .generator_grad import TAIL_NORM_NAMES
-    return [n + s for n in TAIL_NORM_NAMES for s in ("_l1", "_linf")]
-
-
-def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False) -> Dict[str, float]:
-    """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
-    of weights.load_vgg_weights; the discriminators' weights come from the latest checkpoint under `ckpt`, from
-    init_discriminator_weights without it.  With `grad` each batch's line also carries GRAD_NAMES, the norms of PER_WEIGHT d per / d con_rgb
-    (they are per batch, not part of the means); with `grad_total` TOTAL_GRAD_NAMES instead, the norms of the whole
-    d g_total_loss / d con_rgb and d g_total_loss / d gs; with `tail` beside it also tail_grad_names(), those two gradients taken through
-    the generator's colour tail."""
-    import torch
-    from . import discriminator as disc
-    from . import train_losses as tl
-    from .fsrnet import Logging
-    from .weights import init_discriminator_weights
-    if tail and not grad_total:
-        raise ValueError("perceptual: --tail goes with --grad-total")
-    vgg_w = load_vgg_weights(vgg)
-    gen_w = tail_runner = None
-    if tail:
-        from . import generator_grad
-        if ckpt is not None:
-            from .tf_bundle import latest_checkpoint, load_generator_weights
-            gen_w = load_generator_weights(latest_checkpoint(ckpt))
-        else:
-            from .weights import init_weights
-            gen_w = init_weights(1)
-    if ckpt is not None:
-        from .tf_bundle import latest_checkpoint, load_discriminator_weights
-        prefix = latest_checkpoint(ckpt)
-        if prefix is None:
-            raise FileNotFoundError("perceptual: no checkpoint under %s" % ckpt)
-        disc_w = load_discriminator_weights(prefix)
-    else:
-        disc_w = init_discriminator_weights(1)
-    runners = weight_d = None
-    acc: Dict[str, List[float]] = {}
-    dev = torch.device("cuda", device)
-    with contextlib.closing(tl.folder_steps(folder, ckpt, batch, device, "perceptual", with_generator=tail)) as batches:
-        for step, steps, im_d, gt_a, mask_a, gs, con_rgb, *gen in batches:
-            tail_norms: List[float] = []
-            if host:
-                torch.cuda.synchronize(dev)
-                con_a = con_rgb.cpu().numpy()
-                if grad_total:
-                    three_g = tl.step_losses_grad(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a, upstream=np.array(tl.G_TOTAL_WEIGHTS, f32))
-                    three = three_g["losses"]
-                    gan_g = disc.gen_grad(disc_w, gt_a, con_a, mask_a)["grad"].astype(f32)
-                else:
-                    three = tl.step_losses(im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_a)["losses"]
-                gan = disc.gan_losses(disc_w, gt_a, con_a, mask_a)["losses"]
-                if grad_total:
-                    res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
-                    per = res["loss"]
-                    g_con = (three_g["grad_con"] + gan_g) + np.asarray(res["grad"], f32)
-                    norms = grad_norms(g_con) + grad_norms(three_g["grad_gs"])
-                    if tail:
-                        tg = generator_grad.tail_grad(gen_w, gs.cpu().numpy(), gen[0].probe("f").cpu().numpy(), g_con, three_g["grad_gs"])
-                        tail_norms = [v for pair in generator_grad.tail_norms(tg).values() for v in pair]
-                elif grad:
-                    res = per_loss_grad(vgg_w, gt_a, con_a, upstream=PER_WEIGHT)
-                    per, norms = res["loss"], grad_norms(res["grad"])
-                else:
-                    per = per_loss(vgg_w, gt_a, con_a)["loss"]
-            else:
-                if runners is None:
-                    from .discriminator_gpu import Discriminators
-                    from .perceptual_gpu import Perceptual
-                    from .train_losses_gpu import TrainLosses
-                    runners = (TrainLosses(device), Discriminators(device), Perceptual(device))
-                    runners[1].load_weights(disc_w)
-                    runners[2].load_weights(vgg_w)
-                gt_d, mask_d = torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev)
-                if (grad or grad_total) and weight_d is None:
-                    weight_d = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=dev)
-                if grad_total:
-                    three_g = runners[0].step_losses_grad(im_d, gt_d, mask_d, gs, con_rgb, upstream=torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(dev))
-                    gan_g = runners[1].gen_grad(gt_d, con_rgb, mask_d)
-                    res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
-                    three, gan, per = three_g[0].cpu().numpy(), gan_g[0].cpu().numpy(), res[0].cpu().numpy()
-                    g_con = (three_g[3] + gan_g[2]) + res[2]
-                    norms = grad_norms(g_con.cpu().numpy()) + grad_norms(three_g[2].cpu().numpy())
-                    if tail:
-                        if tail_runner is None:
-                            from .clr_tail_gpu import ColourTail
-                            tail_runner = ColourTail(device)
-                            tail_runner.load_weights(gen_w)
-                        tg = tail_runner.backward(gen[0], gs, g_con, three_g[2])
-                        tail_norms = [v for pair in generator_grad.tail_norms({k: t.cpu().numpy() for k, t in tg.items()}).values() for v in pair]
-                else:
-                    three = runners[0].step_losses(im_d, gt_d, mask_d, gs, con_rgb)[0].cpu().numpy()
-                    gan = runners[1].gan_losses(gt_d, con_rgb, mask_d)[0].cpu().numpy()
-                    if grad:
-                        res = runners[2].per_loss_grad(gt_d, con_rgb, upstream=weight_d)
-                        per, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy())
-                    else:
-                        per = runners[2].per_loss(gt_d, con_rgb)[0].cpu().numpy()
-            vals = [float(v) for v in three] + [float(v) for v in gan] + [float(per[0])]
-            vals.append(float(g_total_loss(three[0], three[1], three[2], gan[0], per[0])))
-            vals.append(float(d_total_loss(gan[1], gan[2])))
-            Logging.accumulate(acc, dict(zip(ALL_NAMES, vals)))
-            if not quiet:
-                shown = list(zip(ALL_NAMES, vals)) + (list(zip(TOTAL_GRAD_NAMES, norms)) if grad_total else list(zip(GRAD_NAMES, norms)) if grad else [])
-                shown += list(zip(tail_grad_names(), tail_norms))
-                print("%d/%d " % (step + 1, steps) + ", ".join("%s:%.9g" % kv for kv in shown), flush=True)
-    return {k: s / max(c, 1) for k, (s, c) in acc.items()}
-
-
 def main(argv=None) -> int:
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m blindshadowremoval_amd.perceptual",
-                                 description="Evaluate train_step's whole objective (six logged losses, per, g_total, d_total) on synthesised pairs.")
-    ap.add_argument("folder")
-    ap.add_argument("--vgg", required=True, help="the VGG19 variables as an .npz (weights.load_vgg_weights)")
-    ap.add_argument("--ckpt", default=None, help="checkpoint directory; without it the weights come from init_weights / init_discriminator_weights")
-    ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
-    ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
-    ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
-    ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
-    a = ap.parse_args(argv)
-    if a.tail and not a.grad_total:
-        ap.error("--tail goes with --grad-total")
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail)
-    print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
-    return 0
+    """The objective command under its earlier name."""
+    from .objective import main as objective_main
+    return objective_main(argv)
 
 
 if __name__ == "__main__":

@@ -76,13 +76,12 @@ come from Dataset(config, 'test'), the generator runs on row 0 of each element (
 init_weights without it), and the step-weighted means of the three losses are printed as Logging.display prints them.  --host
 computes the losses with this statement from the same generator outputs.  --grad adds, per batch, the L1 and L-infinity norms of the
 gradients with respect to gs and con_rgb under G_TOTAL_WEIGHTS (GRAD_NAMES), on either route.
+The folder handling and the loop are objective.py's (folder_steps, score_steps), as is the objective these losses are terms of.
 """
 from __future__ import annotations
 
-import contextlib
-import os
 import sys
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -400,89 +399,38 @@ def example_inputs(S: int, B: int, seed: int = 0):
 
 
 # ---- the command-line entry
-def folder_steps(folder: str, ckpt: Optional[str] = None, batch: int = 8, device: int = 0, who: str = "train_losses", with_generator: bool = False):
-    """The folder handling of the commands that score a generator on synthesised pairs: for every step of `batch` item folders
-    `<folder>/<name>/` (the last one may hold fewer) yields (step, steps, img on the device, gt [b,S,S,3], mask_sv [b,S,S,3] (numpy), gs,
-    con_rgb (the generator's outputs on the device)), with `with_generator` also the generator itself, whose last forward is the
-    step's (Generator.last_f, Generator.probe).  The generator's weights come from the latest checkpoint under `ckpt`, from init_weights
-    without it."""
-    import torch
-    from . import Generator, init_weights
-    from .dataset import Dataset
-    from .fsrnet import SPLIT_FFHQ, Config
-    from .pngio import read_rgb_u8
-    cfg = Config(device)
-    cfg.DATA_DIR_TEST = [os.path.join(folder, "*")]
-    ds = Dataset(cfg, "test")
-    if not ds.name_list:
-        raise ValueError("%s: no item folder with a .npy under %s" % (who, folder))
-    S = cfg.IMG_SIZE
-    dev = torch.device("cuda", device)
-    gen = Generator(device=device)
-    if ckpt is not None:
-        gen.restore(ckpt)
-        gen._require_weights()
-    else:
-        gen.load_weights(init_weights(1))
-    batch = max(1, int(batch))
-    steps = (len(ds.name_list) + batch - 1) // batch
-    try:
-        for step in range(steps):
-            names = ds.name_list[step * batch:(step + 1) * batch]
-            rows, gts, masks = [], [], []
-            for lm_path in names:
-                element = next(ds.feed)[0]
-                rows.append(torch.as_tensor(np.asarray(element)).reshape(-1, S, S, sum(SPLIT_FFHQ))[:1])
-                stem = os.path.splitext(lm_path)[0]
-                for path, dst in ((stem + "-gt.png", gts), (stem + "-mask.png", masks)):
-                    a = read_rgb_u8(path)
-                    if a.shape != (S, S, 3):
-                        raise ValueError("%s: %s is %s, not %d x %d x 3" % (who, path, a.shape, S, S))
-                    dst.append(a.astype(f32) / f32(255))
-            im, _, uv, _, _ = torch.split(torch.cat(rows, 0).float(), list(SPLIT_FFHQ), dim=3)
-            im_d = im.contiguous().to(dev)
-            gs, con_rgb, _, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
-            yield (step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb) + ((gen,) if with_generator else ())
-    finally:                    # also when the consumer stops early or raises: the handle is closed with the generator
-        gen.close()
-
-
 def score_folder(folder: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0, quiet: bool = False,
                  grad: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of recon_gs, recon_c and grad, a
     step being `batch` items (the last one may hold fewer).  With `grad` also those of GRAD_NAMES: the norms of each batch's gradients
     with respect to gs and con_rgb under G_TOTAL_WEIGHTS."""
     import torch
-    from .fsrnet import Logging
+    from .objective import score_steps
     dev = torch.device("cuda", device)
-    runner = None
-    acc: Dict[str, List[float]] = {}
-    with contextlib.closing(folder_steps(folder, ckpt, batch, device)) as batches:          # closes the generator handle on any way out
-        for step, steps, im_d, gt_a, mask_a, gs, con_rgb in batches:
-            norms = {}
-            if host:
-                torch.cuda.synchronize(dev)
-                arrays = (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy())
-                if grad:
-                    res = step_losses_grad(*arrays, upstream=np.array(G_TOTAL_WEIGHTS, f32))
-                    loss, norms = res["losses"], grad_norms(res["grad_gs"], res["grad_con"])
-                else:
-                    loss = step_losses(*arrays)["losses"]
-            else:
-                from .train_losses_gpu import TrainLosses
-                runner = runner or TrainLosses(device)
-                tensors = (im_d, torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev), gs, con_rgb)
-                if grad:
-                    res = runner.step_losses_grad(*tensors, upstream=torch.tensor(G_TOTAL_WEIGHTS, dtype=torch.float32).to(dev))
-                    loss, norms = res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy(), res[3].cpu().numpy())
-                else:
-                    loss = runner.step_losses(*tensors)[0].cpu().numpy()
-            Logging.accumulate(acc, dict({k: float(v) for k, v in zip(LOSS_NAMES, loss)}, **norms))
-            if not quiet:
-                print(Logging.format_line(acc, step, steps), end="", flush=True)
-    if not quiet:
-        print("")
-    return {k: s / max(c, 1) for k, (s, c) in acc.items()}
+    if host:
+        def step(im_d, gt_a, mask_a, gs, con_rgb):
+            torch.cuda.synchronize(dev)
+            arrays = (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy())
+            if not grad:
+                return step_losses(*arrays)["losses"], {}
+            res = step_losses_grad(*arrays, upstream=np.array(G_TOTAL_WEIGHTS, f32))
+            return res["losses"], grad_norms(res["grad_gs"], res["grad_con"])
+    else:
+        from .train_losses_gpu import TrainLosses
+        runner, weights_d = TrainLosses(device), torch.tensor(G_TOTAL_WEIGHTS, dtype=torch.float32).to(dev)
+
+        def step(im_d, gt_a, mask_a, gs, con_rgb):
+            tensors = (im_d, torch.from_numpy(gt_a).to(dev), torch.from_numpy(mask_a).to(dev), gs, con_rgb)
+            if not grad:
+                return runner.step_losses(*tensors)[0].cpu().numpy(), {}
+            res = runner.step_losses_grad(*tensors, upstream=weights_d)
+            return res[0].cpu().numpy(), grad_norms(res[2].cpu().numpy(), res[3].cpu().numpy())
+
+    def record(*tensors):
+        loss, norms = step(*tensors)
+        return dict({k: float(v) for k, v in zip(LOSS_NAMES, loss)}, **norms), ()
+
+    return score_steps(folder, ckpt, batch, device, "train_losses", record, quiet)
 
 
 def main(argv=None) -> int:

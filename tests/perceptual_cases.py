@@ -15,6 +15,8 @@ f32 = np.float32
 TAPS = [(a, b) for a in range(3) for b in range(3)]
 GPU_SIZES = ((32, 1), (32, 3), (64, 2), (128, 1))
 SUM_REL = 1e-9            # float64 sums of at most 2^22 non-negative float32 terms taken in another order: 2^22 * 2^-53 = 5e-10
+E2E_MEASURED = 3.6e-6          # the largest scaled error of a tapped feature measured on GPU_SIZES: block5_conv1 at S = 128 (tools/perceptual_bench.py --parity)
+E2E_BOUND = min(4 * E2E_MEASURED, 1e-3)
 
 
 def one_ulp_apart(a, b) -> bool:

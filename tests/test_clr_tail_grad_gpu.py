@@ -300,54 +300,6 @@ def test_backward_reads_the_generators_f_in_place(runner, generated):
         runner.backward(gen, gs[:1].contiguous(), g_con[:1].contiguous(), None)
 
 
-@pytest.fixture(scope="module")
-def pairs_folder(tmp_path_factory):
-    """One synthesised pair of side 256, as the shadow_synth command writes it."""
-    from blindshadowremoval_amd import shadow_synth
-    from blindshadowremoval_amd.pngio import write_png
-    tmp_path = tmp_path_factory.mktemp("tail_pairs")
-    rng = np.random.default_rng(6)
-    S = 256
-    ang = np.linspace(0, 2 * np.pi, 40, endpoint=False)
-    lm = np.concatenate([np.stack([128 + 96 * np.cos(ang), 128 + 96 * np.sin(ang)], 1), rng.uniform(64, 192, (28, 2))]).astype(np.float32)
-    yy, xx = np.meshgrid(np.linspace(0, 1, S), np.linspace(0, 1, S), indexing="ij")
-    crop = np.stack([120 + 80 * np.sin(6 * (yy * (c + 1) + xx) + rng.uniform(0, 6)) for c in range(3)], axis=2) + rng.normal(0, 4, (S, S, 3))
-    write_png(str(tmp_path / "src" / "a" / "a.png"), np.clip(crop, 0, 255).astype(np.uint8))
-    np.save(str(tmp_path / "src" / "a" / "a.npy"), lm)
-    folder = str(tmp_path / "pairs")
-    assert shadow_synth.synthesise_folder(str(tmp_path / "src"), folder, 3, host=False, batch=1) == ["a"]
-    return folder
-
-
-def test_command_grad_total_tail_device_route_matches_the_host_route(pairs_folder, tmp_path, capsys):
-    """`python -m blindshadowremoval_amd.perceptual --grad-total --tail` on one item at 256 x 256: both routes print the same fields, and
-    each of the 24 tail norms agrees within 1e-3 of its own magnitude, the ceiling of every end-to-end bound of the project (the routes
-    feed the tail gradients that already differ by their own terms' end-to-end errors, tests/test_train_losses_grad_gpu.py, and the
-    host route takes its masks from its own float64 forward, so single masks may differ at pre-activations that round across 0)."""
-    from blindshadowremoval_amd import perceptual
-    from blindshadowremoval_amd.weights import init_vgg_weights, save_vgg_weights
-    vgg = str(tmp_path / "vgg.npz")
-    save_vgg_weights(vgg, init_vgg_weights(21))
-    names = perceptual.tail_grad_names()
-    assert len(names) == 24 and names[:4] == ["d_f_l1", "d_f_linf", "d_gs_l1", "d_gs_linf"]
-    printed = []
-    for extra in ([], ["--host"]):
-        assert perceptual.main([pairs_folder, "--vgg", vgg, "--batch", "1", "--grad-total", "--tail"] + extra) == 0
-        lines = capsys.readouterr().out.strip().split("\n")
-        assert len(lines) == 2 and lines[0].startswith("1/1 ")
-        fields = dict(f.rsplit(":", 1) for f in lines[0][4:].split(", "))
-        assert tuple(fields) == perceptual.ALL_NAMES + perceptual.TOTAL_GRAD_NAMES + tuple(names)
-        printed.append({k: float(v) for k, v in fields.items()})
-    dev_route, host_route = printed
-    for k in names:
-        d = abs(dev_route[k] - host_route[k])
-        print("perceptual command --grad-total --tail %s: device %.9g host %.9g, relative difference %.3g" % (k, dev_route[k], host_route[k], d / host_route[k]))
-        assert host_route[k] > 0 and d <= 1e-3 * host_route[k], k
-    with pytest.raises(SystemExit):
-        perceptual.main([pairs_folder, "--vgg", vgg, "--tail"])
-    capsys.readouterr()
-
-
 def test_last_f_is_refused_for_a_sixteen_bit_generator():
     from blindshadowremoval_amd import Generator
     gen = Generator(device=0, dtype="f16")

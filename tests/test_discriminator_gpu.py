@@ -13,6 +13,7 @@ from blindshadowremoval_amd import discriminator as host
 from blindshadowremoval_amd.weights import init_discriminator_weights
 
 import discriminator_cases as cases
+import pairs_cases
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -231,19 +232,7 @@ def test_argument_errors_raise_before_any_launch(runner):
 
 
 def test_command_device_route_matches_the_host_route(tmp_path, capsys):
-    from blindshadowremoval_amd import shadow_synth
-    from blindshadowremoval_amd.pngio import write_png
-    rng = np.random.default_rng(6)
-    S = 256
-    ang = np.linspace(0, 2 * np.pi, 40, endpoint=False)
-    lm = np.concatenate([np.stack([128 + 96 * np.cos(ang), 128 + 96 * np.sin(ang)], 1), rng.uniform(64, 192, (28, 2))]).astype(np.float32)
-    yy, xx = np.meshgrid(np.linspace(0, 1, S), np.linspace(0, 1, S), indexing="ij")
-    for name in ("a", "b"):
-        crop = np.stack([120 + 80 * np.sin(6 * (yy * (c + 1) + xx) + rng.uniform(0, 6)) for c in range(3)], axis=2) + rng.normal(0, 4, (S, S, 3))
-        write_png(str(tmp_path / "src" / name / (name + ".png")), np.clip(crop, 0, 255).astype(np.uint8))
-        np.save(str(tmp_path / "src" / name / (name + ".npy")), lm)
-    folder = str(tmp_path / "pairs")
-    assert shadow_synth.synthesise_folder(str(tmp_path / "src"), folder, 3, host=False, batch=2) == ["a", "b"]
+    folder = pairs_cases.write_pairs(tmp_path, ("a", "b"), batch=2)
     printed = []
     for extra in ([], ["--host"]):
         assert host.main([folder, "--batch", "2"] + extra) == 0

@@ -9,7 +9,7 @@ the device's activations) within 4 x E2E_MEASURED on the scale of the largest ma
 over these sizes (profiles/discriminator_grad_bench.json), never above 1e-3; the difference from the statement on
 its own float64 forward is printed and not asserted, since masks flip at pre-activations that round across 0.
 
-The command runs at S = 256, the only size train_losses.folder_steps' generator takes, on one item."""
+The command runs at S = 256, the only size objective.folder_steps' generator takes, on one item."""
 import numpy as np
 import pytest
 
@@ -17,13 +17,13 @@ from blindshadowremoval_amd import discriminator as host
 from blindshadowremoval_amd.weights import N_LAYER_D, init_discriminator_weights
 
 import discriminator_grad_cases as gcases
+import pairs_cases
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 f32 = np.float32
 STAGE_BUDGET = 1e-5
-E2E_MEASURED = 6.6e-7          # the largest scaled error of grad measured on GPU_SIZES: S = 32, B = 1 (tools/discriminator_bench.py --grad --parity)
-E2E_BOUND = min(4 * E2E_MEASURED, 1e-3)
+E2E_BOUND = gcases.E2E_BOUND
 
 
 @pytest.fixture(scope="module")
@@ -303,18 +303,7 @@ def test_argument_errors_raise_before_any_launch(runner, weights):
 
 
 def test_command_grad_device_route_matches_the_host_route(tmp_path, capsys):
-    from blindshadowremoval_amd import shadow_synth
-    from blindshadowremoval_amd.pngio import write_png
-    rng = np.random.default_rng(6)
-    S = 256
-    ang = np.linspace(0, 2 * np.pi, 40, endpoint=False)
-    lm = np.concatenate([np.stack([128 + 96 * np.cos(ang), 128 + 96 * np.sin(ang)], 1), rng.uniform(64, 192, (28, 2))]).astype(np.float32)
-    yy, xx = np.meshgrid(np.linspace(0, 1, S), np.linspace(0, 1, S), indexing="ij")
-    crop = np.stack([120 + 80 * np.sin(6 * (yy * (c + 1) + xx) + rng.uniform(0, 6)) for c in range(3)], axis=2) + rng.normal(0, 4, (S, S, 3))
-    write_png(str(tmp_path / "src" / "a" / "a.png"), np.clip(crop, 0, 255).astype(np.uint8))
-    np.save(str(tmp_path / "src" / "a" / "a.npy"), lm)
-    folder = str(tmp_path / "pairs")
-    assert shadow_synth.synthesise_folder(str(tmp_path / "src"), folder, 3, host=False, batch=1) == ["a"]
+    folder = pairs_cases.write_pairs(tmp_path)
     printed = []
     for extra in ([], ["--host"]):
         assert host.main([folder, "--batch", "1", "--grad"] + extra) == 0
@@ -331,7 +320,7 @@ def test_command_grad_device_route_matches_the_host_route(tmp_path, capsys):
     print("discriminator command --grad: device %s\ndiscriminator command --grad: host %s" % (dev_route, host_route))
     # the end-to-end tolerance, E2E_BOUND of the largest magnitude per element: the L-infinity norm moves by at most that, the L1 norm
     # by at most that for each of its S * S * 3 elements
-    n, linf = S * S * 3, host_route["gen_grad_linf"]
+    n, linf = pairs_cases.S * pairs_cases.S * 3, host_route["gen_grad_linf"]
     d_linf, d_l1 = abs(dev_route["gen_grad_linf"] - linf), abs(dev_route["gen_grad_l1"] - host_route["gen_grad_l1"])
     print("discriminator command --grad: |device - host| linf %.3g (bound %.3g), l1 %.3g (bound %.3g)" % (d_linf, E2E_BOUND * linf, d_l1, E2E_BOUND * n * linf))
     assert linf > 0 and host_route["gen_grad_l1"] > linf

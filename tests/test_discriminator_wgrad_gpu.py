@@ -11,7 +11,7 @@ discriminator_grad_cases.GPU_SIZES and the hinge case (S = 128, B = 2): S = 32 h
 discriminator 1's conv0 has 128 tiles of its 16384 output pixels for 43 partials (a workgroup walks at least three tiles where there
 are three) and its conv1 32 for 11, so the partial count divides neither the tile count nor the pixel count.
 
-The command runs at S = 256, the only size train_losses.folder_steps' generator takes, on one item."""
+The command runs at S = 256, the only size objective.folder_steps' generator takes, on one item."""
 import numpy as np
 import pytest
 
@@ -21,6 +21,7 @@ from blindshadowremoval_amd.weights import BN_EPS, N_LAYER_D, init_discriminator
 import discriminator_cases as dcases
 import discriminator_grad_cases as gcases
 import discriminator_wgrad_cases as cases
+import pairs_cases
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -309,18 +310,7 @@ def test_argument_errors_raise_before_any_launch(runner, weights):
 
 
 def test_command_wgrad_device_route_matches_the_host_route(tmp_path, capsys):
-    from blindshadowremoval_amd import shadow_synth
-    from blindshadowremoval_amd.pngio import write_png
-    rng = np.random.default_rng(6)
-    S = 256
-    ang = np.linspace(0, 2 * np.pi, 40, endpoint=False)
-    lm = np.concatenate([np.stack([128 + 96 * np.cos(ang), 128 + 96 * np.sin(ang)], 1), rng.uniform(64, 192, (28, 2))]).astype(np.float32)
-    yy, xx = np.meshgrid(np.linspace(0, 1, S), np.linspace(0, 1, S), indexing="ij")
-    crop = np.stack([120 + 80 * np.sin(6 * (yy * (c + 1) + xx) + rng.uniform(0, 6)) for c in range(3)], axis=2) + rng.normal(0, 4, (S, S, 3))
-    write_png(str(tmp_path / "src" / "a" / "a.png"), np.clip(crop, 0, 255).astype(np.uint8))
-    np.save(str(tmp_path / "src" / "a" / "a.npy"), lm)
-    folder = str(tmp_path / "pairs")
-    assert shadow_synth.synthesise_folder(str(tmp_path / "src"), folder, 3, host=False, batch=1) == ["a"]
+    folder = pairs_cases.write_pairs(tmp_path)
     printed = []
     for extra in ([], ["--host"]):
         assert host.main([folder, "--batch", "1", "--wgrad"] + extra) == 0

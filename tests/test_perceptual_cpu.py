@@ -3,7 +3,7 @@ preprocessing, the totals, and the constructed cases of tests/perceptual_cases.p
 import numpy as np
 import pytest
 
-from blindshadowremoval_amd import pack
+from blindshadowremoval_amd import objective, pack
 from blindshadowremoval_amd import perceptual as host
 from blindshadowremoval_amd import weights as W
 
@@ -116,10 +116,10 @@ def test_totals_are_float32_in_the_reference_order():
     gs, c, grad, gen, per = f32(0.0123), f32(0.0345), f32(0.31), f32(-0.72), f32(39.5)
     recon = (gs + c) / f32(2)
     want = ((recon * f32(400) + gen) + per * f32(.005)) + grad * f32(2)
-    got = host.g_total_loss(gs, c, grad, gen, per)
+    got = objective.g_total_loss(gs, c, grad, gen, per)
     assert got.dtype == f32 and got.tobytes() == f32(want).tobytes()
     assert abs(float(got) - ((0.0123 + 0.0345) / 2 * 400 - 0.72 + 39.5 * .005 + 0.62)) < 1e-5
-    d = host.d_total_loss(f32(0.4), f32(0.7))
+    d = objective.d_total_loss(f32(0.4), f32(0.7))
     assert d.dtype == f32 and d == f32(0.4) + f32(0.7)
 
 

@@ -9,20 +9,20 @@ E2E_MEASURED the largest scaled error seen on the MI355X over these sizes (profi
 Figures of the MI355X (scaled errors): g_l at most 4.9e-8 (the float32 rounding of a float64 sum), d_grad fed the device's maps at most
 5.2e-8, grad_con end to end at most 8.3e-8 (S = 32, B = 3), so the bound is 3.3e-7.
 
-The commands run at S = 256, the only size train_losses.folder_steps' generator takes, on one item."""
+The commands run at S = 256, the only size objective.folder_steps' generator takes, on one item."""
 import numpy as np
 import pytest
 
 from blindshadowremoval_amd import train_losses as host
 
 import train_losses_grad_cases as cases
+import pairs_cases
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 f32 = np.float32
 STAGE_BUDGET = 1e-5
-E2E_MEASURED = 8.3e-8          # the largest scaled error of grad_con measured on GPU_SIZES: S = 32, B = 3 (tools/train_losses_bench.py --grad --parity)
-E2E_BOUND = min(4 * E2E_MEASURED, 1e-4)
+E2E_BOUND = cases.E2E_BOUND
 NAMES = ("losses", "sums", "grad_gs", "grad_con", "d_recon_c", "d_grad")
 
 
@@ -218,20 +218,7 @@ def test_argument_errors_raise_before_any_launch(runner):
 @pytest.fixture(scope="module")
 def pairs_folder(tmp_path_factory):
     """One synthesised pair of side 256, as the shadow_synth command writes it."""
-    from blindshadowremoval_amd import shadow_synth
-    from blindshadowremoval_amd.pngio import write_png
-    tmp_path = tmp_path_factory.mktemp("grad_pairs")
-    rng = np.random.default_rng(6)
-    S = 256
-    ang = np.linspace(0, 2 * np.pi, 40, endpoint=False)
-    lm = np.concatenate([np.stack([128 + 96 * np.cos(ang), 128 + 96 * np.sin(ang)], 1), rng.uniform(64, 192, (28, 2))]).astype(np.float32)
-    yy, xx = np.meshgrid(np.linspace(0, 1, S), np.linspace(0, 1, S), indexing="ij")
-    crop = np.stack([120 + 80 * np.sin(6 * (yy * (c + 1) + xx) + rng.uniform(0, 6)) for c in range(3)], axis=2) + rng.normal(0, 4, (S, S, 3))
-    write_png(str(tmp_path / "src" / "a" / "a.png"), np.clip(crop, 0, 255).astype(np.uint8))
-    np.save(str(tmp_path / "src" / "a" / "a.npy"), lm)
-    folder = str(tmp_path / "pairs")
-    assert shadow_synth.synthesise_folder(str(tmp_path / "src"), folder, 3, host=False, batch=1) == ["a"]
-    return folder
+    return pairs_cases.write_pairs(tmp_path_factory.mktemp("grad_pairs"))
 
 
 def test_command_grad_device_route_matches_the_host_route(pairs_folder, capsys):
@@ -257,34 +244,3 @@ def test_command_grad_device_route_matches_the_host_route(pairs_folder, capsys):
     assert linf > 0 and host_route["grad_con_l1"] > linf and host_route["grad_gs_linf"] > 0
     assert abs(dev_route["grad_con_linf"] - linf) <= E2E_BOUND * linf + 1e-9 * linf          # and the nine printed digits
     assert abs(dev_route["grad_con_l1"] - host_route["grad_con_l1"]) <= E2E_BOUND * n * linf + 1e-9 * host_route["grad_con_l1"]
-
-
-def test_command_grad_total_device_route_matches_the_host_route(pairs_folder, tmp_path, capsys):
-    """`python -m blindshadowremoval_amd.perceptual --grad-total`: the whole d g_total_loss / d (con_rgb, gs).  The three terms' own
-    end-to-end bounds add (test_discriminator_grad_gpu.E2E_BOUND 2.64e-6, test_perceptual_grad_gpu.E2E_BOUND 3.52e-6, this file's), each on
-    the scale of its own term's largest magnitude; two float32 additions put 2^-23 on top.  A term's largest magnitude is at most the
-    total's plus the other two's, so twice the total's largest magnitude stands for each of them here, where the reconstruction terms
-    under weights of 200 carry the total."""
-    from blindshadowremoval_amd import perceptual
-    from blindshadowremoval_amd.weights import init_vgg_weights, save_vgg_weights
-    S, vgg = 256, str(tmp_path / "vgg.npz")
-    save_vgg_weights(vgg, init_vgg_weights(21))
-    printed = []
-    for extra in ([], ["--host"]):
-        assert perceptual.main([pairs_folder, "--vgg", vgg, "--batch", "1", "--grad-total"] + extra) == 0
-        lines = capsys.readouterr().out.strip().split("\n")
-        assert len(lines) == 2 and lines[0].startswith("1/1 ")
-        fields = dict(f.split(":") for f in lines[0][4:].split(", "))
-        assert tuple(fields) == perceptual.ALL_NAMES + perceptual.TOTAL_GRAD_NAMES
-        assert tuple(dict(f.split(":") for f in lines[1].split(", "))) == perceptual.ALL_NAMES
-        printed.append({k: float(v) for k, v in fields.items()})
-    dev_route, host_route = printed
-    print("perceptual command --grad-total: device %s\nperceptual command --grad-total: host %s" % (dev_route, host_route))
-    for k in ("recon_gs", "recon_c", "grad", "g_total_grad_gs_l1", "g_total_grad_gs_linf"):          # bit-identical tensors
-        assert dev_route[k] == host_route[k], k
-    bound = 2 * (E2E_BOUND + 2.64e-6 + 3.52e-6 + 2.0 ** -23)
-    n, linf = S * S * 3, host_route["g_total_grad_con_linf"]
-    d_linf, d_l1 = abs(dev_route["g_total_grad_con_linf"] - linf), abs(dev_route["g_total_grad_con_l1"] - host_route["g_total_grad_con_l1"])
-    print("perceptual command --grad-total: |device - host| linf %.3g (bound %.3g), l1 %.3g (bound %.3g)" % (d_linf, bound * linf, d_l1, bound * n * linf))
-    assert linf > 0 and host_route["g_total_grad_con_l1"] > linf and host_route["g_total_grad_gs_linf"] > 0
-    assert d_linf <= bound * linf and d_l1 <= bound * n * linf

@@ -12,6 +12,8 @@ CPU_SIZES = ((32, 3), (64, 2))                          # (S, B)
 GPU_SIZES = ((32, 1), (32, 3), (64, 2), (256, 1))      # S = 32: level 4 is 2 x 2, every coarse pixel an edge pixel of U_4; B = 3: item order
 NEAR_ZERO = 1e-9
 SIGN_FLIP_CAP = 1e-3                                    # the share of signs that float32 rounding may turn, a condition on the inputs
+E2E_MEASURED = 8.3e-8          # the largest scaled error of grad_con measured on GPU_SIZES: S = 32, B = 3 (tools/train_losses_bench.py --grad --parity)
+E2E_BOUND = min(4 * E2E_MEASURED, 1e-4)
 
 
 # ---- the float64 restatement for autograd

@@ -40,6 +40,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from blindshadowremoval_amd import objective                                   # noqa: E402
 from blindshadowremoval_amd import perceptual as host                          # noqa: E402
 from blindshadowremoval_amd.weights import init_vgg_weights                    # noqa: E402
 
@@ -209,8 +210,8 @@ def host_values(case):
     total = r["sums"].sum(axis=0)
     means = np.array([total[k] / (B * h * h * host.TAP_CH[k]) for k, h in enumerate(host.tap_sides(S))])
     tm = loss_terms(seed)
-    g = host.g_total_loss(tm["recon_loss_gs"], tm["recon_loss_c"], tm["grad_loss"], tm["gan_loss"], r["loss"][0])
-    d = host.d_total_loss(tm["d_loss_r"], tm["d_loss_s"])
+    g = objective.g_total_loss(tm["recon_loss_gs"], tm["recon_loss_c"], tm["grad_loss"], tm["gan_loss"], r["loss"][0])
+    d = objective.d_total_loss(tm["d_loss_r"], tm["d_loss_s"])
     return np.append(means, float(r["loss"][0])), np.array([float(g), float(d)])
 
 
