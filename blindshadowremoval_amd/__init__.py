@@ -2,8 +2,8 @@
 ``FSRNet.test*`` inference path).  See DESIGN.md."""
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
-__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "generator_variable_shapes",
-           "init_weights"]
+__all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
+           "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "ColourTail":
         from .clr_tail_gpu import ColourTail
         return ColourTail
+    if name == "ColourDecoder":
+        from .clr_decoder_gpu import ColourDecoder
+        return ColourDecoder
     raise AttributeError(name)

@@ -42,6 +42,7 @@
 #include "disc_grad_kernels.h"
 #include "disc_wgrad_kernels.h"
 #include "clr_tail_grad_kernels.h"
+#include "clr_up_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1636,6 +1637,67 @@ int bsr_debug_clr_tail_grad(int device, const void* d_blob, size_t blob_bytes, c
                        stream);
 }
 
+size_t bsr_clr_decoder_grad_blob_bytes(void) { return bsr::up_blob_off(3, 0) * sizeof(float); }
+
+size_t bsr_clr_decoder_grad_scratch_bytes(int B, int H, int W, int keep) { return bsr::up_size_ok(B, H, W) ? bsr::up_plan(B, H, W, keep != 0).total : 0; }
+
+size_t bsr_clr_decoder_grad_floats(void) { return bsr::up_var_offset(bsr::kUpVars); }
+
+size_t bsr_clr_decoder_grad_var_offset(int index) { return index < 0 || index >= bsr::kUpVars ? SIZE_MAX : bsr::up_var_offset(index); }
+
+size_t bsr_clr_decoder_grad_offset(int B, int H, int W, int map) {
+  if (!bsr::up_size_ok(B, H, W) || map < 0 || map > 8) return SIZE_MAX;
+  return bsr::up_plan(B, H, W, true).map[map];
+}
+
+int bsr_clr_decoder_grad_partials(int B, int H, int W, int layer) {
+  return bsr::up_size_ok(B, H, W) && layer >= 1 && layer <= 3 ? bsr::up_plan(B, H, W, false).P[layer - 1] : 0;
+}
+
+namespace {
+
+int clr_decoder_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2,
+                     int f2_cs, const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch, int stop_after,
+                     void* stream) {
+  const std::string n(name);
+  for (const void* p : {d_blob, (const void*)x, (const void*)f1, (const void*)f2, (const void*)f, (const void*)d_f, (const void*)d_x, (const void*)grads,
+                        (const void*)scratch})
+    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
+  if (!bsr::up_size_ok(B, H, W))
+    return fail(BSR_ERR_ARG, n + ": B must be positive, H a multiple of 32 and W a multiple of 256 (the generator's rule), at most 2^26 pixels in all");
+  if (blob_bytes != bsr_clr_decoder_grad_blob_bytes())
+    return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_clr_decoder_grad_blob_bytes() (pack.pack_clr_decoder_grad; the GSC width 261 only, not TSM's 877)");
+  if (x_cs < 261) return fail(BSR_ERR_ARG, n + ": x_cs must be at least 261");
+  if (f1_cs < 128 || f1_cs % 4 != 0 || f2_cs < 96 || f2_cs % 4 != 0 || f_cs < 64 || f_cs % 4 != 0)
+    return fail(BSR_ERR_ARG, n + ": f1_cs, f2_cs, f_cs must be multiples of 4 and at least 128, 96, 64");
+  for (const void* p : {d_blob, (const void*)f1, (const void*)f2, (const void*)f, (const void*)d_f})
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(BSR_ERR_ARG, n + ": d_blob, f1, f2, f and d_f must be 16-byte aligned");
+  for (const void* p : {(const void*)x, (const void*)d_x, (const void*)grads})
+    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": x, d_x and grads must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kUpLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..9");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_clr_decoder_grad(static_cast<const float*>(d_blob), x, x_cs, f1, f1_cs, f2, f2_cs, f, f_cs, d_f, B, H, W, d_x, grads, keep != 0, scratch,
+                                       stop_after, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+}  // namespace
+
+int bsr_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2, int f2_cs,
+                         const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch, void* stream) {
+  return clr_decoder_grad("bsr_clr_decoder_grad", device, d_blob, blob_bytes, x, x_cs, f1, f1_cs, f2, f2_cs, f, f_cs, d_f, B, H, W, d_x, grads, keep, scratch,
+                          bsr::kUpLaunches, stream);
+}
+
+int bsr_debug_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2,
+                               int f2_cs, const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch,
+                               int stop_after, void* stream) {
+  return clr_decoder_grad("bsr_debug_clr_decoder_grad", device, d_blob, blob_bytes, x, x_cs, f1, f1_cs, f2, f2_cs, f, f_cs, d_f, B, H, W, d_x, grads, keep,
+                          scratch, stop_after, stream);
+}
+
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
 
 size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
@@ -2012,6 +2074,23 @@ int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]) {
   if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_f: no forward has run on this handle");
   *f = h->ws + h->plan.cf;
   *f_cs = CS_CF;
+  shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
+  return BSR_OK;
+}
+
+int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1, const float** f2, const float** f, int shape4[4]) {
+  if (h == nullptr || x == nullptr || x_cs == nullptr || f1 == nullptr || f2 == nullptr || f == nullptr || shape4 == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_last_decoder: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_decoder: an RGB handle has no colour decoder");
+  if (h->var.tsm) return fail(BSR_ERR_STATE, "bsr_last_decoder: the colour decoder's backward takes the GSC width 261 only, not a TSM handle's 877");
+  if (h->dtype != BSR_DTYPE_F32)
+    return fail(BSR_ERR_STATE, "bsr_last_decoder: the decoder's tensors are fp32 in BSR_DTYPE_F32 handles only (the 16-bit modes keep them as fp16)");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_decoder: no forward has run on this handle");
+  *x = h->ws + h->plan.r[5];
+  *x_cs = h->var.cs_h;
+  *f1 = h->ws + h->plan.f1;
+  *f2 = h->ws + h->plan.f2;
+  *f = h->ws + h->plan.cf;
   shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
   return BSR_OK;
 }

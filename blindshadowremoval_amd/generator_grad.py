@@ -1,7 +1,9 @@
 """The host statement of the generator's backward pass, from the output down, training=False (moving statistics).  So far the colour
 tail (model.py:217-219, 267-269): clr_conv1 (3x3, cat[gs, f] 65 -> 16, BN, LeakyReLU), clr_conv2 (1x1, 16 -> 16, BN, LeakyReLU) and
 clr_conv3 (1x1, 16 -> 3).  `tail_grad` writes the arithmetic out in float64 from the float32 variables; csrc/clr_tail_grad_kernels.h
-is held to it (clr_tail_gpu.ColourTail)."""
+is held to it (clr_tail_gpu.ColourTail).  Below it the colour decoder (model.py:214-216, 264-266): clr_up1, clr_up2, clr_up3, each
+Conv2DTranspose(3, stride 2, SAME), BN, LeakyReLU; `decoder_grad` is its statement, any input width (261 for GSC, 877 for TSM), and
+csrc/clr_up_grad_kernels.h is held to it (clr_decoder_gpu.ColourDecoder)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -9,10 +11,12 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
-from .weights import BN_EPS, LRELU_ALPHA, generator_tail_trainable_names
+from .weights import BN_EPS, LRELU_ALPHA, generator_decoder_trainable_names, generator_tail_trainable_names
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
+DECODER_LAYERS = ("clr_up1", "clr_up2", "clr_up3")
+DECODER_NORM_NAMES = ("d_x",) + tuple(generator_decoder_trainable_names())
 
 
 def bn_vectors(weights: Dict[str, np.ndarray], stem: str, dtype=np.float64):
@@ -160,3 +164,129 @@ def example_inputs(H: int, W: int, B: int, seed: int = 0):
     g_con = (rng.standard_normal((B, H, W, 3)) / (B * H * W)).astype(np.float32)
     g_gs = (rng.standard_normal((B, H, W, 1)) / (B * H * W)).astype(np.float32)
     return gs, f, g_con, g_gs
+
+
+# ---- the colour decoder: clr_up1, clr_up2, clr_up3
+def convt3x3_same(x: np.ndarray, kernel: np.ndarray) -> np.ndarray:
+    """[N,h,w,C] x [3,3,O,C] -> [N,2h,2w,O] in x's type: Conv2DTranspose(3, stride 2, SAME) without bias,
+    y[n, 2i + a, 2j + b, o] += x[n, i, j, c] K[a, b, o, c], the (2h + 1, 2w + 1) scatter cropped at the end; taps in index order."""
+    n, h, w, _ = x.shape
+    full = np.zeros((n, 2 * h + 1, 2 * w + 1, kernel.shape[2]), x.dtype)
+    for a in range(3):
+        for b in range(3):
+            full[:, a:a + 2 * h:2, b:b + 2 * w:2] += x @ kernel[a, b].astype(x.dtype).T
+    return full[:, :2 * h, :2 * w].copy()
+
+
+def _fine_padded(gz: np.ndarray) -> np.ndarray:
+    """[N,2h,2w,O] -> float64 [N,2h+1,2w+1,O] with fine row 2h and column 2w zero."""
+    n, h2, w2, o = gz.shape
+    gp = np.zeros((n, h2 + 1, w2 + 1, o), np.float64)
+    gp[:, :h2, :w2] = gz
+    return gp
+
+
+def convt3x3_same_wgrad(x: np.ndarray, gz: np.ndarray) -> np.ndarray:
+    """A ConvT's input [N,h,w,C] and the gradient [N,2h,2w,O] at its output -> float64 [3,3,O,C]:
+    Wg[a, b, o, c] = sum gz[n, 2i + a, 2j + b, o] x[n, i, j, c], fine rows 2h and columns 2w counting as 0."""
+    x = np.asarray(x, np.float64)
+    n, h, w, c = x.shape
+    gp = _fine_padded(gz)
+    out = np.zeros((3, 3, gz.shape[3], c), np.float64)
+    for a in range(3):
+        for b in range(3):
+            out[a, b] = np.tensordot(gp[:, a:a + 2 * h:2, b:b + 2 * w:2], x, axes=([0, 1, 2], [0, 1, 2]))
+    return out
+
+
+def convt3x3_same_dgrad(gz: np.ndarray, kernel: np.ndarray) -> np.ndarray:
+    """The gradient [N,2h,2w,O] at a ConvT's output -> float64 [N,h,w,C] at its input: dx[n, i, j, c] = sum gz[n, 2i + a, 2j + b, o]
+    K[a, b, o, c], a 3x3 stride-2 correlation over the fine grid with padding 0 before and 1 after."""
+    kernel = np.asarray(kernel, np.float64)
+    n, h2, w2, _ = gz.shape
+    h, w = h2 // 2, w2 // 2
+    gp = _fine_padded(gz)
+    out = np.zeros((n, h, w, kernel.shape[3]), np.float64)
+    for a in range(3):
+        for b in range(3):
+            out += gp[:, a:a + 2 * h:2, b:b + 2 * w:2] @ kernel[a, b]
+    return out
+
+
+def decoder_forward(weights: Dict[str, np.ndarray], x, dtype=np.float64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """x [B,h,w,C] (C = clr_up1's kernel's width) -> (f1 [B,2h,2w,128], f2 [B,4h,4w,96], f [B,8h,8w,64]) in `dtype`: per layer
+    c = ConvT(a_in, K) + bias, z = (c - mean) rstd gamma + beta, a_out = lrelu_0.3(z)."""
+    T = dtype
+    h = np.asarray(x, T)
+    outs = []
+    for stem in DECODER_LAYERS:
+        bias, _, mean, rstd, beta = bn_vectors(weights, stem, T)
+        c = convt3x3_same(h, np.asarray(weights[stem + "/conv/kernel"], T)) + bias
+        h = _lrelu((c - mean) * rstd * np.asarray(weights[stem + "/bnorm/gamma"], T) + beta)
+        outs.append(h)
+    return tuple(outs)
+
+
+def decoder_grad(weights: Dict[str, np.ndarray], x, d_f, acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """The gradient d_f [B,8h,8w,64] at f -> dict(the twelve variables of weights.generator_decoder_trainable_names() in their own shapes,
+    `d_x` [B,h,w,C] at clr_up1's input x, the stage maps `gz3` [B,8h,8w,64], `gz2` [B,4h,4w,96], `gz1` [B,2h,2w,128] — the gradients at
+    each BatchNormalization output — and `f1`, `f2`, `f` as used), all float64 from the float32 variables.  Per layer from the top down,
+    a_in its input, a_out its output, g the gradient at a_out, K [3,3,O,C]:
+      gz = leaky_grad(g, a_out);  S = sum gz;  Wg = convt3x3_same_wgrad(a_in, gz)
+      d kernel = Wg inv;  d beta = S;  d bias = inv S;  d gamma = ((KW + bias S) - moving_mean S) rstd with KW[o] = sum_{a,b,c} K Wg
+      (the pre-activation is sum K a_in + bias, so no second pass over the activations is needed)
+      dx = convt3x3_same_dgrad(gz inv, K), the g of the layer below; clr_up1's is d_x and gets no mask (res_stack/5's LeakyReLU belongs
+      to that block's own backward).
+    With `acts` given (a dict with `f1`, `f2`, `f`, for example the device's), the masks and the layer inputs are read from it."""
+    T = np.float64
+    x = np.asarray(x, T)
+    if acts is not None:
+        f1, f2, f = (np.asarray(acts[k], T) for k in ("f1", "f2", "f"))
+    else:
+        f1, f2, f = decoder_forward(weights, x, T)
+    out: Dict[str, np.ndarray] = {"f1": f1, "f2": f2, "f": f}
+    g = np.asarray(d_f, T)
+    ax = (0, 1, 2)
+    for i, a_in, a_out in ((3, f2, f), (2, f1, f2), (1, x, f1)):
+        stem = DECODER_LAYERS[i - 1]
+        K = np.asarray(weights[stem + "/conv/kernel"], T)
+        bias, inv, mean, rstd, _ = bn_vectors(weights, stem)
+        gz = leaky_grad(g, a_out)
+        out["gz%d" % i] = gz
+        S = gz.sum(axis=ax)
+        Wg = convt3x3_same_wgrad(a_in, gz)
+        KW = (K * Wg).sum(axis=(0, 1, 3))
+        out[stem + "/conv/kernel"] = Wg * inv[:, None]
+        out[stem + "/conv/bias"] = inv * S
+        out[stem + "/bnorm/gamma"] = ((KW + bias * S) - mean * S) * rstd
+        out[stem + "/bnorm/beta"] = S
+        g = convt3x3_same_dgrad(gz * inv, K)
+    out["d_x"] = g
+    return out
+
+
+def decoder_objective_f64(weights: Dict[str, np.ndarray], x, d_f, masks: Optional[list] = None, dtype=np.float64):
+    """<d_f, f> in `dtype` with no float32 rounding anywhere: the scalar whose gradient decoder_grad states.  A list given as `masks`
+    receives the three LeakyReLU masks (z > 0) of f1, f2, f."""
+    fs = decoder_forward(weights, x, dtype)
+    if masks is not None:
+        masks += [a > 0 for a in fs]
+    return (np.asarray(d_f, dtype) * fs[2]).sum()
+
+
+def decoder_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
+    """name -> (L1, L-infinity) of `d_x` and each of the twelve variable gradients (DECODER_NORM_NAMES)."""
+    out = {}
+    for name in DECODER_NORM_NAMES:
+        m = np.abs(np.asarray(grads[name], np.float64))
+        out[name] = (float(m.sum()), float(m.max()))
+    return out
+
+
+def decoder_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
+    """Seeded (x [B,h,w,C], d_f [B,8h,8w,64]) float32 at a coarse grid: x like a LeakyReLU output."""
+    rng = np.random.default_rng(2000 + seed)
+    x = rng.standard_normal((B, h, w, C)).astype(np.float32)
+    x = np.where(x >= 0, x, np.float32(LRELU_ALPHA) * x).astype(np.float32)
+    d_f = (rng.standard_normal((B, 8 * h, 8 * w, 64)) / (B * h * w * 64)).astype(np.float32)
+    return x, d_f

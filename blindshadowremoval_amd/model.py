@@ -224,6 +224,18 @@ class Generator:
         _lib.check(self._lib.bsr_last_f(self._handle, ctypes.byref(ptr), ctypes.byref(cs), ctypes.byref(shape)), "bsr_last_f")
         return int(ptr.value), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
 
+    def last_decoder(self) -> Tuple[Tuple[int, int, int, int], int, Tuple[int, int, int, int]]:
+        """((x, f1, f2, f) device addresses, x's floats between pixels, (B, H, W, 64)) of the last forward's colour decoder tensors in the
+        handle's workspace (bsr_last_decoder): x = res_stack/5's output [B,H/8,W/8,261 of x_cs], f1 [B,H/4,W/4,128], f2 [B,H/2,W/2,96],
+        f [B,H,W,64], the last three dense.  No copy; valid until the next forward on this generator.  fp32 GSC generators only:
+        RuntimeError before any forward, for the 16-bit modes and for TSM weights."""
+        self._require_weights()
+        ptrs = [ctypes.c_void_p() for _ in range(4)]
+        cs, shape = ctypes.c_int(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_decoder(self._handle, ctypes.byref(ptrs[0]), ctypes.byref(cs), ctypes.byref(ptrs[1]), ctypes.byref(ptrs[2]),
+                                              ctypes.byref(ptrs[3]), ctypes.byref(shape)), "bsr_last_decoder")
+        return tuple(int(p.value) for p in ptrs), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

@@ -9,18 +9,19 @@ THE TOTALS, float32 in the reference's order:
 THE TOTAL GRADIENT, d g_total_loss / d (con_rgb, gs).  grad_gs is step_losses_grad's under train_losses.G_TOTAL_WEIGHTS: no other term reads
 gs.  grad_con = (step_losses_grad's grad_con + gen_grad's grad) + per_loss_grad's grad under PER_WEIGHT, three float32 tensors added in
 that order.  Through the generator's colour tail both become d / d f at clr_up3's output, the complete d / d gs and the gradients of the
-tail's ten variables (generator_grad.tail_grad).
+tail's ten variables (generator_grad.tail_grad), and d / d f through the colour decoder becomes d / d x at res_stack/5's output and the
+gradients of the decoder's twelve variables (generator_grad.decoder_grad).
 
 THE ROUTES.  HostRoute states all of that over the three host statements, DeviceRoute over TrainLosses, Discriminators, Perceptual and
 ColourTail, with the same methods; a command chooses one before its loop.  The methods take (img, gt, mask_sv, gs, con_rgb) as `bring`
 returns them and return losses as float32 numpy arrays and gradients in the route's own type: numpy arrays or device tensors.
 
-`python -m blindshadowremoval_amd.objective FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total] [--tail]` evaluates
+`python -m blindshadowremoval_amd.objective FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total] [--tail] [--decoder]` evaluates
 the whole objective on a folder written by `python -m blindshadowremoval_amd.shadow_synth` (folder_steps): ALL_NAMES per batch and as
 step-weighted means, on the device route or with --host on the host route.  With --grad each batch's line also carries per_grad_l1 and
 per_grad_linf, the L1 and L-infinity norms of the perceptual term's share of the total gradient; with --grad-total instead
 TOTAL_GRAD_NAMES, the norms of the total gradient; with --tail beside it also tail_grad_names(), those of the total gradient taken
-through the colour tail.  `python -m blindshadowremoval_amd.perceptual` is the same command under its earlier name.
+through the colour tail, and with --decoder beside both decoder_grad_names(), those of d_f taken on through the colour decoder.  `python -m blindshadowremoval_amd.perceptual` is the same command under its earlier name.
 """
 from __future__ import annotations
 
@@ -69,18 +70,28 @@ def tail_grad_names() -> List[str]:
     return [n + s for n in TAIL_NORM_NAMES for s in ("_l1", "_linf")]
 
 
+def decoder_grad_names() -> List[str]:
+    """`<name>_l1`, `<name>_linf` for generator_grad.DECODER_NORM_NAMES: d_x and the colour decoder's twelve variables."""
+    from .generator_grad import DECODER_NORM_NAMES
+    return [n + s for n in DECODER_NORM_NAMES for s in ("_l1", "_linf")]
+
+
 # ---- the two routes
 class HostRoute:
     """The objective over the three host statements, on numpy arrays."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None):
+    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False):
         self.disc_w, self.vgg_w, self.gen_w = disc_w, vgg_w, gen_w
+        self.decoder = decoder                 # --decoder: bring also copies the decoder's kept tensors
 
     def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None):
         """A step of folder_steps -> (img, gt, mask_sv, gs, con_rgb) as the methods take them, and f: a copy of the generator's, if one is given."""
         import torch
         torch.cuda.synchronize(im_d.device)
         f = None if generator is None else generator.probe("f").cpu().numpy()
+        if self.decoder:
+            self.acts = {k: generator.probe(k).cpu().numpy() for k in ("res5", "f1", "f2")}
+            self.acts["f"] = f
         return (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy()), f
 
     def losses(self, img, gt, mask_sv, gs, con_rgb, per_grad: bool = False):
@@ -101,15 +112,22 @@ class HostRoute:
     def tail_norms(self, gs, f, grad_con, grad_gs) -> List[float]:
         """tail_grad_names() of the two gradients taken through the colour tail at f [B,H,W,64]."""
         from .generator_grad import tail_grad, tail_norms
-        return [v for pair in tail_norms(tail_grad(self.gen_w, gs, f, grad_con, grad_gs)).values() for v in pair]
+        grads = tail_grad(self.gen_w, gs, f, grad_con, grad_gs)
+        self.d_f = grads["d_f"]
+        return [v for pair in tail_norms(grads).values() for v in pair]
+
+    def decoder_norms(self) -> List[float]:
+        """decoder_grad_names() of the last tail_norms' d_f taken through the colour decoder at the generator's kept res5, f1, f2, f."""
+        from .generator_grad import decoder_grad, decoder_norms
+        return [v for pair in decoder_norms(decoder_grad(self.gen_w, self.acts["res5"], self.d_f, acts=self.acts)).values() for v in pair]
 
 
 class DeviceRoute:
     """The objective over TrainLosses, Discriminators, Perceptual and ColourTail, on tensors of the device; f is read in the generator's workspace."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0):
+    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False):
         import torch
-        from . import ColourTail, Discriminators, Perceptual, TrainLosses
+        from . import ColourDecoder, ColourTail, Discriminators, Perceptual, TrainLosses
         self.dev = torch.device("cuda", device)
         self.three, self.gan, self.per = TrainLosses(device), Discriminators(device), Perceptual(device)
         self.gan.load_weights(disc_w)
@@ -117,6 +135,9 @@ class DeviceRoute:
         if gen_w is not None:
             self.tail = ColourTail(device)
             self.tail.load_weights(gen_w)
+            if decoder:
+                self.dec = ColourDecoder(device)
+                self.dec.load_weights(gen_w)
         self.three_weights = torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(self.dev)
         self.per_weight = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=self.dev)
 
@@ -140,8 +161,15 @@ class DeviceRoute:
 
     def tail_norms(self, gs, generator, grad_con, grad_gs) -> List[float]:
         from .generator_grad import tail_norms
-        grads = {k: t.cpu().numpy() for k, t in self.tail.backward(generator, gs, grad_con, grad_gs).items()}
+        res = self.tail.backward(generator, gs, grad_con, grad_gs)
+        self.d_f, self.generator = res["d_f"], generator
+        grads = {k: t.cpu().numpy() for k, t in res.items()}
         return [v for pair in tail_norms(grads).values() for v in pair]
+
+    def decoder_norms(self) -> List[float]:
+        from .generator_grad import decoder_norms
+        grads = {k: t.cpu().numpy() for k, t in self.dec.backward(self.generator, self.d_f).items()}
+        return [v for pair in decoder_norms(grads).values() for v in pair]
 
 
 def _norms(grad) -> List[float]:
@@ -234,12 +262,14 @@ def score_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: 
 
 
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False) -> Dict[str, float]:
+                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False, decoder: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the other weights come from the latest checkpoint under `ckpt`, from init_weights and
-    init_discriminator_weights without it.  `grad`, `grad_total` and `tail` add to each batch's line what --grad, --grad-total and --tail do."""
+    init_discriminator_weights without it.  `grad`, `grad_total`, `tail` and `decoder` add to each batch's line what --grad, --grad-total, --tail and --decoder do."""
     if tail and not grad_total:
         raise ValueError("perceptual: --tail goes with --grad-total")
+    if decoder and not tail:
+        raise ValueError("perceptual: --decoder goes with --grad-total --tail")
     vgg_w = load_vgg_weights(vgg)
     gen_w = None
     if tail:
@@ -247,7 +277,7 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         from .weights import init_weights
         gen_w = init_weights(1) if ckpt is None else load_generator_weights(latest_checkpoint(ckpt))
     disc_w = discriminator_weights(ckpt, "perceptual")
-    route = HostRoute(disc_w, vgg_w, gen_w) if host else DeviceRoute(disc_w, vgg_w, gen_w, device)
+    route = HostRoute(disc_w, vgg_w, gen_w, decoder=decoder) if host else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder)
 
     def step(*tensors):
         arrays, f = route.bring(*tensors)
@@ -258,6 +288,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         extras = list(zip(TOTAL_GRAD_NAMES, _norms(grad_con) + _norms(grad_gs)))
         if tail:
             extras += zip(tail_grad_names(), route.tail_norms(arrays[3], f, grad_con, grad_gs))
+        if decoder:
+            extras += zip(decoder_grad_names(), route.decoder_norms())
         return loss_record(three, gan, per), extras
 
     return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True)
@@ -275,10 +307,13 @@ def main(argv=None) -> int:
     ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
     ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
     ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
+    ap.add_argument("--decoder", action="store_true", help="with --grad-total --tail: also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients")
     a = ap.parse_args(argv)
     if a.tail and not a.grad_total:
         ap.error("--tail goes with --grad-total")
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail)
+    if a.decoder and not a.tail:
+        ap.error("--decoder goes with --grad-total --tail")
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

@@ -736,6 +736,64 @@ def unpack_clr_tail_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the generator's colour decoder backward (csrc/clr_up_grad_kernels.h): a blob of its own, no header, float32 ----
+CLR_DECODER_SHAPES = ((128, 261, 288), (96, 128, 128), (64, 96, 96))          # (O, C, C padded) of clr_up1, clr_up2, clr_up3
+CLR_DECODER_TSM_TEXT = "the colour decoder's device chain takes the GSC width only: clr_up1's kernel must be [3,3,128,261], got %s (TSM's 877 is covered by generator_grad.decoder_grad)"
+
+
+def clr_decoder_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the colour decoder's gradient blob, per layer i = 1, 2, 3:
+      k<i>       the UNFOLDED kernel [9 taps (a * 3 + b)][O][C], the variable's own order (d gamma is formed from it)
+      kf<i>      the data gradient's kernel inv[o] K [9][O][C padded]: clr_up1's 261 columns padded with zeros to 288
+      vecs<i>    [4][O]: the convolution's bias, inv, moving_mean, rstd (CLR_TAIL_VECS)
+    inv, rstd and the folded kernel are formed in float64 and rounded once."""
+    out, off = [], 0
+    for i, (o, c, cp) in enumerate(CLR_DECODER_SHAPES, 1):
+        for name, shape in (("k%d" % i, (9, o, c)), ("kf%d" % i, (9, o, cp)), ("vecs%d" % i, (4, o))):
+            out.append((name, off, shape))
+            off += int(np.prod(shape))
+    return out, off
+
+
+def clr_decoder_grad_record(weights: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """name -> float32 array of clr_decoder_grad_layout's shapes.  ValueError for any width but the GSC one."""
+    from .weights import BN_EPS
+    rec = {}
+    for i, (o, c, cp) in enumerate(CLR_DECODER_SHAPES, 1):
+        stem = "clr_up%d" % i
+        k = np.asarray(weights[stem + "/conv/kernel"], np.float64)
+        if k.shape != (3, 3, o, c):
+            raise ValueError(CLR_DECODER_TSM_TEXT % (k.shape,) if i == 1 else "%s/conv/kernel must be [3,3,%d,%d], got %s" % (stem, o, c, k.shape))
+        k = k.reshape(9, o, c)
+        rstd = 1.0 / np.sqrt(np.asarray(weights[stem + "/bnorm/moving_variance"], np.float64) + BN_EPS)
+        inv = np.asarray(weights[stem + "/bnorm/gamma"], np.float64) * rstd
+        kf = np.zeros((9, o, cp), np.float64)
+        kf[:, :, :c] = k * inv[None, :, None]
+        rec["k%d" % i], rec["kf%d" % i] = k, kf
+        rec["vecs%d" % i] = np.stack([np.asarray(weights[stem + "/conv/bias"], np.float64), inv, np.asarray(weights[stem + "/bnorm/moving_mean"], np.float64), rstd])
+    return {name: np.ascontiguousarray(a, np.float32) for name, a in rec.items()}
+
+
+def pack_clr_decoder_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (the colour decoder's 18 are read) -> the blob bsr_clr_decoder_grad takes (clr_decoder_grad_layout)."""
+    layout, total = clr_decoder_grad_layout()
+    rec = clr_decoder_grad_record(weights)
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        assert rec[name].shape == tuple(shape), name
+        blob[off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_clr_decoder_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_clr_decoder_grad: clr_decoder_grad_record's dict."""
+    layout, total = clr_decoder_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a colour decoder gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

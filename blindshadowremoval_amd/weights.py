@@ -125,6 +125,13 @@ def generator_tail_trainable_names() -> List[str]:
             and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_decoder_trainable_names(variant: str = "gsc") -> List[str]:
+    """The twelve trainable variables of the generator's colour decoder (clr_up1, clr_up2, clr_up3) in generator_variable_shapes' order,
+    467 424 floats for GSC: every kernel [3,3,out,in], bias, gamma and beta; moving_mean and moving_variance take no gradient."""
+    return [n for n in generator_variable_shapes(variant) if n.split("/", 1)[0] in ("clr_up1", "clr_up2", "clr_up3")
+            and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
 DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
 DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)

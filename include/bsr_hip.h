@@ -114,6 +114,10 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
  * the handle, for work ordered after that forward on its stream (bsr_clr_tail_grad reads it in place).  BSR_DTYPE_F32 GSC / TSM handles
  * only: BSR_ERR_STATE before any forward, for the 16-bit modes (f is fp16 there) and for RGB handles.  Added under ABI 8. */
 int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]);
+/* The colour decoder's tensors of the last forward in the handle's workspace: *x res_stack/5's output (261 channels, *x_cs floats between
+ * pixels) at [B,H/8,W/8], *f1 [B,H/4,W/4,128], *f2 [B,H/2,W/2,96], *f [B,H,W,64], all dense but x; shape4 = [B,H,W,64], the image's.  The
+ * same rules and error codes as bsr_last_f, GSC handles only (BSR_ERR_STATE for TSM handles too).  Added under ABI 8. */
+int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1, const float** f2, const float** f, int shape4[4]);
 
 /* Per-kernel-class device time (ms) of the last forward run with timing enabled; classes are indexed
  * 0: conv3x3 (+stride-2), 1: transposed 3x3 (all but class 6), 2: conv1x1, 3: attention, 4: conv7 (stem + heads), 5: glue,
@@ -349,6 +353,34 @@ int bsr_clr_tail_grad(int device, const void* d_blob, size_t blob_bytes, const f
 int bsr_debug_clr_tail_grad(int device, const void* d_blob, size_t blob_bytes, const float* gs, const float* f, int f_cs, const float* g_con,
                             const float* g_gs, int B, int H, int W, float* d_f, float* d_gs, float* grads, int keep, void* scratch, int stop_after,
                             void* stream);
+
+/* The next layer group of the generator's backward, training=False: the colour decoder clr_up1 (261 -> 128), clr_up2 (128 -> 96), clr_up3
+ * (96 -> 64), each Conv2DTranspose(3, stride 2, SAME) + BN + LeakyReLU (model.py:214-216, 264-266).  Stateless; all pointers are
+ * caller-owned device pointers.  H, W are the IMAGE's (H a multiple of 32, W of 256, the generator's own rule).  Inputs: d_blob,
+ * bsr_clr_decoder_grad_blob_bytes() bytes of pack.pack_clr_decoder_grad (GSC width only), 16-byte aligned; x [B,H/8,W/8,261], clr_up1's
+ * input, with x_cs >= 261 floats between pixels; f1 [B,H/4,W/4,128], f2 [B,H/2,W/2,96], f [B,H,W,64], the three layers' outputs as the
+ * forward kept them, with f1_cs, f2_cs, f_cs floats between pixels (multiples of 4, 16-byte aligned); d_f [B,H,W,64] dense = d loss / d f,
+ * never written.  Outputs: d_x [B,H/8,W/8,261] dense, and grads, bsr_clr_decoder_grad_floats() float32: the twelve variables of
+ * weights.generator_decoder_trainable_names() in that order, each dense in its own shape, variable `index` (0..11) at float offset
+ * bsr_clr_decoder_grad_var_offset(index); SIZE_MAX out of range.  Nine launches on `stream`, one after the other
+ * (csrc/clr_up_grad_kernels.h), no host synchronisation, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_clr_decoder_grad_scratch_bytes(B, H, W, keep) bytes, 256-byte aligned; every word read is written earlier in the same call.
+ * bsr_clr_decoder_grad_offset(B, H, W, map) is the byte offset of map 0 gz1 [B,H/4,W/4,128], 1 gz2 [B,H/2,W/2,96], 2 gz3 [B,H,W,64]
+ * (float32; gz3 is the scratch's last part, there and written only with keep != 0), 3..5 Wg of clr_up1..3 [9][O][C] float64, 6..8 the sums
+ * S of clr_up1..3 [O] float64; SIZE_MAX out of range.  bsr_clr_decoder_grad_partials(B, H, W, layer) is the number of partials P of layer
+ * 1..3's kernel gradient (0 for bad arguments).  A bad argument gives BSR_ERR_ARG with a message and nothing launched.
+ * bsr_debug_clr_decoder_grad stops after `stop_after` (0..9) launches.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_clr_decoder_grad_blob_bytes(void);
+size_t bsr_clr_decoder_grad_scratch_bytes(int B, int H, int W, int keep);
+size_t bsr_clr_decoder_grad_floats(void);
+size_t bsr_clr_decoder_grad_var_offset(int index);
+size_t bsr_clr_decoder_grad_offset(int B, int H, int W, int map);
+int bsr_clr_decoder_grad_partials(int B, int H, int W, int layer);
+int bsr_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2, int f2_cs,
+                         const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch, void* stream);
+int bsr_debug_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2,
+                               int f2_cs, const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch,
+                               int stop_after, void* stream);
 
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host

@@ -1,0 +1,160 @@
+"""Time of the generator's colour decoder backward on the device (bsr_clr_decoder_grad, csrc/clr_up_grad_kernels.h), one JSON line, also
+written to --out (profiles/clr_decoder_grad_bench.json).
+
+B items of S x S: the generator's forward on random images (weights from init_weights(1)) supplies res5, f1, f2, f, d_f comes from
+generator_grad.decoder_example_inputs(seed 0), and ColourDecoder.backward reads the four tensors in place.
+  device_ms_per_call     device events around --iters calls after a warm-up, divided by --iters; the window holds the allocation of
+                         the outputs, as a caller pays it; device_ms_per_call_repeats two more windows.
+  kernel_ms              the mean device time of each of the chain's launches, from the profiler's kernel statistics of a SEPARATE run:
+                             rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/clr_decoder_bench.py --calls-only
+                             python tools/clr_decoder_bench.py --stats DIR/<host>/<pid>_kernel_stats.csv
+                         null, with kernel_ms_unmeasured true, without --stats.  The --calls-only program also runs the generator's
+                         forward, so the same trace holds the forward's transposed-convolution launches (forward_convt_rows: every
+                         igemm_conv_kernel<3, 3, 1, true, ...> row of the statistics).
+  forward_layer_ms       the forward's own per-launch device events (Generator.get_launch_timing) of clr_up1, clr_up2, clr_up3: the
+                         launches of the same FLOP as each layer's two gradient launches.
+  rates                  with --stats: per matrix launch its GFLOP (2 x 9 x C_in x C_out per coarse pixel), TFLOP/s and share of the
+                         157.3 TFLOP/s fp32 matrix bound, beside the forward layer's TFLOP/s.
+  parity                 with --parity, per (H, W, B) of the device tests' sizes the worst scaled error of the thirteen outputs against
+                         generator_grad.decoder_grad on the device's own activations; e2e_measured is the largest, the figure the
+                         device test's bound is 4 x of.
+  build                  with --build FILE, the compiler's register and LDS figures of the new kernels (a JSON object, merged in as is).
+
+    python tools/clr_decoder_bench.py [--batch 32] [--size 256] [--iters 1000] [--parity] [--stats CSV] [--build FILE] [--out FILE] [--calls-only]
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MATRIX_FLOPS = 157.3e12
+# the launches in order (the mask launch runs only when maps are kept: not in a plain call)
+KERNELS = ("up_wgrad_kernel<3, true>", "up_dgrad_kernel<6, true, 8>", "up_wgrad_kernel<2, true>", "up_dgrad_kernel<8, true, 8>", "up_wgrad_kernel<3, false>",
+           "up_dgrad_kernel<6, false, 8>", "up_fold_kernel", "up_finish_kernel")
+LAYER_OF = ("clr_up3", "clr_up3", "clr_up2", "clr_up2", "clr_up1", "clr_up1")
+CHANNELS = {"clr_up1": (261, 128, 8), "clr_up2": (128, 96, 4), "clr_up3": (96, 64, 2)}       # C_in, C_out, the image's size over the coarse grid's
+FORWARD_PREFIX = "igemm_conv_kernel<3, 3, 1, true"
+PARITY_SIZES = ((32, 256, 1), (64, 256, 2), (96, 256, 3), (32, 512, 1))
+
+
+def kernel_stats(path, kernels):
+    found, rows = {}, []
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            for name in kernels:
+                if name in row["Name"]:
+                    found[name] = found.get(name, 0.0) + float(row["AverageNs"]) / 1e6
+            if FORWARD_PREFIX in row["Name"]:
+                rows.append({"name": row["Name"][:120], "calls": int(row["Calls"]), "average_ms": round(float(row["AverageNs"]) / 1e6, 5)})
+    return {k: round(found[k], 5) for k in kernels if k in found}, rows
+
+
+def parity():
+    """The device tests' cases: clr_decoder_grad_cases.case(H / 8, W / 8, B, 1), f1, f2, f from decoder_forward in float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import clr_decoder_grad_cases as cases
+    from blindshadowremoval_amd import ColourDecoder, generator_grad as host
+    out, dev = [], torch.device("cuda", 0)
+    runner = ColourDecoder(0)
+    for H, W, B in PARITY_SIZES:
+        w, x, d_f = cases.case(H // 8, W // 8, B, 1)
+        f1, f2, f = (np.ascontiguousarray(a, np.float32) for a in host.decoder_forward(w, x, np.float32))
+        runner.load_weights(w)
+        res = runner.decoder_grad(*[torch.from_numpy(a).to(dev) for a in (x, f1, f2, f, d_f)])
+        torch.cuda.synchronize()
+        got = {k: v.cpu().numpy() for k, v in res.items()}
+        worst = cases.worst_scaled_diff(got, host.decoder_grad(w, x, d_f, acts={"f1": f1, "f2": f2, "f": f}))
+        out.append({"H": H, "W": W, "batch": B, "scaled_error_device_acts": float("%.3g" % worst[0]), "at": worst[1]})
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--stats", default=None, help="the kernel statistics CSV of a profiled --calls-only run")
+    ap.add_argument("--calls-only", action="store_true", help="the warm-up and the calls, nothing else: the program to profile")
+    ap.add_argument("--parity", action="store_true", help="the end-to-end scaled errors over the device tests' sizes")
+    ap.add_argument("--build", default=None, help="a JSON file of the compiler's register and LDS figures, merged in under `build`")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clr_decoder_grad_bench.json"))
+    args = ap.parse_args()
+    import torch
+    from blindshadowremoval_amd import ColourDecoder, Generator, generator_grad as host, init_weights
+    if not torch.cuda.is_available():
+        raise SystemExit("clr_decoder_bench: no GPU; nothing is measured without one")
+    B, S = args.batch, args.size
+    dev = torch.device("cuda", 0)
+    weights = init_weights(1)
+    runner = ColourDecoder(0)
+    runner.load_weights(weights)
+    d_f = torch.from_numpy(host.decoder_example_inputs(S // 8, S // 8, B, seed=0)[1]).to(dev)
+
+    def timed(fn, iters):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            res = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters, res
+
+    gen = Generator(device=0)
+    gen.load_weights(weights)
+    im, uv = torch.rand((B, S, S, 3), device=dev), torch.rand((B, S, S, 3), device=dev)
+    forward = lambda: gen(im, uv, None, chuck=2, training=False)                      # noqa: E731
+    if args.calls_only:
+        timed(forward, 10)
+        timed(lambda: runner.backward(gen, d_f), min(args.iters, 20))
+        return
+    gen_ms = [timed(forward, 20)[0] for _ in range(3)]
+    gen.set_timing(True)
+    forward()
+    torch.cuda.synchronize()
+    layer_ms = {name: round(ms, 5) for name, ms, _ in gen.get_launch_timing() if name in CHANNELS}
+    gen.set_timing(False)
+    forward()
+    ms, res = timed(lambda: runner.backward(gen, d_f), args.iters)
+    spread = [timed(lambda: runner.backward(gen, d_f), args.iters)[0] for _ in range(2)]
+    gen.close()
+    kernel_ms, forward_rows = kernel_stats(args.stats, KERNELS) if args.stats else (None, None)
+    rates = None
+    if kernel_ms and all(k in kernel_ms for k in KERNELS):
+        rates = []
+        for kernel, layer in zip(KERNELS[:6], LAYER_OF):
+            cin, cout, div = CHANNELS[layer]
+            flop = 2 * 9 * cin * cout * B * (S // div) * (S // div)
+            t = flop / kernel_ms[kernel] / 1e9
+            rates.append({"launch": kernel, "layer": layer, "gflop": round(flop / 1e9, 2), "tflops": round(t, 1),
+                          "share_of_matrix_bound": round(t * 1e12 / MATRIX_FLOPS, 3),
+                          "forward_layer_tflops": round(flop / layer_ms[layer] / 1e9, 1) if layer in layer_ms else None})
+    flat = res[""]
+    line = {"batch": B, "size": S, "grad_l1": float(flat.abs().sum().cpu()), "grad_linf": float(flat.abs().max().cpu()),
+            "d_x_l1": float(res["d_x"].abs().sum().cpu()), "device_ms_per_call": round(ms, 4), "device_ms_per_call_repeats": [round(v, 4) for v in spread],
+            "generator_ms_per_call": [round(v, 3) for v in gen_ms], "forward_layer_ms": layer_ms, "kernel_ms": kernel_ms,
+            "kernel_ms_unmeasured": kernel_ms is None, "forward_convt_rows": forward_rows, "rates": rates,
+            "chain_kernel_ms": round(sum(kernel_ms[k] for k in KERNELS), 5) if rates else None, "stage_budget": 1e-5}
+    if args.parity:
+        line["parity"] = parity()
+        line["e2e_measured"] = max(p["scaled_error_device_acts"] for p in line["parity"])
+    if args.build:
+        with open(args.build) as f:
+            line["build"] = json.load(f)
+    text = json.dumps(line)
+    print(text)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
