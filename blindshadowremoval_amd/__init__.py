@@ -3,7 +3,7 @@
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
 __all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
-           "generator_variable_shapes", "init_weights"]
+           "NonLocalGrad",           "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name == "ColourDecoder":
         from .clr_decoder_gpu import ColourDecoder
         return ColourDecoder
+    if name == "NonLocalGrad":
+        from .nonlocal_grad_gpu import NonLocalGrad
+        return NonLocalGrad
     raise AttributeError(name)

@@ -112,6 +112,16 @@ SIGNATURES = {
     "bsr_debug_clr_decoder_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_i, c_v, c_i, c_v]),
     "bsr_last_decoder": (c_i, [c_v, ctypes.POINTER(c_v), ctypes.POINTER(c_i), ctypes.POINTER(c_v), ctypes.POINTER(c_v), ctypes.POINTER(c_v),
                                ctypes.POINTER(c_i * 4)]),
+    "bsr_last_block5": (c_i, [c_v, ctypes.POINTER(c_v), ctypes.POINTER(c_i), ctypes.POINTER(c_v), ctypes.POINTER(c_v), ctypes.POINTER(c_i),
+                              ctypes.POINTER(c_i * 4)]),
+    "bsr_nonlocal_grad_blob_bytes": (c_sz, []),
+    "bsr_nonlocal_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "bsr_nonlocal_grad_floats": (c_sz, []),
+    "bsr_nonlocal_grad_var_offset": (c_sz, [c_i]),
+    "bsr_nonlocal_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_nonlocal_grad_partials": (c_i, [c_i, c_i, c_i]),
+    "bsr_nonlocal_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_v]),
+    "bsr_debug_nonlocal_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_i, c_v]),
     "bsr_vgg_blob_bytes": (c_sz, []),
     "bsr_vgg_scratch_bytes": (c_sz, _BS),
     "bsr_vgg_act_offset": (c_sz, [c_i, c_i, c_i]),
@@ -123,9 +133,9 @@ SIGNATURES = {
     "bsr_debug_vgg_per_loss_grad": (c_i, [c_i] + _BLOBS + [c_v, c_v, c_v, c_i, c_i, c_v, c_v, c_v, c_v, c_i, c_v]),
 }
 
-# every symbol include/bsr_hip.h declares: all of the above but bsr_debug_attention_kv1, which tests/test_cabi.py's header scan (names
-# without digits) cannot see
-EXPORTS = tuple(name for name in SIGNATURES if name != "bsr_debug_attention_kv1")
+# every symbol include/bsr_hip.h declares: all of the above but bsr_debug_attention_kv1 and bsr_last_block5, which tests/test_cabi.py's
+# header scan (names without digits) cannot see
+EXPORTS = tuple(name for name in SIGNATURES if name not in ("bsr_debug_attention_kv1", "bsr_last_block5"))
 
 
 def load() -> ctypes.CDLL:

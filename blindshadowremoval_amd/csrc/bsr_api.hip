@@ -43,6 +43,7 @@
 #include "disc_wgrad_kernels.h"
 #include "clr_tail_grad_kernels.h"
 #include "clr_up_grad_kernels.h"
+#include "nonlocal_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1698,6 +1699,62 @@ int bsr_debug_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes
                           scratch, stop_after, stream);
 }
 
+size_t bsr_nonlocal_grad_blob_bytes(void) { return bsr::nl_blob_off(6) * sizeof(float); }
+
+size_t bsr_nonlocal_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::nl_plan(B, h, w).total : 0; }
+
+size_t bsr_nonlocal_grad_floats(void) { return bsr::nl_var_offset(bsr::kNlVars); }
+
+size_t bsr_nonlocal_grad_var_offset(int index) { return index < 0 || index >= bsr::kNlVars ? SIZE_MAX : bsr::nl_var_offset(index); }
+
+size_t bsr_nonlocal_grad_offset(int B, int h, int w, int map) {
+  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kNlMaps) return SIZE_MAX;
+  return bsr::nl_plan(B, h, w).map[map];
+}
+
+int bsr_nonlocal_grad_partials(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::nl_plan(B, h, w).P : 0; }
+
+namespace {
+
+int nonlocal_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs,
+                  const float* out, int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch,
+                  int stop_after, void* stream) {
+  const std::string n(name);
+  for (const void* p : {d_blob, (const void*)y3x, (const void*)xin, (const void*)out, (const void*)d_out, (const void*)d_y3, (const void*)d_skip,
+                        (const void*)grads, (const void*)scratch})
+    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
+  if (!bsr::nl_size_ok(B, h, w))
+    return fail(BSR_ERR_ARG, n + ": B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 tokens in all");
+  if (blob_bytes != bsr_nonlocal_grad_blob_bytes())
+    return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_nonlocal_grad_blob_bytes() (pack.pack_nonlocal_grad; the GSC width 261 only, not TSM's 877)");
+  if (y3x_cs < 257 || xin_cs < 261 || out_cs < 261) return fail(BSR_ERR_ARG, n + ": y3x_cs must be at least 257, xin_cs and out_cs at least 261");
+  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0) return fail(BSR_ERR_ARG, n + ": d_blob must be 16-byte aligned");
+  for (const void* p : {(const void*)y3x, (const void*)xin, (const void*)out, (const void*)d_out, (const void*)d_y3, (const void*)d_skip, (const void*)grads})
+    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": y3x, xin, out, d_out, d_y3, d_skip and grads must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
+  if (stop_after < 0 || stop_after > bsr::kNlLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..12");
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  HIP_TRY(bsr::launch_nonlocal_grad(static_cast<const float*>(d_blob), y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads, scratch,
+                                    stop_after, static_cast<hipStream_t>(stream)));
+  return BSR_OK;
+}
+
+}  // namespace
+
+int bsr_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs, const float* out,
+                      int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, void* stream) {
+  return nonlocal_grad("bsr_nonlocal_grad", device, d_blob, blob_bytes, y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads, scratch,
+                       bsr::kNlLaunches, stream);
+}
+
+int bsr_debug_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs, const float* out,
+                            int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, int stop_after,
+                            void* stream) {
+  return nonlocal_grad("bsr_debug_nonlocal_grad", device, d_blob, blob_bytes, y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads,
+                       scratch, stop_after, stream);
+}
+
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
 
 size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
@@ -2092,6 +2149,23 @@ int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1
   *f2 = h->ws + h->plan.f2;
   *f = h->ws + h->plan.cf;
   shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
+  return BSR_OK;
+}
+
+int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]) {
+  if (h == nullptr || y3x == nullptr || y3x_cs == nullptr || xin == nullptr || out == nullptr || x_cs == nullptr || shape4 == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_last_block5: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_block5: an RGB handle has no res_stack/5");
+  if (h->var.tsm) return fail(BSR_ERR_STATE, "bsr_last_block5: the non-local block's backward takes the GSC width 261 only, not a TSM handle's 877");
+  if (h->dtype != BSR_DTYPE_F32)
+    return fail(BSR_ERR_STATE, "bsr_last_block5: the block's tensors are kept for the backward in BSR_DTYPE_F32 handles only, not in the 16-bit modes");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_block5: no forward has run on this handle");
+  *y3x = h->ws + h->plan.y3[5];
+  *y3x_cs = h->var.cs_y3x;
+  *xin = h->ws + h->plan.r[4];
+  *out = h->ws + h->plan.r[5];
+  *x_cs = h->var.cs_h;
+  shape4[0] = h->B; shape4[1] = h->H / 8; shape4[2] = h->W / 8; shape4[3] = 261;
   return BSR_OK;
 }
 

@@ -3,7 +3,11 @@ tail (model.py:217-219, 267-269): clr_conv1 (3x3, cat[gs, f] 65 -> 16, BN, Leaky
 clr_conv3 (1x1, 16 -> 3).  `tail_grad` writes the arithmetic out in float64 from the float32 variables; csrc/clr_tail_grad_kernels.h
 is held to it (clr_tail_gpu.ColourTail).  Below it the colour decoder (model.py:214-216, 264-266): clr_up1, clr_up2, clr_up3, each
 Conv2DTranspose(3, stride 2, SAME), BN, LeakyReLU; `decoder_grad` is its statement, any input width (261 for GSC, 877 for TSM), and
-csrc/clr_up_grad_kernels.h is held to it (clr_decoder_gpu.ColourDecoder)."""
+csrc/clr_up_grad_kernels.h is held to it (clr_decoder_gpu.ColourDecoder).  Below that the upper half of res_stack/5 (model.py:6-61, 102-113): the
+NonLocalBlock — theta, phi, g (1x1, 257 -> 128), softmax(theta phi^T) g, w (1x1, 128 -> 257), BN, z = y3 + w_y — then the block's zero-padded
+skip and relu3; `nonlocal_grad` is its statement, from the gradient at the block's output to the gradient at bnorm3's output y3, the gradient
+the skip carries to the block's input and the ten variables of the non-local block, any input width; csrc/nonlocal_grad_kernels.h is held to
+it (nonlocal_grad_gpu.NonLocalGrad)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -11,12 +15,15 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
-from .weights import BN_EPS, LRELU_ALPHA, generator_decoder_trainable_names, generator_tail_trainable_names
+from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_decoder_trainable_names, generator_nonlocal_trainable_names,
+                      generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
 DECODER_LAYERS = ("clr_up1", "clr_up2", "clr_up3")
 DECODER_NORM_NAMES = ("d_x",) + tuple(generator_decoder_trainable_names())
+NONLOCAL_NORM_NAMES = ("d_y3", "d_skip") + tuple(generator_nonlocal_trainable_names())
+NONLOCAL_MAPS = ("gz", "dA", "D", "d_theta", "d_phi", "d_g")
 
 
 def bn_vectors(weights: Dict[str, np.ndarray], stem: str, dtype=np.float64):
@@ -290,3 +297,125 @@ def decoder_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
     x = np.where(x >= 0, x, np.float32(LRELU_ALPHA) * x).astype(np.float32)
     d_f = (rng.standard_normal((B, 8 * h, 8 * w, 64)) / (B * h * w * 64)).astype(np.float32)
     return x, d_f
+
+
+# ---- the upper half of res_stack/<block>: the non-local block, the skip and relu3
+def _nl_stem(block: int) -> str:
+    return "res_stack/%d/non_local/" % block
+
+
+def nonlocal_bn_vectors(weights: Dict[str, np.ndarray], block: int = 5, dtype=np.float64):
+    """(w's bias, inv, moving_mean, rstd, gamma, beta) of res_stack/<block>/non_local in `dtype`."""
+    T = dtype
+    st = _nl_stem(block)
+    gamma, beta, mean, var = (np.asarray(weights[st + "bnorm/" + p], T) for p in ("gamma", "beta", "moving_mean", "moving_variance"))
+    rstd = T(1) / np.sqrt(var + T(BN_EPS))
+    return np.asarray(weights[st + "w/bias"], T), gamma * rstd, mean, rstd, gamma, beta
+
+
+def nonlocal_forward(weights: Dict[str, np.ndarray], y3, xin, block: int = 5, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """y3 [B,h,w,257] (bnorm3's output), xin [B,h,w,C] (the block's input, C >= 257) -> dict(theta, phi, g, A [B,T,128], c [B,T,257],
+    z [B,h,w,257], out [B,h,w,C]) in `dtype`, T = h w tokens per image, X = y3 as [B,T,257]:
+      theta = X Wt + bt, phi = X Wp + bp, g = X Wg + bg;  S = theta phi^T, P = softmax_rows(S) per image with the row maximum subtracted;
+      A = P g;  c = A Ww + bw;  z = X + ((c - mean) rstd gamma + beta);  out = lrelu_0.3(pad_C(z) + xin)."""
+    T = dtype
+    st = _nl_stem(block)
+    y3 = np.asarray(y3, T)
+    xin = np.asarray(xin, T)
+    B, h, w, n = y3.shape
+    C = xin.shape[3]
+    X = y3.reshape(B, h * w, n)
+    proj = {}
+    for name in ("theta", "phi", "g"):
+        proj[name] = X @ np.asarray(weights[st + name + "/kernel"], T)[0, 0] + np.asarray(weights[st + name + "/bias"], T)
+    S = proj["theta"] @ np.transpose(proj["phi"], (0, 2, 1))
+    E = np.exp(S - S.max(axis=2, keepdims=True))
+    P = E / E.sum(axis=2, keepdims=True)
+    A = P @ proj["g"]
+    bw, _, mean, rstd, gamma, beta = nonlocal_bn_vectors(weights, block, T)
+    c = A @ np.asarray(weights[st + "w/kernel"], T)[0, 0] + bw
+    z = (X + ((c - mean) * rstd * gamma + beta)).reshape(B, h, w, n)
+    s = xin.copy()
+    s[..., :n] += z
+    out = dict(proj)
+    out.update({"S": S, "P": P, "A": A, "c": c, "z": z, "pre": s, "out": _lrelu(s)})
+    return out
+
+
+def nonlocal_grad(weights: Dict[str, np.ndarray], y3, xin, d_out, block: int = 5, acts: Optional[Dict[str, np.ndarray]] = None,
+                  dtype=np.float64) -> Dict[str, np.ndarray]:
+    """The gradient d_out [B,h,w,C] at res_stack/<block>'s output -> dict(the ten variables of
+    weights.generator_nonlocal_trainable_names(block) in their own shapes, `d_y3` [B,h,w,257] at bnorm3's output, `d_skip` [B,h,w,C] the
+    gradient the skip carries to the block's input, the stage maps `gz` [B,h,w,C], `dA`, `d_theta`, `d_phi`, `d_g` [B,T,128], `D` [B,T],
+    and `out`, `A` as used), float64 from the float32 variables (`dtype` float32 runs the same arithmetic in float32: the error model of
+    the device's hard-softmax bound).  In this order:
+      gz = leaky_grad(d_out, out) (an activation of exactly +-0 takes the slope);  d_skip = gz;  dz = gz[..., :257];  Sz = sum dz
+      d beta = Sz;  dc = dz inv;  d bw = inv Sz;  Wgd[k, n] = sum A[k] dz[n];  d Ww = Wgd inv[n]
+      d gamma = ((KW + bw Sz) - mean Sz) rstd with KW[n] = sum_k Ww[k, n] Wgd[k, n]      (no second pass over c)
+      dA = dc Ww^T;  D[i] = dA_i . A_i;  dP = dA g^T;  dS = P o (dP - D[:, None])
+      d_g = P^T dA;  d_theta = dS phi;  d_phi = dS^T theta
+      for each of theta, phi, g:  d W = X^T d_proj, d b = sum d_proj
+      d_y3 = dz + d_theta Wt^T + d_phi Wp^T + d_g Wg^T
+    With `acts` given (a dict with `out`, and optionally `A`, for example the device's), the mask and w's input are read from it."""
+    T = dtype
+    st = _nl_stem(block)
+    fw = nonlocal_forward(weights, y3, xin, block, T)
+    out_a = np.asarray(acts["out"], T) if acts is not None else fw["out"]
+    A = np.asarray(acts["A"], T).reshape(fw["A"].shape) if acts is not None and "A" in acts else fw["A"]
+    X = np.asarray(y3, T)
+    B, h, w, n = X.shape
+    X = X.reshape(B, h * w, n)
+    Wt, Wp, Wg, Ww = (np.asarray(weights[st + k + "/kernel"], T)[0, 0] for k in ("theta", "phi", "g", "w"))
+    bw, inv, mean, rstd, _, _ = nonlocal_bn_vectors(weights, block, T)
+    gz = leaky_grad(np.asarray(d_out, T), out_a).astype(T)
+    res: Dict[str, np.ndarray] = {"out": out_a, "A": A, "gz": gz, "d_skip": gz.copy()}
+    dz = gz[..., :n].reshape(B, h * w, n)
+    Sz = dz.sum(axis=(0, 1))
+    Wgd = np.tensordot(A, dz, axes=([0, 1], [0, 1]))
+    KW = (Ww * Wgd).sum(axis=0)
+    res[st + "bnorm/beta"] = Sz
+    res[st + "w/bias"] = inv * Sz
+    res[st + "w/kernel"] = (Wgd * inv).reshape(1, 1, *Ww.shape)
+    res[st + "bnorm/gamma"] = ((KW + bw * Sz) - mean * Sz) * rstd
+    dA = (dz * inv) @ Ww.T
+    D = (dA * A).sum(axis=2)
+    P = fw["P"]
+    dS = P * (dA @ np.transpose(fw["g"], (0, 2, 1)) - D[:, :, None])
+    d = {"g": np.transpose(P, (0, 2, 1)) @ dA, "theta": dS @ fw["phi"], "phi": np.transpose(dS, (0, 2, 1)) @ fw["theta"]}
+    res.update({"dA": dA, "D": D, "d_theta": d["theta"], "d_phi": d["phi"], "d_g": d["g"]})
+    d_y3 = dz.copy()
+    for name, Wk in (("theta", Wt), ("phi", Wp), ("g", Wg)):
+        res[st + name + "/kernel"] = np.tensordot(X, d[name], axes=([0, 1], [0, 1])).reshape(1, 1, *Wk.shape)
+        res[st + name + "/bias"] = d[name].sum(axis=(0, 1))
+        d_y3 = d_y3 + d[name] @ Wk.T
+    res["d_y3"] = d_y3.reshape(B, h, w, n)
+    return res
+
+
+def nonlocal_objective_f64(weights: Dict[str, np.ndarray], y3, xin, d_out, block: int = 5, masks: Optional[list] = None, dtype=np.float64):
+    """<d_out, out> in `dtype` with no float32 rounding anywhere: the scalar whose gradient nonlocal_grad states.  A list given as `masks`
+    receives relu3's mask (pad(z) + xin > 0)."""
+    fw = nonlocal_forward(weights, y3, xin, block, dtype)
+    if masks is not None:
+        masks.append(fw["pre"] > 0)
+    return (np.asarray(d_out, dtype) * fw["out"]).sum()
+
+
+def nonlocal_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
+    """name -> (L1, L-infinity) of `d_y3`, `d_skip` and each of the ten variable gradients (NONLOCAL_NORM_NAMES)."""
+    out = {}
+    for name in NONLOCAL_NORM_NAMES:
+        m = np.abs(np.asarray(grads[name], np.float64))
+        out[name] = (float(m.sum()), float(m.max()))
+    return out
+
+
+def nonlocal_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
+    """Seeded (y3 [B,h,w,257], xin [B,h,w,C], d_out [B,h,w,C]) float32 at a coarse grid: y3 like a BatchNormalization output, xin like a
+    LeakyReLU output."""
+    rng = np.random.default_rng(3000 + seed)
+    y3 = (0.25 * rng.standard_normal((B, h, w, RES_CH))).astype(np.float32)
+    xin = rng.standard_normal((B, h, w, C)).astype(np.float32)
+    xin = np.where(xin >= 0, xin, np.float32(LRELU_ALPHA) * xin).astype(np.float32)
+    d_out = (rng.standard_normal((B, h, w, C)) / (B * h * w * C)).astype(np.float32)
+    return y3, xin, d_out

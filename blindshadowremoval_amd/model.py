@@ -236,6 +236,18 @@ class Generator:
                                               ctypes.byref(ptrs[3]), ctypes.byref(shape)), "bsr_last_decoder")
         return tuple(int(p.value) for p in ptrs), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
 
+    def last_block5(self) -> Tuple[Tuple[int, int, int], Tuple[int, int, int], Tuple[int, int, int, int]]:
+        """((y3x, xin, out) device addresses, their floats between pixels, (B, H/8, W/8, 261)) of what the last forward kept of res_stack/5
+        in the handle's workspace (bsr_last_block5): y3x = bnorm3's output + pad(xin) (257 channels read), xin the block's input, out its
+        output.  No copy; valid until the next forward on this generator.  fp32 GSC generators only: RuntimeError before any forward, for
+        the 16-bit modes and for TSM weights."""
+        self._require_weights()
+        ptrs = [ctypes.c_void_p() for _ in range(3)]
+        y_cs, x_cs, shape = ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_block5(self._handle, ctypes.byref(ptrs[0]), ctypes.byref(y_cs), ctypes.byref(ptrs[1]), ctypes.byref(ptrs[2]),
+                                             ctypes.byref(x_cs), ctypes.byref(shape)), "bsr_last_block5")
+        return tuple(int(p.value) for p in ptrs), (int(y_cs.value), int(x_cs.value), int(x_cs.value)), (shape[0], shape[1], shape[2], shape[3])
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

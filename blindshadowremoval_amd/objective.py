@@ -76,13 +76,20 @@ def decoder_grad_names() -> List[str]:
     return [n + s for n in DECODER_NORM_NAMES for s in ("_l1", "_linf")]
 
 
+def nonlocal_grad_names() -> List[str]:
+    """`<name>_l1`, `<name>_linf` for generator_grad.NONLOCAL_NORM_NAMES: d_y3, d_skip and the ten variables of res_stack/5's non-local block."""
+    from .generator_grad import NONLOCAL_NORM_NAMES
+    return [n + s for n in NONLOCAL_NORM_NAMES for s in ("_l1", "_linf")]
+
+
 # ---- the two routes
 class HostRoute:
     """The objective over the three host statements, on numpy arrays."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False):
         self.disc_w, self.vgg_w, self.gen_w = disc_w, vgg_w, gen_w
         self.decoder = decoder                 # --decoder: bring also copies the decoder's kept tensors
+        self.nonlocal_ = nonlocal_             # --nonlocal: and res_stack/5's
 
     def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None):
         """A step of folder_steps -> (img, gt, mask_sv, gs, con_rgb) as the methods take them, and f: a copy of the generator's, if one is given."""
@@ -92,6 +99,8 @@ class HostRoute:
         if self.decoder:
             self.acts = {k: generator.probe(k).cpu().numpy() for k in ("res5", "f1", "f2")}
             self.acts["f"] = f
+        if self.nonlocal_:
+            self.block5 = {k: generator.probe(k).cpu().numpy() for k in ("y3x5", "res4")}
         return (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy()), f
 
     def losses(self, img, gt, mask_sv, gs, con_rgb, per_grad: bool = False):
@@ -119,15 +128,25 @@ class HostRoute:
     def decoder_norms(self) -> List[float]:
         """decoder_grad_names() of the last tail_norms' d_f taken through the colour decoder at the generator's kept res5, f1, f2, f."""
         from .generator_grad import decoder_grad, decoder_norms
-        return [v for pair in decoder_norms(decoder_grad(self.gen_w, self.acts["res5"], self.d_f, acts=self.acts)).values() for v in pair]
+        grads = decoder_grad(self.gen_w, self.acts["res5"], self.d_f, acts=self.acts)
+        self.d_x = grads["d_x"]
+        return [v for pair in decoder_norms(grads).values() for v in pair]
+
+    def nonlocal_norms(self) -> List[float]:
+        """nonlocal_grad_names() of the last decoder_norms' d_x taken through res_stack/5's upper half at the generator's kept y3x5, res4
+        and res5: y3 = y3x5 - pad(res4) in float32, as the device chain forms it."""
+        from .generator_grad import nonlocal_grad, nonlocal_norms
+        xin = self.block5["res4"]
+        y3 = (self.block5["y3x5"][..., :257] - xin[..., :257]).astype(f32)
+        return [v for pair in nonlocal_norms(nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]})).values() for v in pair]
 
 
 class DeviceRoute:
     """The objective over TrainLosses, Discriminators, Perceptual and ColourTail, on tensors of the device; f is read in the generator's workspace."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False):
         import torch
-        from . import ColourDecoder, ColourTail, Discriminators, Perceptual, TrainLosses
+        from . import ColourDecoder, ColourTail, Discriminators, NonLocalGrad, Perceptual, TrainLosses
         self.dev = torch.device("cuda", device)
         self.three, self.gan, self.per = TrainLosses(device), Discriminators(device), Perceptual(device)
         self.gan.load_weights(disc_w)
@@ -138,6 +157,9 @@ class DeviceRoute:
             if decoder:
                 self.dec = ColourDecoder(device)
                 self.dec.load_weights(gen_w)
+            if nonlocal_:
+                self.nl = NonLocalGrad(device)
+                self.nl.load_weights(gen_w)
         self.three_weights = torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(self.dev)
         self.per_weight = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=self.dev)
 
@@ -168,8 +190,15 @@ class DeviceRoute:
 
     def decoder_norms(self) -> List[float]:
         from .generator_grad import decoder_norms
-        grads = {k: t.cpu().numpy() for k, t in self.dec.backward(self.generator, self.d_f).items()}
+        res = self.dec.backward(self.generator, self.d_f)
+        self.d_x = res["d_x"]
+        grads = {k: t.cpu().numpy() for k, t in res.items()}
         return [v for pair in decoder_norms(grads).values() for v in pair]
+
+    def nonlocal_norms(self) -> List[float]:
+        from .generator_grad import nonlocal_norms
+        grads = {k: t.cpu().numpy() for k, t in self.nl.backward(self.generator, self.d_x).items()}
+        return [v for pair in nonlocal_norms(grads).values() for v in pair]
 
 
 def _norms(grad) -> List[float]:
@@ -262,14 +291,18 @@ def score_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: 
 
 
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
-                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False, decoder: bool = False) -> Dict[str, float]:
+                 quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False, decoder: bool = False,
+                 nonlocal_: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the other weights come from the latest checkpoint under `ckpt`, from init_weights and
-    init_discriminator_weights without it.  `grad`, `grad_total`, `tail` and `decoder` add to each batch's line what --grad, --grad-total, --tail and --decoder do."""
+    init_discriminator_weights without it.  `grad`, `grad_total`, `tail`, `decoder` and `nonlocal_` add to each batch's line what --grad, --grad-total, --tail, --decoder and
+    --nonlocal do."""
     if tail and not grad_total:
         raise ValueError("perceptual: --tail goes with --grad-total")
     if decoder and not tail:
         raise ValueError("perceptual: --decoder goes with --grad-total --tail")
+    if nonlocal_ and not decoder:
+        raise ValueError("perceptual: --nonlocal goes with --grad-total --tail --decoder")
     vgg_w = load_vgg_weights(vgg)
     gen_w = None
     if tail:
@@ -277,7 +310,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         from .weights import init_weights
         gen_w = init_weights(1) if ckpt is None else load_generator_weights(latest_checkpoint(ckpt))
     disc_w = discriminator_weights(ckpt, "perceptual")
-    route = HostRoute(disc_w, vgg_w, gen_w, decoder=decoder) if host else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder)
+    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_) if host
+             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_))
 
     def step(*tensors):
         arrays, f = route.bring(*tensors)
@@ -290,6 +324,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
             extras += zip(tail_grad_names(), route.tail_norms(arrays[3], f, grad_con, grad_gs))
         if decoder:
             extras += zip(decoder_grad_names(), route.decoder_norms())
+        if nonlocal_:
+            extras += zip(nonlocal_grad_names(), route.nonlocal_norms())
         return loss_record(three, gan, per), extras
 
     return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True)
@@ -308,12 +344,16 @@ def main(argv=None) -> int:
     ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
     ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
     ap.add_argument("--decoder", action="store_true", help="with --grad-total --tail: also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients")
+    ap.add_argument("--nonlocal", dest="nonlocal_", action="store_true", help="with --grad-total --tail --decoder: also the norms of d g_total_loss / d y3 at res_stack/5's bnorm3 output, of what the block's skip carries to its input, and of the non-local block's ten variable gradients")
     a = ap.parse_args(argv)
     if a.tail and not a.grad_total:
         ap.error("--tail goes with --grad-total")
     if a.decoder and not a.tail:
         ap.error("--decoder goes with --grad-total --tail")
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder)
+    if a.nonlocal_ and not a.decoder:
+        ap.error("--nonlocal goes with --grad-total --tail --decoder")
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder,
+                         nonlocal_=a.nonlocal_)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

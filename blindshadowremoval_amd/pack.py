@@ -794,6 +794,78 @@ def unpack_clr_decoder_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the generator's non-local block backward (csrc/nonlocal_grad_kernels.h): a blob of its own, no header, float32 ----
+NONLOCAL_TSM_TEXT = "the non-local block's device chain takes the GSC width only (TSM's 877 is covered by generator_grad.nonlocal_grad)"
+NONLOCAL_CP = 272            # 257 channels padded to the GEMMs' 16-channel steps
+
+
+def nonlocal_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the non-local block's gradient blob:
+      wqkv   [272][384]  the FORWARD image [Wt | Wp | Wg], rows = y3's channels (257..271 zero)
+      bqkv   [384]       [bt | bp | bg]
+      wwf    [272][128]  the TRANSPOSED, BN-folded image of w for the data gradient: wwf[n][k] = inv[n] Ww[k][n] (rows 257..271 zero)
+      wqkvT  [384][384]  the TRANSPOSED image of [Wt | Wp | Wg] for the data gradient: wqkvT[j][c] = wqkv[c][j] (columns 257.. zero)
+      ww     [128][257]  w's kernel in the variable's own order (d gamma is formed from it)
+      vecs   [4][257]    w's bias, inv, moving_mean, rstd (CLR_TAIL_VECS)
+    inv, rstd and the folded image are formed in float64 and rounded once."""
+    out, off = [], 0
+    for name, shape in (("wqkv", (NONLOCAL_CP, 384)), ("bqkv", (384,)), ("wwf", (NONLOCAL_CP, 128)), ("wqkvT", (384, 384)), ("ww", (128, 257)),
+                        ("vecs", (4, 257))):
+        out.append((name, off, shape))
+        off += int(np.prod(shape))
+    return out, off
+
+
+def nonlocal_grad_record(weights: Dict[str, np.ndarray], block: int = 5) -> Dict[str, np.ndarray]:
+    """name -> float32 array of nonlocal_grad_layout's shapes.  ValueError for shapes other than the GSC generator's."""
+    from .weights import BN_EPS
+    st = "res_stack/%d/non_local/" % block
+    k = {}
+    for name in ("theta", "phi", "g"):
+        k[name] = np.asarray(weights[st + name + "/kernel"], np.float64)
+        if k[name].shape != (1, 1, 257, 128):
+            raise ValueError("%s%s/kernel must be [1,1,257,128], got %s" % (st, name, k[name].shape))
+    ww = np.asarray(weights[st + "w/kernel"], np.float64)
+    if ww.shape != (1, 1, 128, 257):
+        raise ValueError("%sw/kernel must be [1,1,128,257], got %s" % (st, ww.shape))
+    ww = ww[0, 0]
+    rstd = 1.0 / np.sqrt(np.asarray(weights[st + "bnorm/moving_variance"], np.float64) + BN_EPS)
+    inv = np.asarray(weights[st + "bnorm/gamma"], np.float64) * rstd
+    wqkv = np.zeros((NONLOCAL_CP, 384), np.float64)
+    wqkv[:257] = np.concatenate([k[n][0, 0] for n in ("theta", "phi", "g")], axis=1)
+    wwf = np.zeros((NONLOCAL_CP, 128), np.float64)
+    wwf[:257] = (ww * inv[None, :]).T
+    wqkvT = np.zeros((384, 384), np.float64)
+    wqkvT[:, :NONLOCAL_CP] = wqkv.T
+    rec = {"wqkv": wqkv, "bqkv": np.concatenate([np.asarray(weights[st + n + "/bias"], np.float64) for n in ("theta", "phi", "g")]), "wwf": wwf,
+           "wqkvT": wqkvT, "ww": ww,
+           "vecs": np.stack([np.asarray(weights[st + "w/bias"], np.float64), inv, np.asarray(weights[st + "bnorm/moving_mean"], np.float64), rstd])}
+    return {name: np.ascontiguousarray(a, np.float32) for name, a in rec.items()}
+
+
+def pack_nonlocal_grad(weights: Dict[str, np.ndarray], block: int = 5) -> bytes:
+    """The generator's variables (res_stack/<block>/non_local's 12 are read) -> the blob bsr_nonlocal_grad takes (nonlocal_grad_layout).
+    ValueError for TSM weights: the chain's skip is 261 wide."""
+    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, 261, 128):
+        raise ValueError(NONLOCAL_TSM_TEXT)
+    layout, total = nonlocal_grad_layout()
+    rec = nonlocal_grad_record(weights, block)
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        assert rec[name].shape == tuple(shape), name
+        blob[off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_nonlocal_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_nonlocal_grad: nonlocal_grad_record's dict."""
+    layout, total = nonlocal_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a non-local gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

@@ -132,6 +132,13 @@ def generator_decoder_trainable_names(variant: str = "gsc") -> List[str]:
             and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_nonlocal_trainable_names(block: int = 5, variant: str = "gsc") -> List[str]:
+    """The ten trainable variables of res_stack/<block>'s NonLocalBlock in generator_variable_shapes' order, 132 739 floats: the kernel
+    and bias of g, phi, theta and w, and bnorm's gamma and beta; moving_mean and moving_variance take no gradient."""
+    stem = "res_stack/%d/non_local/" % block
+    return [n for n in generator_variable_shapes(variant) if n.startswith(stem) and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
 DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
 DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)

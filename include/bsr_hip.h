@@ -118,6 +118,11 @@ int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]);
  * pixels) at [B,H/8,W/8], *f1 [B,H/4,W/4,128], *f2 [B,H/2,W/2,96], *f [B,H,W,64], all dense but x; shape4 = [B,H,W,64], the image's.  The
  * same rules and error codes as bsr_last_f, GSC handles only (BSR_ERR_STATE for TSM handles too).  Added under ABI 8. */
 int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1, const float** f2, const float** f, int shape4[4]);
+/* What the last forward kept of res_stack/5 in the handle's workspace, at [B,H/8,W/8]: *y3x = y3 + pad(xin) (bnorm3's output plus the
+ * block's input; *y3x_cs floats between pixels, the first 257 channels are read), *xin the block's input (res_stack/4's output) and *out
+ * the block's output, 261 channels each with *x_cs floats between pixels; shape4 = [B,H/8,W/8,261].  Each lies in a slot of its own that
+ * nothing after the block overwrites.  The same rules and error codes as bsr_last_decoder.  Added under ABI 8. */
+int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]);
 
 /* Per-kernel-class device time (ms) of the last forward run with timing enabled; classes are indexed
  * 0: conv3x3 (+stride-2), 1: transposed 3x3 (all but class 6), 2: conv1x1, 3: attention, 4: conv7 (stem + heads), 5: glue,
@@ -381,6 +386,34 @@ int bsr_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, cons
 int bsr_debug_clr_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2,
                                int f2_cs, const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch,
                                int stop_after, void* stream);
+
+/* The next layer group of the generator's backward, training=False: the upper half of res_stack/5 — relu3, the block's zero-padded skip
+ * and the NonLocalBlock (model.py:6-61, 102-113).  Stateless; all pointers are caller-owned device pointers.  h, w are the 1/8-resolution
+ * GRID's (h a multiple of 4, w of 32: the generator's rule there; T = h w tokens per image).  Inputs: d_blob,
+ * bsr_nonlocal_grad_blob_bytes() bytes of pack.pack_nonlocal_grad (GSC width only), 16-byte aligned; y3x = y3 + pad(xin), xin, out as
+ * bsr_last_block5 hands them out (or dense tensors), with y3x_cs >= 257, xin_cs, out_cs >= 261 floats between pixels; d_out [B,h,w,261]
+ * dense = d loss / d out, never written.  Outputs: d_y3 [B,h,w,257] dense (at bnorm3's output), d_skip [B,h,w,261] dense (what the skip
+ * carries to the block's input), and grads, bsr_nonlocal_grad_floats() float32: the ten variables of
+ * weights.generator_nonlocal_trainable_names() in that order, each dense in its own shape, variable `index` (0..9) at float offset
+ * bsr_nonlocal_grad_var_offset(index); SIZE_MAX out of range.  Twelve launches on `stream`, one after the other
+ * (csrc/nonlocal_grad_kernels.h), no host synchronisation, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_nonlocal_grad_scratch_bytes(B, h, w) bytes, 256-byte aligned; every word read is written earlier in the same call.
+ * bsr_nonlocal_grad_offset(B, h, w, map) is the byte offset of map 0 y3 [N][272], 1 dz [N][272], 2 theta | phi | g [N][384], 3 A [N][128],
+ * 4 L [N][2] (the row maximum m and r = 1 / sum exp(S - m)), 5 dA [N][128], 6 D [N], 7 d_theta | d_phi | d_g [N][384] (float32, N = B T), 8 Wgd [128][257] float64, 9 Sz [257] float64;
+ * SIZE_MAX out of range.  bsr_nonlocal_grad_partials(B, h, w) is the number of row slices of the two kernel gradients (0 for bad
+ * arguments).  A bad argument gives BSR_ERR_ARG with a message and nothing launched.  bsr_debug_nonlocal_grad stops after `stop_after`
+ * (0..12) launches.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_nonlocal_grad_blob_bytes(void);
+size_t bsr_nonlocal_grad_scratch_bytes(int B, int h, int w);
+size_t bsr_nonlocal_grad_floats(void);
+size_t bsr_nonlocal_grad_var_offset(int index);
+size_t bsr_nonlocal_grad_offset(int B, int h, int w, int map);
+int bsr_nonlocal_grad_partials(int B, int h, int w);
+int bsr_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs, const float* out,
+                      int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, void* stream);
+int bsr_debug_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs, const float* out,
+                            int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, int stop_after,
+                            void* stream);
 
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
