@@ -1,7 +1,9 @@
 // Small HBM-bound kernels around the MFMA convolutions: the glue of Generator.call
 // (/root/reference/model.py:237,238,246-252,256-259,267-269,288).  fp contraction is disabled so the
 // grayscale / gs / dif arithmetic rounds like the reference's separate TF ops (matters at the hard
-// 0.1 threshold of model.py:256).
+// 0.1 threshold of model.py:256), and the 8x resizes run in the operation order of TensorFlow's CPU kernel
+// (resize8_lerp below).  tests/glue_cases.py states all of it in float32; tests/test_glue_exact_gpu.py holds
+// these kernels to that statement bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "igemm_conv.h"
@@ -15,8 +17,19 @@ __device__ __forceinline__ float gray3(float r, float g, float b) {
   return (r * 0.2989f + g * 0.5870f) + b * 0.1140f;
 }
 
-// tf.image.resize(uv, [H/8, W/8]) bilinear, half-pixel centres (model.py:237): for an exact 8x reduction
-// the sample point is 8o+3.5, i.e. the mean of the centre 2x2 block.  Writes the 3 channels into two
+// tf.image.resize(x, [H/8, W/8]) bilinear, half-pixel centres (model.py:237,256, warp.py:146): for an exact 8x reduction
+// the sample point of cell (o, p) is (8o+3.5, 8p+3.5), so the taps are rows 8o+3, 8o+4 x columns 8p+3, 8p+4 and both lerp
+// weights are 0.5.  The arithmetic is compute_lerp's of TensorFlow's resize_bilinear_op.cc — the one ucb_post.resize_bilinear
+// states and csrc/ucb_kernels.h executes — every step a rounded float32 operation.  It is NOT the same bits as
+// 0.5 * (0.5 tl + 0.5 tr) + 0.5 * (0.5 bl + 0.5 br), which these kernels ran before: that differs from it in the last bit of
+// a fifth to two fifths of the d32 cells, enough to put a cell on the other side of the 0.1 threshold.
+__device__ __forceinline__ float resize8_lerp(float tl, float tr, float bl, float br) {
+  const float top = tl + (tr - tl) * 0.5f;
+  const float bottom = bl + (br - bl) * 0.5f;
+  return top + (bottom - top) * 0.5f;
+}
+
+// uv = resize(uv, [H/8, W/8]) (model.py:237).  Writes the 3 channels into two
 // concat slots: dst_a[..., coff_a..] (model.py:238) and dst_b[..., coff_b..] (model.py:259).
 __global__ void uv_resize8_kernel(const float* __restrict__ uv, int H, int W, float* __restrict__ dst_a, int cs_a, int coff_a,
                                   float* __restrict__ dst_b, int cs_b, int coff_b, size_t ncell) {
@@ -28,8 +41,7 @@ __global__ void uv_resize8_kernel(const float* __restrict__ uv, int H, int W, fl
   const int p = (int)(cell % w8), o = (int)((cell / w8) % h8);
   const size_t img = cell / ((size_t)w8 * h8);
   const float* src = uv + ((img * H + 8 * o + 3) * W + 8 * p + 3) * 3 + c;
-  const float a = src[0], b = src[3], cc = src[(size_t)W * 3], d = src[(size_t)W * 3 + 3];
-  const float v = 0.5f * (0.5f * a + 0.5f * b) + 0.5f * (0.5f * cc + 0.5f * d);
+  const float v = resize8_lerp(src[0], src[3], src[(size_t)W * 3], src[(size_t)W * 3 + 3]);
   dst_a[cell * cs_a + coff_a + c] = v;
   dst_b[cell * cs_b + coff_b + c] = v;
 }
@@ -62,7 +74,7 @@ __global__ void heads_post_kernel(const float* __restrict__ q, const float* __re
   mask22[pix * 3 + 2] = fmaxf(-mask, 0.f);
 }
 
-// model.py:251,256-259: dif = gs - gray(inputs); d32 = resize(dif, /8) (centre 2x2 mean);
+// model.py:251,256-259: dif = gs - gray(inputs); d32 = resize(dif, /8) (resize8_lerp of the centre 2x2 block);
 // bmask = d32 > 0.1 (strict); x_hole = x*(1-bmask); xh = cat[x_hole, bmask, uv] (uv slot filled by uv_resize8).
 // One workgroup of 64 threads per 32x32 cell; r [B,cells,r_cs] -> xh [B,cells,xh_cs]; probe [cells][2] = {d32, bmask}.
 __global__ void bmask_xhole_kernel(const float* __restrict__ gs, const float* __restrict__ inputs, int H, int W,
@@ -80,7 +92,7 @@ __global__ void bmask_xhole_kernel(const float* __restrict__ gs, const float* __
     const float g0 = gray3(inputs[px * 3], inputs[px * 3 + 1], inputs[px * 3 + 2]);
     d[k] = gs[px] - g0;
   }
-  const float d32 = 0.5f * (0.5f * d[0] + 0.5f * d[1]) + 0.5f * (0.5f * d[2] + 0.5f * d[3]);
+  const float d32 = resize8_lerp(d[0], d[1], d[2], d[3]);
   const float bm = d32 > 0.1f ? 1.f : 0.f;
   const float keep = 1.f - bm;
   for (int c = threadIdx.x; c < r_c; c += blockDim.x) xh[cell * xh_cs + c] = r[cell * r_cs + c] * keep;
@@ -92,8 +104,8 @@ __global__ void bmask_xhole_kernel(const float* __restrict__ gs, const float* __
 }
 
 // ---- TSM ShareLayer (/root/reference/model_with_TSM.py:199-229) = offset warp -> group max|mean -> tile -> inverse warp ----
-// tf_batch_map_offsets (/root/reference/warp.py:134-165): offsets = resize(reg, [S,S]) * S (centre-2x2 mean for the exact
-// 8x reduction), channels 0:2; coords = offsets + (i, j); clamp to [0, S-1]; corners floor / ceil; lerp along axis 0
+// tf_batch_map_offsets (/root/reference/warp.py:134-165): offsets = resize(reg, [S,S]) * S (resize8_lerp of the centre 2x2 block for
+// the exact 8x reduction), channels 0:2; coords = offsets + (i, j); clamp to [0, S-1]; corners floor / ceil; lerp along axis 0
 // first, then axis 1 (warp.py:111-113).
 
 // reg [B,H,W,6] = reg_in(3) | reg_out(3) -> reg32 [B*cells][4] = (in0, in1, out0, out1) * S
@@ -107,8 +119,7 @@ __global__ void reg_resize8_kernel(const float* __restrict__ reg, int H, int W, 
   const int p = (int)(cell % w8), o = (int)((cell / w8) % h8);
   const size_t img = cell / ((size_t)w8 * h8);
   const float* src = reg + ((img * H + 8 * o + 3) * W + 8 * p + 3) * 6 + c;
-  const float a = src[0], b = src[6], cc = src[(size_t)W * 6], d = src[(size_t)W * 6 + 6];
-  const float v = 0.5f * (0.5f * a + 0.5f * b) + 0.5f * (0.5f * cc + 0.5f * d);
+  const float v = resize8_lerp(src[0], src[6], src[(size_t)W * 6], src[(size_t)W * 6 + 6]);
   reg32[gid] = v * (float)h8;
 }
 
