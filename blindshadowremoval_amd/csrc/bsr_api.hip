@@ -92,6 +92,38 @@ int run_post(const char* name, std::initializer_list<const void*> required, int 
   return launch();
 }
 
+// ---- the generator backward's stage entry points (bsr_clr_tail_grad, bsr_clr_decoder_grad, bsr_nonlocal_grad): one order of checks ----
+struct StageRule {
+  bool ok;
+  const char* text;
+};
+struct StageAligned {
+  unsigned bytes;
+  const char* names;      // as the text lists them: "<names> must be <bytes>-byte aligned"
+  std::initializer_list<const void*> ptrs;
+};
+
+// `name`'s checks in this order, all before the device switch and none reading through a pointer: the required pointers, `rules` (the
+// size rule, the blob's bytes, the pixel strides), the alignment groups, the scratch, `stop_after` against the chain's `launches`; then
+// `launch` (which returns a BSR_* code) on `device`.
+template <class Launch>
+int run_grad_stage(const char* name, std::initializer_list<const void*> required, std::initializer_list<StageRule> rules,
+                   std::initializer_list<StageAligned> aligned, const void* scratch, int stop_after, int launches, int device, Launch launch) {
+  const std::string n(name);
+  for (const void* p : required)
+    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
+  for (const StageRule& r : rules)
+    if (!r.ok) return fail(BSR_ERR_ARG, n + ": " + r.text);
+  for (const StageAligned& g : aligned)
+    for (const void* p : g.ptrs)
+      if (reinterpret_cast<uintptr_t>(p) % g.bytes != 0) return fail(BSR_ERR_ARG, n + ": " + g.names + " must be " + std::to_string(g.bytes) + "-byte aligned");
+  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
+  if (stop_after < 0 || stop_after > launches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0.." + std::to_string(launches));
+  DeviceGuard guard(device);
+  HIP_TRY(guard.err);
+  return launch();
+}
+
 // ---- packed-weight blob (written by blindshadowremoval_amd/pack.py) ----
 constexpr uint32_t kBlobMagic = 0x57525342u;  // "BSRW"
 constexpr uint32_t kBlobVersion = 1;
@@ -1603,24 +1635,17 @@ namespace {
 
 int clr_tail_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* gs, const float* f, int f_cs, const float* g_con,
                   const float* g_gs, int B, int H, int W, float* d_f, float* d_gs, float* grads, int keep, void* scratch, int stop_after, void* stream) {
-  const std::string n(name);
-  for (const void* p : {d_blob, (const void*)gs, (const void*)f, (const void*)g_con, (const void*)d_f, (const void*)d_gs, (const void*)grads, (const void*)scratch})
-    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
-  if (!bsr::clr_tail_size_ok(B, H, W))
-    return fail(BSR_ERR_ARG, n + ": B must be positive, H a multiple of 8 and W a multiple of 32 (conv_n16_kernel's tile), at most 2^26 pixels in all");
-  if (blob_bytes != bsr_clr_tail_grad_blob_bytes()) return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_clr_tail_grad_blob_bytes() (pack.pack_clr_tail_grad)");
-  if (f_cs < 64 || f_cs % 4 != 0) return fail(BSR_ERR_ARG, n + ": f_cs must be a multiple of 4 and at least 64");
-  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0 || reinterpret_cast<uintptr_t>(f) % 16 != 0 || reinterpret_cast<uintptr_t>(d_f) % 16 != 0)
-    return fail(BSR_ERR_ARG, n + ": d_blob, f and d_f must be 16-byte aligned");
-  for (const void* p : {(const void*)gs, (const void*)g_con, (const void*)g_gs, (const void*)d_gs, (const void*)grads})
-    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": gs, g_con, g_gs, d_gs and grads must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
-  if (stop_after < 0 || stop_after > bsr::kClrTailLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..6");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_clr_tail_grad(static_cast<const float*>(d_blob), gs, f, f_cs, g_con, g_gs, B, H, W, d_f, d_gs, grads, keep != 0, scratch, stop_after,
-                                    static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_grad_stage(
+      name, {d_blob, gs, f, g_con, d_f, d_gs, grads, scratch},
+      {{bsr::clr_tail_size_ok(B, H, W), "B must be positive, H a multiple of 8 and W a multiple of 32 (conv_n16_kernel's tile), at most 2^26 pixels in all"},
+       {blob_bytes == bsr_clr_tail_grad_blob_bytes(), "blob_bytes must be bsr_clr_tail_grad_blob_bytes() (pack.pack_clr_tail_grad)"},
+       {f_cs >= 64 && f_cs % 4 == 0, "f_cs must be a multiple of 4 and at least 64"}},
+      {{16, "d_blob, f and d_f", {d_blob, f, d_f}}, {4, "gs, g_con, g_gs, d_gs and grads", {gs, g_con, g_gs, d_gs, grads}}}, scratch, stop_after,
+      bsr::kClrTailLaunches, device, [&] {
+        HIP_TRY(bsr::launch_clr_tail_grad(static_cast<const float*>(d_blob), gs, f, f_cs, g_con, g_gs, B, H, W, d_f, d_gs, grads, keep != 0, scratch,
+                                          stop_after, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
 }
 
 }  // namespace
@@ -1660,28 +1685,20 @@ namespace {
 int clr_decoder_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* f1, int f1_cs, const float* f2,
                      int f2_cs, const float* f, int f_cs, const float* d_f, int B, int H, int W, float* d_x, float* grads, int keep, void* scratch, int stop_after,
                      void* stream) {
-  const std::string n(name);
-  for (const void* p : {d_blob, (const void*)x, (const void*)f1, (const void*)f2, (const void*)f, (const void*)d_f, (const void*)d_x, (const void*)grads,
-                        (const void*)scratch})
-    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
-  if (!bsr::up_size_ok(B, H, W))
-    return fail(BSR_ERR_ARG, n + ": B must be positive, H a multiple of 32 and W a multiple of 256 (the generator's rule), at most 2^26 pixels in all");
-  if (blob_bytes != bsr_clr_decoder_grad_blob_bytes())
-    return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_clr_decoder_grad_blob_bytes() (pack.pack_clr_decoder_grad; the GSC width 261 only, not TSM's 877)");
-  if (x_cs < 261) return fail(BSR_ERR_ARG, n + ": x_cs must be at least 261");
-  if (f1_cs < 128 || f1_cs % 4 != 0 || f2_cs < 96 || f2_cs % 4 != 0 || f_cs < 64 || f_cs % 4 != 0)
-    return fail(BSR_ERR_ARG, n + ": f1_cs, f2_cs, f_cs must be multiples of 4 and at least 128, 96, 64");
-  for (const void* p : {d_blob, (const void*)f1, (const void*)f2, (const void*)f, (const void*)d_f})
-    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(BSR_ERR_ARG, n + ": d_blob, f1, f2, f and d_f must be 16-byte aligned");
-  for (const void* p : {(const void*)x, (const void*)d_x, (const void*)grads})
-    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": x, d_x and grads must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
-  if (stop_after < 0 || stop_after > bsr::kUpLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..9");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_clr_decoder_grad(static_cast<const float*>(d_blob), x, x_cs, f1, f1_cs, f2, f2_cs, f, f_cs, d_f, B, H, W, d_x, grads, keep != 0, scratch,
-                                       stop_after, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_grad_stage(
+      name, {d_blob, x, f1, f2, f, d_f, d_x, grads, scratch},
+      {{bsr::up_size_ok(B, H, W), "B must be positive, H a multiple of 32 and W a multiple of 256 (the generator's rule), at most 2^26 pixels in all"},
+       {blob_bytes == bsr_clr_decoder_grad_blob_bytes(),
+        "blob_bytes must be bsr_clr_decoder_grad_blob_bytes() (pack.pack_clr_decoder_grad; the GSC width 261 only, not TSM's 877)"},
+       {x_cs >= 261, "x_cs must be at least 261"},
+       {f1_cs >= 128 && f1_cs % 4 == 0 && f2_cs >= 96 && f2_cs % 4 == 0 && f_cs >= 64 && f_cs % 4 == 0,
+        "f1_cs, f2_cs, f_cs must be multiples of 4 and at least 128, 96, 64"}},
+      {{16, "d_blob, f1, f2, f and d_f", {d_blob, f1, f2, f, d_f}}, {4, "x, d_x and grads", {x, d_x, grads}}}, scratch, stop_after, bsr::kUpLaunches, device,
+      [&] {
+        HIP_TRY(bsr::launch_clr_decoder_grad(static_cast<const float*>(d_blob), x, x_cs, f1, f1_cs, f2, f2_cs, f, f_cs, d_f, B, H, W, d_x, grads, keep != 0,
+                                             scratch, stop_after, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
 }
 
 }  // namespace
@@ -1719,25 +1736,19 @@ namespace {
 int nonlocal_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* y3x, int y3x_cs, const float* xin, int xin_cs,
                   const float* out, int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch,
                   int stop_after, void* stream) {
-  const std::string n(name);
-  for (const void* p : {d_blob, (const void*)y3x, (const void*)xin, (const void*)out, (const void*)d_out, (const void*)d_y3, (const void*)d_skip,
-                        (const void*)grads, (const void*)scratch})
-    if (p == nullptr) return fail(BSR_ERR_ARG, n + ": null argument");
-  if (!bsr::nl_size_ok(B, h, w))
-    return fail(BSR_ERR_ARG, n + ": B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 tokens in all");
-  if (blob_bytes != bsr_nonlocal_grad_blob_bytes())
-    return fail(BSR_ERR_ARG, n + ": blob_bytes must be bsr_nonlocal_grad_blob_bytes() (pack.pack_nonlocal_grad; the GSC width 261 only, not TSM's 877)");
-  if (y3x_cs < 257 || xin_cs < 261 || out_cs < 261) return fail(BSR_ERR_ARG, n + ": y3x_cs must be at least 257, xin_cs and out_cs at least 261");
-  if (reinterpret_cast<uintptr_t>(d_blob) % 16 != 0) return fail(BSR_ERR_ARG, n + ": d_blob must be 16-byte aligned");
-  for (const void* p : {(const void*)y3x, (const void*)xin, (const void*)out, (const void*)d_out, (const void*)d_y3, (const void*)d_skip, (const void*)grads})
-    if (reinterpret_cast<uintptr_t>(p) % 4 != 0) return fail(BSR_ERR_ARG, n + ": y3x, xin, out, d_out, d_y3, d_skip and grads must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0) return fail(BSR_ERR_ARG, n + ": scratch must be 256-byte aligned");
-  if (stop_after < 0 || stop_after > bsr::kNlLaunches) return fail(BSR_ERR_ARG, n + ": stop_after must be 0..12");
-  DeviceGuard guard(device);
-  HIP_TRY(guard.err);
-  HIP_TRY(bsr::launch_nonlocal_grad(static_cast<const float*>(d_blob), y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads, scratch,
-                                    stop_after, static_cast<hipStream_t>(stream)));
-  return BSR_OK;
+  return run_grad_stage(
+      name, {d_blob, y3x, xin, out, d_out, d_y3, d_skip, grads, scratch},
+      {{bsr::nl_size_ok(B, h, w),
+        "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 tokens in all"},
+       {blob_bytes == bsr_nonlocal_grad_blob_bytes(),
+        "blob_bytes must be bsr_nonlocal_grad_blob_bytes() (pack.pack_nonlocal_grad; the GSC width 261 only, not TSM's 877)"},
+       {y3x_cs >= 257 && xin_cs >= 261 && out_cs >= 261, "y3x_cs must be at least 257, xin_cs and out_cs at least 261"}},
+      {{16, "d_blob", {d_blob}}, {4, "y3x, xin, out, d_out, d_y3, d_skip and grads", {y3x, xin, out, d_out, d_y3, d_skip, grads}}}, scratch, stop_after,
+      bsr::kNlLaunches, device, [&] {
+        HIP_TRY(bsr::launch_nonlocal_grad(static_cast<const float*>(d_blob), y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads,
+                                          scratch, stop_after, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
 }
 
 }  // namespace

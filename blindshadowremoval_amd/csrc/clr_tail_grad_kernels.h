@@ -45,7 +45,7 @@
 // GRADS: the ten variables dense in their own shapes in weights.generator_tail_trainable_names' order (clr_tail_var_offset).
 #pragma once
 #include "conv_n16.h"
-#include "disc_wgrad_kernels.h"
+#include "grad_common.h"
 
 namespace bsr {
 
@@ -95,14 +95,13 @@ inline ClrTailPlan clr_tail_plan(int B, int H, int W) {
   pl.P = want < kClrWgradCap / 4 ? want : kClrWgradCap / 4;
   const size_t chunks = pl.npix / 256;
   pl.G = (int)(chunks < (size_t)kClrPixCap ? chunks : (size_t)kClrPixCap);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
-  for (int m = 0; m < 3; ++m) pl.map[m] = take(pl.npix * 16 * sizeof(float));
-  pl.map[3] = take((size_t)pl.G * kClrSumsLd * sizeof(double));
-  pl.map[4] = take((size_t)pl.P * 4 * kClrWRows * 16 * sizeof(float));
-  pl.map[5] = take((size_t)kClrK1 * sizeof(double));
-  pl.map[6] = take((size_t)kClrSumsLd * sizeof(double));
-  pl.total = o;
+  BumpBytes bump;
+  for (int m = 0; m < 3; ++m) pl.map[m] = bump.take(pl.npix * 16 * sizeof(float));
+  pl.map[3] = bump.take((size_t)pl.G * kClrSumsLd * sizeof(double));
+  pl.map[4] = bump.take((size_t)pl.P * 4 * kClrWRows * 16 * sizeof(float));
+  pl.map[5] = bump.take((size_t)kClrK1 * sizeof(double));
+  pl.map[6] = bump.take((size_t)kClrSumsLd * sizeof(double));
+  pl.total = bump.o;
   return pl;
 }
 
@@ -481,11 +480,9 @@ __global__ __launch_bounds__(64) void clr_finish_kernel(const ClrFinishArgs a) {
     if (lane < 2) {
       const float* v = lane == 0 ? a.vecs1 : a.vecs2;
       const double KW = lane == 0 ? kw1 : kw2, S = a.S[(lane == 0 ? 307 : 323) + o];
-      const double bias = v[o], inv = v[16 + o], mean = v[32 + o], rstd = v[48 + o];
       const int first = lane == 0 ? 1 : 5;
-      a.grads[clr_tail_var_offset(first) + o] = (float)(inv * S);
-      a.grads[clr_tail_var_offset(first + 1) + o] = (float)(((KW + bias * S) - mean * S) * rstd);
-      a.grads[clr_tail_var_offset(first + 2) + o] = (float)S;
+      bn_channel_grads(KW, S, v, 16, o, a.grads[clr_tail_var_offset(first) + o], a.grads[clr_tail_var_offset(first + 1) + o],
+                       a.grads[clr_tail_var_offset(first + 2) + o]);
     }
   } else {
     for (int i = lane; i < 256; i += 64) a.grads[clr_tail_var_offset(4) + i] = (float)((double)a.vecs2[16 + (i & 15)] * a.S[i]);
@@ -534,12 +531,8 @@ inline hipError_t launch_clr_tail_grad(const float* blob, const float* gs, const
   if (stop_after < 4) return hipSuccess;
   {
     static PerDeviceOnce once;               // the dynamic LDS limit is set once per device
-    const int dev = PerDeviceOnce::current();
     constexpr int bytes = kClrDgradSmemFloats * (int)sizeof(float);
-    if (dev < 0 || !once.done[dev]) {
-      if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(clr_dgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) != hipSuccess) return e;
-      if (dev >= 0) once.done[dev] = true;
-    }
+    if ((e = dynamic_lds_once(clr_dgrad_kernel, bytes, once)) != hipSuccess) return e;
     ClrDgradArgs a;
     a.gz1 = gz1; a.w = blob + kClrOffDgradW; a.g_gs = g_gs; a.d_f = d_f; a.d_gs = d_gs; a.H = H; a.W = W;
     a.tiles_x = pl.tiles_x; a.tiles_per_img = pl.tiles_per_img; a.T = pl.T;

@@ -84,24 +84,23 @@ struct UpPlan {
 };
 inline UpPlan up_plan(int B, int H, int W, bool keep) {
   UpPlan pl;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  BumpBytes bump;
   for (int l = 0; l < 3; ++l) {
     pl.h[l] = H >> (3 - l);
     pl.w[l] = W >> (3 - l);
     pl.T[l] = B * (pl.h[l] / 4) * (pl.w[l] / 16);
     const int want = (pl.T[l] + kUpMinTiles - 1) / kUpMinTiles;
     pl.P[l] = want < kUpPcap[l] ? want : kUpPcap[l];
-    pl.wpart[l] = take((size_t)pl.P[l] * 9 * kUpO[l] * kUpCp[l] * sizeof(float));
-    pl.spart[l] = take((size_t)pl.P[l] * (kUpO[l] / 32) * 256 * sizeof(double));
-    pl.map[3 + l] = take((size_t)9 * kUpO[l] * kUpC[l] * sizeof(double));
-    pl.map[6 + l] = take((size_t)kUpO[l] * sizeof(double));
+    pl.wpart[l] = bump.take((size_t)pl.P[l] * 9 * kUpO[l] * kUpCp[l] * sizeof(float));
+    pl.spart[l] = bump.take((size_t)pl.P[l] * (kUpO[l] / 32) * 256 * sizeof(double));
+    pl.map[3 + l] = bump.take((size_t)9 * kUpO[l] * kUpC[l] * sizeof(double));
+    pl.map[6 + l] = bump.take((size_t)kUpO[l] * sizeof(double));
   }
-  pl.map[0] = take((size_t)B * (H / 4) * (W / 4) * 128 * sizeof(float));
-  pl.map[1] = take((size_t)B * (H / 2) * (W / 2) * 96 * sizeof(float));
-  pl.map[2] = o;
-  if (keep) take((size_t)B * H * W * 64 * sizeof(float));
-  pl.total = o;
+  pl.map[0] = bump.take((size_t)B * (H / 4) * (W / 4) * 128 * sizeof(float));
+  pl.map[1] = bump.take((size_t)B * (H / 2) * (W / 2) * 96 * sizeof(float));
+  pl.map[2] = bump.o;
+  if (keep) bump.take((size_t)B * H * W * 64 * sizeof(float));
+  pl.total = bump.o;
   return pl;
 }
 
@@ -420,30 +419,14 @@ __global__ __launch_bounds__(64) void up_finish_kernel(const UpFinishArgs a) {
       kw += (double)L.k[at] * L.Wg[at];
     }
   kw = wave_sum(kw);
-  if (lane == 0) {
-    const double S = L.S[o], bias = L.vecs[o], inv = L.vecs[L.O + o], mean = L.vecs[2 * L.O + o], rstd = L.vecs[3 * L.O + o];
-    L.bias[o] = (float)(inv * S);
-    L.gamma[o] = (float)(((kw + bias * S) - mean * S) * rstd);
-    L.beta[o] = (float)S;
-  }
-}
-
-template <typename K>
-inline hipError_t up_dynamic_lds(K kernel, int bytes, PerDeviceOnce& once) {
-  const int dev = PerDeviceOnce::current();
-  if (dev < 0 || !once.done[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    if (dev >= 0) once.done[dev] = true;
-  }
-  return hipSuccess;
+  if (lane == 0) bn_channel_grads(kw, L.S[o], L.vecs, L.O, o, L.bias[o], L.gamma[o], L.beta[o]);
 }
 
 template <int CTW, bool VEC>
 inline hipError_t launch_up_wgrad(const UpWgradArgs& a, int layer, hipStream_t stream) {
   static PerDeviceOnce once;
   constexpr int bytes = up_wgrad_smem_floats<CTW>() * (int)sizeof(float);
-  const hipError_t e = up_dynamic_lds(up_wgrad_kernel<CTW, VEC>, bytes, once);
+  const hipError_t e = dynamic_lds_once(up_wgrad_kernel<CTW, VEC>, bytes, once);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((up_wgrad_kernel<CTW, VEC>), dim3(a.P, kUpO[layer] / 32, kUpCp[layer] / (32 * CTW)), dim3(256), bytes, stream, a);
   return hipGetLastError();
@@ -453,7 +436,7 @@ template <int NT, bool VEC>
 inline hipError_t launch_up_dgrad(const UpDgradArgs& a, int B, hipStream_t stream) {
   static PerDeviceOnce once;
   constexpr int bytes = up_dgrad_smem_floats<NT, kUpOc>() * (int)sizeof(float);
-  const hipError_t e = up_dynamic_lds(up_dgrad_kernel<NT, VEC, kUpOc>, bytes, once);
+  const hipError_t e = dynamic_lds_once(up_dgrad_kernel<NT, VEC, kUpOc>, bytes, once);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((up_dgrad_kernel<NT, VEC, kUpOc>), dim3(B * a.tiles_per_img, a.Cp / (16 * NT)), dim3(256), bytes, stream, a);
   return hipGetLastError();

@@ -42,6 +42,7 @@
 // GRADS: the 54 variables dense in their own shapes in weights.discriminator_trainable_names' order (disc_wgrad_var_offset).
 #pragma once
 #include "disc_grad_kernels.h"
+#include "grad_common.h"
 
 namespace bsr {
 
@@ -100,8 +101,7 @@ struct DiscWgradPlan {
 };
 inline DiscWgradPlan disc_wgrad_plan(int B, int S) {
   DiscWgradPlan pl;
-  size_t o = disc_wgrad_map_offset(B, S, 3, 1);
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  BumpBytes bump{disc_wgrad_map_offset(B, S, 3, 1)};
   for (int i = 0; i < kDiscLayers; ++i) {
     size_t all = 0;
     for (int k = 0; k < 3; ++k) {
@@ -120,12 +120,12 @@ inline DiscWgradPlan disc_wgrad_plan(int B, int S) {
   for (int k = 0; k < 3; ++k)
     for (int i = 0; i < kDiscLayers; ++i) {
       const size_t mn = (size_t)kDiscTaps * disc_cin(i) * disc_ch(i);
-      pl.wpart[k][i] = take((size_t)pl.P[k][i] * mn * sizeof(float));
-      pl.spart[k][i] = take((size_t)pl.P[k][i] * disc_ch(i) * sizeof(double));
-      pl.W[k][i] = take(mn * sizeof(double));
+      pl.wpart[k][i] = bump.take((size_t)pl.P[k][i] * mn * sizeof(float));
+      pl.spart[k][i] = bump.take((size_t)pl.P[k][i] * disc_ch(i) * sizeof(double));
+      pl.W[k][i] = bump.take(mn * sizeof(double));
     }
-  pl.hpart = take((size_t)3 * kDiscHeadChunks * kDiscTaps * 64 * sizeof(double));
-  pl.total = o;
+  pl.hpart = bump.take((size_t)3 * kDiscHeadChunks * kDiscTaps * 64 * sizeof(double));
+  pl.total = bump.o;
   return pl;
 }
 
@@ -359,11 +359,6 @@ struct DiscFinishArgs {
   unsigned channels;      // the twelve layers' channels: 576
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // grid (576 + 48 + 3), one wave each
 __global__ __launch_bounds__(64) void disc_wgrad_finish_kernel(const DiscFinishArgs args) {
   const int lane = threadIdx.x;
@@ -379,13 +374,7 @@ __global__ __launch_bounds__(64) void disc_wgrad_finish_kernel(const DiscFinishA
     for (int mm = lane; mm < s.M; mm += 64) KW += (double)s.K[(size_t)mm * s.N + o] * s.W[(size_t)mm * s.N + o];
     S = wave_sum(S);
     KW = wave_sum(KW);
-    if (lane == 0) {
-      const float* v = s.K + (size_t)s.M * s.N;
-      const double bias = v[o], inv = v[s.N + o], mean = v[2 * s.N + o], rstd = v[3 * s.N + o];
-      s.beta[o] = (float)S;
-      s.bias[o] = (float)(inv * S);
-      s.gamma[o] = (float)(((KW + bias * S) - mean * S) * rstd);
-    }
+    if (lane == 0) bn_channel_grads(KW, S, s.K + (size_t)s.M * s.N, s.N, o, s.bias[o], s.gamma[o], s.beta[o]);
   } else if (b < args.channels + 3 * kDiscTaps) {
     const int k = (int)(b - args.channels) / kDiscTaps, tap = (int)(b - args.channels) % kDiscTaps;
     double a = 0.0;

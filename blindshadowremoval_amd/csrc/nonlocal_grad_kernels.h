@@ -72,28 +72,27 @@ struct NlPlan {
 };
 inline NlPlan nl_plan(int B, int h, int w) {
   NlPlan pl;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  BumpBytes bump;
   pl.T = h * w;
   pl.N = B * pl.T;
   const int chunks = pl.N / 128;
   pl.P = chunks < 64 ? chunks : 64;
   const size_t N = (size_t)pl.N;
-  pl.map[0] = take(N * kNlCp * sizeof(float));
-  pl.map[1] = take(N * kNlCp * sizeof(float));
-  pl.map[2] = take(N * kNlQ * sizeof(float));
-  pl.map[3] = take(N * kNlD * sizeof(float));
-  pl.map[4] = take(N * 2 * sizeof(float));
-  pl.map[5] = take(N * kNlD * sizeof(float));
-  pl.map[6] = take(N * sizeof(float));
-  pl.map[7] = take(N * kNlQ * sizeof(float));
-  pl.map[8] = take((size_t)kNlD * kNlC * sizeof(double));
-  pl.map[9] = take((size_t)kNlC * sizeof(double));
-  pl.szpart = take((N / 64) * kNlCp * sizeof(double));
-  pl.bpart = take((N / 128) * kNlQ * sizeof(double));
-  pl.part1 = take((size_t)pl.P * kNlTnMp * kNlQ * sizeof(float));
-  pl.part2 = take((size_t)pl.P * kNlD * kNlQ * sizeof(float));
-  pl.total = o;
+  pl.map[0] = bump.take(N * kNlCp * sizeof(float));
+  pl.map[1] = bump.take(N * kNlCp * sizeof(float));
+  pl.map[2] = bump.take(N * kNlQ * sizeof(float));
+  pl.map[3] = bump.take(N * kNlD * sizeof(float));
+  pl.map[4] = bump.take(N * 2 * sizeof(float));
+  pl.map[5] = bump.take(N * kNlD * sizeof(float));
+  pl.map[6] = bump.take(N * sizeof(float));
+  pl.map[7] = bump.take(N * kNlQ * sizeof(float));
+  pl.map[8] = bump.take((size_t)kNlD * kNlC * sizeof(double));
+  pl.map[9] = bump.take((size_t)kNlC * sizeof(double));
+  pl.szpart = bump.take((N / 64) * kNlCp * sizeof(double));
+  pl.bpart = bump.take((N / 128) * kNlQ * sizeof(double));
+  pl.part1 = bump.take((size_t)pl.P * kNlTnMp * kNlQ * sizeof(float));
+  pl.part2 = bump.take((size_t)pl.P * kNlD * kNlQ * sizeof(float));
+  pl.total = bump.o;
   return pl;
 }
 
@@ -524,11 +523,8 @@ __global__ __launch_bounds__(64) void nl_finish_kernel(const NlFinishArgs a) {
     sz = wave_sum(sz);
     kw = wave_sum(kw);
     if (lane == 0) {
-      const double bias = a.vecs[b], inv = a.vecs[kNlC + b], mean = a.vecs[2 * kNlC + b], rstd = a.vecs[3 * kNlC + b];
       a.Sz[b] = sz;
-      a.grads[nl_var_offset(7) + b] = (float)(inv * sz);
-      a.grads[nl_var_offset(8) + b] = (float)(((kw + bias * sz) - mean * sz) * rstd);
-      a.grads[nl_var_offset(9) + b] = (float)sz;
+      bn_channel_grads(kw, sz, a.vecs, kNlC, b, a.grads[nl_var_offset(7) + b], a.grads[nl_var_offset(8) + b], a.grads[nl_var_offset(9) + b]);
     }
   } else {
     const int col = b - kNlC, slot = col / kNlD, j = col % kNlD;     // slot: theta, phi, g
@@ -542,7 +538,7 @@ __global__ __launch_bounds__(64) void nl_finish_kernel(const NlFinishArgs a) {
 template <typename K>
 inline hipError_t launch_nl_att(K kernel, PerDeviceOnce& once, const NlAttArgs& a, int N, hipStream_t stream) {
   constexpr int bytes = kNlAttSmemFloats * (int)sizeof(float);
-  const hipError_t e = up_dynamic_lds(kernel, bytes, once);
+  const hipError_t e = dynamic_lds_once(kernel, bytes, once);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kernel, dim3(N / 64), dim3(256), bytes, stream, a);
   return hipGetLastError();

@@ -26,6 +26,7 @@ through the colour tail, and with --decoder beside both decoder_grad_names(), th
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 import sys
 from typing import Callable, Dict, List, Optional
@@ -64,22 +65,26 @@ def loss_record(three, gan, per) -> Dict[str, float]:
     return dict(zip(ALL_NAMES, vals))
 
 
-def tail_grad_names() -> List[str]:
-    """`<name>_l1`, `<name>_linf` for generator_grad.TAIL_NORM_NAMES: d_f, d_gs and the colour tail's ten variables."""
-    from .generator_grad import TAIL_NORM_NAMES
-    return [n + s for n in TAIL_NORM_NAMES for s in ("_l1", "_linf")]
+# the stages of the generator's backward pass from the output down: generator_grad's <STAGE>_NORM_NAMES and <stage>_norms, and here
+# <stage>_grad_names() and the routes' <stage>_norms
+STAGES = ("tail", "decoder", "nonlocal")
 
 
-def decoder_grad_names() -> List[str]:
-    """`<name>_l1`, `<name>_linf` for generator_grad.DECODER_NORM_NAMES: d_x and the colour decoder's twelve variables."""
-    from .generator_grad import DECODER_NORM_NAMES
-    return [n + s for n in DECODER_NORM_NAMES for s in ("_l1", "_linf")]
+def stage_grad_names(stage: str) -> List[str]:
+    """`<name>_l1`, `<name>_linf` for generator_grad's <STAGE>_NORM_NAMES: the stage's data gradients (tail: d_f, d_gs; decoder: d_x;
+    nonlocal: d_y3, d_skip), then its variables."""
+    from . import generator_grad
+    return [n + s for n in getattr(generator_grad, stage.upper() + "_NORM_NAMES") for s in ("_l1", "_linf")]
 
 
-def nonlocal_grad_names() -> List[str]:
-    """`<name>_l1`, `<name>_linf` for generator_grad.NONLOCAL_NORM_NAMES: d_y3, d_skip and the ten variables of res_stack/5's non-local block."""
-    from .generator_grad import NONLOCAL_NORM_NAMES
-    return [n + s for n in NONLOCAL_NORM_NAMES for s in ("_l1", "_linf")]
+tail_grad_names, decoder_grad_names, nonlocal_grad_names = (functools.partial(stage_grad_names, stage) for stage in STAGES)
+
+
+def _stage_norms(stage: str, grads) -> List[float]:
+    """stage_grad_names(stage)'s values of a stage's result on either route: name -> numpy array or device tensor."""
+    from . import generator_grad
+    arrays = {k: t.cpu().numpy() if hasattr(t, "cpu") else t for k, t in grads.items()}
+    return [v for pair in getattr(generator_grad, stage + "_norms")(arrays).values() for v in pair]
 
 
 # ---- the two routes
@@ -120,25 +125,25 @@ class HostRoute:
 
     def tail_norms(self, gs, f, grad_con, grad_gs) -> List[float]:
         """tail_grad_names() of the two gradients taken through the colour tail at f [B,H,W,64]."""
-        from .generator_grad import tail_grad, tail_norms
+        from .generator_grad import tail_grad
         grads = tail_grad(self.gen_w, gs, f, grad_con, grad_gs)
         self.d_f = grads["d_f"]
-        return [v for pair in tail_norms(grads).values() for v in pair]
+        return _stage_norms("tail", grads)
 
     def decoder_norms(self) -> List[float]:
         """decoder_grad_names() of the last tail_norms' d_f taken through the colour decoder at the generator's kept res5, f1, f2, f."""
-        from .generator_grad import decoder_grad, decoder_norms
+        from .generator_grad import decoder_grad
         grads = decoder_grad(self.gen_w, self.acts["res5"], self.d_f, acts=self.acts)
         self.d_x = grads["d_x"]
-        return [v for pair in decoder_norms(grads).values() for v in pair]
+        return _stage_norms("decoder", grads)
 
     def nonlocal_norms(self) -> List[float]:
         """nonlocal_grad_names() of the last decoder_norms' d_x taken through res_stack/5's upper half at the generator's kept y3x5, res4
         and res5: y3 = y3x5 - pad(res4) in float32, as the device chain forms it."""
-        from .generator_grad import nonlocal_grad, nonlocal_norms
+        from .generator_grad import nonlocal_grad
         xin = self.block5["res4"]
         y3 = (self.block5["y3x5"][..., :257] - xin[..., :257]).astype(f32)
-        return [v for pair in nonlocal_norms(nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]})).values() for v in pair]
+        return _stage_norms("nonlocal", nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]}))
 
 
 class DeviceRoute:
@@ -152,14 +157,10 @@ class DeviceRoute:
         self.gan.load_weights(disc_w)
         self.per.load_weights(vgg_w)
         if gen_w is not None:
-            self.tail = ColourTail(device)
-            self.tail.load_weights(gen_w)
-            if decoder:
-                self.dec = ColourDecoder(device)
-                self.dec.load_weights(gen_w)
-            if nonlocal_:
-                self.nl = NonLocalGrad(device)
-                self.nl.load_weights(gen_w)
+            for name, stage, wanted in (("tail", ColourTail, True), ("dec", ColourDecoder, decoder), ("nl", NonLocalGrad, nonlocal_)):
+                if wanted:
+                    setattr(self, name, stage(device))
+                    getattr(self, name).load_weights(gen_w)
         self.three_weights = torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(self.dev)
         self.per_weight = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=self.dev)
 
@@ -182,23 +183,17 @@ class DeviceRoute:
         return three[0].cpu().numpy(), gan[0].cpu().numpy(), per[0].cpu().numpy(), grad_con, three[2]
 
     def tail_norms(self, gs, generator, grad_con, grad_gs) -> List[float]:
-        from .generator_grad import tail_norms
         res = self.tail.backward(generator, gs, grad_con, grad_gs)
         self.d_f, self.generator = res["d_f"], generator
-        grads = {k: t.cpu().numpy() for k, t in res.items()}
-        return [v for pair in tail_norms(grads).values() for v in pair]
+        return _stage_norms("tail", res)
 
     def decoder_norms(self) -> List[float]:
-        from .generator_grad import decoder_norms
         res = self.dec.backward(self.generator, self.d_f)
         self.d_x = res["d_x"]
-        grads = {k: t.cpu().numpy() for k, t in res.items()}
-        return [v for pair in decoder_norms(grads).values() for v in pair]
+        return _stage_norms("decoder", res)
 
     def nonlocal_norms(self) -> List[float]:
-        from .generator_grad import nonlocal_norms
-        grads = {k: t.cpu().numpy() for k, t in self.nl.backward(self.generator, self.d_x).items()}
-        return [v for pair in nonlocal_norms(grads).values() for v in pair]
+        return _stage_norms("nonlocal", self.nl.backward(self.generator, self.d_x))
 
 
 def _norms(grad) -> List[float]:
@@ -320,12 +315,9 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
             return loss_record(three, gan, per), list(zip(GRAD_NAMES, _norms(g))) if grad else []
         three, gan, per, grad_con, grad_gs = route.total_grad(*arrays)
         extras = list(zip(TOTAL_GRAD_NAMES, _norms(grad_con) + _norms(grad_gs)))
-        if tail:
-            extras += zip(tail_grad_names(), route.tail_norms(arrays[3], f, grad_con, grad_gs))
-        if decoder:
-            extras += zip(decoder_grad_names(), route.decoder_norms())
-        if nonlocal_:
-            extras += zip(nonlocal_grad_names(), route.nonlocal_norms())
+        for stage, wanted, args in zip(STAGES, (tail, decoder, nonlocal_), ((arrays[3], f, grad_con, grad_gs), (), ())):
+            if wanted:
+                extras += zip(stage_grad_names(stage), getattr(route, stage + "_norms")(*args))
         return loss_record(three, gan, per), extras
 
     return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True)
