@@ -261,6 +261,8 @@ struct bsr_handle {
                                  // and A/B measurements compare against; same operands, another summation order)
   bool fuse_attw = true;         // env BSR_FUSE_ATTW=0: attention and the `w` GEMM as two launches (A/B measurements, bit-identity tests)
   bool wino_conv2 = true;        // env BSR_WINO_CONV2=0: the fp32 res*.conv2 on the direct implicit-GEMM kernel instead of the Winograd F(2x2, 3x3) one (A/B measurements, the two-forms test)
+  bool wino_pairs = true;        // env BSR_WINO_PAIRS=0: full grids of the Winograd res*.conv2 on the 4-wave workgroup (one wave per SIMD) instead of the 8-wave one
+                                 // (A/B measurements, the bit-identity test of the two shapes in a whole forward)
   bool keys_conv2 = true;        // env BSR_KEYS_CONV2=0: the fp32 attention with phi projected by res*.c3q (N = 672, conv2's output in a buffer of its own) instead of conv2's
                                  // output as the keys (A/B measurements, the two-forms test)
   bool values_conv2 = true;      // env BSR_VALUES_CONV2=0 (read only while keys_conv2 is on): g projected by res*.c3q (N = 544) and the attention on [q' | t2 | g] rows instead
@@ -608,7 +610,7 @@ struct Launcher {
     if (rc != BSR_OK) return;
     if (H % 4 != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': feature map is not a multiple of the 4x32 tile"); return; }
     begin(K_CONV3, name);
-    check(bsr::launch_wino_conv2(wino_args(in, out, h->d_wino + (size_t)i * kWinoFloats, l.b, H, W, out_cs), h->B, s), name);
+    check(bsr::launch_wino_conv2(wino_args(in, out, h->d_wino + (size_t)i * kWinoFloats, l.b, H, W, out_cs), h->B, s, 0, h->wino_pairs), name);
     end();
   }
 
@@ -762,7 +764,7 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   h->dtype = dtype;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
-                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2},
+                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}, {"BSR_WINO_PAIRS", &h->wino_pairs},
                                                             {"BSR_KEYS_CONV2", &h->keys_conv2}, {"BSR_VALUES_CONV2", &h->values_conv2}};
   for (const auto& sw : switches)
     if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
@@ -1997,7 +1999,7 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
   if (x == nullptr || w == nullptr || bias == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: null argument");
   if (B <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 32 != 0) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: H must be a positive multiple of 4 and W of 32");
   if ((long long)B * H * W * 128 * 4 >= (1LL << 31)) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: tensor too large");
-  if (nw != 0 && nw != 2 && nw != 4) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: nw must be 0 (automatic), 2 or 4 waves per workgroup");
+  if (nw != 0 && nw != 2 && nw != 4 && nw != 8) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: nw must be 0 (automatic), 2, 4 or 8 waves per workgroup");
   HIP_TRY(bsr::launch_wino_conv2(wino_args(x, y, w, bias, H, W), B, static_cast<hipStream_t>(stream), nw));
   return BSR_OK;
 }

@@ -563,7 +563,8 @@ int bsr_debug_attention_qw(const float* qkv, float* y, int B, int tokens, int qw
 /* Test hook (additive in ABI 8, no existing signature changed): the Winograd F(2x2, 3x3) kernel of the fp32 res*.conv2 alone
  * (csrc/wino_conv2.h).  x [B,H,W,128] -> y [B,H,W,128] = LeakyReLU_0.3(conv3x3_SAME(x) + bias); w = the [8][16][128][16] transformed
  * weights of blindshadowremoval_amd.pack.pack_wino (what bsr_create derives from the blob), bias [128]; H % 4 == 0, W % 32 == 0 (device pointers).  nw = waves per workgroup:
- * 4 (128 output channels), 2 (64), 0 = what the forward picks for this grid.  Both shapes give bit-identical outputs. */
+ * 8 (128 output channels, two waves per SIMD), 4 (128, one wave per SIMD), 2 (64), 0 = what the forward picks for this grid.  All shapes give
+ * bit-identical outputs. */
 int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int nw, void* stream);
 /* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct image of each res<i>.conv2 of an
  * fp32 blob.  direct = the layer's [4][9][128][36] image (HOST pointer), out = [8][16][128][16] floats (HOST pointer). */
