@@ -34,6 +34,7 @@
 #include "ucb_tsm_kernels.h"
 #include "sfw_kernels.h"
 #include "wino_conv2.h"
+#include "wino_convt.h"
 #include "wild_crop_kernels.h"
 #include "wild_paste_kernels.h"
 #include "shadow_synth_kernels.h"
@@ -230,6 +231,7 @@ struct bsr_handle {
   int device = 0;
   float* d_blob = nullptr;
   float* d_wino = nullptr;       // fp32 GSC / TSM handles: the Winograd weight streams of res0..5.conv2 (wino_conv2.h), derived from the blob's direct images at bsr_create
+  float* d_winot = nullptr;      // fp32 GSC handles: the 25-position weight streams of up2, up3 and clr_up3 (wino_convt.h), derived from the blob's direct images at bsr_create
   float* d_keys = nullptr;       // fp32 GSC / TSM handles: the res0..5.c3q images with theta composed onto phi, N = [y3 | q' | g] (keys_compose), derived from the blob's at bsr_create
   float* d_values = nullptr;     // fp32 GSC / TSM handles: per block the `w` image with g composed onto it, the c3q image of N = [y3 | q'] and the g image the att<i> probe
                                  // applies (values_compose), derived from the blob's at bsr_create
@@ -263,6 +265,8 @@ struct bsr_handle {
   bool wino_conv2 = true;        // env BSR_WINO_CONV2=0: the fp32 res*.conv2 on the direct implicit-GEMM kernel instead of the Winograd F(2x2, 3x3) one (A/B measurements, the two-forms test)
   bool wino_pairs = true;        // env BSR_WINO_PAIRS=0: full grids of the Winograd res*.conv2 on the 4-wave workgroup (one wave per SIMD) instead of the 8-wave one
                                  // (A/B measurements, the bit-identity test of the two shapes in a whole forward)
+  bool wino_convt = true;        // env BSR_WINO_CONVT=0: the fp32 GSC up2 / up3 / clr_up3 on the direct implicit-GEMM kernel instead of the 25-product form of wino_convt.h
+                                 // (A/B measurements, the two-forms test)
   bool keys_conv2 = true;        // env BSR_KEYS_CONV2=0: the fp32 attention with phi projected by res*.c3q (N = 672, conv2's output in a buffer of its own) instead of conv2's
                                  // output as the keys (A/B measurements, the two-forms test)
   bool values_conv2 = true;      // env BSR_VALUES_CONV2=0 (read only while keys_conv2 is on): g projected by res*.c3q (N = 544) and the attention on [q' | t2 | g] rows instead
@@ -301,6 +305,36 @@ void wino_filter_transform(const float* direct, float* out) {
           double acc = 0.0;
           for (int b = 0; b < 3; ++b) acc += t[x][b] * G[y][b];
           out[((size_t)((k / 16) * 16 + 4 * x + y) * 128 + n) * 16 + k % 16] = (float)acc;
+        }
+    }
+}
+
+// The 25-position filter transform U = G g G^T of a transposed 3x3 layer Cin -> 64 (wino_convt.h), G = rows (w1, w1, w2, w0 + w2, w0) of the
+// taps, in float64, rounded once: the layer's direct image [ceil(cin / 32) chunks][9 taps (a, b)][64 cout][32 + 4 channels] -> the
+// stream [cin / 16 chunks][25 positions 5 r + s][2 cout halves][2 K groups][64 lanes 32 h + n][4].
+// blindshadowremoval_amd/pack.py: pack_wino_convt states the same in numpy.
+constexpr int kWinoTLayers = 3;
+const char* const kWinoTNames[kWinoTLayers] = {"up2", "up3", "clr_up3"};
+constexpr int kWinoTCin[kWinoTLayers] = {160, 128, 96};
+constexpr size_t wino_convt_floats(int cin) { return (size_t)(cin / 16) * 25 * 64 * 16; }
+constexpr size_t wino_convt_offset(int layer) { return layer == 0 ? 0 : wino_convt_offset(layer - 1) + wino_convt_floats(kWinoTCin[layer - 1]); }
+void wino_convt_filter_transform(const float* direct, float* out, int cin) {
+  static const double G[5][3] = {{0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}, {1.0, 0.0, 1.0}, {1.0, 0.0, 0.0}};
+  for (int k = 0; k < cin; ++k)
+    for (int n = 0; n < 64; ++n) {
+      double t[5][3];
+      for (int x = 0; x < 5; ++x)
+        for (int b = 0; b < 3; ++b) {
+          double acc = 0.0;
+          for (int a = 0; a < 3; ++a) acc += G[x][a] * (double)direct[((size_t)((k / 32) * 9 + a * 3 + b) * 64 + n) * 36 + k % 32];
+          t[x][b] = acc;
+        }
+      const int kk = k % 16, g = kk / 8, hh = (kk % 8) / 4, j = kk % 4;
+      for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y) {
+          double acc = 0.0;
+          for (int b = 0; b < 3; ++b) acc += t[x][b] * G[y][b];
+          out[(((((size_t)(k / 16) * 25 + 5 * x + y) * 2 + n / 32) * 2 + g) * 64 + 32 * hh + n % 32) * 4 + j] = (float)acc;
         }
     }
 }
@@ -614,6 +648,23 @@ struct Launcher {
     end();
   }
 
+  // fp32 GSC up2 / up3 / clr_up3 (ConvT 3x3 stride 2, Cin -> 64, + BN + LeakyReLU) in the 25-product form of wino_convt.h.  The blob's
+  // layer gives the bias; the weights are the handle's transformed stream.  Same timing class and name as the direct kernel's launch.
+  void winot(const char* name, int layer, const float* in, int in_cs, int H, int W, float* out, int out_cs) {
+    if (rc != BSR_OK) return;
+    const int cin = kWinoTCin[layer];
+    LayerW l;
+    rc = find_layer(h, name, cin / 32, 9, 36, 64, &l);
+    if (rc != BSR_OK) return;
+    if (const char* why = bsr::wino_convt_refusal(h->B, H, W, cin, 64, in_cs, out_cs)) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': " + why); return; }
+    bsr::WinoTArgs a{};
+    a.in = in; a.out = out; a.w = h->d_winot + wino_convt_offset(layer); a.bias = l.b; a.H = H; a.W = W;
+    a.in_cs = in_cs; a.out_cs = out_cs; a.nchunk = cin / 16; a.act = 1;
+    begin(K_CONVT_NI2, name);
+    check(bsr::launch_wino_convt(a, h->B, s), name);
+    end();
+  }
+
   // RGB head conv2 (7x7, 128 -> 3) as a 7x1 implicit GEMM over N = (kx, co): rgb_head.h
   void conv71(const char* name, const float* in, int in_cs, int k_pad, int H, int W, float* out, int out_cs) {
     if (rc != BSR_OK) return;
@@ -764,7 +815,7 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   h->dtype = dtype;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
-                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}, {"BSR_WINO_PAIRS", &h->wino_pairs},
+                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}, {"BSR_WINO_PAIRS", &h->wino_pairs}, {"BSR_WINO_CONVT", &h->wino_convt},
                                                             {"BSR_KEYS_CONV2", &h->keys_conv2}, {"BSR_VALUES_CONV2", &h->values_conv2}};
   for (const auto& sw : switches)
     if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
@@ -848,6 +899,17 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
     e = hipMalloc(reinterpret_cast<void**>(&h->d_wino), u.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_wino, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: Winograd weights: ") + hipGetErrorString(e)); }
+    if (!h->var.tsm) {      // GSC: the 25-position streams of up2, up3 and clr_up3, once per handle (kept whatever BSR_WINO_CONVT says: 2.4 MB)
+      std::vector<float> ut(wino_convt_offset(kWinoTLayers));
+      for (int i = 0; i < kWinoTLayers; ++i) {
+        LayerW l;
+        if (find_layer(h, kWinoTNames[i], kWinoTCin[i] / 32, 9, 36, 64, &l) != BSR_OK || l.n_pad != 64) { bsr_destroy(h); return fail(BSR_ERR_BLOB, std::string("bsr_create: layer '") + kWinoTNames[i] + "' is not a [Cin / 32][9][64][36] image"); }
+        wino_convt_filter_transform(reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(l.w) - reinterpret_cast<const uint8_t*>(h->d_blob))), ut.data() + wino_convt_offset(i), kWinoTCin[i]);
+      }
+      e = hipMalloc(reinterpret_cast<void**>(&h->d_winot), ut.size() * sizeof(float));
+      if (e == hipSuccess) e = hipMemcpy(h->d_winot, ut.data(), ut.size() * sizeof(float), hipMemcpyHostToDevice);
+      if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: transposed-layer Winograd weights: ") + hipGetErrorString(e)); }
+    }
     // the res0..5.c3q images for conv2's output as the attention keys, once per handle (kept whatever BSR_KEYS_CONV2 says: 2 MB)
     std::vector<float> q(6 * kKeysFloats);
     auto host = [&](const float* dev) { return reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(dev) - reinterpret_cast<const uint8_t*>(h->d_blob))); };
@@ -892,6 +954,7 @@ void bsr_destroy(bsr_handle* h) {
   if (h->ws) hipFree(h->ws);
   if (h->d_blob) hipFree(h->d_blob);
   if (h->d_wino) hipFree(h->d_wino);
+  if (h->d_winot) hipFree(h->d_winot);
   if (h->d_keys) hipFree(h->d_keys);
   if (h->d_values) hipFree(h->d_values);
   if (h->att_scratch) hipFree(h->att_scratch);
@@ -1155,8 +1218,16 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
 
   // greyscale decoder: up1..3 = ConvT (model.py:243-245)
   L.conv<3, 3, 1, true, 1, 24, 1>(K_CONVT, "up1", ws + p.r[2], V.cs_r, 0, V.cs_r, H8, W8, ws + p.c2, 160, 0, 96, 1, io_out);
-  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up2", ws + p.c2, 160, 0, 160, H4, W4, ws + p.c3, 128, 0, 64, 1, io_both);
-  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up3", ws + p.c3, 128, 0, 128, H2, W2, ws + p.ybuf, 64, 0, 64, 1, io_both);
+  // fp32 GSC: up2, up3 and clr_up3 in the 25-product form of wino_convt.h, at EVERY batch and image size (an image gets the same bits in
+  // any batch); BSR_WINO_CONVT=0 keeps the direct kernel.  TSM handles and the 16-bit modes keep theirs.
+  const bool winot = h->dtype == BSR_DTYPE_F32 && !V.tsm && h->wino_convt && h->d_winot != nullptr;
+  if (winot) {
+    L.winot("up2", 0, ws + p.c2, 160, H4, W4, ws + p.c3, 128);
+    L.winot("up3", 1, ws + p.c3, 128, H2, W2, ws + p.ybuf, 64);
+  } else {
+    L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up2", ws + p.c2, 160, 0, 160, H4, W4, ws + p.c3, 128, 0, 64, 1, io_both);
+    L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "up3", ws + p.c3, 128, 0, 128, H2, W2, ws + p.ybuf, 64, 0, 64, 1, io_both);
+  }
   // heads conv2 (mask) / conv3 (con): 7x7, 64 -> 1 each (model.py:246-247) as one 7x1 MFMA conv with N = (kx, head); the 7 horizontal
   // taps + tanh / gs / mask22 (model.py:246-252) either inside the same kernel (row-strip workgroups, when the batch has enough
   // strips to fill the chip) or by heads_post_kernel from the qh scratch tensor — bit-identical results either way
@@ -1175,7 +1246,8 @@ static int forward_impl(bsr_handle* h, const float* inputs, const float* uv, con
   // colour decoder (model.py:264-269)
   L.conv<3, 3, 1, true, 2, 24, 1>(K_CONVT, "clr_up1", ws + p.r[5], V.cs_h, 0, V.cs_h, H8, W8, ws + p.f1, 128, 0, 128, 1, io_out);
   L.conv<3, 3, 1, true, 1, 32, 1>(K_CONVT, "clr_up2", ws + p.f1, 128, 0, 128, H4, W4, ws + p.f2, 96, 0, 96, 1, io_both);
-  L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "clr_up3", ws + p.f2, 96, 0, 96, H2, W2, ws + p.cf, CS_CF, 0, 64, 1, io_both);
+  if (winot) L.winot("clr_up3", 2, ws + p.f2, 96, H2, W2, ws + p.cf, CS_CF);
+  else L.conv<3, 3, 1, true, 2, 32, 1>(K_CONVT_NI2, "clr_up3", ws + p.f2, 96, 0, 96, H2, W2, ws + p.cf, CS_CF, 0, 64, 1, io_both);
   // clr_conv1 (3x3 over cat[gs, f]) + clr_conv2 + clr_conv3 + dif, one kernel (model.py:267-269,288)
   L.conv16<3, 3, true, true, 2>(K_CONV3, "clr_conv1", ws + p.cf, CS_CF, H, W, nullptr, 0, 1, gs, inputs, con_rgb, dif, packed);
   if (L.rc == BSR_OK) h->ran = true;
@@ -2001,6 +2073,35 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
   if ((long long)B * H * W * 128 * 4 >= (1LL << 31)) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: tensor too large");
   if (nw != 0 && nw != 2 && nw != 4 && nw != 8) return fail(BSR_ERR_ARG, "bsr_debug_wino_conv: nw must be 0 (automatic), 2, 4 or 8 waves per workgroup");
   HIP_TRY(bsr::launch_wino_conv2(wino_args(x, y, w, bias, H, W), B, static_cast<hipStream_t>(stream), nw));
+  return BSR_OK;
+}
+
+int bsr_debug_wino_convt(const float* x, const float* w_direct, const float* bias, float* y, int B, int H, int W, int cin, int cout, int in_cs,
+                         int out_cs, int act, void* stream) {
+  if (x == nullptr || w_direct == nullptr || bias == nullptr || y == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt: null argument");
+  if (const char* why = bsr::wino_convt_refusal(B, H, W, cin, cout, in_cs, out_cs)) return fail(BSR_ERR_ARG, std::string("bsr_debug_wino_convt: ") + why);
+  if ((long long)B * H * W * in_cs * 4 >= (1LL << 40)) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt: tensor too large");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::vector<float> u(wino_convt_floats(cin));
+  wino_convt_filter_transform(w_direct, u.data(), cin);
+  float* d_u = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_u), u.size() * sizeof(float)));
+  hipError_t e = hipMemcpy(d_u, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    bsr::WinoTArgs a{};
+    a.in = x; a.out = y; a.w = d_u; a.bias = bias; a.H = H; a.W = W; a.in_cs = in_cs; a.out_cs = out_cs; a.nchunk = cin / 16; a.act = act ? 1 : 0;
+    e = bsr::launch_wino_convt(a, B, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(d_u);
+  HIP_TRY(e);
+  return BSR_OK;
+}
+
+int bsr_debug_wino_convt_filter(const float* direct, float* out, int cin) {
+  if (direct == nullptr || out == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt_filter: null argument");
+  if (cin <= 0 || cin % 16 != 0) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt_filter: Cin must be a positive multiple of 16");
+  wino_convt_filter_transform(direct, out, cin);
   return BSR_OK;
 }
 

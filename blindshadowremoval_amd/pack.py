@@ -228,6 +228,39 @@ def pack_wino(kernel_tkn: np.ndarray, bias: np.ndarray):
     return arr, bias.astype(np.float32)
 
 
+# The transposed 3x3 layers (stride 2) in 25 products per 2x2 input patch instead of 36 (csrc/wino_convt.h).  Per axis
+# out(2i) = w0 x(i) + w2 x(i-1), out(2i+1) = w1 x(i); for the patch i = 2p:  t = Bt [x(i-1), x(i), x(i+1)],  u = G [w0, w1, w2],
+# m = t . u,  [out(2i) .. out(2i+3)] = At m.
+WINO_CONVT_BT = np.array([[0.0, 1, 0], [0, 0, 1], [1, -1, 0], [0, 1, 0], [0, 1, -1]])
+WINO_CONVT_G = np.array([[0.0, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 0, 0]])
+WINO_CONVT_AT = np.array([[0.0, 0, 1, 1, 0], [1, 0, 0, 0, 0], [0, 0, 0, 1, -1], [0, 1, 0, 0, 0]])
+
+
+def wino_convt_filter_transform(kernel_tkn: np.ndarray, dtype=np.float32) -> np.ndarray:
+    """A folded transposed 3x3 kernel [9 = (a, b), K, N] -> its 25 position matrices U[5 r + s] = sum_ab G[r, a] g[a, b] G[s, b],
+    [25, K, N], computed in float64 and rounded ONCE to ``dtype`` (float32 for the kernel)."""
+    taps, k, n = kernel_tkn.shape
+    assert taps == 9
+    g = kernel_tkn.astype(np.float64).reshape(3, 3, k, n)
+    return np.einsum("xa,abkn,yb->xykn", WINO_CONVT_G, g, WINO_CONVT_G).reshape(25, k, n).astype(dtype)
+
+
+def pack_wino_convt(kernel_tkn: np.ndarray, bias: np.ndarray):
+    """up2 / up3 / clr_up3 ([9, K, 64] folded, K a multiple of 16) as the weight stream of csrc/wino_convt.h, in the order a wave reads its
+    B fragments: [K / 16 chunks][25 positions 5 r + s][2 cout halves][2 K groups g][64 lanes 32 h + n][4 j] float32, where the element is
+    U[5 r + s, channel 16 chunk + 8 g + 4 h + j, cout 32 half + n].  Returns ([K / 16, 25, 2, 2, 64, 4], [64] bias).
+
+    Like pack_wino's, the stream is not a blob entry: bsr_create derives it, once per fp32 GSC handle, from the float32 weights of the
+    layer's direct image with this very arithmetic (bsr_api.hip: wino_convt_filter_transform).  This function is its statement;
+    tests/test_wino_convt_pack_cpu.py holds the library's transform to it."""
+    taps, k, n = kernel_tkn.shape
+    assert k % WINO_CC == 0 and n == 64
+    u = wino_convt_filter_transform(kernel_tkn.astype(np.float32))                    # [25, K, N]
+    u = u.reshape(25, k // WINO_CC, 2, 2, 4, 2, 32)                                   # [pos, chunk, g, h, j, half, n]
+    arr = np.ascontiguousarray(u.transpose(1, 0, 5, 2, 3, 6, 4)).reshape(k // WINO_CC, 25, 2, 2, 64, 4)
+    return arr, bias.astype(np.float32)
+
+
 KEYS_N = 288 + 256        # [y3 288 | q' 128 | g 128]
 KEYS_N_PAD = KEYS_N + 64  # + two zero tiles of slack (gemm_nloop group reads, NI = 3)
 

@@ -569,6 +569,16 @@ int bsr_debug_wino_conv(const float* x, const float* w, const float* bias, float
 /* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct image of each res<i>.conv2 of an
  * fp32 blob.  direct = the layer's [4][9][128][36] image (HOST pointer), out = [8][16][128][16] floats (HOST pointer). */
 int bsr_debug_wino_filter(const float* direct, float* out);
+/* Test hook (additive): the 25-product transposed-conv kernel of the fp32 GSC up2 / up3 / clr_up3 alone (csrc/wino_convt.h).
+ * x [B,H,W,in_cs] (cin channels read) -> y [B,2H,2W,out_cs] (channels 0..63 written, the rest untouched) =
+ * act(ConvT3x3_stride2_SAME(x) + bias), act != 0: LeakyReLU_0.3.  x, bias [64], y are device pointers; w_direct is the layer's direct
+ * image [ceil(cin / 32)][9][cout][36] as in the blob (HOST pointer): the entry transforms it as bsr_create does, launches and waits.
+ * H and W even, cin a multiple of 16, cout = 64, in_cs >= cin, out_cs >= 64; anything else is refused before any launch. */
+int bsr_debug_wino_convt(const float* x, const float* w_direct, const float* bias, float* y, int B, int H, int W, int cin, int cout, int in_cs,
+                         int out_cs, int act, void* stream);
+/* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct images of up2, up3 and clr_up3 of
+ * an fp32 GSC blob.  direct = the layer's [ceil(cin / 32)][9][64][36] image, out = [cin / 16][25][2][2][64][4] floats (HOST pointers). */
+int bsr_debug_wino_convt_filter(const float* direct, float* out, int cin);
 /* Test hook (additive, host only, no GPU call): the image bsr_create derives from each res<i>.c3q of an fp32 GSC / TSM blob for the
  * attention that takes conv2's output as its keys (env BSR_KEYS_CONV2, default on): N = [y3 288 | q' 128 | g 128 | 64 zero] with
  * q' = theta composed onto phi's weights in float64 (blindshadowremoval_amd.pack.compose_keys_c3q).  c3q_w = the layer's [4][1][768][36]
