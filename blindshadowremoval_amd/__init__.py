@@ -3,7 +3,7 @@
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
 __all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
-           "NonLocalGrad",           "generator_variable_shapes", "init_weights"]
+           "NonLocalGrad", "BottleneckGrad", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -31,4 +31,7 @@ def __getattr__(name):
     if name == "NonLocalGrad":
         from .nonlocal_grad_gpu import NonLocalGrad
         return NonLocalGrad
+    if name == "BottleneckGrad":
+        from .bottleneck_grad_gpu import BottleneckGrad
+        return BottleneckGrad
     raise AttributeError(name)

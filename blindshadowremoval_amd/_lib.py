@@ -124,6 +124,14 @@ SIGNATURES = {
     "bsr_nonlocal_grad_partials": (c_i, [c_i, c_i, c_i]),
     "bsr_nonlocal_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_v]),
     "bsr_debug_nonlocal_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_i, c_v]),
+    "bsr_bottleneck_grad_blob_bytes": (c_sz, []),
+    "bsr_bottleneck_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "bsr_bottleneck_grad_floats": (c_sz, []),
+    "bsr_bottleneck_grad_var_offset": (c_sz, [c_i]),
+    "bsr_bottleneck_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_bottleneck_grad_partials": (c_i, [c_i, c_i, c_i]),
+    "bsr_bottleneck_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
+    "bsr_debug_bottleneck_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
     "bsr_vgg_blob_bytes": (c_sz, []),
     "bsr_vgg_scratch_bytes": (c_sz, _BS),
     "bsr_vgg_act_offset": (c_sz, [c_i, c_i, c_i]),

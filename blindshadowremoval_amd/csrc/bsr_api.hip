@@ -45,6 +45,7 @@
 #include "clr_tail_grad_kernels.h"
 #include "clr_up_grad_kernels.h"
 #include "nonlocal_grad_kernels.h"
+#include "bottleneck_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1838,6 +1839,54 @@ int bsr_debug_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, c
                             void* stream) {
   return nonlocal_grad("bsr_debug_nonlocal_grad", device, d_blob, blob_bytes, y3x, y3x_cs, xin, xin_cs, out, out_cs, d_out, B, h, w, d_y3, d_skip, grads,
                        scratch, stop_after, stream);
+}
+
+size_t bsr_bottleneck_grad_blob_bytes(void) { return bsr::bn_blob_off(13) * sizeof(float); }
+
+size_t bsr_bottleneck_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::bn_plan(B, h, w).total : 0; }
+
+size_t bsr_bottleneck_grad_floats(void) { return bsr::bn_var_offset(bsr::kBnVars); }
+
+size_t bsr_bottleneck_grad_var_offset(int index) { return index < 0 || index >= bsr::kBnVars ? SIZE_MAX : bsr::bn_var_offset(index); }
+
+size_t bsr_bottleneck_grad_offset(int B, int h, int w, int map) {
+  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kBnMaps) return SIZE_MAX;
+  return bsr::bn_plan(B, h, w).map[map];
+}
+
+int bsr_bottleneck_grad_partials(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::bn_plan(B, h, w).P : 0; }
+
+namespace {
+
+int bottleneck_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3,
+                    const float* d_skip, int B, int h, int w, float* d_xin, float* grads, void* scratch, int stop_after, void* stream) {
+  return run_grad_stage(
+      name, {d_blob, xin, d_y3, d_xin, grads, scratch},
+      {{bsr::nl_size_ok(B, h, w),
+        "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 pixels in all"},
+       {blob_bytes == bsr_bottleneck_grad_blob_bytes(),
+        "blob_bytes must be bsr_bottleneck_grad_blob_bytes() (pack.pack_bottleneck_grad; the GSC width 261 only, not TSM's 877)"},
+       {xin_cs >= 261, "xin_cs must be at least 261"}},
+      {{16, "d_blob", {d_blob}}, {4, "xin, d_y3, d_skip, d_xin and grads", {xin, d_y3, d_skip, d_xin, grads}}}, scratch, stop_after,
+      bsr::kBnLaunches, device, [&] {
+        HIP_TRY(bsr::launch_bottleneck_grad(static_cast<const float*>(d_blob), xin, xin_cs, d_y3, d_skip, B, h, w, d_xin, grads, scratch, stop_after,
+                                            static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
+}  // namespace
+
+int bsr_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip, int B,
+                        int h, int w, float* d_xin, float* grads, void* scratch, void* stream) {
+  return bottleneck_grad("bsr_bottleneck_grad", device, d_blob, blob_bytes, xin, xin_cs, d_y3, d_skip, B, h, w, d_xin, grads, scratch, bsr::kBnLaunches,
+                         stream);
+}
+
+int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip,
+                              int B, int h, int w, float* d_xin, float* grads, void* scratch, int stop_after, void* stream) {
+  return bottleneck_grad("bsr_debug_bottleneck_grad", device, d_blob, blob_bytes, xin, xin_cs, d_y3, d_skip, B, h, w, d_xin, grads, scratch, stop_after,
+                         stream);
 }
 
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }

@@ -7,7 +7,10 @@ csrc/clr_up_grad_kernels.h is held to it (clr_decoder_gpu.ColourDecoder).  Below
 NonLocalBlock — theta, phi, g (1x1, 257 -> 128), softmax(theta phi^T) g, w (1x1, 128 -> 257), BN, z = y3 + w_y — then the block's zero-padded
 skip and relu3; `nonlocal_grad` is its statement, from the gradient at the block's output to the gradient at bnorm3's output y3, the gradient
 the skip carries to the block's input and the ten variables of the non-local block, any input width; csrc/nonlocal_grad_kernels.h is held to
-it (nonlocal_grad_gpu.NonLocalGrad)."""
+it (nonlocal_grad_gpu.NonLocalGrad).  Below that the lower half of the same block (model.py:84-101): conv1 (1x1, C -> 128), conv2 (3x3, 128 -> 128),
+conv3 (1x1, 128 -> 257), each with its BatchNormalization and the first two with a LeakyReLU; `bottleneck_grad` is its statement, from d_y3
+and d_skip to the gradient at the block's input and the twelve variables; csrc/bottleneck_grad_kernels.h is held to it
+(bottleneck_grad_gpu.BottleneckGrad)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -15,8 +18,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
-from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_decoder_trainable_names, generator_nonlocal_trainable_names,
-                      generator_tail_trainable_names)
+from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_decoder_trainable_names,
+                      generator_nonlocal_trainable_names, generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
@@ -419,3 +422,122 @@ def nonlocal_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261)
     xin = np.where(xin >= 0, xin, np.float32(LRELU_ALPHA) * xin).astype(np.float32)
     d_out = (rng.standard_normal((B, h, w, C)) / (B * h * w * C)).astype(np.float32)
     return y3, xin, d_out
+
+
+# ---- the lower half of res_stack/<block>: conv1/bnorm1/relu1, conv2/bnorm2/relu2, conv3/bnorm3
+BOTTLENECK_NORM_NAMES = ("d_xin",) + tuple(generator_bottleneck_trainable_names())
+
+
+def bottleneck_bn_vectors(weights: Dict[str, np.ndarray], j: int, block: int = 5, dtype=np.float64):
+    """(conv<j>'s bias, inv, moving_mean, rstd, gamma, beta) of res_stack/<block>'s layer j = 1, 2, 3 in `dtype`."""
+    T = dtype
+    st = "res_stack/%d/" % block
+    gamma, beta, mean, var = (np.asarray(weights[st + "bnorm%d/%s" % (j, p)], T) for p in ("gamma", "beta", "moving_mean", "moving_variance"))
+    rstd = T(1) / np.sqrt(var + T(BN_EPS))
+    return np.asarray(weights[st + "conv%d/bias" % j], T), gamma * rstd, mean, rstd, gamma, beta
+
+
+def bottleneck_forward(weights: Dict[str, np.ndarray], xin, block: int = 5, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """xin [B,h,w,C] (the block's input; C is conv1's width, 261 for GSC, 877 for TSM) -> dict(c1, a1, c2, a2 [B,h,w,128], c3, y3
+    [B,h,w,257]) in `dtype`:
+      c1 = xin W1 + b1,  a1 = lrelu_0.3((c1 - mean1) rstd1 gamma1 + beta1)
+      c2 = conv3x3_same(a1, K2) + b2,  a2 = lrelu_0.3(bn2(c2))
+      c3 = a2 W3 + b3,  y3 = bn3(c3)
+    with rstd = 1 / sqrt(moving_variance + eps)."""
+    T = dtype
+    st = "res_stack/%d/" % block
+    x = np.asarray(xin, T)
+    K1, K2, K3 = (np.asarray(weights[st + "conv%d/kernel" % j], T) for j in (1, 2, 3))
+    out: Dict[str, np.ndarray] = {}
+    h = x
+    for j, K in ((1, K1), (2, K2), (3, K3)):
+        bias, _, mean, rstd, gamma, beta = bottleneck_bn_vectors(weights, j, block, T)
+        c = (conv3x3_same(h, K) if j == 2 else h @ K[0, 0]) + bias
+        z = (c - mean) * rstd * gamma + beta
+        out["c%d" % j] = c
+        if j < 3:
+            h = _lrelu(z)
+            out["a%d" % j] = h
+        else:
+            out["y3"] = z
+    return out
+
+
+def bottleneck_grad(weights: Dict[str, np.ndarray], xin, d_y3, d_skip=None, block: int = 5, acts: Optional[Dict[str, np.ndarray]] = None,
+                    dtype=np.float64) -> Dict[str, np.ndarray]:
+    """The gradient d_y3 [B,h,w,257] at bnorm3's output and d_skip [B,h,w,C] (what the block's skip carries to its input; None: zero) ->
+    dict(the twelve variables of weights.generator_bottleneck_trainable_names(block) in their own shapes, `d_xin` [B,h,w,C] the gradient at
+    the block's input, and the stage maps `gz2`, `gz1` [B,h,w,128] and `a1`, `a2` as used), float64 from the float32 variables (`dtype`
+    float32 runs the same arithmetic in float32).  Per layer j, gz the gradient at that BN's output and Wg the unscaled kernel gradient:
+      S = sum gz;  d beta = S;  d bias = inv S;  d kernel = Wg inv[o];  d gamma = ((KW + bias S) - mean S) rstd, KW[o] = sum K[..., o] Wg[..., o]
+    in this order:
+      layer 3   gz = d_y3;  Wg3 = a2^T d_y3
+      layer 2   gz2 = leaky_grad((d_y3 inv3) W3^T, a2);  Wg2 = conv3x3_same_wgrad(a1, gz2)
+      layer 1   gz1 = leaky_grad(conv3x3_same_dgrad(gz2 inv2, K2), a1);  Wg1 = xin^T gz1;  d_xin = d_skip + (gz1 inv1) W1^T
+    An activation of exactly +-0 takes the slope.  With `acts` given (a dict with `a1` and `a2`, for example the device's), the masks and
+    the inputs of Wg2 and Wg3 are read from them."""
+    T = dtype
+    st = "res_stack/%d/" % block
+    x = np.asarray(xin, T)
+    if acts is not None:
+        a1, a2 = np.asarray(acts["a1"], T), np.asarray(acts["a2"], T)
+    else:
+        fw = bottleneck_forward(weights, x, block, T)
+        a1, a2 = fw["a1"], fw["a2"]
+    K1, K2, K3 = (np.asarray(weights[st + "conv%d/kernel" % j], T) for j in (1, 2, 3))
+    ax = (0, 1, 2)
+    out: Dict[str, np.ndarray] = {"a1": a1, "a2": a2}
+
+    def layer(j, K, gz, Wg):
+        bias, inv, mean, rstd, _, _ = bottleneck_bn_vectors(weights, j, block, T)
+        S = gz.sum(axis=ax)
+        KW = (K * Wg).sum(axis=(0, 1, 2))
+        out[st + "conv%d/kernel" % j] = (Wg * inv).astype(T)
+        out[st + "conv%d/bias" % j] = inv * S
+        out[st + "bnorm%d/gamma" % j] = ((KW + bias * S) - mean * S) * rstd
+        out[st + "bnorm%d/beta" % j] = S
+        return inv
+
+    gz3 = np.asarray(d_y3, T)
+    inv3 = layer(3, K3, gz3, np.tensordot(a2, gz3, axes=(ax, ax)).reshape(K3.shape).astype(T))
+    gz2 = leaky_grad(((gz3 * inv3) @ K3[0, 0].T).astype(T), a2)
+    out["gz2"] = gz2
+    inv2 = layer(2, K2, gz2, conv3x3_same_wgrad(a1, gz2).astype(T))
+    gz1 = leaky_grad(conv3x3_same_dgrad(gz2 * inv2, K2).astype(T), a1)
+    out["gz1"] = gz1
+    inv1 = layer(1, K1, gz1, np.tensordot(x, gz1, axes=(ax, ax)).reshape(K1.shape).astype(T))
+    dx = ((gz1 * inv1) @ K1[0, 0].T).astype(T)
+    out["d_xin"] = dx if d_skip is None else np.asarray(d_skip, T) + dx
+    return out
+
+
+def bottleneck_objective_f64(weights: Dict[str, np.ndarray], xin, d_y3, d_skip=None, block: int = 5, masks: Optional[list] = None,
+                             dtype=np.float64):
+    """<d_y3, y3> + <d_skip, xin> in `dtype` with no float32 rounding anywhere: the scalar whose gradient bottleneck_grad states.  A list
+    given as `masks` receives the two LeakyReLU masks (z > 0) of a1 and a2."""
+    fw = bottleneck_forward(weights, xin, block, dtype)
+    if masks is not None:
+        masks += [fw["a1"] > 0, fw["a2"] > 0]
+    s = (np.asarray(d_y3, dtype) * fw["y3"]).sum()
+    if d_skip is not None:
+        s = s + (np.asarray(d_skip, dtype) * np.asarray(xin, dtype)).sum()
+    return s
+
+
+def bottleneck_norms(grads: Dict[str, np.ndarray], block: int = 5) -> Dict[str, Tuple[float, float]]:
+    """name -> (L1, L-infinity) of `d_xin` and each of the twelve variable gradients (BOTTLENECK_NORM_NAMES for block 5)."""
+    out = {}
+    for name in ("d_xin",) + tuple(generator_bottleneck_trainable_names(block)):
+        m = np.abs(np.asarray(grads[name], np.float64))
+        out[name] = (float(m.sum()), float(m.max()))
+    return out
+
+
+def bottleneck_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
+    """Seeded (xin [B,h,w,C], d_y3 [B,h,w,257], d_skip [B,h,w,C]) float32 at a coarse grid: xin like a LeakyReLU output."""
+    rng = np.random.default_rng(4000 + seed)
+    xin = rng.standard_normal((B, h, w, C)).astype(np.float32)
+    xin = np.where(xin >= 0, xin, np.float32(LRELU_ALPHA) * xin).astype(np.float32)
+    d_y3 = (rng.standard_normal((B, h, w, RES_CH)) / (B * h * w * RES_CH)).astype(np.float32)
+    d_skip = (rng.standard_normal((B, h, w, C)) / (B * h * w * C)).astype(np.float32)
+    return xin, d_y3, d_skip

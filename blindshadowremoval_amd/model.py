@@ -248,6 +248,12 @@ class Generator:
                                              ctypes.byref(x_cs), ctypes.byref(shape)), "bsr_last_block5")
         return tuple(int(p.value) for p in ptrs), (int(y_cs.value), int(x_cs.value), int(x_cs.value)), (shape[0], shape[1], shape[2], shape[3])
 
+    def last_block5_input(self) -> Tuple[int, int, Tuple[int, int, int, int]]:
+        """(xin's device address, its floats between pixels, (B, H/8, W/8, 261)) of res_stack/5's input in the handle's workspace: what
+        last_block5 gives for xin, under the same conditions."""
+        ptrs, strides, shape = self.last_block5()
+        return ptrs[1], strides[1], shape
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

@@ -67,17 +67,17 @@ def loss_record(three, gan, per) -> Dict[str, float]:
 
 # the stages of the generator's backward pass from the output down: generator_grad's <STAGE>_NORM_NAMES and <stage>_norms, and here
 # <stage>_grad_names() and the routes' <stage>_norms
-STAGES = ("tail", "decoder", "nonlocal")
+STAGES = ("tail", "decoder", "nonlocal", "bottleneck")
 
 
 def stage_grad_names(stage: str) -> List[str]:
     """`<name>_l1`, `<name>_linf` for generator_grad's <STAGE>_NORM_NAMES: the stage's data gradients (tail: d_f, d_gs; decoder: d_x;
-    nonlocal: d_y3, d_skip), then its variables."""
+    nonlocal: d_y3, d_skip; bottleneck: d_xin), then its variables."""
     from . import generator_grad
     return [n + s for n in getattr(generator_grad, stage.upper() + "_NORM_NAMES") for s in ("_l1", "_linf")]
 
 
-tail_grad_names, decoder_grad_names, nonlocal_grad_names = (functools.partial(stage_grad_names, stage) for stage in STAGES)
+tail_grad_names, decoder_grad_names, nonlocal_grad_names, bottleneck_grad_names = (functools.partial(stage_grad_names, stage) for stage in STAGES)
 
 
 def _stage_norms(stage: str, grads) -> List[float]:
@@ -91,7 +91,7 @@ def _stage_norms(stage: str, grads) -> List[float]:
 class HostRoute:
     """The objective over the three host statements, on numpy arrays."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False):
         self.disc_w, self.vgg_w, self.gen_w = disc_w, vgg_w, gen_w
         self.decoder = decoder                 # --decoder: bring also copies the decoder's kept tensors
         self.nonlocal_ = nonlocal_             # --nonlocal: and res_stack/5's
@@ -143,21 +143,30 @@ class HostRoute:
         from .generator_grad import nonlocal_grad
         xin = self.block5["res4"]
         y3 = (self.block5["y3x5"][..., :257] - xin[..., :257]).astype(f32)
-        return _stage_norms("nonlocal", nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]}))
+        grads = nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]})
+        self.d_y3, self.d_skip = grads["d_y3"], grads["d_skip"]
+        return _stage_norms("nonlocal", grads)
+
+    def bottleneck_norms(self) -> List[float]:
+        """bottleneck_grad_names() of the last nonlocal_norms' d_y3 and d_skip taken through res_stack/5's lower half at the generator's
+        kept res4."""
+        from .generator_grad import bottleneck_grad
+        return _stage_norms("bottleneck", bottleneck_grad(self.gen_w, self.block5["res4"], self.d_y3, self.d_skip))
 
 
 class DeviceRoute:
     """The objective over TrainLosses, Discriminators, Perceptual and ColourTail, on tensors of the device; f is read in the generator's workspace."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False):
         import torch
-        from . import ColourDecoder, ColourTail, Discriminators, NonLocalGrad, Perceptual, TrainLosses
+        from . import BottleneckGrad, ColourDecoder, ColourTail, Discriminators, NonLocalGrad, Perceptual, TrainLosses
         self.dev = torch.device("cuda", device)
         self.three, self.gan, self.per = TrainLosses(device), Discriminators(device), Perceptual(device)
         self.gan.load_weights(disc_w)
         self.per.load_weights(vgg_w)
         if gen_w is not None:
-            for name, stage, wanted in (("tail", ColourTail, True), ("dec", ColourDecoder, decoder), ("nl", NonLocalGrad, nonlocal_)):
+            for name, stage, wanted in (("tail", ColourTail, True), ("dec", ColourDecoder, decoder), ("nl", NonLocalGrad, nonlocal_),
+                                       ("bn", BottleneckGrad, bottleneck)):
                 if wanted:
                     setattr(self, name, stage(device))
                     getattr(self, name).load_weights(gen_w)
@@ -193,7 +202,12 @@ class DeviceRoute:
         return _stage_norms("decoder", res)
 
     def nonlocal_norms(self) -> List[float]:
-        return _stage_norms("nonlocal", self.nl.backward(self.generator, self.d_x))
+        res = self.nl.backward(self.generator, self.d_x)
+        self.d_y3, self.d_skip = res["d_y3"], res["d_skip"]
+        return _stage_norms("nonlocal", res)
+
+    def bottleneck_norms(self) -> List[float]:
+        return _stage_norms("bottleneck", self.bn.backward(self.generator, self.d_y3, self.d_skip))
 
 
 def _norms(grad) -> List[float]:
@@ -287,17 +301,19 @@ def score_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: 
 
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
                  quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False, decoder: bool = False,
-                 nonlocal_: bool = False) -> Dict[str, float]:
+                 nonlocal_: bool = False, bottleneck: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the other weights come from the latest checkpoint under `ckpt`, from init_weights and
-    init_discriminator_weights without it.  `grad`, `grad_total`, `tail`, `decoder` and `nonlocal_` add to each batch's line what --grad, --grad-total, --tail, --decoder and
-    --nonlocal do."""
+    init_discriminator_weights without it.  `grad`, `grad_total`, `tail`, `decoder`, `nonlocal_` and `bottleneck` add to each batch's line what
+    --grad, --grad-total, --tail, --decoder, --nonlocal and --bottleneck do."""
     if tail and not grad_total:
         raise ValueError("perceptual: --tail goes with --grad-total")
     if decoder and not tail:
         raise ValueError("perceptual: --decoder goes with --grad-total --tail")
     if nonlocal_ and not decoder:
         raise ValueError("perceptual: --nonlocal goes with --grad-total --tail --decoder")
+    if bottleneck and not nonlocal_:
+        raise ValueError("perceptual: --bottleneck goes with --grad-total --tail --decoder --nonlocal")
     vgg_w = load_vgg_weights(vgg)
     gen_w = None
     if tail:
@@ -305,8 +321,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         from .weights import init_weights
         gen_w = init_weights(1) if ckpt is None else load_generator_weights(latest_checkpoint(ckpt))
     disc_w = discriminator_weights(ckpt, "perceptual")
-    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_) if host
-             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_))
+    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck) if host
+             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck))
 
     def step(*tensors):
         arrays, f = route.bring(*tensors)
@@ -315,7 +331,7 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
             return loss_record(three, gan, per), list(zip(GRAD_NAMES, _norms(g))) if grad else []
         three, gan, per, grad_con, grad_gs = route.total_grad(*arrays)
         extras = list(zip(TOTAL_GRAD_NAMES, _norms(grad_con) + _norms(grad_gs)))
-        for stage, wanted, args in zip(STAGES, (tail, decoder, nonlocal_), ((arrays[3], f, grad_con, grad_gs), (), ())):
+        for stage, wanted, args in zip(STAGES, (tail, decoder, nonlocal_, bottleneck), ((arrays[3], f, grad_con, grad_gs), (), (), ())):
             if wanted:
                 extras += zip(stage_grad_names(stage), getattr(route, stage + "_norms")(*args))
         return loss_record(three, gan, per), extras
@@ -337,6 +353,7 @@ def main(argv=None) -> int:
     ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
     ap.add_argument("--decoder", action="store_true", help="with --grad-total --tail: also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients")
     ap.add_argument("--nonlocal", dest="nonlocal_", action="store_true", help="with --grad-total --tail --decoder: also the norms of d g_total_loss / d y3 at res_stack/5's bnorm3 output, of what the block's skip carries to its input, and of the non-local block's ten variable gradients")
+    ap.add_argument("--bottleneck", action="store_true", help="with --grad-total --tail --decoder --nonlocal: also the norms of d g_total_loss / d xin at res_stack/5's input and of the twelve variable gradients of the block's conv1, conv2, conv3 and their batch norms")
     a = ap.parse_args(argv)
     if a.tail and not a.grad_total:
         ap.error("--tail goes with --grad-total")
@@ -344,8 +361,10 @@ def main(argv=None) -> int:
         ap.error("--decoder goes with --grad-total --tail")
     if a.nonlocal_ and not a.decoder:
         ap.error("--nonlocal goes with --grad-total --tail --decoder")
+    if a.bottleneck and not a.nonlocal_:
+        ap.error("--bottleneck goes with --grad-total --tail --decoder --nonlocal")
     means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder,
-                         nonlocal_=a.nonlocal_)
+                         nonlocal_=a.nonlocal_, bottleneck=a.bottleneck)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

@@ -899,6 +899,92 @@ def unpack_nonlocal_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the generator's bottleneck backward (csrc/bottleneck_grad_kernels.h): a blob of its own, no header, float32 ----
+BOTTLENECK_TSM_TEXT = "the bottleneck's device chain takes the GSC width only (TSM's 877 is covered by generator_grad.bottleneck_grad)"
+BOTTLENECK_BLOCK_TEXT = "block must be 3, 4 or 5 (the colour branch's blocks share their shapes), got %r"
+
+
+def bottleneck_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the bottleneck's gradient blob, d = 128, taps in row-major order t = 3 a + b:
+      w1f   [272][128]     the BN-folded FORWARD image of conv1: w1f[c][k] = W1[c][k] inv1[k] (rows 261..271 zero)
+      b1f   [128]          (b1 - mean1) inv1 + beta1
+      w2f   [9][128][128]  the folded forward image of conv2: w2f[t][c][o] = K2[a][b][c][o] inv2[o]
+      b2f   [128]          (b2 - mean2) inv2 + beta2
+      w3t   [272][128]     conv3 for the data gradient: w3t[n][k] = inv3[n] W3[k][n] (rows 257..271 zero)
+      w2t   [9][128][128]  conv2 for the data gradient, taps turned by 180 degrees, channel roles swapped:
+                           w2t[t][o][c] = inv2[o] K2[2 - a][2 - b][c][o]
+      w1t   [128][384]     conv1 for the data gradient: w1t[k][c] = inv1[k] W1[c][k] (columns 261.. zero)
+      k1    [261][128], k2 [9][128][128], k3 [128][257]   the three kernels in the variables' own order (d gamma is formed from them)
+      vecs1 [4][128], vecs2 [4][128], vecs3 [4][257]      per layer: bias, inv, moving_mean, rstd
+    inv, rstd and every folded image are formed in float64 and rounded once."""
+    out, off = [], 0
+    for name, shape in (("w1f", (NONLOCAL_CP, 128)), ("b1f", (128,)), ("w2f", (9, 128, 128)), ("b2f", (128,)), ("w3t", (NONLOCAL_CP, 128)),
+                        ("w2t", (9, 128, 128)), ("w1t", (128, 384)), ("k1", (261, 128)), ("k2", (9, 128, 128)), ("k3", (128, 257)),
+                        ("vecs1", (4, 128)), ("vecs2", (4, 128)), ("vecs3", (4, 257))):
+        out.append((name, off, shape))
+        off += int(np.prod(shape))
+    return out, off
+
+
+def bottleneck_grad_record(weights: Dict[str, np.ndarray], block: int = 5) -> Dict[str, np.ndarray]:
+    """name -> float32 array of bottleneck_grad_layout's shapes.  ValueError for shapes other than the GSC generator's."""
+    from .weights import BN_EPS
+    if block not in (3, 4, 5):
+        raise ValueError(BOTTLENECK_BLOCK_TEXT % (block,))
+    st = "res_stack/%d/" % block
+    k = {}
+    for j, shape in ((1, (1, 1, 261, 128)), (2, (3, 3, 128, 128)), (3, (1, 1, 128, 257))):
+        k[j] = np.asarray(weights[st + "conv%d/kernel" % j], np.float64)
+        if k[j].shape != shape:
+            raise ValueError("%sconv%d/kernel must be %s, got %s" % (st, j, list(shape), k[j].shape))
+    vec = {}
+    for j in (1, 2, 3):
+        bias = np.asarray(weights[st + "conv%d/bias" % j], np.float64)
+        gamma, beta, mean, var = (np.asarray(weights[st + "bnorm%d/%s" % (j, p)], np.float64)
+                                  for p in ("gamma", "beta", "moving_mean", "moving_variance"))
+        rstd = 1.0 / np.sqrt(var + BN_EPS)
+        vec[j] = (bias, gamma * rstd, mean, rstd, beta)
+    inv1, inv2, inv3 = vec[1][1], vec[2][1], vec[3][1]
+    w1, w2, w3 = k[1][0, 0], k[2].reshape(9, 128, 128), k[3][0, 0]
+    w1f = np.zeros((NONLOCAL_CP, 128), np.float64)
+    w1f[:261] = w1 * inv1[None, :]
+    w3t = np.zeros((NONLOCAL_CP, 128), np.float64)
+    w3t[:257] = (w3 * inv3[None, :]).T
+    w1t = np.zeros((128, 384), np.float64)
+    w1t[:, :261] = (w1 * inv1[None, :]).T
+    w2f = w2 * inv2[None, None, :]
+    rec = {"w1f": w1f, "b1f": (vec[1][0] - vec[1][2]) * inv1 + vec[1][4], "w2f": w2f, "b2f": (vec[2][0] - vec[2][2]) * inv2 + vec[2][4],
+           "w3t": w3t, "w2t": np.transpose(w2f[::-1], (0, 2, 1)), "w1t": w1t, "k1": w1, "k2": w2, "k3": w3}
+    for j in (1, 2, 3):
+        rec["vecs%d" % j] = np.stack(vec[j][:4])
+    return {name: np.ascontiguousarray(a, np.float32) for name, a in rec.items()}
+
+
+def pack_bottleneck_grad(weights: Dict[str, np.ndarray], block: int = 5) -> bytes:
+    """The generator's variables (res_stack/<block>'s 18 outside non_local are read; block 3, 4 or 5) -> the blob bsr_bottleneck_grad
+    takes (bottleneck_grad_layout).  ValueError for TSM weights: the chain's input is 261 wide."""
+    if block not in (3, 4, 5):
+        raise ValueError(BOTTLENECK_BLOCK_TEXT % (block,))
+    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, 261, 128):
+        raise ValueError(BOTTLENECK_TSM_TEXT)
+    layout, total = bottleneck_grad_layout()
+    rec = bottleneck_grad_record(weights, block)
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        assert rec[name].shape == tuple(shape), name
+        blob[off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_bottleneck_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_bottleneck_grad: bottleneck_grad_record's dict."""
+    layout, total = bottleneck_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a bottleneck gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

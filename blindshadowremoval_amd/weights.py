@@ -139,6 +139,15 @@ def generator_nonlocal_trainable_names(block: int = 5, variant: str = "gsc") -> 
     return [n for n in generator_variable_shapes(variant) if n.startswith(stem) and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_bottleneck_trainable_names(block: int = 5, variant: str = "gsc") -> List[str]:
+    """The twelve trainable variables of res_stack/<block>'s bottleneck convolutions in generator_variable_shapes' order, 215 299 floats
+    for GSC: the kernel and bias of conv1, conv2, conv3 and the gamma and beta of bnorm1, bnorm2, bnorm3; the non-local block's are
+    generator_nonlocal_trainable_names', and moving_mean and moving_variance take no gradient."""
+    stem = "res_stack/%d/" % block
+    return [n for n in generator_variable_shapes(variant)
+            if n.startswith(stem) and not n.startswith(stem + "non_local/") and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
 DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
 DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)

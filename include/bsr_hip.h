@@ -415,6 +415,31 @@ int bsr_debug_nonlocal_grad(int device, const void* d_blob, size_t blob_bytes, c
                             int out_cs, const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, int stop_after,
                             void* stream);
 
+/* The backward of the lower half of the generator's res_stack/5 (training=False, fp32, GSC width): conv1/bnorm1/relu1 (1x1, 261 -> 128),
+ * conv2/bnorm2/relu2 (3x3, 128 -> 128), conv3/bnorm3 (1x1, 128 -> 257) and the sum with what the skip carries.  d_blob:
+ * bsr_bottleneck_grad_blob_bytes() bytes of pack.pack_bottleneck_grad (GSC width only; block 3, 4 or 5: their shapes are the same), 16-byte
+ * aligned; xin [B,h,w,261 of xin_cs] the block's input, d_y3 dense [B,h,w,257] the gradient at bnorm3's output, d_skip dense [B,h,w,261]
+ * or null for none.  Outputs: d_xin dense [B,h,w,261] and grads, bsr_bottleneck_grad_floats() float32: the twelve variables of
+ * weights.generator_bottleneck_trainable_names() in that order, each dense in its own shape, variable `index` (0..11) at float offset
+ * bsr_bottleneck_grad_var_offset(index); SIZE_MAX out of range.  The chain forms a1 and a2 again from xin and reads nothing else of the
+ * forward.  Twelve launches on `stream`, one after the other (csrc/bottleneck_grad_kernels.h), no host synchronisation, no floating-point
+ * atomics: a call repeats its bits.  scratch: bsr_bottleneck_grad_scratch_bytes(B, h, w) bytes, 256-byte aligned; every word read is
+ * written earlier in the same call.  bsr_bottleneck_grad_offset(B, h, w, map) is the byte offset of map 0 xin [N][272], 1 d_y3 [N][272],
+ * 2 a1, 3 a2, 4 gz2, 5 gz1 [N][128], 6 the three kernel gradients before the BN factor (float64 [261 x 128 | 9 x 128 x 128 | 128 x 257]),
+ * 7 the column sums of gz1, gz2, d_y3 (float64 [128 | 128 | 257]); SIZE_MAX out of range.  bsr_bottleneck_grad_partials(B, h, w) is the
+ * number of row slices of the three kernel gradients (0 for bad arguments).  A bad argument gives BSR_ERR_ARG with a message and nothing
+ * launched.  bsr_debug_bottleneck_grad stops after `stop_after` (0..12) of the launches. */
+size_t bsr_bottleneck_grad_blob_bytes(void);
+size_t bsr_bottleneck_grad_scratch_bytes(int B, int h, int w);
+size_t bsr_bottleneck_grad_floats(void);
+size_t bsr_bottleneck_grad_var_offset(int index);
+size_t bsr_bottleneck_grad_offset(int B, int h, int w, int map);
+int bsr_bottleneck_grad_partials(int B, int h, int w);
+int bsr_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip, int B,
+                        int h, int w, float* d_xin, float* grads, void* scratch, void* stream);
+int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip,
+                              int B, int h, int w, float* d_xin, float* grads, void* scratch, int stop_after, void* stream);
+
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
  * statement and writes the arithmetic out.  d_blob: the device copy of pack.pack_vgg's blob, blob_bytes = bsr_vgg_blob_bytes() (about
