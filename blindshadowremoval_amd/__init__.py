@@ -3,7 +3,7 @@
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
 __all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
-           "NonLocalGrad", "BottleneckGrad", "generator_variable_shapes", "init_weights"]
+           "NonLocalGrad", "BottleneckGrad", "HeadsGrad", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -34,4 +34,7 @@ def __getattr__(name):
     if name == "BottleneckGrad":
         from .bottleneck_grad_gpu import BottleneckGrad
         return BottleneckGrad
+    if name == "HeadsGrad":
+        from .heads_grad_gpu import HeadsGrad
+        return HeadsGrad
     raise AttributeError(name)

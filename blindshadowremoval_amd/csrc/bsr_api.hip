@@ -46,6 +46,7 @@
 #include "clr_up_grad_kernels.h"
 #include "nonlocal_grad_kernels.h"
 #include "bottleneck_grad_kernels.h"
+#include "heads_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
 
@@ -1889,6 +1890,50 @@ int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes,
                          stream);
 }
 
+size_t bsr_heads_grad_blob_bytes(void) { return (size_t)bsr::kHgBlobFloats * sizeof(float); }
+
+size_t bsr_heads_grad_scratch_bytes(int B, int H, int W) { return bsr::hg_size_ok(B, H, W) ? bsr::hg_plan(B, H, W).total : 0; }
+
+size_t bsr_heads_grad_floats(void) { return bsr::hg_var_offset(bsr::kHgVars); }
+
+size_t bsr_heads_grad_var_offset(int index) { return index < 0 || index >= bsr::kHgVars ? SIZE_MAX : bsr::hg_var_offset(index); }
+
+size_t bsr_heads_grad_offset(int B, int H, int W, int map) {
+  if (!bsr::hg_size_ok(B, H, W) || map < 0 || map >= bsr::kHgMaps) return SIZE_MAX;
+  return bsr::hg_plan(B, H, W).map[map];
+}
+
+int bsr_heads_grad_partials(int B, int H, int W) { return bsr::hg_size_ok(B, H, W) ? bsr::hg_plan(B, H, W).P : 0; }
+
+namespace {
+
+int heads_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
+               const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, int stop_after, void* stream) {
+  return run_grad_stage(
+      name, {d_blob, inputs, mask22, y, d_gs, d_y, grads, scratch},
+      {{bsr::hg_size_ok(B, H, W), "B must be positive, H a multiple of 8 and W a multiple of 32 (the forward heads' tile), at most 2^26 pixels in all"},
+       {blob_bytes == bsr_heads_grad_blob_bytes(), "blob_bytes must be bsr_heads_grad_blob_bytes() (pack.pack_heads_grad)"},
+       {y_cs >= 64 && y_cs % 4 == 0, "y_cs must be a multiple of 4 and at least 64"}},
+      {{16, "d_blob, y and d_y", {d_blob, y, d_y}}, {4, "inputs, mask22, d_gs and grads", {inputs, mask22, d_gs, grads}}}, scratch, stop_after,
+      bsr::kHgLaunches, device, [&] {
+        HIP_TRY(bsr::launch_heads_grad(static_cast<const float*>(d_blob), inputs, mask22, y, y_cs, d_gs, B, H, W, d_y, grads, scratch, stop_after,
+                                       static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
+}  // namespace
+
+int bsr_heads_grad(int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
+                   const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, void* stream) {
+  return heads_grad("bsr_heads_grad", device, d_blob, blob_bytes, inputs, mask22, y, y_cs, d_gs, B, H, W, d_y, grads, scratch, bsr::kHgLaunches, stream);
+}
+
+int bsr_debug_heads_grad(int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
+                         const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, int stop_after, void* stream) {
+  return heads_grad("bsr_debug_heads_grad", device, d_blob, blob_bytes, inputs, mask22, y, y_cs, d_gs, B, H, W, d_y, grads, scratch, stop_after, stream);
+}
+
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
 
 size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
@@ -2294,6 +2339,17 @@ int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]) {
   if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_f: no forward has run on this handle");
   *f = h->ws + h->plan.cf;
   *f_cs = CS_CF;
+  shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
+  return BSR_OK;
+}
+
+int bsr_last_y(bsr_handle* h, const float** y, int* y_cs, int shape4[4]) {
+  if (h == nullptr || y == nullptr || y_cs == nullptr || shape4 == nullptr) return fail(BSR_ERR_ARG, "bsr_last_y: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_y: an RGB handle has no grey heads");
+  if (h->dtype != BSR_DTYPE_F32) return fail(BSR_ERR_STATE, "bsr_last_y: y is an fp32 tensor of BSR_DTYPE_F32 handles only (the 16-bit modes keep it as fp16)");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_y: no forward has run on this handle");
+  *y = h->ws + h->plan.ybuf;
+  *y_cs = h->var.cs_y;
   shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
   return BSR_OK;
 }

@@ -10,7 +10,9 @@ the skip carries to the block's input and the ten variables of the non-local blo
 it (nonlocal_grad_gpu.NonLocalGrad).  Below that the lower half of the same block (model.py:84-101): conv1 (1x1, C -> 128), conv2 (3x3, 128 -> 128),
 conv3 (1x1, 128 -> 257), each with its BatchNormalization and the first two with a LeakyReLU; `bottleneck_grad` is its statement, from d_y3
 and d_skip to the gradient at the block's input and the twelve variables; csrc/bottleneck_grad_kernels.h is held to it
-(bottleneck_grad_gpu.BottleneckGrad)."""
+(bottleneck_grad_gpu.BottleneckGrad).  On the grey branch the heads (model.py:246-250): conv2 (7x7, 64 -> 1, tanh) gives mask, conv3
+(7x7, 64 -> 1) gives con, gs = gray(inputs) (1 + mask) + con; `heads_grad` is its statement, from the complete d_gs to the gradient at up3's
+output y and the four variables; csrc/heads_grad_kernels.h is held to it (heads_grad_gpu.HeadsGrad)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -19,7 +21,7 @@ import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
 from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_decoder_trainable_names,
-                      generator_nonlocal_trainable_names, generator_tail_trainable_names)
+                      generator_heads_trainable_names, generator_nonlocal_trainable_names, generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
@@ -541,3 +543,130 @@ def bottleneck_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 26
     d_y3 = (rng.standard_normal((B, h, w, RES_CH)) / (B * h * w * RES_CH)).astype(np.float32)
     d_skip = (rng.standard_normal((B, h, w, C)) / (B * h * w * C)).astype(np.float32)
     return xin, d_y3, d_skip
+
+
+# ---- the grey heads: conv2 (mask), conv3 (con), gs
+HEADS_NORM_NAMES = ("d_y",) + tuple(generator_heads_trainable_names())
+
+
+def convk_same(x: np.ndarray, kernel: np.ndarray) -> np.ndarray:
+    """conv3x3_same for any odd k: [N,H,W,C] x HWIO [k,k,C,O] -> [N,H,W,O] in x's type: stride 1, zero outside the image, no bias; taps in
+    index order.  The image may be narrower than the window."""
+    n, h, w, c = x.shape
+    k = kernel.shape[0]
+    r = k // 2
+    xp = np.zeros((n, h + 2 * r, w + 2 * r, c), x.dtype)
+    xp[:, r:r + h, r:r + w] = x
+    out = np.zeros((n, h, w, kernel.shape[3]), x.dtype)
+    for a in range(k):
+        for b in range(k):
+            out += xp[:, a:a + h, b:b + w] @ kernel[a, b].astype(x.dtype)
+    return out
+
+
+def convk_same_wgrad(x: np.ndarray, gy: np.ndarray, k: int = 7, dtype=np.float64) -> np.ndarray:
+    """conv3x3_same_wgrad for any odd k: the input [N,H,W,C] of a k x k stride-1 SAME convolution and the gradient [N,H,W,O] at its output
+    -> `dtype` [k,k,C,O]: gk[a, b, c, o] = sum x[n, i + a - r, j + b - r, c] gy[n, i, j, o], r = k // 2, zero outside the image."""
+    x, gy = np.asarray(x, dtype), np.asarray(gy, dtype)
+    n, h, w, c = x.shape
+    r = k // 2
+    xp = np.zeros((n, h + 2 * r, w + 2 * r, c), dtype)
+    xp[:, r:r + h, r:r + w] = x
+    out = np.zeros((k, k, c, gy.shape[3]), dtype)
+    for a in range(k):
+        for b in range(k):
+            out[a, b] = np.tensordot(xp[:, a:a + h, b:b + w], gy, axes=([0, 1, 2], [0, 1, 2]))
+    return out
+
+
+def convk_same_dgrad(gy: np.ndarray, kernel: np.ndarray, dtype=np.float64) -> np.ndarray:
+    """conv3x3_same_dgrad for any odd k: the gradient [N,H,W,O] at a k x k stride-1 SAME convolution's output -> `dtype` [N,H,W,C] at its
+    input: dx[n, i, j, c] = sum_{a, b, o} gy[n, i - a + r, j - b + r, o] kernel[a, b, c, o], zero outside the image; taps in index order."""
+    gy, kernel = np.asarray(gy, dtype), np.asarray(kernel, dtype)
+    n, h, w, _ = gy.shape
+    k = kernel.shape[0]
+    r = k // 2
+    gp = np.zeros((n, h + 2 * r, w + 2 * r, kernel.shape[2]), dtype)
+    for a in range(k):
+        for b in range(k):
+            gp[:, a:a + h, b:b + w] += gy @ kernel[a, b].T
+    return gp[:, r:r + h, r:r + w].copy()
+
+
+def _heads_vars(weights: Dict[str, np.ndarray], dtype):
+    K2, b2, K3, b3 = (np.asarray(weights[n], dtype) for n in ("conv2/conv/kernel", "conv2/conv/bias", "conv3/conv/kernel", "conv3/conv/bias"))
+    if K2.shape != (7, 7, 64, 1) or K3.shape != (7, 7, 64, 1):
+        raise ValueError("the grey heads are 7x7, 64 -> 1 (GSC or TSM weights), got %s and %s" % (K2.shape, K3.shape))
+    return K2, b2, K3, b3
+
+
+def heads_forward(weights: Dict[str, np.ndarray], inputs, y, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """inputs [B,H,W,3], y [B,H,W,64] (up3's output) -> dict(m, mask, con, gray, gs), each [B,H,W,1] in `dtype`:
+    m = conv7x7_SAME(y, K2) + b2, mask = tanh(m), con = conv7x7_SAME(y, K3) + b3, gray = train_losses.gray(inputs) (float32, the float32
+    weights, (r 0.2989 + g 0.587) + b 0.114: glue_kernels.h's gray3 bit for bit; a constant of the backward), gs = gray (1 + mask) + con."""
+    from .train_losses import gray as gray_f32
+    T = dtype
+    K2, b2, K3, b3 = _heads_vars(weights, T)
+    y = np.asarray(y, T)
+    m = convk_same(y, K2) + b2
+    mask = np.tanh(m)
+    con = convk_same(y, K3) + b3
+    gray = np.asarray(gray_f32(inputs), T)[..., None]          # float32 arithmetic, as the forward and the device chain form it
+    return {"m": m, "mask": mask, "con": con, "gray": gray, "gs": gray * (T(1) + mask) + con}
+
+
+def heads_grad(weights: Dict[str, np.ndarray], inputs, y, d_gs, acts: Optional[Dict[str, np.ndarray]] = None,
+               dtype=np.float64) -> Dict[str, np.ndarray]:
+    """The complete gradient d_gs [B,H,W,1] at gs -> dict(the four variables of weights.generator_heads_trainable_names() in their own
+    shapes, `d_y` [B,H,W,64] at up3's output, and the stage maps `g_m`, `g_con` [B,H,W,1] and `mask` as used), in `dtype` from the float32
+    variables, in this order:
+      g_con = d_gs;  g_m = (d_gs gray) (1 - mask^2)
+      d b3 = sum g_con;  d b2 = sum g_m
+      d K3[a, b, c, 0] = sum y[n, i + a - 3, j + b - 3, c] g_con[n, i, j], zero outside the image;  d K2 the same with g_m
+      d_y[n, i, j, c] = sum_{a, b} g_m[n, i - a + 3, j - b + 3] K2[a, b, c] + g_con[n, i - a + 3, j - b + 3] K3[a, b, c]
+    With `acts` given (a dict with `mask`, for example the device's), that mask is used in place of tanh(m)."""
+    T = dtype
+    K2, _, K3, _ = _heads_vars(weights, T)
+    y = np.asarray(y, T)
+    if acts is not None:
+        from .train_losses import gray as gray_f32
+        gray = np.asarray(gray_f32(inputs), T)[..., None]
+        mask = np.asarray(acts["mask"], T).reshape(gray.shape)
+    else:
+        fw = heads_forward(weights, inputs, y, T)
+        gray, mask = fw["gray"], fw["mask"]
+    g_con = np.asarray(d_gs, T).reshape(gray.shape)
+    g_m = (g_con * gray) * (T(1) - mask * mask)
+    ax = (0, 1, 2)
+    out: Dict[str, np.ndarray] = {"g_m": g_m, "g_con": g_con, "mask": mask}
+    out["conv3/conv/bias"] = g_con.sum(axis=ax)
+    out["conv2/conv/bias"] = g_m.sum(axis=ax)
+    out["conv3/conv/kernel"] = convk_same_wgrad(y, g_con, 7, T)
+    out["conv2/conv/kernel"] = convk_same_wgrad(y, g_m, 7, T)
+    out["d_y"] = convk_same_dgrad(g_m, K2, T) + convk_same_dgrad(g_con, K3, T)
+    return out
+
+
+def heads_objective_f64(weights: Dict[str, np.ndarray], inputs, y, d_gs, dtype=np.float64):
+    """<d_gs, gs> in `dtype` with no float32 rounding anywhere: the scalar whose gradient heads_grad states."""
+    fw = heads_forward(weights, inputs, y, dtype)
+    return (np.asarray(d_gs, dtype).reshape(fw["gs"].shape) * fw["gs"]).sum()
+
+
+def heads_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
+    """name -> (L1, L-infinity) of `d_y` and each of the four variable gradients (HEADS_NORM_NAMES)."""
+    out = {}
+    for name in HEADS_NORM_NAMES:
+        m = np.abs(np.asarray(grads[name], np.float64))
+        out[name] = (float(m.sum()), float(m.max()))
+    return out
+
+
+def heads_example_inputs(H: int, W: int, B: int, seed: int = 0):
+    """Seeded (inputs [B,H,W,3] in [0, 1], y [B,H,W,64] like a LeakyReLU output, d_gs [B,H,W,1] of the order 1 / (B H W)) float32."""
+    rng = np.random.default_rng(5000 + seed)
+    inputs = rng.uniform(0.0, 1.0, (B, H, W, 3)).astype(np.float32)
+    y = rng.standard_normal((B, H, W, 64)).astype(np.float32)
+    y = np.where(y >= 0, y, np.float32(LRELU_ALPHA) * y).astype(np.float32)
+    d_gs = (rng.standard_normal((B, H, W, 1)) / (B * H * W)).astype(np.float32)
+    return inputs, y, d_gs

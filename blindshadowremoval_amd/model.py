@@ -254,6 +254,14 @@ class Generator:
         ptrs, strides, shape = self.last_block5()
         return ptrs[1], strides[1], shape
 
+    def last_y(self) -> Tuple[int, int, Tuple[int, int, int, int]]:
+        """(y's device address, its floats between pixels, (B, H, W, 64)) of the last forward's y, up3's output and the grey heads' input,
+        in the handle's workspace (bsr_last_y): no copy; valid until the next forward on this generator.  Under last_f's conditions."""
+        self._require_weights()
+        ptr, cs, shape = ctypes.c_void_p(), ctypes.c_int(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_y(self._handle, ctypes.byref(ptr), ctypes.byref(cs), ctypes.byref(shape)), "bsr_last_y")
+        return int(ptr.value), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

@@ -72,12 +72,13 @@ STAGES = ("tail", "decoder", "nonlocal", "bottleneck")
 
 def stage_grad_names(stage: str) -> List[str]:
     """`<name>_l1`, `<name>_linf` for generator_grad's <STAGE>_NORM_NAMES: the stage's data gradients (tail: d_f, d_gs; decoder: d_x;
-    nonlocal: d_y3, d_skip; bottleneck: d_xin), then its variables."""
+    nonlocal: d_y3, d_skip; bottleneck: d_xin; heads: d_y), then its variables."""
     from . import generator_grad
     return [n + s for n in getattr(generator_grad, stage.upper() + "_NORM_NAMES") for s in ("_l1", "_linf")]
 
 
 tail_grad_names, decoder_grad_names, nonlocal_grad_names, bottleneck_grad_names = (functools.partial(stage_grad_names, stage) for stage in STAGES)
+heads_grad_names = functools.partial(stage_grad_names, "heads")      # the grey branch's first stage: its columns follow the colour branch's
 
 
 def _stage_norms(stage: str, grads) -> List[float]:
@@ -91,16 +92,19 @@ def _stage_norms(stage: str, grads) -> List[float]:
 class HostRoute:
     """The objective over the three host statements, on numpy arrays."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False, heads: bool = False):
         self.disc_w, self.vgg_w, self.gen_w = disc_w, vgg_w, gen_w
         self.decoder = decoder                 # --decoder: bring also copies the decoder's kept tensors
         self.nonlocal_ = nonlocal_             # --nonlocal: and res_stack/5's
+        self.heads = heads                     # --heads: and the heads' input y and the forward's mask22
 
-    def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None):
+    def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None, mask22=None):
         """A step of folder_steps -> (img, gt, mask_sv, gs, con_rgb) as the methods take them, and f: a copy of the generator's, if one is given."""
         import torch
         torch.cuda.synchronize(im_d.device)
         f = None if generator is None else generator.probe("f").cpu().numpy()
+        if self.heads:
+            self.y, self.mask22 = generator.probe("y").cpu().numpy(), mask22.cpu().numpy()
         if self.decoder:
             self.acts = {k: generator.probe(k).cpu().numpy() for k in ("res5", "f1", "f2")}
             self.acts["f"] = f
@@ -127,7 +131,7 @@ class HostRoute:
         """tail_grad_names() of the two gradients taken through the colour tail at f [B,H,W,64]."""
         from .generator_grad import tail_grad
         grads = tail_grad(self.gen_w, gs, f, grad_con, grad_gs)
-        self.d_f = grads["d_f"]
+        self.d_f, self.d_gs = grads["d_f"], grads["d_gs"]
         return _stage_norms("tail", grads)
 
     def decoder_norms(self) -> List[float]:
@@ -153,28 +157,37 @@ class HostRoute:
         from .generator_grad import bottleneck_grad
         return _stage_norms("bottleneck", bottleneck_grad(self.gen_w, self.block5["res4"], self.d_y3, self.d_skip))
 
+    def heads_norms(self, img) -> List[float]:
+        """heads_grad_names() of the last tail_norms' complete d_gs taken through the grey heads at the generator's kept y, with the mask
+        the forward wrote (mask22[..., 0] - mask22[..., 2]), as the device chain reads it."""
+        from .generator_grad import heads_grad
+        mask = (self.mask22[..., 0:1] - self.mask22[..., 2:3]).astype(f32)
+        return _stage_norms("heads", heads_grad(self.gen_w, img, self.y, self.d_gs.astype(f32), acts={"mask": mask}))
+
 
 class DeviceRoute:
     """The objective over TrainLosses, Discriminators, Perceptual and ColourTail, on tensors of the device; f is read in the generator's workspace."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False,
+                 heads: bool = False):
         import torch
-        from . import BottleneckGrad, ColourDecoder, ColourTail, Discriminators, NonLocalGrad, Perceptual, TrainLosses
+        from . import BottleneckGrad, ColourDecoder, ColourTail, Discriminators, HeadsGrad, NonLocalGrad, Perceptual, TrainLosses
         self.dev = torch.device("cuda", device)
         self.three, self.gan, self.per = TrainLosses(device), Discriminators(device), Perceptual(device)
         self.gan.load_weights(disc_w)
         self.per.load_weights(vgg_w)
         if gen_w is not None:
             for name, stage, wanted in (("tail", ColourTail, True), ("dec", ColourDecoder, decoder), ("nl", NonLocalGrad, nonlocal_),
-                                       ("bn", BottleneckGrad, bottleneck)):
+                                       ("bn", BottleneckGrad, bottleneck), ("hd", HeadsGrad, heads)):
                 if wanted:
                     setattr(self, name, stage(device))
                     getattr(self, name).load_weights(gen_w)
         self.three_weights = torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(self.dev)
         self.per_weight = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=self.dev)
 
-    def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None):
+    def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None, mask22=None):
         import torch
+        self.mask22 = mask22
         return (im_d, torch.from_numpy(gt_a).to(self.dev), torch.from_numpy(mask_a).to(self.dev), gs, con_rgb), generator
 
     def losses(self, img, gt, mask_sv, gs, con_rgb, per_grad: bool = False):
@@ -193,7 +206,7 @@ class DeviceRoute:
 
     def tail_norms(self, gs, generator, grad_con, grad_gs) -> List[float]:
         res = self.tail.backward(generator, gs, grad_con, grad_gs)
-        self.d_f, self.generator = res["d_f"], generator
+        self.d_f, self.d_gs, self.generator = res["d_f"], res["d_gs"], generator
         return _stage_norms("tail", res)
 
     def decoder_norms(self) -> List[float]:
@@ -208,6 +221,9 @@ class DeviceRoute:
 
     def bottleneck_norms(self) -> List[float]:
         return _stage_norms("bottleneck", self.bn.backward(self.generator, self.d_y3, self.d_skip))
+
+    def heads_norms(self, img) -> List[float]:
+        return _stage_norms("heads", self.hd.backward(self.generator, img, self.mask22, self.d_gs))
 
 
 def _norms(grad) -> List[float]:
@@ -229,11 +245,11 @@ def discriminator_weights(ckpt: Optional[str], who: str) -> Dict[str, np.ndarray
     return load_discriminator_weights(prefix)
 
 
-def folder_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: str, with_generator: bool = False):
+def folder_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: str, with_generator: bool = False, with_mask22: bool = False):
     """The folder handling of the commands that score a generator on synthesised pairs: for every step of `batch` item folders
     `<folder>/<name>/` (the last one may hold fewer) yields (step, steps, img on the device, gt [b,S,S,3], mask_sv [b,S,S,3] (numpy), gs,
     con_rgb (the generator's outputs on the device)), with `with_generator` also the generator itself, whose last forward is the
-    step's (Generator.last_f, Generator.probe).  The generator's weights come from the latest checkpoint under `ckpt`, from init_weights
+    step's (Generator.last_f, Generator.probe), and with `with_mask22` after it the forward's mask22.  The generator's weights come from the latest checkpoint under `ckpt`, from init_weights
     without it."""
     import torch
     from . import Generator, init_weights
@@ -270,21 +286,22 @@ def folder_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who:
                     dst.append(a.astype(f32) / f32(255))
             im, _, uv, _, _ = torch.split(torch.cat(rows, 0).float(), list(SPLIT_FFHQ), dim=3)
             im_d = im.contiguous().to(dev)
-            gs, con_rgb, _, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
-            yield (step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb) + ((gen,) if with_generator else ())
+            gs, con_rgb, mask22, _ = gen(im_d, uv.contiguous().to(dev), None, chuck=2, training=False)
+            yield ((step, steps, im_d, np.stack(gts), np.stack(masks), gs, con_rgb) + ((gen,) if with_generator else ())
+                   + ((mask22,) if with_mask22 else ()))
     finally:                    # also when the consumer stops early or raises: the handle is closed with the generator
         gen.close()
 
 
 def score_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: str, step_fn: Callable, quiet: bool = False,
-                with_generator: bool = False, nine_digits: bool = False) -> Dict[str, float]:
+                with_generator: bool = False, nine_digits: bool = False, with_mask22: bool = False) -> Dict[str, float]:
     """The loop of the three commands: `step_fn(img, gt, mask_sv, gs, con_rgb[, generator])` on every step of folder_steps returns the
     step's record name -> value, and a list of (name, value) that is printed with it and not averaged -> the step-weighted means of the
     records.  Each step prints the running means as Logging.display does, with a blank line after the last; with `nine_digits` it
     prints "step/steps " and the step's own values as name:%.9g."""
     from .fsrnet import Logging
     acc: Dict[str, List[float]] = {}
-    with contextlib.closing(folder_steps(folder, ckpt, batch, device, who, with_generator)) as batches:      # closes the generator handle on any way out
+    with contextlib.closing(folder_steps(folder, ckpt, batch, device, who, with_generator, with_mask22)) as batches:      # closes the generator handle on any way out
         for step, steps, *tensors in batches:
             record, extras = step_fn(*tensors)
             Logging.accumulate(acc, record)
@@ -301,11 +318,11 @@ def score_steps(folder: str, ckpt: Optional[str], batch: int, device: int, who: 
 
 def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int = 8, host: bool = False, device: int = 0,
                  quiet: bool = False, grad: bool = False, grad_total: bool = False, tail: bool = False, decoder: bool = False,
-                 nonlocal_: bool = False, bottleneck: bool = False) -> Dict[str, float]:
+                 nonlocal_: bool = False, bottleneck: bool = False, heads: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the other weights come from the latest checkpoint under `ckpt`, from init_weights and
     init_discriminator_weights without it.  `grad`, `grad_total`, `tail`, `decoder`, `nonlocal_` and `bottleneck` add to each batch's line what
-    --grad, --grad-total, --tail, --decoder, --nonlocal and --bottleneck do."""
+    --grad, --grad-total, --tail, --decoder, --nonlocal and --bottleneck do; `heads` appends what --heads does after them."""
     if tail and not grad_total:
         raise ValueError("perceptual: --tail goes with --grad-total")
     if decoder and not tail:
@@ -314,6 +331,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         raise ValueError("perceptual: --nonlocal goes with --grad-total --tail --decoder")
     if bottleneck and not nonlocal_:
         raise ValueError("perceptual: --bottleneck goes with --grad-total --tail --decoder --nonlocal")
+    if heads and not tail:
+        raise ValueError("perceptual: --heads goes with --grad-total --tail")
     vgg_w = load_vgg_weights(vgg)
     gen_w = None
     if tail:
@@ -321,8 +340,8 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         from .weights import init_weights
         gen_w = init_weights(1) if ckpt is None else load_generator_weights(latest_checkpoint(ckpt))
     disc_w = discriminator_weights(ckpt, "perceptual")
-    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck) if host
-             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck))
+    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck, heads=heads) if host
+             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck, heads=heads))
 
     def step(*tensors):
         arrays, f = route.bring(*tensors)
@@ -334,9 +353,11 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
         for stage, wanted, args in zip(STAGES, (tail, decoder, nonlocal_, bottleneck), ((arrays[3], f, grad_con, grad_gs), (), (), ())):
             if wanted:
                 extras += zip(stage_grad_names(stage), getattr(route, stage + "_norms")(*args))
+        if heads:
+            extras += zip(heads_grad_names(), route.heads_norms(arrays[0]))
         return loss_record(three, gan, per), extras
 
-    return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True)
+    return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True, with_mask22=heads)
 
 
 def main(argv=None) -> int:
@@ -354,6 +375,7 @@ def main(argv=None) -> int:
     ap.add_argument("--decoder", action="store_true", help="with --grad-total --tail: also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients")
     ap.add_argument("--nonlocal", dest="nonlocal_", action="store_true", help="with --grad-total --tail --decoder: also the norms of d g_total_loss / d y3 at res_stack/5's bnorm3 output, of what the block's skip carries to its input, and of the non-local block's ten variable gradients")
     ap.add_argument("--bottleneck", action="store_true", help="with --grad-total --tail --decoder --nonlocal: also the norms of d g_total_loss / d xin at res_stack/5's input and of the twelve variable gradients of the block's conv1, conv2, conv3 and their batch norms")
+    ap.add_argument("--heads", action="store_true", help="with --grad-total --tail: after the other columns the norms of d g_total_loss / d y at up3's output and of the four variable gradients of the grey heads conv2 and conv3, from the tail's complete d / d gs")
     a = ap.parse_args(argv)
     if a.tail and not a.grad_total:
         ap.error("--tail goes with --grad-total")
@@ -363,8 +385,10 @@ def main(argv=None) -> int:
         ap.error("--nonlocal goes with --grad-total --tail --decoder")
     if a.bottleneck and not a.nonlocal_:
         ap.error("--bottleneck goes with --grad-total --tail --decoder --nonlocal")
+    if a.heads and not a.tail:
+        ap.error("--heads goes with --grad-total --tail")
     means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder,
-                         nonlocal_=a.nonlocal_, bottleneck=a.bottleneck)
+                         nonlocal_=a.nonlocal_, bottleneck=a.bottleneck, heads=a.heads)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

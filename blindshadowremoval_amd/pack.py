@@ -985,6 +985,48 @@ def unpack_bottleneck_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the generator's grey heads' backward (csrc/heads_grad_kernels.h): a blob of its own, no header, float32 ----
+HEADS_RGB_TEXT = "the heads' device chain takes the GSC / TSM heads (7x7, 64 -> 1 twice); model_RGB.py's are 128 -> 3 and chained"
+HEADS_K, HEADS_KP = 98, 100
+
+
+def heads_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the heads' gradient blob: one image,
+      kt    [100][64]   the data-gradient image of both heads: kt[2 (7 a + b) + j][c] = K_j[a][b][c][0], j = 0 conv2 (the mask head),
+                        j = 1 conv3 (the con head); rows 98, 99 zero.
+    The taps are NOT turned: the kernel's operand reads g2 at the pixel p - (a - 3, b - 3), which is the turning.  98 is padded to 100, the
+    next multiple of the MFMA's k = 4 (25 k-steps); the kernel feeds zeros against the two pad rows as well."""
+    return [("kt", 0, (HEADS_KP, 64))], HEADS_KP * 64
+
+
+def heads_grad_record(weights: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """name -> float32 array of heads_grad_layout's shapes.  ValueError for the RGB baseline's weights."""
+    k2, k3 = (np.asarray(weights[n + "/conv/kernel"], np.float32) if n + "/conv/kernel" in weights else None for n in ("conv2", "conv3"))
+    if k2 is None or k3 is None or k2.shape != (7, 7, 64, 1) or k3.shape != (7, 7, 64, 1):
+        raise ValueError(HEADS_RGB_TEXT)
+    kt = np.zeros((HEADS_KP, 64), np.float32)
+    kt[0:HEADS_K:2] = k2[..., 0].reshape(49, 64)
+    kt[1:HEADS_K:2] = k3[..., 0].reshape(49, 64)
+    return {"kt": kt}
+
+
+def pack_heads_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (conv2's and conv3's kernels are read; GSC or TSM) -> the blob bsr_heads_grad takes (heads_grad_layout).
+    ValueError for RGB weights."""
+    return heads_grad_record(weights)["kt"].tobytes()
+
+
+def unpack_heads_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_heads_grad: dict(`kt` [100,64], and the two kernels it holds, `conv2/conv/kernel`, `conv3/conv/kernel`
+    [7,7,64,1])."""
+    _, total = heads_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a heads gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    kt = arr.reshape(HEADS_KP, 64).copy()
+    return {"kt": kt, "conv2/conv/kernel": kt[0:HEADS_K:2].reshape(7, 7, 64, 1).copy(), "conv3/conv/kernel": kt[1:HEADS_K:2].reshape(7, 7, 64, 1).copy()}
+
+
 # ---- VGG19 up to block5_conv1 (csrc/vgg_kernels.h): a blob of its own, no header, float32 ----
 VGG_NB = 64                  # output channels per workgroup of vgg_conv_kernel
 VGG_IN_C = 8                 # the first layer's 3 input channels (BGR) are padded to 8

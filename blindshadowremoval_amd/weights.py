@@ -148,6 +148,13 @@ def generator_bottleneck_trainable_names(block: int = 5, variant: str = "gsc") -
             if n.startswith(stem) and not n.startswith(stem + "non_local/") and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_heads_trainable_names(variant: str = "gsc") -> List[str]:
+    """The four trainable variables of the generator's grey heads in generator_variable_shapes' order, 6 274 floats: the kernel
+    [7,7,64,1] and bias of conv2 ('tconv3', the mask head) and of conv3 ('tconv4', the con head).  GSC and TSM share them; the RGB
+    baseline's heads are 128 -> 3 and chained."""
+    return [n for n in generator_variable_shapes(variant) if n in ("conv2/conv/kernel", "conv2/conv/bias", "conv3/conv/kernel", "conv3/conv/bias")]
+
+
 N_LAYER_D = 4                   # Config.n_layer_D (/root/reference/train_test_GSC.py:121-123)
 DISC_CH = [32, 32, 64, 64]      # the first n_layer_D entries of Discriminator's n_ch (/root/reference/model.py:295)
 DISC_IN_CH = 6                  # cat[image 3 | mask_sv 3] (/root/reference/train_test_GSC.py:264-268)

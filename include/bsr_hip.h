@@ -114,6 +114,10 @@ int bsr_probe(bsr_handle* h, const char* name, float* dst, size_t cap_floats, in
  * the handle, for work ordered after that forward on its stream (bsr_clr_tail_grad reads it in place).  BSR_DTYPE_F32 GSC / TSM handles
  * only: BSR_ERR_STATE before any forward, for the 16-bit modes (f is fp16 there) and for RGB handles.  Added under ABI 8. */
 int bsr_last_f(bsr_handle* h, const float** f, int* f_cs, int shape4[4]);
+/* Where the last forward's y (up3's output, the grey heads' input) lies in the handle's workspace: *y the device pointer, *y_cs the
+ * floats between pixels, shape4 = [B,H,W,64].  up3 alone writes the slot and the heads alone read it, so it holds until the next
+ * forward; bsr_heads_grad reads it in place.  The same rules and error codes as bsr_last_f.  Added under ABI 8. */
+int bsr_last_y(bsr_handle* h, const float** y, int* y_cs, int shape4[4]);
 /* The colour decoder's tensors of the last forward in the handle's workspace: *x res_stack/5's output (261 channels, *x_cs floats between
  * pixels) at [B,H/8,W/8], *f1 [B,H/4,W/4,128], *f2 [B,H/2,W/2,96], *f [B,H,W,64], all dense but x; shape4 = [B,H,W,64], the image's.  The
  * same rules and error codes as bsr_last_f, GSC handles only (BSR_ERR_STATE for TSM handles too).  Added under ABI 8. */
@@ -439,6 +443,32 @@ int bsr_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const
                         int h, int w, float* d_xin, float* grads, void* scratch, void* stream);
 int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip,
                               int B, int h, int w, float* d_xin, float* grads, void* scratch, int stop_after, void* stream);
+
+/* The backward of the generator's grey heads (training=False, fp32; the reference's model.py:246-250): conv2 (7x7, 64 -> 1, tanh) gives
+ * mask, conv3 (7x7, 64 -> 1) gives con, gs = gray(inputs) (1 + mask) + con.  d_blob: bsr_heads_grad_blob_bytes() bytes of
+ * pack.pack_heads_grad (GSC or TSM weights), 16-byte aligned; inputs and mask22 dense [B,H,W,3], the forward's input and output (mask is
+ * read as mask22[.., 0] - mask22[.., 2], exactly the forward's tanh); y [B,H,W,64 of y_cs] the heads' input as bsr_last_y hands it out
+ * (or a dense tensor), y_cs a multiple of 4; d_gs dense [B,H,W,1] the complete gradient at gs (bsr_clr_tail_grad's).  H a multiple of 8,
+ * W of 32.  Outputs: d_y dense [B,H,W,64] and grads, bsr_heads_grad_floats() = 6274 float32: the four variables of
+ * weights.generator_heads_trainable_names() in that order (conv2's kernel and bias, conv3's kernel and bias), variable `index` (0..3) at
+ * float offset bsr_heads_grad_var_offset(index); SIZE_MAX out of range.  Five launches on `stream`, one after the other
+ * (csrc/heads_grad_kernels.h), no host synchronisation, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_heads_grad_scratch_bytes(B, H, W) bytes, 256-byte aligned; every word read is written earlier in the same call.
+ * bsr_heads_grad_offset(B, H, W, map) is the byte offset of map 0 g2 = (g_m, g_con) [N][2], 1 mask [N], 2 the two kernel gradients in
+ * float64 [2][7][7][64] (head 0 mask, 1 con), 3 the sums of g_m and g_con (float64 [2]); SIZE_MAX out of range.
+ * bsr_heads_grad_partials(B, H, W) is the number of tile slices of the kernel gradient, each of which writes four partials, one per wave
+ * (0 for bad arguments).  A bad argument gives BSR_ERR_ARG with a message and nothing launched.  bsr_debug_heads_grad stops after
+ * `stop_after` (0..5) of the launches.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_heads_grad_blob_bytes(void);
+size_t bsr_heads_grad_scratch_bytes(int B, int H, int W);
+size_t bsr_heads_grad_floats(void);
+size_t bsr_heads_grad_var_offset(int index);
+size_t bsr_heads_grad_offset(int B, int H, int W, int map);
+int bsr_heads_grad_partials(int B, int H, int W);
+int bsr_heads_grad(int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
+                   const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, void* stream);
+int bsr_debug_heads_grad(int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
+                         const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, int stop_after, void* stream);
 
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
