@@ -15,6 +15,7 @@ and d_skip to the gradient at the block's input and the twelve variables; csrc/b
 output y and the four variables; csrc/heads_grad_kernels.h is held to it (heads_grad_gpu.HeadsGrad)."""
 from __future__ import annotations
 
+import functools
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -158,13 +159,17 @@ def objective_f64(weights: Dict[str, np.ndarray], gs, f, g_con, masks: Optional[
     return (np.asarray(g_con, dtype) * fw["con_rgb"]).sum()
 
 
-def tail_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
-    """name -> (L1, L-infinity) of `d_f`, the complete `d_gs` and each of the ten variable gradients (TAIL_NORM_NAMES)."""
+def grad_norms(grads: Dict[str, np.ndarray], names) -> Dict[str, Tuple[float, float]]:
+    """name -> (L1, L-infinity) of grads[name] for every name of `names`: the sum and the largest of its magnitudes, in float64.
+    <stage>_norms(grads) is this over the stage's <STAGE>_NORM_NAMES."""
     out = {}
-    for name in TAIL_NORM_NAMES:
+    for name in names:
         m = np.abs(np.asarray(grads[name], np.float64))
         out[name] = (float(m.sum()), float(m.max()))
     return out
+
+
+tail_norms = functools.partial(grad_norms, names=TAIL_NORM_NAMES)          # of `d_f`, the complete `d_gs` and each of the ten variable gradients
 
 
 def example_inputs(H: int, W: int, B: int, seed: int = 0):
@@ -286,13 +291,7 @@ def decoder_objective_f64(weights: Dict[str, np.ndarray], x, d_f, masks: Optiona
     return (np.asarray(d_f, dtype) * fs[2]).sum()
 
 
-def decoder_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
-    """name -> (L1, L-infinity) of `d_x` and each of the twelve variable gradients (DECODER_NORM_NAMES)."""
-    out = {}
-    for name in DECODER_NORM_NAMES:
-        m = np.abs(np.asarray(grads[name], np.float64))
-        out[name] = (float(m.sum()), float(m.max()))
-    return out
+decoder_norms = functools.partial(grad_norms, names=DECODER_NORM_NAMES)    # of `d_x` and each of the twelve variable gradients
 
 
 def decoder_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
@@ -406,13 +405,7 @@ def nonlocal_objective_f64(weights: Dict[str, np.ndarray], y3, xin, d_out, block
     return (np.asarray(d_out, dtype) * fw["out"]).sum()
 
 
-def nonlocal_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
-    """name -> (L1, L-infinity) of `d_y3`, `d_skip` and each of the ten variable gradients (NONLOCAL_NORM_NAMES)."""
-    out = {}
-    for name in NONLOCAL_NORM_NAMES:
-        m = np.abs(np.asarray(grads[name], np.float64))
-        out[name] = (float(m.sum()), float(m.max()))
-    return out
+nonlocal_norms = functools.partial(grad_norms, names=NONLOCAL_NORM_NAMES)  # of `d_y3`, `d_skip` and each of the ten variable gradients
 
 
 def nonlocal_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
@@ -528,11 +521,7 @@ def bottleneck_objective_f64(weights: Dict[str, np.ndarray], xin, d_y3, d_skip=N
 
 def bottleneck_norms(grads: Dict[str, np.ndarray], block: int = 5) -> Dict[str, Tuple[float, float]]:
     """name -> (L1, L-infinity) of `d_xin` and each of the twelve variable gradients (BOTTLENECK_NORM_NAMES for block 5)."""
-    out = {}
-    for name in ("d_xin",) + tuple(generator_bottleneck_trainable_names(block)):
-        m = np.abs(np.asarray(grads[name], np.float64))
-        out[name] = (float(m.sum()), float(m.max()))
-    return out
+    return grad_norms(grads, ("d_xin",) + tuple(generator_bottleneck_trainable_names(block)))
 
 
 def bottleneck_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
@@ -653,13 +642,7 @@ def heads_objective_f64(weights: Dict[str, np.ndarray], inputs, y, d_gs, dtype=n
     return (np.asarray(d_gs, dtype).reshape(fw["gs"].shape) * fw["gs"]).sum()
 
 
-def heads_norms(grads: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
-    """name -> (L1, L-infinity) of `d_y` and each of the four variable gradients (HEADS_NORM_NAMES)."""
-    out = {}
-    for name in HEADS_NORM_NAMES:
-        m = np.abs(np.asarray(grads[name], np.float64))
-        out[name] = (float(m.sum()), float(m.max()))
-    return out
+heads_norms = functools.partial(grad_norms, names=HEADS_NORM_NAMES)        # of `d_y` and each of the four variable gradients
 
 
 def heads_example_inputs(H: int, W: int, B: int, seed: int = 0):

@@ -8,32 +8,35 @@ THE TOTALS, float32 in the reference's order:
 
 THE TOTAL GRADIENT, d g_total_loss / d (con_rgb, gs).  grad_gs is step_losses_grad's under train_losses.G_TOTAL_WEIGHTS: no other term reads
 gs.  grad_con = (step_losses_grad's grad_con + gen_grad's grad) + per_loss_grad's grad under PER_WEIGHT, three float32 tensors added in
-that order.  Through the generator's colour tail both become d / d f at clr_up3's output, the complete d / d gs and the gradients of the
-tail's ten variables (generator_grad.tail_grad), and d / d f through the colour decoder becomes d / d x at res_stack/5's output and the
-gradients of the decoder's twelve variables (generator_grad.decoder_grad).
+that order.  BACKWARD, the one table of the generator's backward stages, takes both on through the generator: the stages' order, what
+each takes from whom and what each needs of the forward.  host_walk and device_walk run its wanted rows over one context dict, and the
+flags, their help and their refusals are read from the same rows.
 
-THE ROUTES.  HostRoute states all of that over the three host statements, DeviceRoute over TrainLosses, Discriminators, Perceptual and
-ColourTail, with the same methods; a command chooses one before its loop.  The methods take (img, gt, mask_sv, gs, con_rgb) as `bring`
+THE ROUTES.  HostRoute states all of that over the host statements, DeviceRoute over TrainLosses, Discriminators, Perceptual and the
+stages' runners, with the same methods; a command chooses one before its loop.  The methods take (img, gt, mask_sv, gs, con_rgb) as `bring`
 returns them and return losses as float32 numpy arrays and gradients in the route's own type: numpy arrays or device tensors.
 
-`python -m blindshadowremoval_amd.objective FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total] [--tail] [--decoder]` evaluates
+`python -m blindshadowremoval_amd.objective FOLDER --vgg FILE.npz [--ckpt DIR] [--batch N] [--host] [--grad] [--grad-total] [--<stage> ...]` evaluates
 the whole objective on a folder written by `python -m blindshadowremoval_amd.shadow_synth` (folder_steps): ALL_NAMES per batch and as
 step-weighted means, on the device route or with --host on the host route.  With --grad each batch's line also carries per_grad_l1 and
 per_grad_linf, the L1 and L-infinity norms of the perceptual term's share of the total gradient; with --grad-total instead
-TOTAL_GRAD_NAMES, the norms of the total gradient; with --tail beside it also tail_grad_names(), those of the total gradient taken
-through the colour tail, and with --decoder beside both decoder_grad_names(), those of d_f taken on through the colour decoder.  `python -m blindshadowremoval_amd.perceptual` is the same command under its earlier name.
+TOTAL_GRAD_NAMES, the norms of the total gradient; with a stage's flag beside it and its ancestors' flags also stage_grad_names(stage),
+those of the gradients the stage hands on and of its variables'.  `python -m blindshadowremoval_amd.perceptual` is the same command under its earlier name.
 """
 from __future__ import annotations
 
 import contextlib
 import functools
+import itertools
+import keyword
 import os
 import sys
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
 from . import discriminator as disc
+from . import generator_grad
 from . import perceptual as vgg19
 from . import train_losses as tl
 from .perceptual import GRAD_NAMES
@@ -65,25 +68,117 @@ def loss_record(three, gan, per) -> Dict[str, float]:
     return dict(zip(ALL_NAMES, vals))
 
 
-# the stages of the generator's backward pass from the output down: generator_grad's <STAGE>_NORM_NAMES and <stage>_norms, and here
-# <stage>_grad_names() and the routes' <stage>_norms
-STAGES = ("tail", "decoder", "nonlocal", "bottleneck")
+# ---- the generator's backward pass: one table of its stages, walked by both routes
+class Stage(NamedTuple):
+    """A stage of the backward pass.  `name` is also its flag --<name>; `parent` the stage whose data gradients it takes; `device` the
+    package's runner class; `takes` the context names its `backward` takes after the generator, in that order; `probes` what `host`
+    needs of the forward, as Generator.probe's names; `host` the adaptor (gen_w, context, probes) -> the stage's statement of
+    generator_grad.  What it adds to the context, `gives`, are the data gradients that lead generator_grad's <NAME>_NORM_NAMES."""
+    name: str
+    parent: Optional[str]
+    device: str
+    takes: Tuple[str, ...]
+    probes: Tuple[str, ...]
+    host: Callable
+    help: str
+
+    @property
+    def dest(self) -> str:                 # score_folder's keyword and argparse's attribute: `nonlocal` is a Python keyword
+        return self.name + "_" * keyword.iskeyword(self.name)
+
+    @property
+    def gives(self) -> Tuple[str, ...]:    # a variable's name has a "/", a data gradient's has none
+        return tuple(itertools.takewhile(lambda n: "/" not in n, getattr(generator_grad, self.name.upper() + "_NORM_NAMES")))
+
+
+# The context starts as {img, gs, mask22, grad_con, grad_gs}; each stage that runs adds its `gives`.  The rows' order is the walks' and
+# the printed columns': the colour branch from the output down, then the grey branch.  A new stage adds one row with its host adaptor.
+# The non-local block's y3 is y3x5 - pad(res4) in float32, as the device chain forms it, and the heads' mask the one the forward wrote.
+BACKWARD = (
+    Stage("tail", None, "ColourTail", ("gs", "grad_con", "grad_gs"), ("f",),
+          lambda w, c, p: generator_grad.tail_grad(w, c["gs"], p["f"], c["grad_con"], c["grad_gs"]),
+          "also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients"),
+    Stage("decoder", "tail", "ColourDecoder", ("d_f",), ("res5", "f1", "f2", "f"),
+          lambda w, c, p: generator_grad.decoder_grad(w, p["res5"], c["d_f"], acts=p),
+          "also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients"),
+    Stage("nonlocal", "decoder", "NonLocalGrad", ("d_x",), ("y3x5", "res4", "res5"),
+          lambda w, c, p: generator_grad.nonlocal_grad(w, (p["y3x5"][..., :257] - p["res4"][..., :257]).astype(f32), p["res4"], c["d_x"], acts={"out": p["res5"]}),
+          "also the norms of d g_total_loss / d y3 at res_stack/5's bnorm3 output, of what the block's skip carries to its input, and of the non-local block's ten variable gradients"),
+    Stage("bottleneck", "nonlocal", "BottleneckGrad", ("d_y3", "d_skip"), ("res4",),
+          lambda w, c, p: generator_grad.bottleneck_grad(w, p["res4"], c["d_y3"], c["d_skip"]),
+          "also the norms of d g_total_loss / d xin at res_stack/5's input and of the twelve variable gradients of the block's conv1, conv2, conv3 and their batch norms"),
+    Stage("heads", "tail", "HeadsGrad", ("img", "mask22", "d_gs"), ("y",),
+          lambda w, c, p: generator_grad.heads_grad(w, c["img"], p["y"], c["d_gs"].astype(f32), acts={"mask": (c["mask22"][..., 0:1] - c["mask22"][..., 2:3]).astype(f32)}),
+          "after the other columns the norms of d g_total_loss / d y at up3's output and of the four variable gradients of the grey heads conv2 and conv3, from the tail's complete d / d gs"),
+)
+_ROWS = {s.name: s for s in BACKWARD}
+
+
+def _above(stage: str) -> Tuple[str, ...]:
+    """The stage's ancestors, the root first."""
+    parent = _ROWS[stage].parent
+    return () if parent is None else _above(parent) + (parent,)
+
+
+STAGES = _above("bottleneck") + ("bottleneck",)            # the colour branch's chain of flags
+
+
+def stage_goes_with(stage: str) -> str:
+    """The flags a stage's flag needs beside it, as the refusals and the help texts spell them."""
+    return " ".join(["--grad-total"] + ["--" + s for s in _above(stage)])
+
+
+def refusal(wanted, grad_total: bool) -> Optional[str]:
+    """None, or for the first row that is wanted without --grad-total and all of its ancestors the text that says so."""
+    for s in BACKWARD:
+        if s.name in wanted and not (grad_total and all(a in wanted for a in _above(s.name))):
+            return "--%s goes with %s" % (s.name, stage_goes_with(s.name))
+    return None
 
 
 def stage_grad_names(stage: str) -> List[str]:
     """`<name>_l1`, `<name>_linf` for generator_grad's <STAGE>_NORM_NAMES: the stage's data gradients (tail: d_f, d_gs; decoder: d_x;
     nonlocal: d_y3, d_skip; bottleneck: d_xin; heads: d_y), then its variables."""
-    from . import generator_grad
     return [n + s for n in getattr(generator_grad, stage.upper() + "_NORM_NAMES") for s in ("_l1", "_linf")]
 
 
-tail_grad_names, decoder_grad_names, nonlocal_grad_names, bottleneck_grad_names = (functools.partial(stage_grad_names, stage) for stage in STAGES)
-heads_grad_names = functools.partial(stage_grad_names, "heads")      # the grey branch's first stage: its columns follow the colour branch's
+tail_grad_names, decoder_grad_names, nonlocal_grad_names, bottleneck_grad_names, heads_grad_names = (
+    functools.partial(stage_grad_names, s.name) for s in BACKWARD)
+
+
+def _walk(wanted, context, run) -> Dict[str, dict]:
+    """`run(row, context)` for every wanted row in the table's order, each on the context the rows before it have added to -> stage
+    name -> its result."""
+    context, out = dict(context), {}
+    for s in BACKWARD:
+        if s.name in wanted:
+            out[s.name] = run(s, context)
+            context.update((n, out[s.name][n]) for n in s.gives)
+    return out
+
+
+def device_runners(wanted, gen_w, device: int = 0) -> Dict[str, object]:
+    """Stage name -> the wanted rows' runners with the generator's weights loaded."""
+    import blindshadowremoval_amd as package
+    runners = {s.name: getattr(package, s.device)(device) for s in BACKWARD if s.name in wanted}
+    for runner in runners.values():
+        runner.load_weights(gen_w)
+    return runners
+
+
+def device_walk(runners, generator, context, keep=()) -> Dict[str, dict]:
+    """The backward pass of `generator`'s last forward over device_runners' stages, in place in its workspace -> stage name -> the
+    runner's result; the stages named in `keep` also give their kept maps."""
+    return _walk(runners, context, lambda s, c: runners[s.name].backward(generator, *[c[n] for n in s.takes], keep=s.name in keep))
+
+
+def host_walk(wanted, gen_w, context, probes) -> Dict[str, dict]:
+    """The same over the host statements, on numpy arrays: `probes` is Generator.probe's name -> array for the wanted rows' `probes`."""
+    return _walk(wanted, context, lambda s, c: s.host(gen_w, c, probes))
 
 
 def _stage_norms(stage: str, grads) -> List[float]:
     """stage_grad_names(stage)'s values of a stage's result on either route: name -> numpy array or device tensor."""
-    from . import generator_grad
     arrays = {k: t.cpu().numpy() if hasattr(t, "cpu") else t for k, t in grads.items()}
     return [v for pair in getattr(generator_grad, stage + "_norms")(arrays).values() for v in pair]
 
@@ -92,25 +187,19 @@ def _stage_norms(stage: str, grads) -> List[float]:
 class HostRoute:
     """The objective over the three host statements, on numpy arrays."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False, heads: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, wanted=()):
         self.disc_w, self.vgg_w, self.gen_w = disc_w, vgg_w, gen_w
-        self.decoder = decoder                 # --decoder: bring also copies the decoder's kept tensors
-        self.nonlocal_ = nonlocal_             # --nonlocal: and res_stack/5's
-        self.heads = heads                     # --heads: and the heads' input y and the forward's mask22
+        self.wanted = tuple(wanted)            # the stages stage_norms walks
 
     def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None, mask22=None):
-        """A step of folder_steps -> (img, gt, mask_sv, gs, con_rgb) as the methods take them, and f: a copy of the generator's, if one is given."""
+        """A step of folder_steps -> (img, gt, mask_sv, gs, con_rgb) as the methods take them, and what the wanted stages need of the
+        forward: copies of their probes by name, and of mask22 if one of them takes it."""
         import torch
         torch.cuda.synchronize(im_d.device)
-        f = None if generator is None else generator.probe("f").cpu().numpy()
-        if self.heads:
-            self.y, self.mask22 = generator.probe("y").cpu().numpy(), mask22.cpu().numpy()
-        if self.decoder:
-            self.acts = {k: generator.probe(k).cpu().numpy() for k in ("res5", "f1", "f2")}
-            self.acts["f"] = f
-        if self.nonlocal_:
-            self.block5 = {k: generator.probe(k).cpu().numpy() for k in ("y3x5", "res4")}
-        return (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy()), f
+        kept = {k: generator.probe(k).cpu().numpy() for k in sorted({k for name in self.wanted for k in _ROWS[name].probes})}
+        if mask22 is not None:                 # handed out when a wanted stage takes it
+            kept["mask22"] = mask22.cpu().numpy()
+        return (im_d.cpu().numpy(), gt_a, mask_a, gs.cpu().numpy(), con_rgb.cpu().numpy()), kept
 
     def losses(self, img, gt, mask_sv, gs, con_rgb, per_grad: bool = False):
         """The terms' losses for a batch: float32 (recon_gs, recon_c, grad), (gen, disc_real, disc_fake), (per,); then None, or with
@@ -127,68 +216,28 @@ class HostRoute:
         grad_con = (three["grad_con"] + gan) + np.asarray(per["grad"], f32)
         return three["losses"], disc.gan_losses(self.disc_w, gt, con_rgb, mask_sv)["losses"], per["loss"], grad_con, three["grad_gs"]
 
-    def tail_norms(self, gs, f, grad_con, grad_gs) -> List[float]:
-        """tail_grad_names() of the two gradients taken through the colour tail at f [B,H,W,64]."""
-        from .generator_grad import tail_grad
-        grads = tail_grad(self.gen_w, gs, f, grad_con, grad_gs)
-        self.d_f, self.d_gs = grads["d_f"], grads["d_gs"]
-        return _stage_norms("tail", grads)
-
-    def decoder_norms(self) -> List[float]:
-        """decoder_grad_names() of the last tail_norms' d_f taken through the colour decoder at the generator's kept res5, f1, f2, f."""
-        from .generator_grad import decoder_grad
-        grads = decoder_grad(self.gen_w, self.acts["res5"], self.d_f, acts=self.acts)
-        self.d_x = grads["d_x"]
-        return _stage_norms("decoder", grads)
-
-    def nonlocal_norms(self) -> List[float]:
-        """nonlocal_grad_names() of the last decoder_norms' d_x taken through res_stack/5's upper half at the generator's kept y3x5, res4
-        and res5: y3 = y3x5 - pad(res4) in float32, as the device chain forms it."""
-        from .generator_grad import nonlocal_grad
-        xin = self.block5["res4"]
-        y3 = (self.block5["y3x5"][..., :257] - xin[..., :257]).astype(f32)
-        grads = nonlocal_grad(self.gen_w, y3, xin, self.d_x, acts={"out": self.acts["res5"]})
-        self.d_y3, self.d_skip = grads["d_y3"], grads["d_skip"]
-        return _stage_norms("nonlocal", grads)
-
-    def bottleneck_norms(self) -> List[float]:
-        """bottleneck_grad_names() of the last nonlocal_norms' d_y3 and d_skip taken through res_stack/5's lower half at the generator's
-        kept res4."""
-        from .generator_grad import bottleneck_grad
-        return _stage_norms("bottleneck", bottleneck_grad(self.gen_w, self.block5["res4"], self.d_y3, self.d_skip))
-
-    def heads_norms(self, img) -> List[float]:
-        """heads_grad_names() of the last tail_norms' complete d_gs taken through the grey heads at the generator's kept y, with the mask
-        the forward wrote (mask22[..., 0] - mask22[..., 2]), as the device chain reads it."""
-        from .generator_grad import heads_grad
-        mask = (self.mask22[..., 0:1] - self.mask22[..., 2:3]).astype(f32)
-        return _stage_norms("heads", heads_grad(self.gen_w, img, self.y, self.d_gs.astype(f32), acts={"mask": mask}))
+    def stage_norms(self, context, kept) -> Dict[str, List[float]]:
+        """The walks' first context and `bring`'s second result -> wanted stage -> stage_grad_names(stage)'s values, in the table's order."""
+        return {stage: _stage_norms(stage, grads) for stage, grads in host_walk(self.wanted, self.gen_w, context, kept).items()}
 
 
 class DeviceRoute:
-    """The objective over TrainLosses, Discriminators, Perceptual and ColourTail, on tensors of the device; f is read in the generator's workspace."""
+    """The objective over TrainLosses, Discriminators, Perceptual and the wanted stages' runners, on tensors of the device."""
 
-    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, decoder: bool = False, nonlocal_: bool = False, bottleneck: bool = False,
-                 heads: bool = False):
+    def __init__(self, disc_w, vgg_w, gen_w=None, device: int = 0, wanted=()):
         import torch
-        from . import BottleneckGrad, ColourDecoder, ColourTail, Discriminators, HeadsGrad, NonLocalGrad, Perceptual, TrainLosses
+        from . import Discriminators, Perceptual, TrainLosses
         self.dev = torch.device("cuda", device)
         self.three, self.gan, self.per = TrainLosses(device), Discriminators(device), Perceptual(device)
         self.gan.load_weights(disc_w)
         self.per.load_weights(vgg_w)
-        if gen_w is not None:
-            for name, stage, wanted in (("tail", ColourTail, True), ("dec", ColourDecoder, decoder), ("nl", NonLocalGrad, nonlocal_),
-                                       ("bn", BottleneckGrad, bottleneck), ("hd", HeadsGrad, heads)):
-                if wanted:
-                    setattr(self, name, stage(device))
-                    getattr(self, name).load_weights(gen_w)
+        self.runners = device_runners(wanted, gen_w, device)
         self.three_weights = torch.tensor(tl.G_TOTAL_WEIGHTS, dtype=torch.float32).to(self.dev)
         self.per_weight = torch.tensor([float(PER_WEIGHT)], dtype=torch.float32, device=self.dev)
 
     def bring(self, im_d, gt_a, mask_a, gs, con_rgb, generator=None, mask22=None):
         import torch
-        self.mask22 = mask22
-        return (im_d, torch.from_numpy(gt_a).to(self.dev), torch.from_numpy(mask_a).to(self.dev), gs, con_rgb), generator
+        return (im_d, torch.from_numpy(gt_a).to(self.dev), torch.from_numpy(mask_a).to(self.dev), gs, con_rgb), dict(generator=generator, mask22=mask22)
 
     def losses(self, img, gt, mask_sv, gs, con_rgb, per_grad: bool = False):
         three, gan = self.three.step_losses(img, gt, mask_sv, gs, con_rgb)[0].cpu().numpy(), self.gan.gan_losses(gt, con_rgb, mask_sv)[0].cpu().numpy()
@@ -204,32 +253,13 @@ class DeviceRoute:
         grad_con = (three[3] + gan[2]) + per[2]
         return three[0].cpu().numpy(), gan[0].cpu().numpy(), per[0].cpu().numpy(), grad_con, three[2]
 
-    def tail_norms(self, gs, generator, grad_con, grad_gs) -> List[float]:
-        res = self.tail.backward(generator, gs, grad_con, grad_gs)
-        self.d_f, self.d_gs, self.generator = res["d_f"], res["d_gs"], generator
-        return _stage_norms("tail", res)
-
-    def decoder_norms(self) -> List[float]:
-        res = self.dec.backward(self.generator, self.d_f)
-        self.d_x = res["d_x"]
-        return _stage_norms("decoder", res)
-
-    def nonlocal_norms(self) -> List[float]:
-        res = self.nl.backward(self.generator, self.d_x)
-        self.d_y3, self.d_skip = res["d_y3"], res["d_skip"]
-        return _stage_norms("nonlocal", res)
-
-    def bottleneck_norms(self) -> List[float]:
-        return _stage_norms("bottleneck", self.bn.backward(self.generator, self.d_y3, self.d_skip))
-
-    def heads_norms(self, img) -> List[float]:
-        return _stage_norms("heads", self.hd.backward(self.generator, img, self.mask22, self.d_gs))
+    def stage_norms(self, context, kept) -> Dict[str, List[float]]:
+        return {stage: _stage_norms(stage, grads) for stage, grads in device_walk(self.runners, kept["generator"], context).items()}
 
 
 def _norms(grad) -> List[float]:
     """The L1 and L-infinity norms of a gradient of either route: the sum and the largest of its magnitudes, in float64."""
-    g = np.abs(np.asarray(grad.cpu().numpy() if hasattr(grad, "cpu") else grad, np.float64))
-    return [float(g.sum()), float(g.max())]
+    return list(generator_grad.grad_norms({"": grad.cpu().numpy() if hasattr(grad, "cpu") else grad}, ("",))[""])
 
 
 # ---- the folder scoring
@@ -321,43 +351,35 @@ def score_folder(folder: str, vgg: str, ckpt: Optional[str] = None, batch: int =
                  nonlocal_: bool = False, bottleneck: bool = False, heads: bool = False) -> Dict[str, float]:
     """Every item folder `<folder>/<name>/` the shadow_synth command wrote -> the step-weighted means of ALL_NAMES.  `vgg`: the `.npz`
     of weights.load_vgg_weights; the other weights come from the latest checkpoint under `ckpt`, from init_weights and
-    init_discriminator_weights without it.  `grad`, `grad_total`, `tail`, `decoder`, `nonlocal_` and `bottleneck` add to each batch's line what
-    --grad, --grad-total, --tail, --decoder, --nonlocal and --bottleneck do; `heads` appends what --heads does after them."""
-    if tail and not grad_total:
-        raise ValueError("perceptual: --tail goes with --grad-total")
-    if decoder and not tail:
-        raise ValueError("perceptual: --decoder goes with --grad-total --tail")
-    if nonlocal_ and not decoder:
-        raise ValueError("perceptual: --nonlocal goes with --grad-total --tail --decoder")
-    if bottleneck and not nonlocal_:
-        raise ValueError("perceptual: --bottleneck goes with --grad-total --tail --decoder --nonlocal")
-    if heads and not tail:
-        raise ValueError("perceptual: --heads goes with --grad-total --tail")
+    init_discriminator_weights without it.  `grad`, `grad_total` and BACKWARD's stages add to each batch's line what their flags do."""
+    given = dict(tail=tail, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck, heads=heads)
+    wanted = tuple(s.name for s in BACKWARD if given[s.dest])
+    refused = refusal(wanted, grad_total)
+    if refused:
+        raise ValueError("perceptual: " + refused)
     vgg_w = load_vgg_weights(vgg)
     gen_w = None
-    if tail:
+    if wanted:
         from .tf_bundle import latest_checkpoint, load_generator_weights
         from .weights import init_weights
         gen_w = init_weights(1) if ckpt is None else load_generator_weights(latest_checkpoint(ckpt))
     disc_w = discriminator_weights(ckpt, "perceptual")
-    route = (HostRoute(disc_w, vgg_w, gen_w, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck, heads=heads) if host
-             else DeviceRoute(disc_w, vgg_w, gen_w, device, decoder=decoder, nonlocal_=nonlocal_, bottleneck=bottleneck, heads=heads))
+    route = HostRoute(disc_w, vgg_w, gen_w, wanted) if host else DeviceRoute(disc_w, vgg_w, gen_w, device, wanted)
 
     def step(*tensors):
-        arrays, f = route.bring(*tensors)
+        arrays, kept = route.bring(*tensors)
         if not grad_total:
             three, gan, per, g = route.losses(*arrays, per_grad=grad)
             return loss_record(three, gan, per), list(zip(GRAD_NAMES, _norms(g))) if grad else []
         three, gan, per, grad_con, grad_gs = route.total_grad(*arrays)
         extras = list(zip(TOTAL_GRAD_NAMES, _norms(grad_con) + _norms(grad_gs)))
-        for stage, wanted, args in zip(STAGES, (tail, decoder, nonlocal_, bottleneck), ((arrays[3], f, grad_con, grad_gs), (), (), ())):
-            if wanted:
-                extras += zip(stage_grad_names(stage), getattr(route, stage + "_norms")(*args))
-        if heads:
-            extras += zip(heads_grad_names(), route.heads_norms(arrays[0]))
+        context = dict(img=arrays[0], gs=arrays[3], mask22=kept.get("mask22"), grad_con=grad_con, grad_gs=grad_gs)
+        for stage, norms in route.stage_norms(context, kept).items():
+            extras += zip(stage_grad_names(stage), norms)
         return loss_record(three, gan, per), extras
 
-    return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=tail, nine_digits=True, with_mask22=heads)
+    return score_steps(folder, ckpt, batch, device, "perceptual", step, quiet, with_generator=bool(wanted), nine_digits=True,
+                       with_mask22=any("mask22" in _ROWS[name].takes for name in wanted))
 
 
 def main(argv=None) -> int:
@@ -371,24 +393,14 @@ def main(argv=None) -> int:
     ap.add_argument("--host", action="store_true", help="compute every term with the host statements instead of the device chains")
     ap.add_argument("--grad", action="store_true", help="per batch also the L1 and L-infinity norms of 0.005 d per / d con_rgb, this term's share of g_total_loss' gradient")
     ap.add_argument("--grad-total", action="store_true", help="per batch instead the norms of the whole d g_total_loss / d con_rgb and d g_total_loss / d gs")
-    ap.add_argument("--tail", action="store_true", help="with --grad-total: also the norms of d g_total_loss / d f, the complete d / d gs and the colour tail's ten variable gradients")
-    ap.add_argument("--decoder", action="store_true", help="with --grad-total --tail: also the norms of d g_total_loss / d x at res_stack/5's output and the colour decoder's twelve variable gradients")
-    ap.add_argument("--nonlocal", dest="nonlocal_", action="store_true", help="with --grad-total --tail --decoder: also the norms of d g_total_loss / d y3 at res_stack/5's bnorm3 output, of what the block's skip carries to its input, and of the non-local block's ten variable gradients")
-    ap.add_argument("--bottleneck", action="store_true", help="with --grad-total --tail --decoder --nonlocal: also the norms of d g_total_loss / d xin at res_stack/5's input and of the twelve variable gradients of the block's conv1, conv2, conv3 and their batch norms")
-    ap.add_argument("--heads", action="store_true", help="with --grad-total --tail: after the other columns the norms of d g_total_loss / d y at up3's output and of the four variable gradients of the grey heads conv2 and conv3, from the tail's complete d / d gs")
+    for s in BACKWARD:
+        ap.add_argument("--" + s.name, dest=s.dest, action="store_true", help="with %s: %s" % (stage_goes_with(s.name), s.help))
     a = ap.parse_args(argv)
-    if a.tail and not a.grad_total:
-        ap.error("--tail goes with --grad-total")
-    if a.decoder and not a.tail:
-        ap.error("--decoder goes with --grad-total --tail")
-    if a.nonlocal_ and not a.decoder:
-        ap.error("--nonlocal goes with --grad-total --tail --decoder")
-    if a.bottleneck and not a.nonlocal_:
-        ap.error("--bottleneck goes with --grad-total --tail --decoder --nonlocal")
-    if a.heads and not a.tail:
-        ap.error("--heads goes with --grad-total --tail")
-    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, tail=a.tail, decoder=a.decoder,
-                         nonlocal_=a.nonlocal_, bottleneck=a.bottleneck, heads=a.heads)
+    stages = {s.dest: getattr(a, s.dest) for s in BACKWARD}
+    refused = refusal([s.name for s in BACKWARD if stages[s.dest]], a.grad_total)
+    if refused:
+        ap.error(refused)
+    means = score_folder(a.folder, a.vgg, ckpt=a.ckpt, batch=a.batch, host=a.host, grad=a.grad, grad_total=a.grad_total, **stages)
     print(", ".join("%s:%.9g" % (k, means[k]) for k in ALL_NAMES))
     return 0
 

@@ -344,22 +344,18 @@ def test_backward_is_refused_before_a_forward_and_for_a_sixteen_bit_generator(ru
 
 
 def test_tail_decoder_nonlocal_and_bottleneck_chained(generated):
-    """ColourTail.backward, ColourDecoder.backward, NonLocalGrad.backward and BottleneckGrad.backward on one forward at (32, 256), against
-    the four statements chained on the device's own activations."""
-    from blindshadowremoval_amd import BottleneckGrad, ColourDecoder, ColourTail, NonLocalGrad
+    """The device walk over the colour branch (ColourTail.backward, ColourDecoder.backward, NonLocalGrad.backward and
+    BottleneckGrad.backward) on one forward at (32, 256), against the four statements chained on the device's own activations."""
+    from blindshadowremoval_amd import objective
     import clr_decoder_grad_cases as dec_cases
     import nonlocal_grad_cases as nl_cases
     import test_clr_tail_grad_gpu as tail_gpu
     gen, w, outs, copies = generated
-    tail, dec, nl, bn = ColourTail(0), ColourDecoder(0), NonLocalGrad(0), BottleneckGrad(0)
-    for r in (tail, dec, nl, bn):
-        r.load_weights(w)
     _, _, g_con_a, g_gs_a = host.example_inputs(32, 256, 2, 9)
     g_con, g_gs = to_dev(g_con_a, g_gs_a)
-    t = tail.backward(gen, outs[0], g_con, g_gs, keep=True)
-    d = dec.backward(gen, t["d_f"])
-    n = nl.backward(gen, d["d_x"])
-    b = to_host(bn.backward(gen, n["d_y3"], n["d_skip"], keep=True))
+    walked = objective.device_walk(objective.device_runners(objective.STAGES, w), gen, dict(gs=outs[0], grad_con=g_con, grad_gs=g_gs),
+                                   keep=("tail", "bottleneck"))
+    t, b = walked["tail"], to_host(walked["bottleneck"])
     torch.cuda.synchronize()
     f1, f2, f = (gen.probe(k).cpu().numpy() for k in ("f1", "f2", "f"))
     y3x, xin, out = (c.cpu().numpy() for c in copies)

@@ -291,17 +291,14 @@ def test_backward_reads_the_generators_tensors_in_place(runner, generated):
 
 
 def test_tail_and_decoder_chained(generated):
-    """ColourTail.backward then ColourDecoder.backward on one forward at (32, 256), against the two statements chained on the device's
-    own activations (the tail's a1, a2 and the decoder's f1, f2, f)."""
-    from blindshadowremoval_amd import ColourDecoder, ColourTail
+    """The device walk over the tail and the decoder (ColourTail.backward then ColourDecoder.backward) on one forward at (32, 256),
+    against the two statements chained on the device's own activations (the tail's a1, a2 and the decoder's f1, f2, f)."""
+    from blindshadowremoval_amd import objective
     gen, w, outs, copies = generated
-    tail, dec = ColourTail(0), ColourDecoder(0)
-    tail.load_weights(w)
-    dec.load_weights(w)
     _, _, g_con_a, g_gs_a = host.example_inputs(32, 256, 2, 9)
     g_con, g_gs = to_dev(g_con_a, g_gs_a)
-    t = tail.backward(gen, outs[0], g_con, g_gs, keep=True)
-    d = to_host(dec.backward(gen, t["d_f"]))
+    walked = objective.device_walk(objective.device_runners(("tail", "decoder"), w), gen, dict(gs=outs[0], grad_con=g_con, grad_gs=g_gs), keep=("tail",))
+    t, d = walked["tail"], to_host(walked["decoder"])
     torch.cuda.synchronize()
     x, f1, f2, f = (c.cpu().numpy() for c in copies)
     st_t = host.tail_grad(w, outs[0].cpu().numpy(), f, g_con_a, g_gs_a, acts={"a1": t["a1"].cpu().numpy(), "a2": t["a2"].cpu().numpy()})

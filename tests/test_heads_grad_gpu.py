@@ -318,19 +318,20 @@ def test_backward_is_refused_before_a_forward_and_for_a_sixteen_bit_generator(ru
 
 
 def test_total_gradient_tail_and_heads_chained(generated):
-    """Forward -> DeviceRoute.total_grad -> ColourTail.backward -> HeadsGrad.backward on one forward at 256 x 256, against the tail's and
-    the heads' statements chained on the device's own activations; the allowance is the two stages' added."""
+    """Forward -> DeviceRoute.total_grad -> the device walk over the tail and the heads (ColourTail.backward -> HeadsGrad.backward) on one
+    forward at 256 x 256, against the tail's and the heads' statements chained on the device's own activations; the allowance is the two
+    stages' added."""
     from blindshadowremoval_amd import objective
     from blindshadowremoval_amd.weights import init_discriminator_weights, init_vgg_weights
     import test_clr_tail_grad_gpu as tail_gpu
     gen, w, inputs, outs, y_copy = generated
-    route = objective.DeviceRoute(init_discriminator_weights(1), init_vgg_weights(21), w, heads=True)
+    route = objective.DeviceRoute(init_discriminator_weights(1), init_vgg_weights(21), w, wanted=("tail", "heads"))
     rng = np.random.default_rng(23)
     gt, mask_sv = to_dev(rng.uniform(0, 1, (1, 256, 256, 3)).astype(f32), rng.uniform(0, 1, (1, 256, 256, 3)).astype(f32))
     gs, con_rgb, mask22, _ = outs
     _, _, _, grad_con, grad_gs = route.total_grad(inputs, gt, mask_sv, gs, con_rgb)
-    t = route.tail.backward(gen, gs, grad_con, grad_gs, keep=True)
-    h = to_host(route.hd.backward(gen, inputs, mask22, t["d_gs"], keep=True))
+    walked = objective.device_walk(route.runners, gen, dict(img=inputs, gs=gs, mask22=mask22, grad_con=grad_con, grad_gs=grad_gs), keep=("tail", "heads"))
+    t, h = walked["tail"], to_host(walked["heads"])
     torch.cuda.synchronize()
     f = gen.probe("f").cpu().numpy()
     st_t = host.tail_grad(w, gs.cpu().numpy(), f, grad_con.cpu().numpy(), grad_gs.cpu().numpy(),

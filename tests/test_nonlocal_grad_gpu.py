@@ -319,20 +319,16 @@ def test_backward_reads_the_generators_tensors_in_place(runner, generated):
 
 
 def test_tail_decoder_and_nonlocal_chained(generated):
-    """ColourTail.backward, ColourDecoder.backward and NonLocalGrad.backward on one forward at (32, 256), against the three statements
-    chained on the device's own activations."""
-    from blindshadowremoval_amd import ColourDecoder, ColourTail, NonLocalGrad
+    """The device walk over the tail, the decoder and the non-local block (ColourTail.backward, ColourDecoder.backward and
+    NonLocalGrad.backward) on one forward at (32, 256), against the three statements chained on the device's own activations."""
+    from blindshadowremoval_amd import objective
     import clr_decoder_grad_cases as dec_cases
     import test_clr_tail_grad_gpu as tail_gpu
     gen, w, outs, copies = generated
-    tail, dec, nl = ColourTail(0), ColourDecoder(0), NonLocalGrad(0)
-    for r in (tail, dec, nl):
-        r.load_weights(w)
     _, _, g_con_a, g_gs_a = host.example_inputs(32, 256, 2, 9)
     g_con, g_gs = to_dev(g_con_a, g_gs_a)
-    t = tail.backward(gen, outs[0], g_con, g_gs, keep=True)
-    d = dec.backward(gen, t["d_f"])
-    n = to_host(nl.backward(gen, d["d_x"]))
+    walked = objective.device_walk(objective.device_runners(objective.STAGES[:3], w), gen, dict(gs=outs[0], grad_con=g_con, grad_gs=g_gs), keep=("tail",))
+    t, n = walked["tail"], to_host(walked["nonlocal"])
     torch.cuda.synchronize()
     f1, f2, f = (gen.probe(k).cpu().numpy() for k in ("f1", "f2", "f"))
     y3x, xin, out = (c.cpu().numpy() for c in copies)
