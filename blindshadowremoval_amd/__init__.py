@@ -3,7 +3,7 @@
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
 __all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
-           "NonLocalGrad", "BottleneckGrad", "HeadsGrad", "generator_variable_shapes", "init_weights"]
+           "NonLocalGrad", "BottleneckGrad", "HeadsGrad", "GreyDecoder", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -37,4 +37,7 @@ def __getattr__(name):
     if name == "HeadsGrad":
         from .heads_grad_gpu import HeadsGrad
         return HeadsGrad
+    if name == "GreyDecoder":
+        from .grey_decoder_gpu import GreyDecoder
+        return GreyDecoder
     raise AttributeError(name)

@@ -141,6 +141,16 @@ SIGNATURES = {
     "bsr_heads_grad": (c_i, [c_i, c_v, c_sz, c_v, c_v, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
     "bsr_debug_heads_grad": (c_i, [c_i, c_v, c_sz, c_v, c_v, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
     "bsr_last_y": (c_i, [c_v, ctypes.POINTER(c_v), ctypes.POINTER(c_i), ctypes.POINTER(c_i * 4)]),
+    "bsr_grey_decoder_grad_blob_bytes": (c_sz, []),
+    "bsr_grey_decoder_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_grey_decoder_grad_floats": (c_sz, []),
+    "bsr_grey_decoder_grad_var_offset": (c_sz, [c_i]),
+    "bsr_grey_decoder_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_grey_decoder_grad_partials": (c_i, [c_i, c_i, c_i, c_i]),
+    "bsr_grey_decoder_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_i, c_v, c_v]),
+    "bsr_debug_grey_decoder_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v, c_i, c_v, c_i,
+                                          c_v]),
+    "bsr_last_grey_decoder": (c_i, [c_v] + [ctypes.POINTER(c_v), ctypes.POINTER(c_i)] * 4 + [ctypes.POINTER(c_i * 4)]),
     "bsr_vgg_blob_bytes": (c_sz, []),
     "bsr_vgg_scratch_bytes": (c_sz, _BS),
     "bsr_vgg_act_offset": (c_sz, [c_i, c_i, c_i]),

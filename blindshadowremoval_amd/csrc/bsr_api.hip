@@ -44,6 +44,7 @@
 #include "disc_wgrad_kernels.h"
 #include "clr_tail_grad_kernels.h"
 #include "clr_up_grad_kernels.h"
+#include "grey_up_grad_kernels.h"
 #include "nonlocal_grad_kernels.h"
 #include "bottleneck_grad_kernels.h"
 #include "heads_grad_kernels.h"
@@ -1934,6 +1935,62 @@ int bsr_debug_heads_grad(int device, const void* d_blob, size_t blob_bytes, cons
   return heads_grad("bsr_debug_heads_grad", device, d_blob, blob_bytes, inputs, mask22, y, y_cs, d_gs, B, H, W, d_y, grads, scratch, stop_after, stream);
 }
 
+size_t bsr_grey_decoder_grad_blob_bytes(void) { return bsr::up_blob_off(bsr::kGreyUp, 3, 0) * sizeof(float); }
+
+size_t bsr_grey_decoder_grad_scratch_bytes(int B, int H, int W, int keep) {
+  return bsr::up_size_ok(B, H, W) ? bsr::up_plan(bsr::kGreyUp, B, H, W, keep != 0).total : 0;
+}
+
+size_t bsr_grey_decoder_grad_floats(void) { return bsr::up_var_offset(bsr::kGreyUp, bsr::kUpVars); }
+
+size_t bsr_grey_decoder_grad_var_offset(int index) { return index < 0 || index >= bsr::kUpVars ? SIZE_MAX : bsr::up_var_offset(bsr::kGreyUp, index); }
+
+size_t bsr_grey_decoder_grad_offset(int B, int H, int W, int map) {
+  if (!bsr::up_size_ok(B, H, W) || map < 0 || map > 8) return SIZE_MAX;
+  return bsr::up_plan(bsr::kGreyUp, B, H, W, true).map[map];
+}
+
+int bsr_grey_decoder_grad_partials(int B, int H, int W, int layer) {
+  return bsr::up_size_ok(B, H, W) && layer >= 1 && layer <= 3 ? bsr::up_plan(bsr::kGreyUp, B, H, W, false).P[layer - 1] : 0;
+}
+
+namespace {
+
+int grey_decoder_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* c2, int c2_cs,
+                      const float* c3, int c3_cs, const float* y, int y_cs, const float* d_y, int B, int H, int W, float* d_x, float* d_x3, float* d_x2,
+                      float* grads, int keep, void* scratch, int stop_after, void* stream) {
+  return run_grad_stage(
+      name, {d_blob, x, c2, c3, y, d_y, d_x, d_x3, d_x2, grads, scratch},
+      {{bsr::up_size_ok(B, H, W), "B must be positive, H a multiple of 32 and W a multiple of 256 (the generator's rule), at most 2^26 pixels in all"},
+       {blob_bytes == bsr_grey_decoder_grad_blob_bytes(),
+        "blob_bytes must be bsr_grey_decoder_grad_blob_bytes() (pack.pack_grey_decoder_grad; the GSC width 257 only, not TSM's 291)"},
+       {x_cs >= 257, "x_cs must be at least 257"},
+       {c2_cs >= 160 && c2_cs % 4 == 0 && c3_cs >= 128 && c3_cs % 4 == 0 && y_cs >= 64 && y_cs % 4 == 0,
+        "c2_cs, c3_cs, y_cs must be multiples of 4 and at least 160, 128, 64"}},
+      {{16, "d_blob, c2, c3, y, d_y, d_x3 and d_x2", {d_blob, c2, c3, y, d_y, d_x3, d_x2}}, {4, "x, d_x and grads", {x, d_x, grads}}}, scratch, stop_after,
+      bsr::kUpLaunches, device, [&] {
+        HIP_TRY(bsr::launch_grey_decoder_grad(static_cast<const float*>(d_blob), x, x_cs, c2, c2_cs, c3, c3_cs, y, y_cs, d_y, B, H, W, d_x, d_x3, d_x2, grads,
+                                              keep != 0, scratch, stop_after, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
+}  // namespace
+
+int bsr_grey_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* c2, int c2_cs, const float* c3, int c3_cs,
+                          const float* y, int y_cs, const float* d_y, int B, int H, int W, float* d_x, float* d_x3, float* d_x2, float* grads, int keep,
+                          void* scratch, void* stream) {
+  return grey_decoder_grad("bsr_grey_decoder_grad", device, d_blob, blob_bytes, x, x_cs, c2, c2_cs, c3, c3_cs, y, y_cs, d_y, B, H, W, d_x, d_x3, d_x2, grads,
+                           keep, scratch, bsr::kUpLaunches, stream);
+}
+
+int bsr_debug_grey_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* c2, int c2_cs, const float* c3,
+                                int c3_cs, const float* y, int y_cs, const float* d_y, int B, int H, int W, float* d_x, float* d_x3, float* d_x2,
+                                float* grads, int keep, void* scratch, int stop_after, void* stream) {
+  return grey_decoder_grad("bsr_debug_grey_decoder_grad", device, d_blob, blob_bytes, x, x_cs, c2, c2_cs, c3, c3_cs, y, y_cs, d_y, B, H, W, d_x, d_x3, d_x2,
+                           grads, keep, scratch, stop_after, stream);
+}
+
 size_t bsr_vgg_blob_bytes(void) { return bsr::vgg_w_off(bsr::kVggLayers) * sizeof(float); }
 
 size_t bsr_vgg_scratch_bytes(int B, int S) { return post_size_ok(B, S) && B <= bsr::kVggMaxB ? bsr::vgg_act_offset(B, S, bsr::kVggMaps + 1) : 0; }
@@ -2367,6 +2424,28 @@ int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1
   *f1 = h->ws + h->plan.f1;
   *f2 = h->ws + h->plan.f2;
   *f = h->ws + h->plan.cf;
+  shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
+  return BSR_OK;
+}
+
+int bsr_last_grey_decoder(bsr_handle* h, const float** x, int* x_cs, const float** c2, int* c2_cs, const float** c3, int* c3_cs, const float** y, int* y_cs,
+                          int shape4[4]) {
+  if (h == nullptr || x == nullptr || x_cs == nullptr || c2 == nullptr || c2_cs == nullptr || c3 == nullptr || c3_cs == nullptr || y == nullptr ||
+      y_cs == nullptr || shape4 == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_last_grey_decoder: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_grey_decoder: the grey decoder's backward takes the GSC widths only, not an RGB handle's 513");
+  if (h->var.tsm) return fail(BSR_ERR_STATE, "bsr_last_grey_decoder: the grey decoder's backward takes the GSC width 257 only, not a TSM handle's 291");
+  if (h->dtype != BSR_DTYPE_F32)
+    return fail(BSR_ERR_STATE, "bsr_last_grey_decoder: the decoder's tensors are fp32 in BSR_DTYPE_F32 handles only (the 16-bit modes keep them as fp16)");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_grey_decoder: no forward has run on this handle");
+  *x = h->ws + h->plan.r[2];
+  *x_cs = h->var.cs_r;
+  *c2 = h->ws + h->plan.c2;
+  *c2_cs = h->var.cs_c2;
+  *c3 = h->ws + h->plan.c3;
+  *c3_cs = h->var.cs_c3;
+  *y = h->ws + h->plan.ybuf;
+  *y_cs = h->var.cs_y;
   shape4[0] = h->B; shape4[1] = h->H; shape4[2] = h->W; shape4[3] = 64;
   return BSR_OK;
 }

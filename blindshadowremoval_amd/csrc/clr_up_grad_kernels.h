@@ -38,6 +38,8 @@
 //                                d K = inv[o] Wg rounded once; a thread per fine channel: S = sum gz in (p, row) order.
 //    9        up_finish_kernel   a wave per (layer, o): KW = sum K Wg -> d beta = S, d bias = inv S, d gamma = ((KW + bias S) - mean S) rstd.
 #pragma once
+#include <type_traits>
+
 #include "clr_tail_grad_kernels.h"
 
 namespace bsr {
@@ -47,17 +49,22 @@ constexpr int kUpVars = 12;
 // index 0: clr_up1, 1: clr_up2, 2: clr_up3
 constexpr int kUpO[3] = {128, 96, 64}, kUpC[3] = {261, 128, 96}, kUpCp[3] = {288, 128, 96};
 constexpr int kUpCtw[3] = {3, 2, 3};             // coarse 16-channel tiles per wave of up_wgrad_kernel: a workgroup has 32 CTW channels
-constexpr int kUpPcap[3] = {64, 85, 256};        // the largest P per layer: 12 P, 6 P, 2 P workgroups fill 256 CUs' one (clr_up1) or two places in whole rounds
+// kClrUp.pcap = 64, 85, 256 is the largest P per layer: 12 P, 6 P, 2 P workgroups fill 256 CUs' one (clr_up1) or two places in whole rounds
 constexpr int kUpMinTiles = 3;                   // P = min(cap, ceil(tiles / 3))
 constexpr int kUpLdo = 40, kUpGPix = 9 * 33;     // up_wgrad_kernel's fine patch
 constexpr int kUpDPix = 9 * 65;                  // up_dgrad_kernel's fine patch
 constexpr int kUpOc = 8;                         // fine channels per chunk of up_dgrad_kernel
 
-__host__ __device__ inline size_t up_blob_off(int layer, int part) {   // part 0: K [9][O][C], 1: Kf [9][O][Cp], 2: vecs [4][O]; layer 3: the total
-  const int O[3] = {128, 96, 64}, C[3] = {261, 128, 96}, Cp[3] = {288, 128, 96};
+// A decoder of three such layers, index 0 the lowest: the colour decoder here, the grey one in grey_up_grad_kernels.h
+struct UpShape {
+  int O[3], C[3], Cp[3], ctw[3], pcap[3];
+};
+constexpr UpShape kClrUp = {{128, 96, 64}, {261, 128, 96}, {288, 128, 96}, {3, 2, 3}, {64, 85, 256}};
+
+inline size_t up_blob_off(const UpShape& sh, int layer, int part) {   // part 0: K [9][O][C], 1: Kf [9][O][Cp], 2: vecs [4][O]; layer 3: the total
   size_t o = 0;
   for (int l = 0; l < 3; ++l) {
-    const size_t n[3] = {(size_t)9 * O[l] * C[l], (size_t)9 * O[l] * Cp[l], (size_t)4 * O[l]};
+    const size_t n[3] = {(size_t)9 * sh.O[l] * sh.C[l], (size_t)9 * sh.O[l] * sh.Cp[l], (size_t)4 * sh.O[l]};
     for (int q = 0; q < 3; ++q) {
       if (l == layer && q == part) return o;
       o += n[q];
@@ -65,24 +72,25 @@ __host__ __device__ inline size_t up_blob_off(int layer, int part) {   // part 0
   }
   return o;
 }
+inline size_t up_blob_off(int layer, int part) { return up_blob_off(kClrUp, layer, part); }
 
-// float offset of variable `index` (0..11: kernel, bias, gamma, beta of clr_up1, clr_up2, clr_up3) inside grads; 12: the total
-__host__ __device__ inline size_t up_var_offset(int index) {
-  const int O[3] = {128, 96, 64}, C[3] = {261, 128, 96};
+// float offset of variable `index` (0..11: kernel, bias, gamma, beta of the three layers) inside grads; 12: the total
+inline size_t up_var_offset(const UpShape& sh, int index) {
   size_t o = 0;
-  for (int v = 0; v < index && v < kUpVars; ++v) o += (v & 3) == 0 ? (size_t)9 * O[v >> 2] * C[v >> 2] : (size_t)O[v >> 2];
+  for (int v = 0; v < index && v < kUpVars; ++v) o += (v & 3) == 0 ? (size_t)9 * sh.O[v >> 2] * sh.C[v >> 2] : (size_t)sh.O[v >> 2];
   return o;
 }
+inline size_t up_var_offset(int index) { return up_var_offset(kClrUp, index); }
 
 inline bool up_size_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 256 == 0 && (long long)B * H * W <= (1ll << 26); }
 
-// Byte offsets inside the scratch.  map[0..2]: gz1 [B,H/4,W/4,128], gz2 [B,H/2,W/2,96], gz3 [B,H,W,64] (the last of the scratch, there only
-// with keep); map[3..5]: Wg of clr_up1..3 [9][O][C] float64; map[6..8]: S of clr_up1..3 [O] float64.
+// Byte offsets inside the scratch.  map[0..2]: gz1 [B,H/4,W/4,O1], gz2 [B,H/2,W/2,O2], gz3 [B,H,W,64] (the last of the scratch, there only
+// with keep); map[3..5]: Wg of the three layers [9][O][C] float64; map[6..8]: their S [O] float64.
 struct UpPlan {
   int h[3], w[3], T[3], P[3];
   size_t wpart[3], spart[3], map[9], total;
 };
-inline UpPlan up_plan(int B, int H, int W, bool keep) {
+inline UpPlan up_plan(const UpShape& sh, int B, int H, int W, bool keep) {
   UpPlan pl;
   BumpBytes bump;
   for (int l = 0; l < 3; ++l) {
@@ -90,19 +98,20 @@ inline UpPlan up_plan(int B, int H, int W, bool keep) {
     pl.w[l] = W >> (3 - l);
     pl.T[l] = B * (pl.h[l] / 4) * (pl.w[l] / 16);
     const int want = (pl.T[l] + kUpMinTiles - 1) / kUpMinTiles;
-    pl.P[l] = want < kUpPcap[l] ? want : kUpPcap[l];
-    pl.wpart[l] = bump.take((size_t)pl.P[l] * 9 * kUpO[l] * kUpCp[l] * sizeof(float));
-    pl.spart[l] = bump.take((size_t)pl.P[l] * (kUpO[l] / 32) * 256 * sizeof(double));
-    pl.map[3 + l] = bump.take((size_t)9 * kUpO[l] * kUpC[l] * sizeof(double));
-    pl.map[6 + l] = bump.take((size_t)kUpO[l] * sizeof(double));
+    pl.P[l] = want < sh.pcap[l] ? want : sh.pcap[l];
+    pl.wpart[l] = bump.take((size_t)pl.P[l] * 9 * sh.O[l] * sh.Cp[l] * sizeof(float));
+    pl.spart[l] = bump.take((size_t)pl.P[l] * (sh.O[l] / 32) * 256 * sizeof(double));
+    pl.map[3 + l] = bump.take((size_t)9 * sh.O[l] * sh.C[l] * sizeof(double));
+    pl.map[6 + l] = bump.take((size_t)sh.O[l] * sizeof(double));
   }
-  pl.map[0] = bump.take((size_t)B * (H / 4) * (W / 4) * 128 * sizeof(float));
-  pl.map[1] = bump.take((size_t)B * (H / 2) * (W / 2) * 96 * sizeof(float));
+  pl.map[0] = bump.take((size_t)B * (H / 4) * (W / 4) * sh.O[0] * sizeof(float));
+  pl.map[1] = bump.take((size_t)B * (H / 2) * (W / 2) * sh.O[1] * sizeof(float));
   pl.map[2] = bump.o;
-  if (keep) bump.take((size_t)B * H * W * 64 * sizeof(float));
+  if (keep) bump.take((size_t)B * H * W * sh.O[2] * sizeof(float));
   pl.total = bump.o;
   return pl;
 }
+inline UpPlan up_plan(int B, int H, int W, bool keep) { return up_plan(kClrUp, B, H, W, keep); }
 
 // ---- launch 1: the entry mask as a map of its own
 __global__ __launch_bounds__(256) void up_mask_kernel(const float* d_f, const float* f, int f_cs, float* gz, size_t n4) {
@@ -244,16 +253,24 @@ struct UpDgradArgs {
   const float* wf;        // the folded kernel [9][O][Cp]
   const float* below;     // the layer's input as the forward kept it, channel stride below_cs: its sign gives the slope; null: none
   float* out;             // [B,h,w,out_cs]
+  float* out2;            // up_dgrad_kernel's SPLIT > 0 alone: the skip half [B,h,w,C - 16 SPLIT]
   int act_cs, below_cs, out_cs, h, w, C, Cp, O, tiles_x, tiles_per_img;
 };
 
+// floats between the folded kernel's rows in LDS: four rows 16 (mod 32) apart
+template <int NT>
+constexpr int up_dgrad_ldw() { return NT * 16 + (NT % 2 ? 32 : 16); }
 template <int NT, int OC>
-constexpr int up_dgrad_smem_floats() { return 9 * OC * (NT * 16 + 16) + kUpDPix * (OC + 1); }
+constexpr int up_dgrad_smem_floats() { return 9 * OC * up_dgrad_ldw<NT>() + kUpDPix * (OC + 1); }
 
-// grid (B h / 4 w / 32, Cp / (16 NT)).  VEC: 16-byte stores of four real channels
-template <int NT, bool VEC, int OC>
+// grid (B h / 4 w / 32, Cp / (16 NT)).  VEC: 16-byte stores of four real channels.  SPLIT > 0 (the grey decoder's skip concatenations; VEC,
+// at most two column blocks): the 16-channel tiles below tile SPLIT take the slope from `below` and go to `out`, the tiles from SPLIT on go
+// unmasked to `out2`, dense [B,h,w,C - 16 SPLIT].  A column block's first skip tile is a constant of the kernel: the store loop is
+// compiled once per column block and the block takes its own, so no stored element meets a branch.
+template <int NT, bool VEC, int OC, int SPLIT = 0>
 __global__ __launch_bounds__(256, 2) void up_dgrad_kernel(const UpDgradArgs a) {
-  constexpr int LDW = NT * 16 + 16, LDG = OC + 1, WN = 9 * OC * NT * 4, GN = kUpDPix * (OC / 4), WV = (WN + 255) / 256, GV = (GN + 255) / 256;
+  static_assert(SPLIT == 0 || VEC, "the split epilogue stores whole tiles of real channels");
+  constexpr int LDW = up_dgrad_ldw<NT>(), LDG = OC + 1, WN = 9 * OC * NT * 4, GN = kUpDPix * (OC / 4), WV = (WN + 255) / 256, GV = (GN + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) float usm[];
   float* s_w = usm;                               // [9][OC][LDW]
   float* s_g = usm + 9 * OC * LDW;                // [585][OC + 1]
@@ -331,26 +348,38 @@ __global__ __launch_bounds__(256, 2) void up_dgrad_kernel(const UpDgradArgs a) {
       }
     }
   }
+  auto store = [&](auto first_skip) {
+    constexpr int LS = decltype(first_skip)::value;                       // this column block's first tile of the skip half; NT: none
 #pragma unroll
-  for (int pt = 0; pt < 2; ++pt) {
-    const size_t pix = ((size_t)img * a.h + y0 + wave) * a.w + x0 + pt * 16 + r;
+    for (int pt = 0; pt < 2; ++pt) {
+      const size_t pix = ((size_t)img * a.h + y0 + wave) * a.w + x0 + pt * 16 + r;
 #pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const int c0 = cb + n * 16 + 4 * q;
-      f32x4 v = acc[n][pt];
-      if constexpr (VEC) {
-        if (a.below != nullptr) {
-          const f32x4 m = *reinterpret_cast<const f32x4*>(a.below + pix * a.below_cs + c0);
+      for (int n = 0; n < NT; ++n) {
+        const int c0 = cb + n * 16 + 4 * q;
+        f32x4 v = acc[n][pt];
+        if (n >= LS) {
+          *reinterpret_cast<f32x4*>(a.out2 + pix * (a.C - 16 * SPLIT) + (c0 - 16 * SPLIT)) = v;
+        } else if constexpr (VEC) {
+          if (a.below != nullptr) {
+            const f32x4 m = *reinterpret_cast<const f32x4*>(a.below + pix * a.below_cs + c0);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = clr_leaky_grad(v[e], m[e]);
+            for (int e = 0; e < 4; ++e) v[e] = clr_leaky_grad(v[e], m[e]);
+          }
+          *reinterpret_cast<f32x4*>(a.out + pix * a.out_cs + c0) = v;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (c0 + e < a.C) a.out[pix * a.out_cs + c0 + e] = a.below != nullptr ? clr_leaky_grad(v[e], a.below[pix * a.below_cs + c0 + e]) : v[e];
         }
-        *reinterpret_cast<f32x4*>(a.out + pix * a.out_cs + c0) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c0 + e < a.C) a.out[pix * a.out_cs + c0 + e] = a.below != nullptr ? clr_leaky_grad(v[e], a.below[pix * a.below_cs + c0 + e]) : v[e];
       }
     }
+  };
+  if constexpr (SPLIT == 0) {
+    store(std::integral_constant<int, NT>{});
+  } else if (blockIdx.y == 0) {
+    store(std::integral_constant<int, (SPLIT < NT ? SPLIT : NT)>{});
+  } else {
+    store(std::integral_constant<int, (SPLIT > NT ? SPLIT - NT : 0)>{});
   }
 }
 
@@ -367,7 +396,8 @@ struct UpFoldLayer {
 struct UpFoldArgs {
   UpFoldLayer L[3];
 };
-inline int up_fold_blocks(int layer) { return (9 * kUpO[layer] * kUpC[layer] + 255) / 256 + 1; }
+inline int up_fold_blocks(const UpShape& sh, int layer) { return (9 * sh.O[layer] * sh.C[layer] + 255) / 256 + 1; }
+inline int up_fold_blocks(int layer) { return up_fold_blocks(kClrUp, layer); }
 
 __global__ __launch_bounds__(256) void up_fold_kernel(const UpFoldArgs a) {
   const int l = (int)blockIdx.x >= a.L[2].first ? 2 : (int)blockIdx.x >= a.L[1].first ? 1 : 0;
@@ -423,22 +453,53 @@ __global__ __launch_bounds__(64) void up_finish_kernel(const UpFinishArgs a) {
 }
 
 template <int CTW, bool VEC>
-inline hipError_t launch_up_wgrad(const UpWgradArgs& a, int layer, hipStream_t stream) {
+inline hipError_t launch_up_wgrad(const UpWgradArgs& a, int Cp, hipStream_t stream) {      // Cp: the layer's channels padded to whole chunks of 32 CTW
   static PerDeviceOnce once;
   constexpr int bytes = up_wgrad_smem_floats<CTW>() * (int)sizeof(float);
   const hipError_t e = dynamic_lds_once(up_wgrad_kernel<CTW, VEC>, bytes, once);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((up_wgrad_kernel<CTW, VEC>), dim3(a.P, kUpO[layer] / 32, kUpCp[layer] / (32 * CTW)), dim3(256), bytes, stream, a);
+  hipLaunchKernelGGL((up_wgrad_kernel<CTW, VEC>), dim3(a.P, a.O / 32, Cp / (32 * CTW)), dim3(256), bytes, stream, a);
   return hipGetLastError();
 }
 
-template <int NT, bool VEC>
+template <int NT, bool VEC, int SPLIT = 0>
 inline hipError_t launch_up_dgrad(const UpDgradArgs& a, int B, hipStream_t stream) {
   static PerDeviceOnce once;
   constexpr int bytes = up_dgrad_smem_floats<NT, kUpOc>() * (int)sizeof(float);
-  const hipError_t e = dynamic_lds_once(up_dgrad_kernel<NT, VEC, kUpOc>, bytes, once);
+  const hipError_t e = dynamic_lds_once(up_dgrad_kernel<NT, VEC, kUpOc, SPLIT>, bytes, once);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((up_dgrad_kernel<NT, VEC, kUpOc>), dim3(B * a.tiles_per_img, a.Cp / (16 * NT)), dim3(256), bytes, stream, a);
+  hipLaunchKernelGGL((up_dgrad_kernel<NT, VEC, kUpOc, SPLIT>), dim3(B * a.tiles_per_img, a.Cp / (16 * NT)), dim3(256), bytes, stream, a);
+  return hipGetLastError();
+}
+
+// launches 8 and 9 of a decoder `sh` whose scratch is laid out by up_plan(sh, ..) and whose blob by up_blob_off(sh, ..)
+inline hipError_t launch_up_fold(const UpShape& sh, const float* blob, const UpPlan& pl, unsigned char* base, float* grads, hipStream_t stream) {
+  UpFoldArgs a;
+  int first = 0;
+  for (int l = 0; l < 3; ++l) {
+    UpFoldLayer& L = a.L[l];
+    L.wpart = reinterpret_cast<const float*>(base + pl.wpart[l]); L.spart = reinterpret_cast<const double*>(base + pl.spart[l]);
+    L.inv = blob + up_blob_off(sh, l, 2) + sh.O[l]; L.Wg = reinterpret_cast<double*>(base + pl.map[3 + l]);
+    L.S = reinterpret_cast<double*>(base + pl.map[6 + l]); L.dk = grads + up_var_offset(sh, 4 * l);
+    L.O = sh.O[l]; L.C = sh.C[l]; L.NC = 32 * sh.ctw[l]; L.CCH = sh.Cp[l] / L.NC; L.P = pl.P[l]; L.first = first;
+    first += up_fold_blocks(sh, l);
+  }
+  hipLaunchKernelGGL(up_fold_kernel, dim3(first), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+inline hipError_t launch_up_finish(const UpShape& sh, const float* blob, const UpPlan& pl, unsigned char* base, float* grads, hipStream_t stream) {
+  UpFinishArgs a;
+  int first = 0;
+  for (int l = 0; l < 3; ++l) {
+    UpFinishLayer& L = a.L[l];
+    L.Wg = reinterpret_cast<const double*>(base + pl.map[3 + l]); L.S = reinterpret_cast<const double*>(base + pl.map[6 + l]);
+    L.k = blob + up_blob_off(sh, l, 0); L.vecs = blob + up_blob_off(sh, l, 2);
+    L.bias = grads + up_var_offset(sh, 4 * l + 1); L.gamma = grads + up_var_offset(sh, 4 * l + 2); L.beta = grads + up_var_offset(sh, 4 * l + 3);
+    L.O = sh.O[l]; L.C = sh.C[l]; L.first = first;
+    first += sh.O[l];
+  }
+  hipLaunchKernelGGL(up_finish_kernel, dim3(first), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -450,12 +511,10 @@ inline hipError_t launch_clr_decoder_grad(const float* blob, const float* x, int
   const UpPlan pl = up_plan(B, H, W, keep);
   unsigned char* base = static_cast<unsigned char*>(scratch);
   float* gz[3];
-  double *Wg[3], *S[3], *spart[3];
+  double* spart[3];
   float* wpart[3];
   for (int l = 0; l < 3; ++l) {
     gz[l] = reinterpret_cast<float*>(base + pl.map[l]);
-    Wg[l] = reinterpret_cast<double*>(base + pl.map[3 + l]);
-    S[l] = reinterpret_cast<double*>(base + pl.map[6 + l]);
     wpart[l] = reinterpret_cast<float*>(base + pl.wpart[l]);
     spart[l] = reinterpret_cast<double*>(base + pl.spart[l]);
   }
@@ -477,7 +536,7 @@ inline hipError_t launch_clr_decoder_grad(const float* blob, const float* x, int
       a.x = in[l]; a.g = g; a.act = l == 2 ? f : nullptr; a.wpart = wpart[l]; a.spart = spart[l];
       a.x_cs = in_cs[l]; a.act_cs = f_cs; a.h = pl.h[l]; a.w = pl.w[l]; a.C = kUpC[l]; a.O = kUpO[l];
       a.tiles_x = pl.w[l] / 16; a.tiles_per_img = a.tiles_x * (pl.h[l] / 4); a.T = pl.T[l]; a.P = pl.P[l];
-      e = l == 2 ? launch_up_wgrad<3, true>(a, l, stream) : l == 1 ? launch_up_wgrad<2, true>(a, l, stream) : launch_up_wgrad<3, false>(a, l, stream);
+      e = l == 2 ? launch_up_wgrad<3, true>(a, kUpCp[l], stream) : l == 1 ? launch_up_wgrad<2, true>(a, kUpCp[l], stream) : launch_up_wgrad<3, false>(a, kUpCp[l], stream);
       if (e != hipSuccess) return e;
     }
     if (stop_after <= done++) return hipSuccess;
@@ -485,7 +544,7 @@ inline hipError_t launch_clr_decoder_grad(const float* blob, const float* x, int
       UpDgradArgs a;
       a.g = g; a.act = l == 2 ? f : nullptr; a.wf = blob + up_blob_off(l, 1);
       a.below = l == 0 ? nullptr : in[l]; a.below_cs = in_cs[l];
-      a.out = l == 0 ? d_x : gz[l - 1]; a.out_cs = kUpC[l];
+      a.out = l == 0 ? d_x : gz[l - 1]; a.out2 = nullptr; a.out_cs = kUpC[l];
       a.act_cs = f_cs; a.h = pl.h[l]; a.w = pl.w[l]; a.C = kUpC[l]; a.Cp = kUpCp[l]; a.O = kUpO[l];
       a.tiles_x = pl.w[l] / 32; a.tiles_per_img = a.tiles_x * (pl.h[l] / 4);
       e = l == 2 ? launch_up_dgrad<6, true>(a, B, stream) : l == 1 ? launch_up_dgrad<8, true>(a, B, stream) : launch_up_dgrad<6, false>(a, B, stream);
@@ -493,30 +552,9 @@ inline hipError_t launch_clr_decoder_grad(const float* blob, const float* x, int
     }
   }
   if (stop_after <= done++) return hipSuccess;
-  {
-    UpFoldArgs a;
-    int first = 0;
-    for (int l = 0; l < 3; ++l) {
-      UpFoldLayer& L = a.L[l];
-      L.wpart = wpart[l]; L.spart = spart[l]; L.inv = blob + up_blob_off(l, 2) + kUpO[l]; L.Wg = Wg[l]; L.S = S[l]; L.dk = grads + up_var_offset(4 * l);
-      L.O = kUpO[l]; L.C = kUpC[l]; L.NC = 32 * kUpCtw[l]; L.CCH = kUpCp[l] / L.NC; L.P = pl.P[l]; L.first = first;
-      first += up_fold_blocks(l);
-    }
-    hipLaunchKernelGGL(up_fold_kernel, dim3(first), dim3(256), 0, stream, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  if ((e = launch_up_fold(kClrUp, blob, pl, base, grads, stream)) != hipSuccess) return e;
   if (stop_after <= done++) return hipSuccess;
-  UpFinishArgs a;
-  int first = 0;
-  for (int l = 0; l < 3; ++l) {
-    UpFinishLayer& L = a.L[l];
-    L.Wg = Wg[l]; L.S = S[l]; L.k = blob + up_blob_off(l, 0); L.vecs = blob + up_blob_off(l, 2);
-    L.bias = grads + up_var_offset(4 * l + 1); L.gamma = grads + up_var_offset(4 * l + 2); L.beta = grads + up_var_offset(4 * l + 3);
-    L.O = kUpO[l]; L.C = kUpC[l]; L.first = first;
-    first += kUpO[l];
-  }
-  hipLaunchKernelGGL(up_finish_kernel, dim3(first), dim3(64), 0, stream, a);
-  return hipGetLastError();
+  return launch_up_finish(kClrUp, blob, pl, base, grads, stream);
 }
 
 }  // namespace bsr

@@ -12,7 +12,10 @@ conv3 (1x1, 128 -> 257), each with its BatchNormalization and the first two with
 and d_skip to the gradient at the block's input and the twelve variables; csrc/bottleneck_grad_kernels.h is held to it
 (bottleneck_grad_gpu.BottleneckGrad).  On the grey branch the heads (model.py:246-250): conv2 (7x7, 64 -> 1, tanh) gives mask, conv3
 (7x7, 64 -> 1) gives con, gs = gray(inputs) (1 + mask) + con; `heads_grad` is its statement, from the complete d_gs to the gradient at up3's
-output y and the four variables; csrc/heads_grad_kernels.h is held to it (heads_grad_gpu.HeadsGrad)."""
+output y and the four variables; csrc/heads_grad_kernels.h is held to it (heads_grad_gpu.HeadsGrad).  Below the heads the grey decoder
+(model.py:243-245): up1, up2 on cat[up1, x3], up3 on cat[up2, x2], the colour decoder's layer type; `grey_decoder_grad` is its statement,
+from d_y to the gradient at res_stack/2's output, the two skip gradients and the twelve variables; csrc/grey_up_grad_kernels.h is held
+to it (grey_decoder_gpu.GreyDecoder)."""
 from __future__ import annotations
 
 import functools
@@ -22,7 +25,7 @@ import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
 from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_decoder_trainable_names,
-                      generator_heads_trainable_names, generator_nonlocal_trainable_names, generator_tail_trainable_names)
+                      generator_grey_decoder_trainable_names, generator_heads_trainable_names, generator_nonlocal_trainable_names, generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
@@ -244,6 +247,22 @@ def decoder_forward(weights: Dict[str, np.ndarray], x, dtype=np.float64) -> Tupl
     return tuple(outs)
 
 
+def _convt_layer_grad(weights: Dict[str, np.ndarray], stem: str, a_in: np.ndarray, a_out: np.ndarray, g: np.ndarray, out: Dict[str, np.ndarray]):
+    """One Conv2DTranspose + BN + LeakyReLU layer of decoder_grad and grey_decoder_grad, in float64: its four variable gradients go into
+    `out` under `stem`'s names -> (gz, dx), the gradient at its BatchNormalization output and at its input a_in (no mask applied)."""
+    K = np.asarray(weights[stem + "/conv/kernel"], np.float64)
+    bias, inv, mean, rstd, _ = bn_vectors(weights, stem)
+    gz = leaky_grad(g, a_out)
+    S = gz.sum(axis=(0, 1, 2))
+    Wg = convt3x3_same_wgrad(a_in, gz)
+    KW = (K * Wg).sum(axis=(0, 1, 3))
+    out[stem + "/conv/kernel"] = Wg * inv[:, None]
+    out[stem + "/conv/bias"] = inv * S
+    out[stem + "/bnorm/gamma"] = ((KW + bias * S) - mean * S) * rstd
+    out[stem + "/bnorm/beta"] = S
+    return gz, convt3x3_same_dgrad(gz * inv, K)
+
+
 def decoder_grad(weights: Dict[str, np.ndarray], x, d_f, acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
     """The gradient d_f [B,8h,8w,64] at f -> dict(the twelve variables of weights.generator_decoder_trainable_names() in their own shapes,
     `d_x` [B,h,w,C] at clr_up1's input x, the stage maps `gz3` [B,8h,8w,64], `gz2` [B,4h,4w,96], `gz1` [B,2h,2w,128] — the gradients at
@@ -263,21 +282,8 @@ def decoder_grad(weights: Dict[str, np.ndarray], x, d_f, acts: Optional[Dict[str
         f1, f2, f = decoder_forward(weights, x, T)
     out: Dict[str, np.ndarray] = {"f1": f1, "f2": f2, "f": f}
     g = np.asarray(d_f, T)
-    ax = (0, 1, 2)
     for i, a_in, a_out in ((3, f2, f), (2, f1, f2), (1, x, f1)):
-        stem = DECODER_LAYERS[i - 1]
-        K = np.asarray(weights[stem + "/conv/kernel"], T)
-        bias, inv, mean, rstd, _ = bn_vectors(weights, stem)
-        gz = leaky_grad(g, a_out)
-        out["gz%d" % i] = gz
-        S = gz.sum(axis=ax)
-        Wg = convt3x3_same_wgrad(a_in, gz)
-        KW = (K * Wg).sum(axis=(0, 1, 3))
-        out[stem + "/conv/kernel"] = Wg * inv[:, None]
-        out[stem + "/conv/bias"] = inv * S
-        out[stem + "/bnorm/gamma"] = ((KW + bias * S) - mean * S) * rstd
-        out[stem + "/bnorm/beta"] = S
-        g = convt3x3_same_dgrad(gz * inv, K)
+        out["gz%d" % i], g = _convt_layer_grad(weights, DECODER_LAYERS[i - 1], a_in, a_out, g, out)
     out["d_x"] = g
     return out
 
@@ -301,6 +307,76 @@ def decoder_example_inputs(h: int, w: int, B: int, seed: int = 0, C: int = 261):
     x = np.where(x >= 0, x, np.float32(LRELU_ALPHA) * x).astype(np.float32)
     d_f = (rng.standard_normal((B, 8 * h, 8 * w, 64)) / (B * h * w * 64)).astype(np.float32)
     return x, d_f
+
+
+# ---- the grey decoder: up1, up2 (on cat[up1, x3]), up3 (on cat[up2, x2])
+GREY_DECODER_LAYERS = ("up1", "up2", "up3")
+GREY_DECODER_NORM_NAMES = ("d_x", "d_x3", "d_x2") + tuple(generator_grey_decoder_trainable_names())
+
+
+def grey_decoder_forward(weights: Dict[str, np.ndarray], x, x3, x2, dtype=np.float64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """x [B,h,w,257] (res_stack/2's output), x3 [B,2h,2w,64], x2 [B,4h,4w,64] (the encoder's skips) -> (up1 [B,2h,2w,96], up2
+    [B,4h,4w,64], y [B,8h,8w,64]) in `dtype` (model.py:243-245): up1 = layer(x), up2 = layer(cat[up1, x3]), y = layer(cat[up2, x2]) with
+    decoder_forward's layer, c = ConvT(a_in, K) + bias, z = (c - mean) rstd gamma + beta, a_out = lrelu_0.3(z)."""
+    T = dtype
+    h = np.asarray(x, T)
+    outs = []
+    for stem, skip in zip(GREY_DECODER_LAYERS, (None, x3, x2)):
+        if skip is not None:
+            h = np.concatenate([h, np.asarray(skip, T)], axis=3)
+        bias, _, mean, rstd, beta = bn_vectors(weights, stem, T)
+        c = convt3x3_same(h, np.asarray(weights[stem + "/conv/kernel"], T)) + bias
+        h = _lrelu((c - mean) * rstd * np.asarray(weights[stem + "/bnorm/gamma"], T) + beta)
+        outs.append(h)
+    return tuple(outs)
+
+
+def grey_decoder_grad(weights: Dict[str, np.ndarray], x, x3, x2, d_y, acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """The gradient d_y [B,8h,8w,64] at y, up3's output -> dict(the twelve variables of weights.generator_grey_decoder_trainable_names()
+    in their own shapes, `d_x` [B,h,w,257] at up1's input, the skip gradients `d_x3` [B,2h,2w,64] and `d_x2` [B,4h,4w,64], the stage maps
+    `gz3` [B,8h,8w,64], `gz2` [B,4h,4w,64], `gz1` [B,2h,2w,96] and `up1`, `up2`, `y` as used), all float64 from the float32 variables.
+    Per layer from the top down the arithmetic is decoder_grad's; the layer inputs are cat[up2, x2], cat[up1, x3] and x, the kernels' C
+    index in that order.  up3's dx has 128 channels: 0..63 are the g of up2 and take up2's LeakyReLU slope there, 64..127 are d_x2 and
+    get no mask (down1's LeakyReLU belongs to the encoder's backward); up2's dx has 160: 0..95 the g of up1, 96..159 d_x3; up1's dx is d_x,
+    no mask (res_stack/2's relu belongs to that block's backward).  With `acts` given (a dict with `up1`, `up2`, `y`, for example the
+    device's), the masks and the layer inputs are read from it."""
+    T = np.float64
+    x, x3, x2 = (np.asarray(a, T) for a in (x, x3, x2))
+    if acts is not None:
+        up1, up2, y = (np.asarray(acts[k], T) for k in ("up1", "up2", "y"))
+    else:
+        up1, up2, y = grey_decoder_forward(weights, x, x3, x2, T)
+    out: Dict[str, np.ndarray] = {"up1": up1, "up2": up2, "y": y}
+    out["gz3"], dx = _convt_layer_grad(weights, "up3", np.concatenate([up2, x2], axis=3), y, np.asarray(d_y, T), out)
+    out["d_x2"] = dx[..., 64:].copy()
+    out["gz2"], dx = _convt_layer_grad(weights, "up2", np.concatenate([up1, x3], axis=3), up2, dx[..., :64], out)
+    out["d_x3"] = dx[..., 96:].copy()
+    out["gz1"], out["d_x"] = _convt_layer_grad(weights, "up1", x, up1, dx[..., :96], out)
+    return out
+
+
+def grey_decoder_objective_f64(weights: Dict[str, np.ndarray], x, x3, x2, d_y, masks: Optional[list] = None, dtype=np.float64):
+    """<d_y, y> in `dtype` with no float32 rounding anywhere: the scalar whose gradient grey_decoder_grad states.  A list given as
+    `masks` receives the three LeakyReLU masks (z > 0) of up1, up2, y."""
+    outs = grey_decoder_forward(weights, x, x3, x2, dtype)
+    if masks is not None:
+        masks += [a > 0 for a in outs]
+    return (np.asarray(d_y, dtype) * outs[2]).sum()
+
+
+grey_decoder_norms = functools.partial(grad_norms, names=GREY_DECODER_NORM_NAMES)    # of `d_x`, `d_x3`, `d_x2` and each of the twelve variable gradients
+
+
+def grey_decoder_example_inputs(h: int, w: int, B: int, seed: int = 0):
+    """Seeded (x [B,h,w,257], x3 [B,2h,2w,64], x2 [B,4h,4w,64], d_y [B,8h,8w,64]) float32 at a coarse grid: x, x3, x2 like LeakyReLU
+    outputs, d_y scaled as decoder_example_inputs scales d_f."""
+    rng = np.random.default_rng(3000 + seed)
+    acts = []
+    for m, c in ((1, 257), (2, 64), (4, 64)):
+        a = rng.standard_normal((B, m * h, m * w, c)).astype(np.float32)
+        acts.append(np.where(a >= 0, a, np.float32(LRELU_ALPHA) * a).astype(np.float32))
+    d_y = (rng.standard_normal((B, 8 * h, 8 * w, 64)) / (B * h * w * 64)).astype(np.float32)
+    return acts[0], acts[1], acts[2], d_y
 
 
 # ---- the upper half of res_stack/<block>: the non-local block, the skip and relu3

@@ -262,6 +262,19 @@ class Generator:
         _lib.check(self._lib.bsr_last_y(self._handle, ctypes.byref(ptr), ctypes.byref(cs), ctypes.byref(shape)), "bsr_last_y")
         return int(ptr.value), int(cs.value), (shape[0], shape[1], shape[2], shape[3])
 
+    def last_grey_decoder(self) -> Tuple[Tuple[int, int, int, int], Tuple[int, int, int, int], Tuple[int, int, int, int]]:
+        """((x, c2, c3, y) device addresses, their floats between pixels, (B, H, W, 64)) of the last forward's grey decoder tensors in the
+        handle's workspace (bsr_last_grey_decoder): x = res_stack/2's output [B,H/8,W/8,257 of x_cs], c2 = [up1 96 | x3 64] at
+        [B,H/4,W/4], c3 = [up2 64 | x2 64] at [B,H/2,W/2], y = up3's output [B,H,W,64].  No copy; valid until the next forward on this
+        generator.  Under last_decoder's conditions."""
+        self._require_weights()
+        ptrs = [ctypes.c_void_p() for _ in range(4)]
+        cs = [ctypes.c_int() for _ in range(4)]
+        shape = (ctypes.c_int * 4)()
+        args = [ctypes.byref(v) for pair in zip(ptrs, cs) for v in pair]
+        _lib.check(self._lib.bsr_last_grey_decoder(self._handle, *args, ctypes.byref(shape)), "bsr_last_grey_decoder")
+        return tuple(int(p.value) for p in ptrs), tuple(int(c.value) for c in cs), (shape[0], shape[1], shape[2], shape[3])
+
     def set_timing(self, enable: bool) -> None:
         _lib.check(self._lib.bsr_set_timing(self._handle, 1 if enable else 0), "bsr_set_timing")
 

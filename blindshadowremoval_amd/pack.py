@@ -827,6 +827,65 @@ def unpack_clr_decoder_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the generator's grey decoder backward (csrc/grey_up_grad_kernels.h): the colour decoder's blob at the grey widths ----
+GREY_DECODER_SHAPES = ((96, 257, 288), (64, 160, 160), (64, 128, 128))          # (O, C, C padded) of up1, up2 (on cat[up1, x3]), up3 (on cat[up2, x2])
+GREY_DECODER_WIDTH_TEXT = ("the grey decoder's device chain takes the GSC widths only: %s/conv/kernel must be [3,3,%d,%d], got %s (TSM's 291-wide up1 and the "
+                           "RGB baseline's 513-wide one are covered by generator_grad.grey_decoder_grad's arithmetic, not by this blob)")
+
+
+def grey_decoder_grad_layout():
+    """([(name, offset in floats, shape)], floats) of the grey decoder's gradient blob, per layer i = 1, 2, 3, as clr_decoder_grad_layout:
+      k<i>       the UNFOLDED kernel [9 taps (a * 3 + b)][O][C], the variable's own order, C in the cat order
+      kf<i>      the data gradient's kernel inv[o] K [9][O][C padded]: up1's 257 columns padded with zeros to 288
+      vecs<i>    [4][O]: the convolution's bias, inv, moving_mean, rstd
+    inv, rstd and the folded kernel are formed in float64 and rounded once."""
+    out, off = [], 0
+    for i, (o, c, cp) in enumerate(GREY_DECODER_SHAPES, 1):
+        for name, shape in (("k%d" % i, (9, o, c)), ("kf%d" % i, (9, o, cp)), ("vecs%d" % i, (4, o))):
+            out.append((name, off, shape))
+            off += int(np.prod(shape))
+    return out, off
+
+
+def grey_decoder_grad_record(weights: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """name -> float32 array of grey_decoder_grad_layout's shapes.  ValueError for any width but the GSC one (TSM, RGB)."""
+    from .weights import BN_EPS
+    rec = {}
+    for i, (o, c, cp) in enumerate(GREY_DECODER_SHAPES, 1):
+        stem = "up%d" % i
+        k = np.asarray(weights[stem + "/conv/kernel"], np.float64)
+        if k.shape != (3, 3, o, c):
+            raise ValueError(GREY_DECODER_WIDTH_TEXT % (stem, o, c, k.shape))
+        k = k.reshape(9, o, c)
+        rstd = 1.0 / np.sqrt(np.asarray(weights[stem + "/bnorm/moving_variance"], np.float64) + BN_EPS)
+        inv = np.asarray(weights[stem + "/bnorm/gamma"], np.float64) * rstd
+        kf = np.zeros((9, o, cp), np.float64)
+        kf[:, :, :c] = k * inv[None, :, None]
+        rec["k%d" % i], rec["kf%d" % i] = k, kf
+        rec["vecs%d" % i] = np.stack([np.asarray(weights[stem + "/conv/bias"], np.float64), inv, np.asarray(weights[stem + "/bnorm/moving_mean"], np.float64), rstd])
+    return {name: np.ascontiguousarray(a, np.float32) for name, a in rec.items()}
+
+
+def pack_grey_decoder_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (the grey decoder's 18 are read) -> the blob bsr_grey_decoder_grad takes (grey_decoder_grad_layout)."""
+    layout, total = grey_decoder_grad_layout()
+    rec = grey_decoder_grad_record(weights)
+    blob = np.zeros(total, np.float32)
+    for name, off, shape in layout:
+        assert rec[name].shape == tuple(shape), name
+        blob[off:off + rec[name].size] = rec[name].reshape(-1)
+    return blob.tobytes()
+
+
+def unpack_grey_decoder_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_grey_decoder_grad: grey_decoder_grad_record's dict."""
+    layout, total = grey_decoder_grad_layout()
+    arr = np.frombuffer(blob, np.float32)
+    if arr.size != total:
+        raise ValueError("a grey decoder gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
+
+
 # ---- the generator's non-local block backward (csrc/nonlocal_grad_kernels.h): a blob of its own, no header, float32 ----
 NONLOCAL_TSM_TEXT = "the non-local block's device chain takes the GSC width only (TSM's 877 is covered by generator_grad.nonlocal_grad)"
 NONLOCAL_CP = 272            # 257 channels padded to the GEMMs' 16-channel steps

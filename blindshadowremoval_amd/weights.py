@@ -132,6 +132,14 @@ def generator_decoder_trainable_names(variant: str = "gsc") -> List[str]:
             and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_grey_decoder_trainable_names(variant: str = "gsc") -> List[str]:
+    """The twelve trainable variables of the generator's grey decoder (up1, up2, up3) in generator_variable_shapes' order, 388 608 floats
+    for GSC: every kernel [3,3,out,in] (in = 257, 160 = cat[up1, x3], 128 = cat[up2, x2]), bias, gamma and beta; moving_mean and
+    moving_variance take no gradient."""
+    return [n for n in generator_variable_shapes(variant) if n.split("/", 1)[0] in ("up1", "up2", "up3")
+            and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 def generator_nonlocal_trainable_names(block: int = 5, variant: str = "gsc") -> List[str]:
     """The ten trainable variables of res_stack/<block>'s NonLocalBlock in generator_variable_shapes' order, 132 739 floats: the kernel
     and bias of g, phi, theta and w, and bnorm's gamma and beta; moving_mean and moving_variance take no gradient."""

@@ -470,6 +470,41 @@ int bsr_heads_grad(int device, const void* d_blob, size_t blob_bytes, const floa
 int bsr_debug_heads_grad(int device, const void* d_blob, size_t blob_bytes, const float* inputs, const float* mask22, const float* y, int y_cs,
                          const float* d_gs, int B, int H, int W, float* d_y, float* grads, void* scratch, int stop_after, void* stream);
 
+/* The backward of the generator's grey decoder (training=False, fp32; the reference's model.py:243-245): up1 (257 -> 96, H/8 -> H/4), up2
+ * (cat[up1, x3] 160 -> 64, -> H/2), up3 (cat[up2, x2] 128 -> 64, -> H), each Conv2DTranspose(3, stride 2, SAME) + BN + LeakyReLU.
+ * Stateless; all pointers are caller-owned device pointers.  H, W are the IMAGE's (H a multiple of 32, W of 256).  Inputs: d_blob,
+ * bsr_grey_decoder_grad_blob_bytes() bytes of pack.pack_grey_decoder_grad (GSC width only), 16-byte aligned; x [B,H/8,W/8,257],
+ * res_stack/2's output, with x_cs >= 257 floats between pixels (any value: lanes past channel 256 are never read); c2 [B,H/4,W/4,160] =
+ * [up1 96 | x3 64], c3 [B,H/2,W/2,128] = [up2 64 | x2 64], y [B,H,W,64] = up3's output, the concatenations whole as the forward laid them
+ * out, with c2_cs, c3_cs, y_cs floats between pixels (multiples of 4, 16-byte aligned); d_y [B,H,W,64] dense = d loss / d y
+ * (bsr_heads_grad's), never written.  Outputs, all dense: d_x [B,H/8,W/8,257]; d_x3 [B,H/4,W/4,64] and d_x2 [B,H/2,W/2,64], the gradients
+ * at the skip halves of c2 and c3, without the encoder's LeakyReLU mask; and grads, bsr_grey_decoder_grad_floats() = 388608 float32: the
+ * twelve variables of weights.generator_grey_decoder_trainable_names() in that order, variable `index` (0..11) at float offset
+ * bsr_grey_decoder_grad_var_offset(index); SIZE_MAX out of range.  Nine launches on `stream`, one after the other
+ * (csrc/grey_up_grad_kernels.h), no host synchronisation, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_grey_decoder_grad_scratch_bytes(B, H, W, keep) bytes, 256-byte aligned; every word read is written earlier in the same call.
+ * bsr_grey_decoder_grad_offset(B, H, W, map) is the byte offset of map 0 gz1 [B,H/4,W/4,96], 1 gz2 [B,H/2,W/2,64], 2 gz3 [B,H,W,64]
+ * (float32; gz3 is the scratch's last part, there and written only with keep != 0), 3..5 Wg of up1..3 [9][O][C] float64, 6..8 the sums S of
+ * up1..3 [O] float64; SIZE_MAX out of range.  bsr_grey_decoder_grad_partials(B, H, W, layer) is the number of partials P of layer 1..3's
+ * kernel gradient, min(cap, ceil(tiles / 3)) with caps 85, 51, 128 (0 for bad arguments).  A bad argument gives BSR_ERR_ARG with a
+ * message and nothing launched.  bsr_debug_grey_decoder_grad stops after `stop_after` (0..9) launches.
+ * bsr_last_grey_decoder: where the last forward's x, c2, c3, y lie in the handle's workspace, with their floats between pixels; shape4 =
+ * [B,H,W,64], the image's.  The rules and error codes of bsr_last_decoder.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_grey_decoder_grad_blob_bytes(void);
+size_t bsr_grey_decoder_grad_scratch_bytes(int B, int H, int W, int keep);
+size_t bsr_grey_decoder_grad_floats(void);
+size_t bsr_grey_decoder_grad_var_offset(int index);
+size_t bsr_grey_decoder_grad_offset(int B, int H, int W, int map);
+int bsr_grey_decoder_grad_partials(int B, int H, int W, int layer);
+int bsr_grey_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* c2, int c2_cs, const float* c3, int c3_cs,
+                          const float* y, int y_cs, const float* d_y, int B, int H, int W, float* d_x, float* d_x3, float* d_x2, float* grads, int keep,
+                          void* scratch, void* stream);
+int bsr_debug_grey_decoder_grad(int device, const void* d_blob, size_t blob_bytes, const float* x, int x_cs, const float* c2, int c2_cs, const float* c3,
+                                int c3_cs, const float* y, int y_cs, const float* d_y, int B, int H, int W, float* d_x, float* d_x3, float* d_x2,
+                                float* grads, int keep, void* scratch, int stop_after, void* stream);
+int bsr_last_grey_decoder(bsr_handle* h, const float** x, int* x_cs, const float** c2, int* c2_cs, const float** c3, int* c3_cs, const float** y, int* y_cs,
+                          int shape4[4]);
+
 /* The VGG19 perceptual term of the reference's train_step (train_test_GSC.py:128-139, 153-160, 303; utils.py:104-114) for a batch on
  * the device: per_loss = style_content_loss(feat_extractor, concat([gt, con_rgb])); blindshadowremoval_amd/perceptual.py is the host
  * statement and writes the arithmetic out.  d_blob: the device copy of pack.pack_vgg's blob, blob_bytes = bsr_vgg_blob_bytes() (about

@@ -33,8 +33,8 @@ sys.path.insert(0, ROOT)
 
 MATRIX_FLOPS = 157.3e12
 # the launches in order (the mask launch runs only when maps are kept: not in a plain call)
-KERNELS = ("up_wgrad_kernel<3, true>", "up_dgrad_kernel<6, true, 8>", "up_wgrad_kernel<2, true>", "up_dgrad_kernel<8, true, 8>", "up_wgrad_kernel<3, false>",
-           "up_dgrad_kernel<6, false, 8>", "up_fold_kernel", "up_finish_kernel")
+KERNELS = ("up_wgrad_kernel<3, true>", "up_dgrad_kernel<6, true, 8, 0>", "up_wgrad_kernel<2, true>", "up_dgrad_kernel<8, true, 8, 0>", "up_wgrad_kernel<3, false>",
+           "up_dgrad_kernel<6, false, 8, 0>", "up_fold_kernel", "up_finish_kernel")
 LAYER_OF = ("clr_up3", "clr_up3", "clr_up2", "clr_up2", "clr_up1", "clr_up1")
 CHANNELS = {"clr_up1": (261, 128, 8), "clr_up2": (128, 96, 4), "clr_up3": (96, 64, 2)}       # C_in, C_out, the image's size over the coarse grid's
 FORWARD_PREFIX = "igemm_conv_kernel<3, 3, 1, true"
