@@ -132,6 +132,16 @@ SIGNATURES = {
     "bsr_bottleneck_grad_partials": (c_i, [c_i, c_i, c_i]),
     "bsr_bottleneck_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
     "bsr_debug_bottleneck_grad": (c_i, [c_i, c_v, c_sz, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
+    "bsr_last_block": (c_i, [c_v, c_i, ctypes.POINTER(c_v), ctypes.POINTER(c_i), ctypes.POINTER(c_v), ctypes.POINTER(c_v), ctypes.POINTER(c_i),
+                             ctypes.POINTER(c_i * 4)]),
+    "bsr_colour_trunk_grad_blob_bytes": (c_sz, []),
+    "bsr_colour_trunk_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "bsr_colour_trunk_grad_floats": (c_sz, []),
+    "bsr_colour_trunk_grad_var_offset": (c_sz, [c_i]),
+    "bsr_colour_trunk_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_colour_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 5 + [c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
+    "bsr_debug_colour_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 5 + [c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
+    "bsr_debug_hole_grad": (c_i, [c_i, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v]),
     "bsr_heads_grad_blob_bytes": (c_sz, []),
     "bsr_heads_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "bsr_heads_grad_floats": (c_sz, []),

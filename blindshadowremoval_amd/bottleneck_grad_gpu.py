@@ -26,6 +26,21 @@ SIZE_TEXT = "the bottleneck takes B >= 1 grids with h a multiple of 4 and w a mu
 NO_WEIGHTS_TEXT = "the bottleneck has no weights: call load_weights or restore first"
 
 
+def read_maps(view, offset, b: int, h: int, w: int) -> Dict[str, torch.Tensor]:
+    """Copies of the chain's maps out of a scratch: `view`(byte offset, shape[, dtype]) gives a tensor over it, `offset`(index) the byte
+    offset of bsr_bottleneck_grad_offset's map `index` (colour_trunk_gpu reads each block's region with its own)."""
+    out = {}
+    for name, (index, cols, kept) in MAPS.items():
+        out[name] = view(offset(index), (b, h, w, cols))[..., :kept].clone()
+    wg = view(offset(6), (C_IN * D + 9 * D * D + D * C_Y,), torch.float64)
+    out["Wg1"] = wg[:C_IN * D].reshape(C_IN, D).clone()
+    out["Wg2"] = wg[C_IN * D:C_IN * D + 9 * D * D].reshape(3, 3, D, D).clone()
+    out["Wg3"] = wg[C_IN * D + 9 * D * D:].reshape(D, C_Y).clone()
+    s = view(offset(7), (2 * D + C_Y,), torch.float64)
+    out["S1"], out["S2"], out["S3"] = s[:D].clone(), s[D:2 * D].clone(), s[2 * D:].clone()
+    return out
+
+
 class BottleneckGrad(GradStage):
     """`BottleneckGrad(device).bottleneck_grad(xin, d_y3, d_skip)` — the gradients of the lower half of the generator's res_stack/5
     (training=False; GSC width) on `device`, after `load_weights(dict)` (the generator's variables; ValueError for TSM weights;
@@ -55,17 +70,7 @@ class BottleneckGrad(GradStage):
         [3,3,128,128], `Wg3` [128,257] and the column sums `S1`, `S2` [128], `S3` [257] of gz1, gz2, d_y3, the last six float64."""
         lib = _lib.load()
         self.scratch3(b, h, w)
-        out = {}
-        for name, (index, cols, kept) in MAPS.items():
-            off = int(lib.bsr_bottleneck_grad_offset(b, h, w, index))
-            out[name] = self.view(off, (b, h, w, cols))[..., :kept].clone()
-        wg = self.view(int(lib.bsr_bottleneck_grad_offset(b, h, w, 6)), (C_IN * D + 9 * D * D + D * C_Y,), torch.float64)
-        out["Wg1"] = wg[:C_IN * D].reshape(C_IN, D).clone()
-        out["Wg2"] = wg[C_IN * D:C_IN * D + 9 * D * D].reshape(3, 3, D, D).clone()
-        out["Wg3"] = wg[C_IN * D + 9 * D * D:].reshape(D, C_Y).clone()
-        s = self.view(int(lib.bsr_bottleneck_grad_offset(b, h, w, 7)), (2 * D + C_Y,), torch.float64)
-        out["S1"], out["S2"], out["S3"] = s[:D].clone(), s[D:2 * D].clone(), s[2 * D:].clone()
-        return out
+        return read_maps(self.view, lambda index: int(lib.bsr_bottleneck_grad_offset(b, h, w, index)), b, h, w)
 
     def bottleneck_grad(self, xin: torch.Tensor, d_y3: torch.Tensor, d_skip: Optional[torch.Tensor] = None, keep: bool = False):
         """xin [B,h,w,261] the block's input, d_y3 [B,h,w,257] the gradient at bnorm3's output, d_skip [B,h,w,261] what the skip carries

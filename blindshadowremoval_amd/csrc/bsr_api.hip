@@ -47,6 +47,7 @@
 #include "grey_up_grad_kernels.h"
 #include "nonlocal_grad_kernels.h"
 #include "bottleneck_grad_kernels.h"
+#include "colour_trunk_grad_kernels.h"
 #include "heads_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
@@ -1891,6 +1892,69 @@ int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes,
                          stream);
 }
 
+size_t bsr_colour_trunk_grad_blob_bytes(void) { return bsr::ct_blob_off(4) * sizeof(float); }
+
+size_t bsr_colour_trunk_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::ct_plan(B, h, w).total : 0; }
+
+size_t bsr_colour_trunk_grad_floats(void) { return bsr::ct_var_offset(bsr::kCtVars); }
+
+size_t bsr_colour_trunk_grad_var_offset(int index) { return index < 0 || index >= bsr::kCtVars ? SIZE_MAX : bsr::ct_var_offset(index); }
+
+size_t bsr_colour_trunk_grad_offset(int B, int h, int w, int map) {
+  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kCtMaps) return SIZE_MAX;
+  return bsr::ct_plan(B, h, w).map[map];
+}
+
+namespace {
+
+int colour_trunk_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
+                      const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin, const float* d_x, int B,
+                      int h, int w, float* d_res2, float* grads, void* scratch, int stop_after, void* stream) {
+  return run_grad_stage(
+      name, {d_blob, y3x4, out4, y3x3, out3, xh, d_xin, d_res2, grads, scratch},
+      {{bsr::nl_size_ok(B, h, w),
+        "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 pixels in all"},
+       {blob_bytes == bsr_colour_trunk_grad_blob_bytes(),
+        "blob_bytes must be bsr_colour_trunk_grad_blob_bytes() (pack.pack_colour_trunk_grad; the GSC width 261 only, not TSM's 877)"},
+       {y3x4_cs >= 257 && y3x3_cs >= 257 && out4_cs >= 261 && out3_cs >= 261 && xh_cs >= 261,
+        "y3x4_cs and y3x3_cs must be at least 257, out4_cs, out3_cs and xh_cs at least 261"}},
+      {{16, "d_blob, d_x and d_res2", {d_blob, d_x, d_res2}},
+       {4, "y3x4, out4, y3x3, out3, xh, d_xin and grads", {y3x4, out4, y3x3, out3, xh, d_xin, grads}}},
+      scratch, stop_after, bsr::kCtLaunches, device, [&] {
+        HIP_TRY(bsr::launch_colour_trunk_grad(static_cast<const float*>(d_blob), y3x4, y3x4_cs, out4, out4_cs, y3x3, y3x3_cs, out3, out3_cs, xh, xh_cs, d_xin,
+                                              d_x, B, h, w, d_res2, grads, scratch, stop_after, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
+}  // namespace
+
+int bsr_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
+                          const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin, const float* d_x,
+                          int B, int h, int w, float* d_res2, float* grads, void* scratch, void* stream) {
+  return colour_trunk_grad("bsr_colour_trunk_grad", device, d_blob, blob_bytes, y3x4, y3x4_cs, out4, out4_cs, y3x3, y3x3_cs, out3, out3_cs, xh, xh_cs, d_xin,
+                           d_x, B, h, w, d_res2, grads, scratch, bsr::kCtLaunches, stream);
+}
+
+int bsr_debug_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
+                                const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin,
+                                const float* d_x, int B, int h, int w, float* d_res2, float* grads, void* scratch, int stop_after, void* stream) {
+  return colour_trunk_grad("bsr_debug_colour_trunk_grad", device, d_blob, blob_bytes, y3x4, y3x4_cs, out4, out4_cs, y3x3, y3x3_cs, out3, out3_cs, xh, xh_cs,
+                           d_xin, d_x, B, h, w, d_res2, grads, scratch, stop_after, stream);
+}
+
+int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_xin3, const float* d_x, int B, int h, int w, float* d_res2, void* stream) {
+  return run_grad_stage(
+      "bsr_debug_hole_grad", {xh, d_xin3, d_res2},
+      {{bsr::nl_size_ok(B, h, w),
+        "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 pixels in all"},
+       {xh_cs >= 258, "xh_cs must be at least 258"}},
+      {{16, "d_xin3, d_x and d_res2", {d_xin3, d_x, d_res2}}, {4, "xh", {xh}}}, nullptr, 0, 0, device, [&] {
+        HIP_TRY(bsr::launch_hole_grad(d_xin3, xh, xh_cs, d_x, B * h * w, d_res2, static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
 size_t bsr_heads_grad_blob_bytes(void) { return (size_t)bsr::kHgBlobFloats * sizeof(float); }
 
 size_t bsr_heads_grad_scratch_bytes(int B, int H, int W) { return bsr::hg_size_ok(B, H, W) ? bsr::hg_plan(B, H, W).total : 0; }
@@ -2450,21 +2514,35 @@ int bsr_last_grey_decoder(bsr_handle* h, const float** x, int* x_cs, const float
   return BSR_OK;
 }
 
-int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]) {
+// bsr_last_block and bsr_last_block5 under the caller's own name
+static int last_block(const char* name, bsr_handle* h, int block, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs,
+                      int shape4[4]) {
+  const std::string n(name);
   if (h == nullptr || y3x == nullptr || y3x_cs == nullptr || xin == nullptr || out == nullptr || x_cs == nullptr || shape4 == nullptr)
-    return fail(BSR_ERR_ARG, "bsr_last_block5: null argument");
-  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_block5: an RGB handle has no res_stack/5");
-  if (h->var.tsm) return fail(BSR_ERR_STATE, "bsr_last_block5: the non-local block's backward takes the GSC width 261 only, not a TSM handle's 877");
+    return fail(BSR_ERR_ARG, n + ": null argument");
+  if (block < 3 || block > 5) return fail(BSR_ERR_ARG, n + ": block must be 3, 4 or 5 (the 261-wide blocks)");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, n + ": an RGB handle has no res_stack/" + std::to_string(block));
+  if (h->var.tsm) return fail(BSR_ERR_STATE, n + ": the non-local block's backward takes the GSC width 261 only, not a TSM handle's 877");
   if (h->dtype != BSR_DTYPE_F32)
-    return fail(BSR_ERR_STATE, "bsr_last_block5: the block's tensors are kept for the backward in BSR_DTYPE_F32 handles only, not in the 16-bit modes");
-  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_block5: no forward has run on this handle");
-  *y3x = h->ws + h->plan.y3[5];
+    return fail(BSR_ERR_STATE, n + ": the block's tensors are kept for the backward in BSR_DTYPE_F32 handles only, not in the 16-bit modes");
+  if (!h->ran) return fail(BSR_ERR_STATE, n + ": no forward has run on this handle");
+  // forward_impl's res_block(i) alone writes y3[i] (c3q) and r[i] (the `w` GEMM, fused into the attention launch or on its own), and
+  // bmask_xhole alone writes xh: on both routes nothing after block 3 or 4 touches their slots
+  *y3x = h->ws + h->plan.y3[block];
   *y3x_cs = h->var.cs_y3x;
-  *xin = h->ws + h->plan.r[4];
-  *out = h->ws + h->plan.r[5];
+  *xin = h->ws + (block == 3 ? h->plan.xh : h->plan.r[block - 1]);
+  *out = h->ws + h->plan.r[block];
   *x_cs = h->var.cs_h;
   shape4[0] = h->B; shape4[1] = h->H / 8; shape4[2] = h->W / 8; shape4[3] = 261;
   return BSR_OK;
+}
+
+int bsr_last_block(bsr_handle* h, int block, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]) {
+  return last_block("bsr_last_block", h, block, y3x, y3x_cs, xin, out, x_cs, shape4);
+}
+
+int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]) {
+  return last_block("bsr_last_block5", h, 5, y3x, y3x_cs, xin, out, x_cs, shape4);
 }
 
 }  // extern "C"

@@ -15,7 +15,10 @@ and d_skip to the gradient at the block's input and the twelve variables; csrc/b
 output y and the four variables; csrc/heads_grad_kernels.h is held to it (heads_grad_gpu.HeadsGrad).  Below the heads the grey decoder
 (model.py:243-245): up1, up2 on cat[up1, x3], up3 on cat[up2, x2], the colour decoder's layer type; `grey_decoder_grad` is its statement,
 from d_y to the gradient at res_stack/2's output, the two skip gradients and the twelve variables; csrc/grey_up_grad_kernels.h is held
-to it (grey_decoder_gpu.GreyDecoder)."""
+to it (grey_decoder_gpu.GreyDecoder).  Where the two branches meet (model.py:256-262): res_stack/4, res_stack/3 and the hole xh =
+cat[x (1 - bmask), bmask, uv]; `colour_trunk_grad` chains the two block statements for blocks 4 and 3 and ends in `hole_grad`, from the
+gradient at res_stack/5's input and the grey decoder's d_x to the complete gradient at res_stack/2's output and the 44 variables;
+csrc/colour_trunk_grad_kernels.h is held to it (colour_trunk_gpu.ColourTrunk)."""
 from __future__ import annotations
 
 import functools
@@ -24,7 +27,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
-from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_decoder_trainable_names,
+from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_colour_trunk_trainable_names, generator_decoder_trainable_names,
                       generator_grey_decoder_trainable_names, generator_heads_trainable_names, generator_nonlocal_trainable_names, generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
@@ -729,3 +732,97 @@ def heads_example_inputs(H: int, W: int, B: int, seed: int = 0):
     y = np.where(y >= 0, y, np.float32(LRELU_ALPHA) * y).astype(np.float32)
     d_gs = (rng.standard_normal((B, H, W, 1)) / (B * H * W)).astype(np.float32)
     return inputs, y, d_gs
+
+
+# ---- res_stack/4, res_stack/3 and the hole: from the gradient at res_stack/5's input to the complete gradient at res_stack/2's output
+COLOUR_TRUNK_BLOCKS = (4, 3)             # in the backward's order
+COLOUR_TRUNK_NORM_NAMES = ("d_res2",) + tuple(generator_colour_trunk_trainable_names())
+COLOUR_TRUNK_DATA = ("d_y3_4", "d_skip_4", "d_xin4", "d_y3_3", "d_skip_3", "d_xin3")
+
+
+def hole_grad(xh, d_xin3, d_x=None, dtype=np.float64):
+    """The backward of the hole (model.py:256-259: x_hole = x (1 - bmask), xh = cat[x_hole 257 | bmask | uv 3], bmask under
+    stop_gradient): xh [B,h,w,261] (its channel 257 is bmask, in {0, 1}), d_xin3 [B,h,w,261] the gradient at xh, d_x [B,h,w,257] the grey
+    branch's gradient at res_stack/2's output (None: no such term) ->
+      d_res2 = d_xin3[..., :257] (1 - bmask) + d_x
+    the complete gradient at res_stack/2's output, in `dtype`.  Channel 257 of d_xin3 reaches nothing (bmask is a constant), nor do
+    channels 258..260 (uv is an input).  With `dtype` float32 this is the device's arithmetic exactly: the factor is 0 or 1, so the product
+    is exact, and there is one float32 addition."""
+    T = dtype
+    keep = T(1) - np.asarray(xh, T)[..., RES_CH:RES_CH + 1]
+    d = np.asarray(d_xin3, T)[..., :RES_CH] * keep
+    return d if d_x is None else d + np.asarray(d_x, T)
+
+
+def trunk_forward(weights: Dict[str, np.ndarray], x, bmask, uv, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """x [B,h,w,257] (res_stack/2's output), bmask [B,h,w,1] in {0, 1}, uv [B,h,w,3] -> dict(`xh` [B,h,w,261] and, per block b = 3, 4,
+    `y3_<b>` [B,h,w,257] (bnorm3's output), `res<b>` [B,h,w,261] (the block's output), the bottleneck's `a1_<b>`, `a2_<b>` [B,h,w,128] and
+    `pre_<b>` (relu3's input)) in `dtype`: xh = cat[x (1 - bmask), bmask, uv], then bottleneck_forward and nonlocal_forward of block 3 on
+    xh and of block 4 on res3 (model.py:256-262)."""
+    T = dtype
+    x, bmask, uv = np.asarray(x, T), np.asarray(bmask, T), np.asarray(uv, T)
+    out = {"xh": np.concatenate([x * (T(1) - bmask), bmask, uv], axis=3)}
+    xin = out["xh"]
+    for b in (3, 4):
+        bf = bottleneck_forward(weights, xin, b, T)
+        nf = nonlocal_forward(weights, bf["y3"], xin, b, T)
+        out.update({"y3_%d" % b: bf["y3"], "res%d" % b: nf["out"], "a1_%d" % b: bf["a1"], "a2_%d" % b: bf["a2"], "pre_%d" % b: nf["pre"]})
+        xin = nf["out"]
+    return out
+
+
+def colour_trunk_grad(weights: Dict[str, np.ndarray], xh, y3_3, res3, y3_4, res4, d_xin5, d_x=None,
+                      acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """The gradient d_xin5 [B,h,w,261] at res_stack/5's input (bottleneck_grad's d_xin) and, optionally, the grey branch's d_x [B,h,w,257]
+    at res_stack/2's output (grey_decoder_grad's d_x) -> dict(`d_res2` [B,h,w,257] the complete gradient at res_stack/2's output, the 44
+    variables of weights.generator_colour_trunk_trainable_names() under their own blocks' names, the intermediate data gradients `d_xin4`,
+    `d_xin3` [B,h,w,261] and `d_y3_<b>`, `d_skip_<b>` per block, and `a1_<b>`, `a2_<b>` as used), float64 from the float32 variables.  The
+    statements above chained, for block 4 on (y3_4, res3, res4) and then block 3 on (y3_3, xh, res3):
+      nonlocal_grad(y3, xin, d_out, block=b, acts={"out": out_b}) -> d_y3, d_skip;  bottleneck_grad(xin, d_y3, d_skip, block=b) -> d_xin
+    with block 4's d_xin as block 3's d_out, and hole_grad(xh, d_xin3, d_x) at the end.  `acts` carries `a1_<b>`, `a2_<b>` (for example the
+    device's): the bottlenecks' masks and kernel-gradient inputs are read from them."""
+    res: Dict[str, np.ndarray] = {}
+    d_out = d_xin5
+    for b, y3, xin, out in ((4, y3_4, res3, res4), (3, y3_3, xh, res3)):
+        n = nonlocal_grad(weights, y3, xin, d_out, block=b, acts={"out": out})
+        a = None if acts is None else {"a1": acts["a1_%d" % b], "a2": acts["a2_%d" % b]}
+        t = bottleneck_grad(weights, xin, n["d_y3"], n["d_skip"], block=b, acts=a)
+        res.update((name, n[name]) for name in generator_nonlocal_trainable_names(b))
+        res.update((name, t[name]) for name in generator_bottleneck_trainable_names(b))
+        res.update({"d_y3_%d" % b: n["d_y3"], "d_skip_%d" % b: n["d_skip"], "d_xin%d" % b: t["d_xin"], "a1_%d" % b: t["a1"], "a2_%d" % b: t["a2"]})
+        d_out = t["d_xin"]
+    res["d_res2"] = hole_grad(xh, d_out, d_x)
+    return res
+
+
+def colour_trunk_objective_f64(weights: Dict[str, np.ndarray], x, bmask, uv, d_xin5, d_x=None, masks: Optional[list] = None, dtype=np.float64):
+    """<d_xin5, res4> + <d_x, x> in `dtype` with no float32 rounding anywhere, bmask and uv constants: the scalar whose gradient with
+    respect to x and the 44 variables colour_trunk_grad states.  A list given as `masks` receives the six LeakyReLU masks (z > 0) of
+    blocks 3 and 4: a1, a2 and relu3's."""
+    fw = trunk_forward(weights, x, bmask, uv, dtype)
+    if masks is not None:
+        masks += [fw[k % b] > 0 for b in (3, 4) for k in ("a1_%d", "a2_%d", "pre_%d")]
+    s = (np.asarray(d_xin5, dtype) * fw["res4"]).sum()
+    if d_x is not None:
+        s = s + (np.asarray(d_x, dtype) * np.asarray(x, dtype)).sum()
+    return s
+
+
+colour_trunk_norms = functools.partial(grad_norms, names=COLOUR_TRUNK_NORM_NAMES)   # of `d_res2` and each of the 44 variable gradients
+
+
+def colour_trunk_example_inputs(h: int, w: int, B: int, seed: int = 0, weights: Optional[Dict[str, np.ndarray]] = None):
+    """Seeded (x [B,h,w,257] like a LeakyReLU output, bmask [B,h,w,1] Bernoulli(1/2) per pixel, uv [B,h,w,3] uniform, d_xin5 [B,h,w,261],
+    d_x [B,h,w,257]) float32 at a coarse grid; with `weights`, followed by (xh, y3_3, res3, y3_4, res4): trunk_forward's on these inputs
+    in float64, rounded to float32."""
+    rng = np.random.default_rng(6000 + seed)
+    x = rng.standard_normal((B, h, w, RES_CH)).astype(np.float32)
+    x = np.where(x >= 0, x, np.float32(LRELU_ALPHA) * x).astype(np.float32)
+    bmask = (rng.uniform(0.0, 1.0, (B, h, w, 1)) < 0.5).astype(np.float32)
+    uv = rng.uniform(0.0, 1.0, (B, h, w, 3)).astype(np.float32)
+    d_xin5 = (rng.standard_normal((B, h, w, RES_CH + 4)) / (B * h * w * (RES_CH + 4))).astype(np.float32)
+    d_x = (rng.standard_normal((B, h, w, RES_CH)) / (B * h * w * RES_CH)).astype(np.float32)
+    if weights is None:
+        return x, bmask, uv, d_xin5, d_x
+    fw = trunk_forward(weights, x, bmask, uv)
+    return (x, bmask, uv, d_xin5, d_x) + tuple(fw[k].astype(np.float32) for k in ("xh", "y3_3", "res3", "y3_4", "res4"))

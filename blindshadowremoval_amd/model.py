@@ -254,6 +254,24 @@ class Generator:
         ptrs, strides, shape = self.last_block5()
         return ptrs[1], strides[1], shape
 
+    def last_block(self, block: int) -> Tuple[Tuple[int, int, int], Tuple[int, int, int], Tuple[int, int, int, int]]:
+        """last_block5's triple for res_stack/`block`, block 3, 4 or 5 (bsr_last_block): y3x and out are the block's own, xin is xh =
+        cat[x_hole | bmask | uv] for block 3 and the block below's output for blocks 4 and 5.  Under last_block5's conditions."""
+        self._require_weights()
+        ptrs = [ctypes.c_void_p() for _ in range(3)]
+        y_cs, x_cs, shape = ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_block(self._handle, int(block), ctypes.byref(ptrs[0]), ctypes.byref(y_cs), ctypes.byref(ptrs[1]),
+                                            ctypes.byref(ptrs[2]), ctypes.byref(x_cs), ctypes.byref(shape)), "bsr_last_block")
+        return tuple(int(p.value) for p in ptrs), (int(y_cs.value), int(x_cs.value), int(x_cs.value)), (shape[0], shape[1], shape[2], shape[3])
+
+    def last_colour_trunk(self) -> Tuple[Tuple[int, int, int, int, int], Tuple[int, int, int, int, int], Tuple[int, int, int, int]]:
+        """((y3x4, out4, y3x3, out3, xh) device addresses, their floats between pixels, (B, H/8, W/8, 261)) of what the last forward kept
+        of res_stack/4 and res_stack/3 in the handle's workspace (last_block(4) and last_block(3)): block 4's input is out3, block 3's
+        is xh, whose channel 257 is bmask.  No copy; valid until the next forward on this generator.  Under last_block5's conditions."""
+        (y4, _, o4), (y4_cs, _, o4_cs), shape = self.last_block(4)      # block 4's xin is out3 (bsr_last_block)
+        (y3, xh, o3), (y3_cs, xh_cs, o3_cs), _ = self.last_block(3)
+        return (y4, o4, y3, o3, xh), (y4_cs, o4_cs, y3_cs, o3_cs, xh_cs), shape
+
     def last_y(self) -> Tuple[int, int, Tuple[int, int, int, int]]:
         """(y's device address, its floats between pixels, (B, H, W, 64)) of the last forward's y, up3's output and the grey heads' input,
         in the handle's workspace (bsr_last_y): no copy; valid until the next forward on this generator.  Under last_f's conditions."""

@@ -27,6 +27,23 @@ SIZE_TEXT = "the non-local block takes B >= 1 grids with h a multiple of 4 and w
 NO_WEIGHTS_TEXT = "the non-local block has no weights: call load_weights or restore first"
 
 
+def read_maps(view, offset, b: int, t: int) -> Dict[str, torch.Tensor]:
+    """Copies of the chain's maps out of a scratch: `view`(byte offset, shape[, dtype]) gives a tensor over it, `offset`(index) the byte
+    offset of bsr_nonlocal_grad_offset's map `index` (colour_trunk_gpu reads each block's region with its own)."""
+    out = {}
+    for name, cols, first, kept in MAPS:
+        off = offset(MAP_INDEX[name])
+        if cols == 0:
+            out[name] = view(off, (b, t)).clone()
+        elif kept == 1:
+            out[name] = view(off, (b, t, cols))[..., first].clone()
+        else:
+            out[name] = view(off, (b, t, cols))[..., first:first + kept].clone()
+    out["Wgd"] = view(offset(8), (128, C_NL), torch.float64).clone()
+    out["Sz"] = view(offset(9), (C_NL,), torch.float64).clone()
+    return out
+
+
 class NonLocalGrad(GradStage):
     """`NonLocalGrad(device).nonlocal_grad(y3x, xin, out, d_out)` — the gradients of the upper half of the generator's res_stack/5
     (training=False; GSC width) on `device`, after `load_weights(dict)` (the generator's variables; ValueError for TSM weights) or
@@ -50,19 +67,7 @@ class NonLocalGrad(GradStage):
         [128,257] (w's kernel gradient before the BN factor) and `Sz` float64 [257]."""
         lib = _lib.load()
         self.scratch3(b, h, w)
-        t = h * w
-        out = {}
-        for name, cols, first, kept in MAPS:
-            off = int(lib.bsr_nonlocal_grad_offset(b, h, w, MAP_INDEX[name]))
-            if cols == 0:
-                out[name] = self.view(off, (b, t)).clone()
-            elif kept == 1:
-                out[name] = self.view(off, (b, t, cols))[..., first].clone()
-            else:
-                out[name] = self.view(off, (b, t, cols))[..., first:first + kept].clone()
-        out["Wgd"] = self.view(int(lib.bsr_nonlocal_grad_offset(b, h, w, 8)), (128, C_NL), torch.float64).clone()
-        out["Sz"] = self.view(int(lib.bsr_nonlocal_grad_offset(b, h, w, 9)), (C_NL,), torch.float64).clone()
-        return out
+        return read_maps(self.view, lambda index: int(lib.bsr_nonlocal_grad_offset(b, h, w, index)), b, h * w)
 
     def _result(self, outs, b, h, w, keep):
         out = super()._result(outs, b, h, w, keep)

@@ -1044,6 +1044,13 @@ def unpack_bottleneck_grad(blob: bytes) -> Dict[str, np.ndarray]:
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
+# ---- the backward of res_stack/4, /3 and the hole (csrc/colour_trunk_grad_kernels.h): the four blobs above end to end ----
+def pack_colour_trunk_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (res_stack/4's and res_stack/3's are read) -> the blob bsr_colour_trunk_grad takes: pack_nonlocal_grad and
+    pack_bottleneck_grad of block 4, then of block 3, in the order of the chain's launches.  ValueError (NONLOCAL_TSM_TEXT) for TSM weights."""
+    return b"".join(pack(weights, block) for block in (4, 3) for pack in (pack_nonlocal_grad, pack_bottleneck_grad))
+
+
 # ---- the generator's grey heads' backward (csrc/heads_grad_kernels.h): a blob of its own, no header, float32 ----
 HEADS_RGB_TEXT = "the heads' device chain takes the GSC / TSM heads (7x7, 64 -> 1 twice); model_RGB.py's are 128 -> 3 and chained"
 HEADS_K, HEADS_KP = 98, 100

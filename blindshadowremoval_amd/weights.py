@@ -156,6 +156,13 @@ def generator_bottleneck_trainable_names(block: int = 5, variant: str = "gsc") -
             if n.startswith(stem) and not n.startswith(stem + "non_local/") and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_colour_trunk_trainable_names() -> List[str]:
+    """The 44 trainable variables of res_stack/3 and res_stack/4 in generator_variable_shapes' order, 696 076 floats: per block the twelve
+    of generator_bottleneck_trainable_names and the ten of generator_nonlocal_trainable_names; moving_mean and moving_variance take no
+    gradient."""
+    return [n for n in generator_variable_shapes() if n.startswith(("res_stack/3/", "res_stack/4/")) and not n.rsplit("/", 1)[1].startswith("moving_")]
+
+
 def generator_heads_trainable_names(variant: str = "gsc") -> List[str]:
     """The four trainable variables of the generator's grey heads in generator_variable_shapes' order, 6 274 floats: the kernel
     [7,7,64,1] and bias of conv2 ('tconv3', the mask head) and of conv3 ('tconv4', the con head).  GSC and TSM share them; the RGB

@@ -127,6 +127,11 @@ int bsr_last_decoder(bsr_handle* h, const float** x, int* x_cs, const float** f1
  * the block's output, 261 channels each with *x_cs floats between pixels; shape4 = [B,H/8,W/8,261].  Each lies in a slot of its own that
  * nothing after the block overwrites.  The same rules and error codes as bsr_last_decoder.  Added under ABI 8. */
 int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]);
+/* The same of res_stack/`block`, block 3, 4 or 5 (bsr_last_block5 is block 5 of it, under its own name in the error texts): *y3x and *out are the block's own; *xin is xh =
+ * cat[x_hole 257 | bmask | uv 3] for block 3 (bmask at channel 257) and the block below's output for blocks 4 and 5.  The forward gives
+ * every block's y3x and output, and xh, a slot of its own, on the fused-attention route and on the separate-launch route, so nothing
+ * after the block overwrites them.  The rules and error codes of bsr_last_block5; any other block gives BSR_ERR_ARG.  Added under ABI 8. */
+int bsr_last_block(bsr_handle* h, int block, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]);
 
 /* Per-kernel-class device time (ms) of the last forward run with timing enabled; classes are indexed
  * 0: conv3x3 (+stride-2), 1: transposed 3x3 (all but class 6), 2: conv1x1, 3: attention, 4: conv7 (stem + heads), 5: glue,
@@ -443,6 +448,42 @@ int bsr_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const
                         int h, int w, float* d_xin, float* grads, void* scratch, void* stream);
 int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes, const float* xin, int xin_cs, const float* d_y3, const float* d_skip,
                               int B, int h, int w, float* d_xin, float* grads, void* scratch, int stop_after, void* stream);
+
+/* The backward of the generator between res_stack/5's input and res_stack/2's output (training=False, fp32, GSC width; the reference's
+ * model.py:256-262): res_stack/4, res_stack/3 and the hole x_hole = x (1 - bmask), xh = cat[x_hole | bmask | uv] with bmask under
+ * stop_gradient.  d_blob: bsr_colour_trunk_grad_blob_bytes() bytes of pack.pack_colour_trunk_grad, the four existing blobs end to end
+ * (block 4's non-local and bottleneck blobs, then block 3's), 16-byte aligned.  Inputs as bsr_last_block hands them out (or dense
+ * tensors): y3x4, out4 of block 4, y3x3, out3 of block 3 and xh, with y3x*_cs >= 257 and out*_cs, xh_cs >= 261 floats between pixels;
+ * block 4's input is out3 and block 3's is xh.  d_xin dense [B,h,w,261] = d loss / d (res_stack/5's input) (bsr_bottleneck_grad's d_xin);
+ * d_x dense [B,h,w,257], the grey branch's gradient at res_stack/2's output (bsr_grey_decoder_grad's d_x), 16-byte aligned, or null for
+ * none.  Neither is written.  Outputs: d_res2 dense [B,h,w,257], 16-byte aligned, = d_xin3[..., :257] (1 - bmask) + d_x with d_xin3 the
+ * gradient at block 3's input and bmask = xh[..., 257] in {0, 1}: the complete gradient at res_stack/2's output (channel 257 of d_xin3,
+ * bmask, and channels 258..260, uv, reach nothing); and grads, bsr_colour_trunk_grad_floats() = 696076 float32: the 44 variables of
+ * weights.generator_colour_trunk_trainable_names() in that order (block 3's twelve bottleneck variables, its ten non-local ones, then
+ * block 4's), variable `index` (0..43) at float offset bsr_colour_trunk_grad_var_offset(index); SIZE_MAX out of range.  49 launches on
+ * `stream`, one after the other (csrc/colour_trunk_grad_kernels.h): bsr_nonlocal_grad's twelve and bsr_bottleneck_grad's twelve for block
+ * 4, the same for block 3, and the hole's one; no host synchronisation, no floating-point atomics: a call repeats its bits.  scratch:
+ * bsr_colour_trunk_grad_scratch_bytes(B, h, w) bytes, 256-byte aligned; every word read is written earlier in the same call; each of
+ * the four sub-chains has a region of its own.  bsr_colour_trunk_grad_offset(B, h, w, map) is the byte offset of map 0..9
+ * bsr_nonlocal_grad_offset's maps of block 4, 10..17 bsr_bottleneck_grad_offset's of block 4, 18..27 and 28..35 the same of block 3,
+ * 36 d_y3 [N][257], 37 d_skip [N][261] and 38 d_xin [N][261] of block 4, 39..41 the same of block 3; SIZE_MAX out of range.  A bad
+ * argument gives BSR_ERR_ARG with a message and nothing launched.  bsr_debug_colour_trunk_grad stops after `stop_after` (0..49) of the
+ * launches, one running count across the sub-chains.  ADDITIONS under ABI 8: bsr_abi_version() stays 8. */
+size_t bsr_colour_trunk_grad_blob_bytes(void);
+size_t bsr_colour_trunk_grad_scratch_bytes(int B, int h, int w);
+size_t bsr_colour_trunk_grad_floats(void);
+size_t bsr_colour_trunk_grad_var_offset(int index);
+size_t bsr_colour_trunk_grad_offset(int B, int h, int w, int map);
+int bsr_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
+                          const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin, const float* d_x,
+                          int B, int h, int w, float* d_res2, float* grads, void* scratch, void* stream);
+int bsr_debug_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
+                                const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin,
+                                const float* d_x, int B, int h, int w, float* d_res2, float* grads, void* scratch, int stop_after, void* stream);
+/* Test hook (additive in ABI 8): the chain's last launch alone (csrc/colour_trunk_grad_kernels.h, hole_grad_kernel), d_res2 =
+ * d_xin3[..., :257] (1 - xh[..., 257]) + d_x with d_xin3 dense [B,h,w,261], d_x dense [B,h,w,257] or null, d_res2 dense [B,h,w,257], the
+ * three 16-byte aligned, and xh_cs >= 258 floats between xh's pixels.  The size rule and error codes of bsr_colour_trunk_grad. */
+int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_xin3, const float* d_x, int B, int h, int w, float* d_res2, void* stream);
 
 /* The backward of the generator's grey heads (training=False, fp32; the reference's model.py:246-250): conv2 (7x7, 64 -> 1, tanh) gives
  * mask, conv3 (7x7, 64 -> 1) gives con, gs = gray(inputs) (1 + mask) + con.  d_blob: bsr_heads_grad_blob_bytes() bytes of

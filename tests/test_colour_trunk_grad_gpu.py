@@ -1,0 +1,419 @@
+"""bsr_colour_trunk_grad (csrc/colour_trunk_grad_kernels.h) against the host statement blindshadowremoval_amd/generator_grad.py:
+colour_trunk_grad.
+
+Stage by stage: the chain is stopped after each of its 49 launches and what the launch wrote is the complete call's, byte for byte; each
+of the 48 launches of the two existing chains, fed the DEVICE's own inputs, is then held to the float64 statement of that launch alone
+within max|got - ref| / max|ref| <= 1e-5, the project's fp32-class stage budget, by the per-launch statements of
+test_nonlocal_grad_gpu.py and test_bottleneck_grad_gpu.py with the block's variables in block 5's names; the hole launch is held bit
+for bit.  End to end: the 45 outputs against colour_trunk_grad(acts = the device's own a1, a2 of both blocks), each on the scale of its
+own largest reference magnitude, within cases.E2E_BOUND = 4 x the largest figure measured on the MI355X over these sizes (DESIGN section
+26).
+
+Grids (h, w, B): (4, 32, 1) one tile row; (8, 32, 2) seams between tiles and between items; (12, 32, 3) an odd tile count; (4, 64, 1)
+wide.  The workload's own grid belongs to tools/colour_trunk_bench.py."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from blindshadowremoval_amd import generator_grad as host
+from blindshadowremoval_amd.weights import generator_bottleneck_trainable_names, generator_nonlocal_trainable_names
+
+import colour_trunk_grad_cases as cases
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+f32 = np.float32
+SIZES = cases.GPU_SIZES
+OUT_KEYS = ("", "d_res2")
+# the launch (1..49) that writes each map, from the two chains' own tables (test_nonlocal_grad_gpu.py, test_bottleneck_grad_gpu.py)
+NL_FIRST = {"y3": 1, "dz": 1, "theta": 2, "phi": 2, "g": 2, "m": 3, "r": 3, "A": 3, "dA": 4, "D": 4, "d_phi": 5, "d_g": 5, "d_theta": 6, "Wgd": 11, "Sz": 12}
+BN_FIRST = {"xp": 1, "dyp": 1, "a1": 2, "a2": 3, "gz2": 4, "gz1": 5, "Wg1": 11, "Wg2": 11, "Wg3": 11, "S1": 12, "S2": 12, "S3": 12}
+FIRST = {}
+for _k, _b in enumerate(cases.BLOCKS):
+    FIRST.update(("nl%d.%s" % (_b, n), 24 * _k + at) for n, at in NL_FIRST.items())
+    FIRST.update(("bn%d.%s" % (_b, n), 24 * _k + 12 + at) for n, at in BN_FIRST.items())
+    FIRST.update({"d_skip_%d" % _b: 24 * _k + 1, "d_y3_%d" % _b: 24 * _k + 10, "d_xin%d" % _b: 24 * _k + 21})
+    FIRST.update((n, 24 * _k + (11 if n.endswith("/kernel") else 12)) for n in generator_nonlocal_trainable_names(_b))
+    FIRST.update((n, 24 * _k + 12 + (11 if n.endswith("/kernel") else 12)) for n in generator_bottleneck_trainable_names(_b))
+FIRST["d_res2"] = 49
+
+
+@pytest.fixture(scope="module")
+def runner():
+    from blindshadowremoval_amd import ColourTrunk
+    r = ColourTrunk(0)
+    r.load_weights(cases.ct_weights())
+    return r
+
+
+def to_dev(*arrays):
+    dev = torch.device("cuda", 0)
+    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
+
+
+def to_host(res):
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def device_run(runner, wt, x, bmask, uv, d_xin, d_x):
+    """The `run` of cases.check_*."""
+    runner.load_weights(wt)
+    arrays, (y3_4, y3_3) = cases.device_inputs(wt, x, bmask, uv)
+    res = runner.colour_trunk_grad(*to_dev(*arrays, d_xin, d_x), keep=True)
+    torch.cuda.synchronize()
+    out = to_host(res)
+    out.update({"res4": arrays[1], "res3": arrays[3], "xh": arrays[4], "y3_4": y3_4, "y3_3": y3_3, "dtype": f32})
+    return out
+
+
+def scaled_error(got, ref):
+    ref = np.asarray(ref, np.float64)
+    return float(np.abs(np.asarray(got, np.float64) - ref).max() / np.abs(ref).max())
+
+
+@pytest.fixture(scope="module")
+def device_results(runner):
+    """Inputs, the device's result and what it left in the scratch, once per size."""
+    out = {}
+    for h, w, B in SIZES:
+        wt, x, bmask, uv, d_xin, d_x = cases.case(h, w, B, 1)
+        arrays, y3s = cases.device_inputs(wt, x, bmask, uv)
+        arrays = arrays + (d_xin, d_x)
+        res = runner.colour_trunk_grad(*to_dev(*arrays), keep=True)
+        torch.cuda.synchronize()
+        out[(h, w, B)] = (wt, arrays, y3s, to_host(res), to_host(runner.maps(B, h, w)))
+    return out
+
+
+@pytest.mark.parametrize("check", cases.CONSTRUCTED, ids=lambda c: c.__name__)
+def test_constructed_case(runner, check):
+    check(lambda *a: device_run(runner, *a))
+    runner.load_weights(cases.ct_weights())
+
+
+@pytest.mark.parametrize("h,w,B", SIZES)
+def test_every_stop_leaves_what_the_complete_call_leaves(runner, device_results, h, w, B):
+    """stages(..., n) for n = 1..49: what launches 1..n write is the complete call's, byte for byte, and the outputs of the launches
+    that did not run are zero.  So every launch of the complete call ran on the inputs the per-launch statements below read."""
+    from blindshadowremoval_amd import ColourTrunk
+    _, arrays, _, _, _ = device_results[(h, w, B)]
+    t = to_dev(*arrays)
+    whole = runner.stages(*t, 49)
+    whole.update(ColourTrunk.split_grads(whole[""]))
+    assert set(FIRST) <= set(whole) and len(runner.LAUNCHES) == 49
+    for stop in range(1, 50):
+        runner._scratch.zero_()                # what a stop leaves was written by this call, not by the one before
+        got = runner.stages(*t, stop)
+        got.update(ColourTrunk.split_grads(got[""]))
+        for name, at in FIRST.items():
+            if stop >= at:
+                assert torch.equal(got[name], whole[name]), (stop, name)
+            elif "/" in name or name == "d_res2":
+                assert not bool(got[name].any()), (stop, name)
+    with pytest.raises(ValueError, match="stop_after"):
+        runner.stages(*t, 50)
+
+
+def _as_block5(wt, res, b):
+    """Block b's variables, and its gradients out of `res`, under res_stack/5's names: what the single-block tests read."""
+    import bottleneck_grad_cases
+    moved = bottleneck_grad_cases.with_block5(wt, b)
+    src = "res_stack/%d/" % b
+    return moved, {"res_stack/5/" + n[len(src):]: v for n, v in res.items() if n.startswith(src)}
+
+
+@pytest.mark.parametrize("h,w,B", SIZES)
+def test_stage_by_stage(device_results, h, w, B):
+    import test_bottleneck_grad_gpu as bn_gpu
+    import test_nonlocal_grad_gpu as nl_gpu
+    wt, (y3x4, out4, y3x3, out3, xh, d_xin, d_x), _, res, maps = device_results[(h, w, B)]
+    feeds = {4: (y3x4, out3, out4, d_xin), 3: (y3x3, xh, out3, maps["d_xin4"])}
+    for b in cases.BLOCKS:
+        y3x, xin, out, d_out = feeds[b]
+        moved, res5 = _as_block5(wt, res, b)
+        y3_used = (y3x - xin[..., :257]).astype(f32)
+        # launches 1..12 and 25..36: the non-local chain's statements on the device's own inputs
+        nl_res = dict(res5, d_y3=maps["d_y3_%d" % b], d_skip=maps["d_skip_%d" % b])
+        nl_maps = {k.split(".", 1)[1]: v for k, v in maps.items() if k.startswith("nl%d." % b)}
+        nl_gpu.test_stage_by_stage({(8 * h, 8 * w, B): (moved, (y3x, xin, out, d_out), y3_used, nl_res, nl_maps)}, 8 * h, 8 * w, B)
+        # launches 13..24 and 37..48: the bottleneck chain's statements on the device's own d_y3 and d_skip
+        bn_res = dict(res5, d_xin=maps["d_xin%d" % b])
+        bn_maps = {k.split(".", 1)[1]: v for k, v in maps.items() if k.startswith("bn%d." % b)}
+        bn_gpu.test_stage_by_stage({(h, w, B): (moved, (xin, maps["d_y3_%d" % b], maps["d_skip_%d" % b]), bn_res, bn_maps)}, h, w, B)
+    # launch 49: the hole on the device's own d_xin3, bit for bit
+    for k in ("d_xin3", "d_xin4"):
+        assert res[k].tobytes() == maps[k].tobytes(), k
+    assert res["d_res2"].tobytes() == host.hole_grad(xh, maps["d_xin3"], d_x, dtype=f32).tobytes()
+    share = float(xh[..., 257].mean())
+    assert 0.25 <= share <= 0.75 and set(np.unique(xh[..., 257])) == {0.0, 1.0}
+
+
+@pytest.mark.parametrize("h,w,B", SIZES)
+def test_end_to_end(device_results, h, w, B):
+    import bottleneck_grad_cases
+    import nonlocal_grad_cases
+    wt, (y3x4, out4, y3x3, out3, xh, d_xin, d_x), (y3_4, y3_3), res, maps = device_results[(h, w, B)]
+    for k in res:
+        if k in maps:
+            assert res[k].tobytes() == maps[k].tobytes(), k                # what keep=True returns is what the scratch holds
+    assert all(k in res for k in ("a1_4", "a2_4", "a1_3", "a2_3") + host.COLOUR_TRUNK_DATA)
+    st = host.colour_trunk_grad(wt, xh, y3_3, out3, y3_4, out4, d_xin, d_x, acts=res)
+    for name in cases.OUTPUTS:
+        print("colour trunk grad h=%d w=%d B=%d %s against the statement on the device's a1, a2: scaled error %.3g (bound %.3g)"
+              % (h, w, B, name, cases.worst_scaled_diff(res, st, (name,))[0], cases.E2E_BOUND))
+    d, at = cases.worst_scaled_diff(res, st)
+    print("colour trunk grad h=%d w=%d B=%d: worst %.3g at %s; twice the two single-block bounds added: %.3g"
+          % (h, w, B, d, at, 2 * (nonlocal_grad_cases.E2E_BOUND + bottleneck_grad_cases.E2E_BOUND)))
+    assert d <= cases.E2E_BOUND, (d, at)
+    # the device's activations are the statement's own within the stage budget, and both signs are present
+    fw = host.trunk_forward(wt, *cases.case(h, w, B, 1)[1:4])
+    for k in ("a1_4", "a2_4", "a1_3", "a2_3"):
+        assert scaled_error(res[k], fw[k]) <= cases.STAGE_BUDGET, k
+        assert (res[k] > 0).any() and (res[k] < 0).any(), k
+
+
+@pytest.mark.parametrize("h,w,B", SIZES + ((32, 32, 2),))
+def test_the_hole_kernel_alone(runner, h, w, B):
+    """hole_grad_kernel on random tensors against hole_grad(dtype=float32), bit for bit: a random hole, no hole, a hole everywhere, with
+    and without d_x.  257 is odd, so at every size three threads in 257 hold floats of two pixels; (32, 32, 2) runs 514 workgroups."""
+    rng = np.random.default_rng(31 + h + w + B)
+    d_xin3 = rng.standard_normal((B, h, w, 261)).astype(f32)
+    d_x = rng.standard_normal((B, h, w, 257)).astype(f32)
+    for hole in (rng.uniform(0, 1, (B, h, w)) < 0.5, np.zeros((B, h, w), bool), np.ones((B, h, w), bool)):
+        xh = rng.standard_normal((B, h, w, 261)).astype(f32)
+        xh[..., 257] = hole
+        for grey in (d_x, None):
+            got = runner.hole_grad(*to_dev(xh, d_xin3, grey)).cpu().numpy()
+            assert got.tobytes() == host.hole_grad(xh, d_xin3, grey, dtype=f32).tobytes()
+            assert not got[hole].any() if grey is None else got[hole].tobytes() == d_x[hole].tobytes()
+
+
+def flat_bytes(res):
+    return [res[k].cpu().numpy().tobytes() for k in OUT_KEYS]
+
+
+def test_a_repeated_call_and_two_sizes_on_one_scratch(runner, device_results):
+    wt, arrays3, _, res3, _ = device_results[(12, 32, 3)]
+    _, arrays1, _, res1, _ = device_results[(4, 32, 1)]
+    t3, t1 = to_dev(*arrays3), to_dev(*arrays1)
+    first3 = flat_bytes(runner.colour_trunk_grad(*t3))
+    first1 = flat_bytes(runner.colour_trunk_grad(*t1))          # B = 3 then B = 1 on the larger call's scratch
+    assert first3 == [res3[k].tobytes() for k in OUT_KEYS] and first1 == [res1[k].tobytes() for k in OUT_KEYS]
+    assert flat_bytes(runner.colour_trunk_grad(*t3)) == first3
+    assert flat_bytes(runner.colour_trunk_grad(*t1)) == first1
+    assert flat_bytes(runner.colour_trunk_grad(*t1, keep=True)) == first1   # keeping the maps changes no output
+    for t, a in zip(t1, arrays1):
+        assert t.cpu().numpy().tobytes() == a.tobytes()                     # no input is ever written
+    fresh = type(runner)(0)
+    fresh.load_weights(wt)
+    assert flat_bytes(fresh.colour_trunk_grad(*t1)) == first1   # a scratch of its own size gives the same bytes
+
+
+def test_no_d_x_is_a_zero_d_x(runner, device_results):
+    _, arrays, _, _, _ = device_results[(8, 32, 2)]
+    t = to_dev(*arrays)
+    none = runner.colour_trunk_grad(*t[:6])
+    zero = runner.colour_trunk_grad(*t[:6], torch.zeros_like(t[6]))
+    assert none["d_res2"].cpu().numpy().tobytes() != runner.colour_trunk_grad(*t)["d_res2"].cpu().numpy().tobytes()
+    np.testing.assert_array_equal(none["d_res2"].cpu().numpy(), zero["d_res2"].cpu().numpy())       # -0 + 0 is +0: equal, not the same bytes
+    assert none[""].cpu().numpy().tobytes() == zero[""].cpu().numpy().tobytes()
+    assert flat_bytes(runner.colour_trunk_grad(*t[:6], None, keep=True)) == flat_bytes(none)
+
+
+def test_the_chain_is_captured_into_a_graph_and_replays_the_same_bytes(runner, device_results):
+    """Stream capture refuses a host synchronisation and work on another stream that is not joined: a call that is captured, replayed
+    and gives the eager call's bytes has neither.  The chain is a line of launches: the captured graph has no branches."""
+    _, arrays, _, _, _ = device_results[(4, 32, 1)]
+    t = to_dev(*arrays)
+    eager = flat_bytes(runner.colour_trunk_grad(*t))
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        runner.colour_trunk_grad(*t)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            res = runner.colour_trunk_grad(*t)
+    torch.cuda.current_stream().wait_stream(side)
+    for k in OUT_KEYS:
+        res[k].zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert flat_bytes(res) == eager
+
+
+def test_argument_errors_raise_before_any_launch(runner, device_results):
+    from blindshadowremoval_amd import ColourTrunk, _lib, pack
+    from blindshadowremoval_amd.colour_trunk_gpu import NO_WEIGHTS_TEXT, SIZE_TEXT
+    dev = torch.device("cuda", 0)
+    _, arrays, _, _, _ = device_results[(4, 32, 1)]
+    t = to_dev(*arrays)
+    with pytest.raises(ValueError) as e:
+        ColourTrunk(0).colour_trunk_grad(*t)
+    assert str(e.value) == NO_WEIGHTS_TEXT
+    with pytest.raises(TypeError) as e:
+        runner.colour_trunk_grad(*t[:4], t[4].cpu(), *t[5:])
+    assert str(e.value) == "xh must be a float32 tensor [B,h,w,261] on %s" % dev
+    with pytest.raises(ValueError) as e:
+        runner.colour_trunk_grad(*t[:6], t[6][..., :256].contiguous())
+    assert str(e.value) == "d_x must be [1,4,32,257] for this d_xin, got (1, 4, 32, 256)"
+    with pytest.raises(ValueError) as e:
+        runner.colour_trunk_grad(*[torch.zeros((1, 6, 32, c), device=dev) for c in (257, 261, 257, 261, 261, 261, 257)])
+    assert str(e.value) == SIZE_TEXT % (1, 6, 32)
+    with pytest.raises(ValueError) as e:
+        runner.load_weights(cases.ct_weights(variant="tsm"))
+    assert str(e.value) == pack.NONLOCAL_TSM_TEXT
+    # the entry point itself: nothing is launched, the outputs keep their bytes
+    lib = _lib.load()
+    d_res2 = torch.full((1, 4, 32, 257), 7.0, device=dev)
+    flat = torch.full((int(lib.bsr_colour_trunk_grad_floats()),), 7.0, device=dev)
+    scratch = runner.scratch3(1, 4, 32)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())                                      # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(h=4, w=32, xh_cs=261, nbytes=runner._blob.numel(), scr=scratch):
+        return lib.bsr_colour_trunk_grad(0, p(runner._blob), nbytes, p(t[0]), 257, p(t[1]), 261, p(t[2]), 257, p(t[3]), 261, p(t[4]), xh_cs, p(t[5]), p(t[6]),
+                                         1, h, w, p(d_res2), p(flat), ctypes.c_void_p(scr), stream), lib.bsr_last_error().decode()
+
+    size = "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 pixels in all"
+    for kw, text in ((dict(h=6), size), (dict(w=16), size),
+                     (dict(xh_cs=260), "y3x4_cs and y3x3_cs must be at least 257, out4_cs, out3_cs and xh_cs at least 261"),
+                     (dict(nbytes=16), "blob_bytes must be bsr_colour_trunk_grad_blob_bytes() (pack.pack_colour_trunk_grad; the GSC width 261 only, not TSM's 877)"),
+                     (dict(scr=scratch + 8), "scratch must be 256-byte aligned")):
+        assert call(**kw) == (1, "bsr_colour_trunk_grad: " + text), kw
+    torch.cuda.synchronize()
+    for o in (d_res2, flat):
+        assert bool((o == 7.0).all())
+
+
+# ---- the generator's own tensors, in place
+PROBES = ("y3x4", "res4", "y3x3", "res3", "xh")
+
+
+def _copies(probes):
+    """The five probes as the tensors call takes them: the first 257 channels of the y3x slots."""
+    return [probes[k][..., :257].contiguous() if k.startswith("y3x") else probes[k] for k in PROBES]
+
+
+@pytest.fixture(scope="module")
+def generated():
+    """A generator's forward at (32, 256), B = 2, with init_weights(1), under which about half of the pixels lie in the hole (the
+    fixtures' usual init_weights(3) puts every pixel there and would hide it): its inputs, outputs and copies of the probes."""
+    from blindshadowremoval_amd import Generator
+    from blindshadowremoval_amd.weights import init_weights
+    w = init_weights(1)
+    gen = Generator(device=0)
+    gen.load_weights(w)
+    for refused in (gen.last_colour_trunk, lambda: gen.last_block(3)):
+        with pytest.raises(RuntimeError, match="no forward has run"):
+            refused()
+    rng = np.random.default_rng(21)
+    inputs, uv = to_dev(rng.uniform(0, 1, (2, 32, 256, 3)).astype(f32), rng.uniform(0, 1, (2, 32, 256, 3)).astype(f32))
+    outs = gen(inputs, uv)
+    torch.cuda.synchronize()
+    names = PROBES + ("y3x5", "res5", "res2", "up1", "x3", "up2", "x2", "y", "f1", "f2", "f")
+    return gen, w, inputs, outs, {k: gen.probe(k).clone() for k in names}
+
+
+def test_backward_reads_the_generators_tensors_in_place(runner, generated):
+    gen, w, inputs, outs, probes = generated
+    runner.load_weights(w)
+    before = [o.cpu().numpy().tobytes() for o in outs]
+    _, _, _, d_xin_a, d_x_a = host.colour_trunk_example_inputs(4, 32, 2, 9)
+    d_xin, d_x = to_dev(d_xin_a, d_x_a)
+    ptrs, strides, shape = gen.last_colour_trunk()
+    assert shape == (2, 4, 32, 261) and len(ptrs) == len(strides) == 5 and len(set(ptrs)) == 5 and all(p % 4 == 0 for p in ptrs)
+    assert strides[0] >= 257 and strides[2] >= 257 and min(strides[1], strides[3], strides[4]) >= 261
+    (y4, x4, o4), _, shape4 = gen.last_block(4)
+    (y3, x3, o3), _, _ = gen.last_block(3)
+    assert (y4, o4, y3, o3, x3) == tuple(ptrs) and x4 == o3 and shape4 == shape
+    (y5, x5, o5), strides5, shape5 = gen.last_block(5)
+    assert ((y5, x5, o5), strides5, shape5) == gen.last_block5() and x5 == o4
+    for block in (2, 6, 0, -1):
+        with pytest.raises(RuntimeError, match="block must be 3, 4 or 5"):
+            gen.last_block(block)
+    # the hole is there: the share of bmask's ones in the device's own xh
+    hole = probes["xh"][..., 257].cpu().numpy()
+    share = float(hole.mean())
+    print("colour trunk: bmask's share of ones in the generator's xh: %.3f (per item %s)" % (share, [round(float(m), 3) for m in hole.mean(axis=(1, 2))]))
+    assert set(np.unique(hole)) == {0.0, 1.0} and 0.25 <= share <= 0.75
+    copies = _copies(probes)
+    for grey in (d_x, None):
+        in_place = runner.backward(gen, d_xin, grey)
+        copied = runner.colour_trunk_grad(*copies, d_xin, grey)
+        torch.cuda.synchronize()
+        assert flat_bytes(in_place) == flat_bytes(copied)
+    kept = runner.backward(gen, d_xin, d_x, keep=True)
+    assert flat_bytes(kept) == flat_bytes(runner.backward(gen, d_xin, d_x)) and all(k in kept for k in type(runner).KEPT)
+    assert [o.cpu().numpy().tobytes() for o in outs] == before                 # the generator's four outputs are untouched
+    for k in probes:
+        assert gen.probe(k).cpu().numpy().tobytes() == probes[k].cpu().numpy().tobytes(), k
+    # the chain differentiates the function the forward computed: y3 = y3x<b> - pad(xin_b) against bottleneck_forward on xin_b
+    p = {k: probes[k].cpu().numpy() for k in PROBES}
+    for b, y3x, xin in ((3, p["y3x3"], p["xh"]), (4, p["y3x4"], p["res3"])):
+        y3 = (y3x[..., :257] - xin[..., :257]).astype(f32)
+        e = scaled_error(y3, host.bottleneck_forward(w, xin, block=b)["y3"])
+        print("colour trunk: the generator's y3x%d - pad(xin) against bottleneck_forward(block=%d) on its own xin in float64: scaled error %.3g" % (b, b, e))
+        assert e <= 1e-5
+    with pytest.raises(ValueError, match="last forward was"):
+        runner.backward(gen, d_xin[:1].contiguous())
+    runner.load_weights(cases.ct_weights())
+
+
+def test_backward_is_refused_before_a_forward_and_for_a_sixteen_bit_generator(runner):
+    from blindshadowremoval_amd import Generator
+    d_xin, = to_dev(host.colour_trunk_example_inputs(4, 32, 1, 9)[3])
+    gen = Generator(device=0)
+    gen.load_weights(cases.ct_weights())
+    with pytest.raises(RuntimeError, match="no forward has run"):
+        runner.backward(gen, d_xin)
+    gen.close()
+    gen = Generator(device=0, dtype="f16")
+    gen.load_weights(cases.ct_weights())
+    rng = np.random.default_rng(22)
+    inputs, uv = to_dev(rng.uniform(0, 1, (1, 32, 256, 3)).astype(f32), rng.uniform(0, 1, (1, 32, 256, 3)).astype(f32))
+    gen(inputs, uv)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match="BSR_DTYPE_F32 handles only"):
+        runner.backward(gen, d_xin)
+    gen.close()
+
+
+def test_both_branches_chained(runner, generated):
+    """On that forward: the device walk over the five table stages, then GreyDecoder.backward and ColourTrunk.backward(generator, the
+    bottleneck's d_xin, the grey decoder's d_x), against the seven host statements chained on the device's own activations: d_res2 is the
+    complete gradient at res_stack/2's output."""
+    from blindshadowremoval_amd import GreyDecoder, objective
+    gen, w, inputs, outs, probes = generated
+    runner.load_weights(w)
+    gs, _, mask22, _ = outs
+    _, _, g_con_a, g_gs_a = host.example_inputs(32, 256, 2, 9)
+    g_con, g_gs = to_dev(g_con_a, g_gs_a)
+    table = tuple(s.name for s in objective.BACKWARD)
+    assert len(table) == 5
+    walked = objective.device_walk(objective.device_runners(table, w), gen, dict(img=inputs, gs=gs, mask22=mask22, grad_con=g_con, grad_gs=g_gs),
+                                   keep=("tail", "bottleneck", "heads"))
+    grey = GreyDecoder(0)
+    grey.load_weights(w)
+    g = grey.backward(gen, walked["heads"]["d_y"])
+    res = to_host(runner.backward(gen, walked["bottleneck"]["d_xin"], g["d_x"], keep=True))
+    torch.cuda.synchronize()
+    t, b, hd = (to_host({k: walked[s][k] for k in keys}) for s, keys in (("tail", ("a1", "a2")), ("bottleneck", ("a1", "a2")), ("heads", ("mask",))))
+    p = {k: v.cpu().numpy() for k, v in probes.items()}
+    st_t = host.tail_grad(w, gs.cpu().numpy(), p["f"], g_con_a, g_gs_a, acts=t)
+    st_d = host.decoder_grad(w, p["res5"], st_t["d_f"], acts={"f1": p["f1"], "f2": p["f2"], "f": p["f"]})
+    st_n = host.nonlocal_grad(w, (p["y3x5"][..., :257] - p["res4"][..., :257]).astype(f32), p["res4"], st_d["d_x"], acts={"out": p["res5"]})
+    st_b = host.bottleneck_grad(w, p["res4"], st_n["d_y3"], st_n["d_skip"], acts=b)
+    st_h = host.heads_grad(w, inputs.cpu().numpy(), p["y"], st_t["d_gs"], acts=hd)
+    st_g = host.grey_decoder_grad(w, p["res2"], p["x3"], p["x2"], st_h["d_y"], acts={"up1": p["up1"], "up2": p["up2"], "y": p["y"]})
+    y3_4 = (p["y3x4"][..., :257] - p["res3"][..., :257]).astype(f32)
+    y3_3 = (p["y3x3"][..., :257] - p["xh"][..., :257]).astype(f32)
+    st_c = host.colour_trunk_grad(w, p["xh"], y3_3, p["res3"], y3_4, p["res4"], st_b["d_xin"], st_g["d_x"], acts=res)
+    worst, at = cases.worst_scaled_diff(res, st_c)
+    print("both branches chained down to res_stack/2's output: worst scaled error %.3g at %s (bound %.3g); d_res2 %.3g"
+          % (worst, at, cases.CHAINED_BOUND, cases.worst_scaled_diff(res, st_c, ("d_res2",))[0]))
+    assert worst <= cases.CHAINED_BOUND, (worst, at)
+    # both branches reach d_res2: it is neither branch alone
+    alone = host.hole_grad(p["xh"], res["d_xin3"], None, dtype=f32)
+    assert np.abs(alone).max() > 0 and np.abs(res["d_res2"] - alone).max() > 0
+    runner.load_weights(cases.ct_weights())
