@@ -3,7 +3,7 @@
 from .weights import generator_variable_shapes, init_weights  # noqa: F401
 
 __all__ = ["Generator", "GeneratorTSM", "GeneratorRGB", "ShadowSynth", "TrainLosses", "Discriminators", "Perceptual", "ColourTail", "ColourDecoder",
-           "NonLocalGrad", "BottleneckGrad", "HeadsGrad", "GreyDecoder", "ColourTrunk", "generator_variable_shapes", "init_weights"]
+           "NonLocalGrad", "BottleneckGrad", "HeadsGrad", "GreyDecoder", "ColourTrunk", "LowerTrunk", "generator_variable_shapes", "init_weights"]
 
 
 def __getattr__(name):
@@ -43,4 +43,7 @@ def __getattr__(name):
     if name == "ColourTrunk":
         from .colour_trunk_gpu import ColourTrunk
         return ColourTrunk
+    if name == "LowerTrunk":
+        from .lower_trunk_gpu import LowerTrunk
+        return LowerTrunk
     raise AttributeError(name)

@@ -142,6 +142,14 @@ SIGNATURES = {
     "bsr_colour_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 5 + [c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
     "bsr_debug_colour_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 5 + [c_v, c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
     "bsr_debug_hole_grad": (c_i, [c_i, c_v, c_i, c_v, c_v, c_i, c_i, c_i, c_v, c_v]),
+    "bsr_last_lower_trunk": (c_i, [c_v, ctypes.POINTER(c_v * 7), ctypes.POINTER(c_i * 7), ctypes.POINTER(c_i * 4)]),
+    "bsr_lower_trunk_grad_blob_bytes": (c_sz, []),
+    "bsr_lower_trunk_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
+    "bsr_lower_trunk_grad_floats": (c_sz, []),
+    "bsr_lower_trunk_grad_var_offset": (c_sz, [c_i]),
+    "bsr_lower_trunk_grad_offset": (c_sz, [c_i, c_i, c_i, c_i]),
+    "bsr_lower_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 7 + [c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_v]),
+    "bsr_debug_lower_trunk_grad": (c_i, [c_i, c_v, c_sz] + [c_v, c_i] * 7 + [c_v, c_i, c_i, c_i, c_v, c_v, c_v, c_i, c_v]),
     "bsr_heads_grad_blob_bytes": (c_sz, []),
     "bsr_heads_grad_scratch_bytes": (c_sz, [c_i, c_i, c_i]),
     "bsr_heads_grad_floats": (c_sz, []),

@@ -26,16 +26,20 @@ SIZE_TEXT = "the bottleneck takes B >= 1 grids with h a multiple of 4 and w a mu
 NO_WEIGHTS_TEXT = "the bottleneck has no weights: call load_weights or restore first"
 
 
-def read_maps(view, offset, b: int, h: int, w: int) -> Dict[str, torch.Tensor]:
+def read_maps(view, offset, b: int, h: int, w: int, width: int = C_IN) -> Dict[str, torch.Tensor]:
     """Copies of the chain's maps out of a scratch: `view`(byte offset, shape[, dtype]) gives a tensor over it, `offset`(index) the byte
-    offset of bsr_bottleneck_grad_offset's map `index` (colour_trunk_gpu reads each block's region with its own)."""
+    offset of bsr_bottleneck_grad_offset's map `index` (colour_trunk_gpu and lower_trunk_gpu read each block's region with its own).
+    `width`: the block's input width, 261 (blocks 3..5), 257 (blocks 1, 2) or 99 (block 0) — xp's rows are `width` rounded up to 16
+    floats and Wg1 is [width,128]."""
     out = {}
     for name, (index, cols, kept) in MAPS.items():
+        if name == "xp":
+            cols, kept = (width + 15) // 16 * 16, width
         out[name] = view(offset(index), (b, h, w, cols))[..., :kept].clone()
-    wg = view(offset(6), (C_IN * D + 9 * D * D + D * C_Y,), torch.float64)
-    out["Wg1"] = wg[:C_IN * D].reshape(C_IN, D).clone()
-    out["Wg2"] = wg[C_IN * D:C_IN * D + 9 * D * D].reshape(3, 3, D, D).clone()
-    out["Wg3"] = wg[C_IN * D + 9 * D * D:].reshape(D, C_Y).clone()
+    wg = view(offset(6), (width * D + 9 * D * D + D * C_Y,), torch.float64)
+    out["Wg1"] = wg[:width * D].reshape(width, D).clone()
+    out["Wg2"] = wg[width * D:width * D + 9 * D * D].reshape(3, 3, D, D).clone()
+    out["Wg3"] = wg[width * D + 9 * D * D:].reshape(D, C_Y).clone()
     s = view(offset(7), (2 * D + C_Y,), torch.float64)
     out["S1"], out["S2"], out["S3"] = s[:D].clone(), s[D:2 * D].clone(), s[2 * D:].clone()
     return out

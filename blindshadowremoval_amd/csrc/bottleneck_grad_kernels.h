@@ -4,6 +4,11 @@
 // output) and d_skip (or none) it writes d_xin and the twelve variable gradients.  blindshadowremoval_amd/generator_grad.py is the host
 // statement (bottleneck_grad); pack.pack_bottleneck_grad writes the blob.
 //
+// The chain is a template on X, the width of the block's input: 261 for blocks 3..5, and for lower_trunk_grad_kernels.h 257 (blocks 1, 2)
+// and 99 (block 0, conv1 99 -> 128).  Where the text below says 261, 272 and 384 it speaks of X, of X rounded up to 16 and of X rounded
+// up to 128; the kernels that carry X in their index arithmetic are instantiated per width, the others take it as K, n_store, strides
+// and grids.
+//
 // The chain keeps nothing of the forward but xin: a1 and a2 are formed again from the BN-folded images, so the same entry serves blocks
 // 3 and 4, whose t1/t2 slots the forward has overwritten by the time it ends.
 //
@@ -31,52 +36,64 @@ namespace bsr {
 
 constexpr int kBnLaunches = 12;
 constexpr int kBnVars = 12;
-constexpr int kBnD = 128, kBnX = 261, kBnXp = 272, kBnY = 257, kBnW1t = 384;
+constexpr int kBnD = 128, kBnX = 261, kBnY = 257, kBnYp = 272;
 constexpr int kBnMaps = 8;
-constexpr int kBnK1 = kBnX * kBnD, kBnK2 = 9 * kBnD * kBnD, kBnK3 = kBnD * kBnY;
-constexpr int kBnKernelElems = kBnK1 + kBnK2 + kBnK3;
+constexpr int kBnK2 = 9 * kBnD * kBnD, kBnK3 = kBnD * kBnY;
 constexpr int kBnChannels = 2 * kBnD + kBnY;
 
+// What the width X of the block's input (conv1's) gives: 261 for blocks 3..5, 257 for blocks 1 and 2, 99 for block 0.  xp = X rounded
+// up to the GEMMs' 16-channel steps (272, 272, 112), w1t = X rounded up to launch 9's 128-column tiles (384, 384, 128), mp = launch
+// 8's partial rows, whole 64-row tiles of xp^T (320, 320, 128).
+__host__ __device__ constexpr bool bn_width_ok(int X) { return X == 261 || X == 257 || X == 99; }
+__host__ __device__ constexpr int bn_xp(int X) { return (X + 15) / 16 * 16; }
+__host__ __device__ constexpr int bn_w1t(int X) { return (X + 127) / 128 * 128; }
+__host__ __device__ constexpr int bn_mp(int X) { return (bn_xp(X) + 63) / 64 * 64; }
+__host__ __device__ constexpr int bn_k1(int X) { return X * kBnD; }
+__host__ __device__ constexpr int bn_kernel_elems(int X) { return bn_k1(X) + kBnK2 + kBnK3; }
+static_assert(bn_xp(261) == 272 && bn_w1t(261) == 384 && bn_mp(261) == kNlTnMp, "the colour branch's widths");
+static_assert(bn_xp(257) == 272 && bn_w1t(257) == 384 && bn_mp(257) == 320, "blocks 1 and 2");
+static_assert(bn_xp(99) == 112 && bn_w1t(99) == 128 && bn_mp(99) == 128, "block 0");
+
 // float offsets inside the blob; part 13: the total
-__host__ __device__ inline size_t bn_blob_off(int part) {
-  // 0: w1f [272][128]  1: b1f [128]  2: w2f [9][128][128]  3: b2f [128]  4: w3t [272][128]  5: w2t [9][128][128]  6: w1t [128][384]
-  // 7: k1 [261][128]  8: k2 [9][128][128]  9: k3 [128][257]  10: vecs1 [4][128]  11: vecs2 [4][128]  12: vecs3 [4][257]
-  const size_t n[13] = {(size_t)kBnXp * kBnD, kBnD, kBnK2, kBnD, (size_t)kBnXp * kBnD, kBnK2, (size_t)kBnD * kBnW1t, kBnK1, kBnK2, kBnK3,
-                        4 * kBnD, 4 * kBnD, 4 * kBnY};
+__host__ __device__ inline size_t bn_blob_off(int part, int X = kBnX) {
+  // 0: w1f [xp][128]  1: b1f [128]  2: w2f [9][128][128]  3: b2f [128]  4: w3t [272][128]  5: w2t [9][128][128]  6: w1t [128][w1t]
+  // 7: k1 [X][128]  8: k2 [9][128][128]  9: k3 [128][257]  10: vecs1 [4][128]  11: vecs2 [4][128]  12: vecs3 [4][257]
+  const size_t n[13] = {(size_t)bn_xp(X) * kBnD, kBnD, kBnK2, kBnD, (size_t)kBnYp * kBnD, kBnK2, (size_t)kBnD * bn_w1t(X), (size_t)bn_k1(X), kBnK2,
+                        kBnK3, 4 * kBnD, 4 * kBnD, 4 * kBnY};
   size_t o = 0;
   for (int i = 0; i < part && i < 13; ++i) o += n[i];
   return o;
 }
 
 // float offset of variable `index` (conv1, conv2, conv3: kernel, bias; bnorm1, bnorm2, bnorm3: gamma, beta) inside grads; 12: the total
-__host__ __device__ inline size_t bn_var_offset(int index) {
-  const size_t n[kBnVars] = {kBnK1, kBnD, kBnK2, kBnD, kBnK3, kBnY, kBnD, kBnD, kBnD, kBnD, kBnY, kBnY};
+__host__ __device__ inline size_t bn_var_offset(int index, int X = kBnX) {
+  const size_t n[kBnVars] = {(size_t)bn_k1(X), kBnD, kBnK2, kBnD, kBnK3, kBnY, kBnD, kBnD, kBnD, kBnD, kBnY, kBnY};
   size_t o = 0;
   for (int v = 0; v < index && v < kBnVars; ++v) o += n[v];
   return o;
 }
 
-// Byte offsets inside the scratch.  map 0: xp [N][272], 1: dyp [N][272], 2: a1, 3: a2, 4: gz2, 5: gz1 [N][128], 6: Wg float64
-// [261 x 128 | 9 x 128 x 128 | 128 x 257], 7: S float64 [128 | 128 | 257] (layers 1, 2, 3).
+// Byte offsets inside the scratch.  map 0: xp [N][xp], 1: dyp [N][272], 2: a1, 3: a2, 4: gz2, 5: gz1 [N][128], 6: Wg float64
+// [X x 128 | 9 x 128 x 128 | 128 x 257], 7: S float64 [128 | 128 | 257] (layers 1, 2, 3).
 struct BnPlan {
   int N, P;
   size_t map[kBnMaps], szpart, bpart, part1, part2, part3, total;
 };
-inline BnPlan bn_plan(int B, int h, int w) {
+inline BnPlan bn_plan(int B, int h, int w, int X = kBnX) {
   BnPlan pl;
   BumpBytes bump;
   pl.N = B * h * w;
   const int chunks = pl.N / 128;
   pl.P = chunks < 64 ? chunks : 64;
   const size_t N = (size_t)pl.N;
-  pl.map[0] = bump.take(N * kBnXp * sizeof(float));
-  pl.map[1] = bump.take(N * kBnXp * sizeof(float));
+  pl.map[0] = bump.take(N * bn_xp(X) * sizeof(float));
+  pl.map[1] = bump.take(N * kBnYp * sizeof(float));
   for (int m = 2; m < 6; ++m) pl.map[m] = bump.take(N * kBnD * sizeof(float));
-  pl.map[6] = bump.take((size_t)kBnKernelElems * sizeof(double));
+  pl.map[6] = bump.take((size_t)bn_kernel_elems(X) * sizeof(double));
   pl.map[7] = bump.take((size_t)kBnChannels * sizeof(double));
-  pl.szpart = bump.take((N / 64) * kBnXp * sizeof(double));
+  pl.szpart = bump.take((N / 64) * kBnYp * sizeof(double));
   pl.bpart = bump.take((N / 128) * 2 * kBnD * sizeof(double));
-  pl.part1 = bump.take((size_t)pl.P * kNlTnMp * kNlQ * sizeof(float));
+  pl.part1 = bump.take((size_t)pl.P * bn_mp(X) * kNlQ * sizeof(float));
   pl.part2 = bump.take((size_t)pl.P * 9 * kBnD * kBnD * sizeof(float));
   pl.part3 = bump.take((size_t)pl.P * kBnD * kNlQ * sizeof(float));
   pl.total = bump.o;
@@ -88,26 +105,28 @@ __device__ __forceinline__ float bn_lrelu(float v) { return v >= 0.f ? v : kLeak
 // ---- launch 1
 struct BnEntryArgs {
   const float *xin, *d_y3;
-  float *xp, *dyp;
+  float *xp, *dyp;      // [N][xp], [N][272]
   double* szpart;      // [N / 64][272]
   int xin_cs;
 };
 
-// grid (N / 64)
+// grid (N / 64).  xin is read for c < X alone: block 0's pixel ends at channel 98 of a 120-float stride
+template <int X>
 __global__ __launch_bounds__(256) void bn_entry_kernel(const BnEntryArgs a) {
+  constexpr int Xp = bn_xp(X);
   const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * 64;
-  for (int c = tid; c < kBnXp; c += 256) {
+  for (int c = tid; c < kBnYp; c += 256) {
     double s = 0.0;
     for (int i = 0; i < 64; ++i) {
       const size_t row = row0 + i;
-      const float x = c < kBnX ? a.xin[row * a.xin_cs + c] : 0.f;
+      const float x = c < X ? a.xin[row * a.xin_cs + c] : 0.f;
       const float g = c < kBnY ? a.d_y3[row * kBnY + c] : 0.f;
-      a.xp[row * kBnXp + c] = x;
-      a.dyp[row * kBnXp + c] = g;
+      if (Xp == kBnYp || c < Xp) a.xp[row * Xp + c] = x;
+      a.dyp[row * kBnYp + c] = g;
       s += (double)g;
     }
-    a.szpart[(size_t)blockIdx.x * kBnXp + c] = s;
+    a.szpart[(size_t)blockIdx.x * kBnYp + c] = s;
   }
 }
 
@@ -345,32 +364,34 @@ struct BnFoldArgs {
   int P;
 };
 
+template <int X>
 __global__ __launch_bounds__(256) void bn_fold_kernel(const BnFoldArgs a) {
+  constexpr int kBnK1 = bn_k1(X);
   const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
-  if (e >= kBnKernelElems) return;
+  if (e >= bn_kernel_elems(X)) return;
   double s = 0.0, inv;
   size_t at;
   if (e < kBnK1) {
     const int c = e / kBnD, k = e % kBnD;
     const float* src = a.part1 + (size_t)c * kNlQ + k;
 #pragma unroll 8
-    for (int p = 0; p < a.P; ++p) s += (double)src[(size_t)p * kNlTnMp * kNlQ];
+    for (int p = 0; p < a.P; ++p) s += (double)src[(size_t)p * bn_mp(X) * kNlQ];
     inv = a.vecs1[kBnD + k];
-    at = bn_var_offset(0) + e;
+    at = bn_var_offset(0, X) + e;
   } else if (e < kBnK1 + kBnK2) {
     const int i = e - kBnK1;
     const float* src = a.part2 + i;
 #pragma unroll 8
     for (int p = 0; p < a.P; ++p) s += (double)src[(size_t)p * kBnK2];
     inv = a.vecs2[kBnD + i % kBnD];
-    at = bn_var_offset(2) + i;
+    at = bn_var_offset(2, X) + i;
   } else {
     const int i = e - kBnK1 - kBnK2, k = i / kBnY, n = i % kBnY;
     const float* src = a.part3 + (size_t)k * kNlQ + n;
 #pragma unroll 8
     for (int p = 0; p < a.P; ++p) s += (double)src[(size_t)p * kBnD * kNlQ];
     inv = a.vecs3[kBnY + n];
-    at = bn_var_offset(4) + i;
+    at = bn_var_offset(4, X) + i;
   }
   a.Wg[e] = s;
   a.grads[at] = (float)(inv * s);
@@ -385,19 +406,21 @@ struct BnFinishArgs {
   int nsz, nb;
 };
 
+template <int X>
 __global__ __launch_bounds__(64) void bn_finish_kernel(const BnFinishArgs a) {
+  constexpr int kBnK1 = bn_k1(X);
   const int lane = threadIdx.x, b = (int)blockIdx.x;
   double s = 0.0, kw = 0.0;
   if (b < kBnD) {
     for (int i = lane; i < a.nb; i += 64) s += a.bpart[(size_t)i * 2 * kBnD + kBnD + b];
-    for (int c = lane; c < kBnX; c += 64) kw += (double)a.k1[c * kBnD + b] * a.Wg[c * kBnD + b];
+    for (int c = lane; c < X; c += 64) kw += (double)a.k1[c * kBnD + b] * a.Wg[c * kBnD + b];
   } else if (b < 2 * kBnD) {
     const int o = b - kBnD;
     for (int i = lane; i < a.nb; i += 64) s += a.bpart[(size_t)i * 2 * kBnD + o];
     for (int i = lane; i < 9 * kBnD; i += 64) kw += (double)a.k2[i * kBnD + o] * a.Wg[kBnK1 + i * kBnD + o];
   } else {
     const int n = b - 2 * kBnD;
-    for (int i = lane; i < a.nsz; i += 64) s += a.szpart[(size_t)i * kBnXp + n];
+    for (int i = lane; i < a.nsz; i += 64) s += a.szpart[(size_t)i * kBnYp + n];
     for (int k = lane; k < kBnD; k += 64) kw += (double)a.k3[k * kBnY + n] * a.Wg[kBnK1 + kBnK2 + k * kBnY + n];
   }
   s = wave_sum(s);
@@ -405,20 +428,29 @@ __global__ __launch_bounds__(64) void bn_finish_kernel(const BnFinishArgs a) {
   if (lane != 0) return;
   a.S[b] = s;
   if (b < kBnD)
-    bn_channel_grads(kw, s, a.vecs1, kBnD, b, a.grads[bn_var_offset(1) + b], a.grads[bn_var_offset(6) + b], a.grads[bn_var_offset(7) + b]);
+    bn_channel_grads(kw, s, a.vecs1, kBnD, b, a.grads[bn_var_offset(1, X) + b], a.grads[bn_var_offset(6, X) + b], a.grads[bn_var_offset(7, X) + b]);
   else if (b < 2 * kBnD)
-    bn_channel_grads(kw, s, a.vecs2, kBnD, b - kBnD, a.grads[bn_var_offset(3) + b - kBnD], a.grads[bn_var_offset(8) + b - kBnD],
-                     a.grads[bn_var_offset(9) + b - kBnD]);
+    bn_channel_grads(kw, s, a.vecs2, kBnD, b - kBnD, a.grads[bn_var_offset(3, X) + b - kBnD], a.grads[bn_var_offset(8, X) + b - kBnD],
+                     a.grads[bn_var_offset(9, X) + b - kBnD]);
   else
-    bn_channel_grads(kw, s, a.vecs3, kBnY, b - 2 * kBnD, a.grads[bn_var_offset(5) + b - 2 * kBnD], a.grads[bn_var_offset(10) + b - 2 * kBnD],
-                     a.grads[bn_var_offset(11) + b - 2 * kBnD]);
+    bn_channel_grads(kw, s, a.vecs3, kBnY, b - 2 * kBnD, a.grads[bn_var_offset(5, X) + b - 2 * kBnD], a.grads[bn_var_offset(10, X) + b - 2 * kBnD],
+                     a.grads[bn_var_offset(11, X) + b - 2 * kBnD]);
 }
 
 // The first `stop_after` of the twelve launches above (kBnLaunches: all of them; fewer are for the tests' stage-by-stage comparison).
-// xin [B,h,w,261 of xin_cs], d_y3 dense 257 wide, d_skip dense 261 wide or null, d_xin dense 261 wide.
+// xin [B,h,w,X of xin_cs], d_y3 dense 257 wide, d_skip dense X wide or null, d_xin dense X wide; blob, grads and scratch are
+// bn_blob_off's, bn_var_offset's and bn_plan's at this X.  A narrow input does not run the wide blocks' work on zeros: launch 2 runs
+// K = xp, launch 8 covers xp^T's own 64-row tiles and launch 9 w1t's own 128-column tiles.
+template <int X = kBnX>
 inline hipError_t launch_bottleneck_grad(const float* blob, const float* xin, int xin_cs, const float* d_y3, const float* d_skip, int B, int h, int w,
                                          float* d_xin, float* grads, void* scratch, int stop_after, hipStream_t stream) {
-  const BnPlan pl = bn_plan(B, h, w);
+  static_assert(bn_width_ok(X), "the input is 261, 257 or 99 wide");
+  constexpr int Xp = bn_xp(X), W1t = bn_w1t(X), Mp = bn_mp(X);
+  constexpr int kRowTiles = Mp / 64, kColTiles = W1t / 128;       // launch 8's grid.y, launch 9's grid.y
+  static_assert(X != 99 || (Xp == 112 && kRowTiles == 2 && kColTiles == 1), "block 0: K = 112, two 64-row tiles, one 128-column tile");
+  static_assert(X == 99 || (Xp == 272 && kRowTiles == 5 && kColTiles == 3), "the wide blocks: K = 272, five row tiles, three column tiles");
+  static_assert(Xp % 16 == 0 && Xp <= Mp && X <= W1t, "the GEMMs' steps and the tiles cover the input");
+  const BnPlan pl = bn_plan(B, h, w, X);
   unsigned char* base = static_cast<unsigned char*>(scratch);
   auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   auto d = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
@@ -432,34 +464,34 @@ inline hipError_t launch_bottleneck_grad(const float* blob, const float* xin, in
   if (stop_after <= done++) return hipSuccess;
   {
     BnEntryArgs a{xin, d_y3, xp, dyp, szpart, xin_cs};
-    hipLaunchKernelGGL(bn_entry_kernel, dim3(N / 64), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(bn_entry_kernel<X>, dim3(N / 64), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
     BnGemmArgs a{};
-    a.a = xp; a.a_cs = kBnXp; a.K = kBnXp; a.w = blob + bn_blob_off(0); a.w_cs = kBnD; a.bias = blob + bn_blob_off(1);
+    a.a = xp; a.a_cs = Xp; a.K = Xp; a.w = blob + bn_blob_off(0, X); a.w_cs = kBnD; a.bias = blob + bn_blob_off(1, X);
     a.out = a1; a.out_cs = kBnD; a.n_store = kBnD;
     hipLaunchKernelGGL(bn_gemm_kernel<0>, dim3(N / 64, 1), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
-    BnConv3Args a{a1, blob + bn_blob_off(2), blob + bn_blob_off(3), nullptr, a2, h, w};
+    BnConv3Args a{a1, blob + bn_blob_off(2, X), blob + bn_blob_off(3, X), nullptr, a2, h, w};
     hipLaunchKernelGGL(bn_conv3_kernel<0>, tiles, dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
     BnGemmArgs a{};
-    a.a = dyp; a.a_cs = kBnXp; a.K = kBnXp; a.w = blob + bn_blob_off(4); a.w_cs = kBnD; a.act = a2;
+    a.a = dyp; a.a_cs = kBnYp; a.K = kBnYp; a.w = blob + bn_blob_off(4, X); a.w_cs = kBnD; a.act = a2;
     a.out = gz2; a.out_cs = kBnD; a.n_store = kBnD;
     hipLaunchKernelGGL(bn_gemm_kernel<1>, dim3(N / 64, 1), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
-    BnConv3Args a{gz2, blob + bn_blob_off(5), nullptr, a1, gz1, h, w};
+    BnConv3Args a{gz2, blob + bn_blob_off(5, X), nullptr, a1, gz1, h, w};
     hipLaunchKernelGGL(bn_conv3_kernel<1>, tiles, dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
@@ -471,22 +503,22 @@ inline hipError_t launch_bottleneck_grad(const float* blob, const float* xin, in
   }
   if (stop_after <= done++) return hipSuccess;
   {
-    NlTnArgs a{a2, dyp, part3, kBnD, kBnD, kBnXp, kBnXp, kBnD, N / 128, pl.P};
+    NlTnArgs a{a2, dyp, part3, kBnD, kBnD, kBnYp, kBnYp, kBnD, N / 128, pl.P};
     hipLaunchKernelGGL(nl_tn_kernel, dim3(pl.P, 2, 3), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
-    NlTnArgs a{xp, gz1, part1, kBnXp, kBnXp, kBnD, kBnD, kNlTnMp, N / 128, pl.P};
-    hipLaunchKernelGGL(nl_tn_kernel, dim3(pl.P, kNlTnMp / 64, 1), dim3(256), 0, stream, a);
+    NlTnArgs a{xp, gz1, part1, Xp, Xp, kBnD, kBnD, Mp, N / 128, pl.P};
+    hipLaunchKernelGGL(nl_tn_kernel, dim3(pl.P, kRowTiles, 1), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
     BnGemmArgs a{};
-    a.a = gz1; a.a_cs = kBnD; a.K = kBnD; a.w = blob + bn_blob_off(6); a.w_cs = kBnW1t; a.res = d_skip; a.res_cs = kBnX;
-    a.out = d_xin; a.out_cs = kBnX; a.n_store = kBnX;
-    hipLaunchKernelGGL(bn_gemm_kernel<2>, dim3(N / 64, 3), dim3(256), 0, stream, a);
+    a.a = gz1; a.a_cs = kBnD; a.K = kBnD; a.w = blob + bn_blob_off(6, X); a.w_cs = W1t; a.res = d_skip; a.res_cs = X;
+    a.out = d_xin; a.out_cs = X; a.n_store = X;
+    hipLaunchKernelGGL(bn_gemm_kernel<2>, dim3(N / 64, kColTiles), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
@@ -494,14 +526,14 @@ inline hipError_t launch_bottleneck_grad(const float* blob, const float* xin, in
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (stop_after <= done++) return hipSuccess;
   {
-    BnFoldArgs a{part1, part2, part3, blob + bn_blob_off(10), blob + bn_blob_off(11), blob + bn_blob_off(12), Wg, grads, pl.P};
-    hipLaunchKernelGGL(bn_fold_kernel, dim3((kBnKernelElems + 255) / 256), dim3(256), 0, stream, a);
+    BnFoldArgs a{part1, part2, part3, blob + bn_blob_off(10, X), blob + bn_blob_off(11, X), blob + bn_blob_off(12, X), Wg, grads, pl.P};
+    hipLaunchKernelGGL(bn_fold_kernel<X>, dim3((bn_kernel_elems(X) + 255) / 256), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
-  BnFinishArgs a{szpart, bpart, Wg, blob + bn_blob_off(7), blob + bn_blob_off(8), blob + bn_blob_off(9), blob + bn_blob_off(10),
-                 blob + bn_blob_off(11), blob + bn_blob_off(12), S, grads, N / 64, N / 128};
-  hipLaunchKernelGGL(bn_finish_kernel, dim3(kBnChannels), dim3(64), 0, stream, a);
+  BnFinishArgs a{szpart, bpart, Wg, blob + bn_blob_off(7, X), blob + bn_blob_off(8, X), blob + bn_blob_off(9, X), blob + bn_blob_off(10, X),
+                 blob + bn_blob_off(11, X), blob + bn_blob_off(12, X), S, grads, N / 64, N / 128};
+  hipLaunchKernelGGL(bn_finish_kernel<X>, dim3(kBnChannels), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -48,6 +48,7 @@
 #include "nonlocal_grad_kernels.h"
 #include "bottleneck_grad_kernels.h"
 #include "colour_trunk_grad_kernels.h"
+#include "lower_trunk_grad_kernels.h"
 #include "heads_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
@@ -1955,6 +1956,60 @@ int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_x
       });
 }
 
+size_t bsr_lower_trunk_grad_blob_bytes(void) { return bsr::lt_blob_off(2 * bsr::kLtBlocks) * sizeof(float); }
+
+size_t bsr_lower_trunk_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::lt_plan(B, h, w).total : 0; }
+
+size_t bsr_lower_trunk_grad_floats(void) { return bsr::lt_var_offset(bsr::kLtVars); }
+
+size_t bsr_lower_trunk_grad_var_offset(int index) { return index < 0 || index >= bsr::kLtVars ? SIZE_MAX : bsr::lt_var_offset(index); }
+
+size_t bsr_lower_trunk_grad_offset(int B, int h, int w, int map) {
+  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kLtMaps) return SIZE_MAX;
+  return bsr::lt_plan(B, h, w).map[map];
+}
+
+namespace {
+
+int lower_trunk_grad(const char* name, int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,
+                     const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0, int out0_cs,
+                     const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads, void* scratch, int stop_after,
+                     void* stream) {
+  return run_grad_stage(
+      name, {d_blob, y3x2, out2, y3x1, out1, y3x0, out0, x0, d_res2, d_x0, grads, scratch},
+      {{bsr::nl_size_ok(B, h, w),
+        "B must be positive, h a multiple of 4 and w a multiple of 32 (the generator's rule at 1/8 resolution), at most 2^21 pixels in all"},
+       {blob_bytes == bsr_lower_trunk_grad_blob_bytes(),
+        "blob_bytes must be bsr_lower_trunk_grad_blob_bytes() (pack.pack_lower_trunk_grad; the GSC widths 99 and 257 only, not TSM's 291 or RGB's 513)"},
+       {y3x2_cs >= 257 && y3x1_cs >= 257 && y3x0_cs >= 257 && out2_cs >= 257 && out1_cs >= 257 && out0_cs >= 257 && x0_cs >= 99,
+        "y3x2_cs, y3x1_cs, y3x0_cs, out2_cs, out1_cs and out0_cs must be at least 257, x0_cs at least 99"}},
+      {{16, "d_blob", {d_blob}},
+       {4, "y3x2, out2, y3x1, out1, y3x0, out0, x0, d_res2, d_x0 and grads", {y3x2, out2, y3x1, out1, y3x0, out0, x0, d_res2, d_x0, grads}}},
+      scratch, stop_after, bsr::kLtLaunches, device, [&] {
+        HIP_TRY(bsr::launch_lower_trunk_grad(static_cast<const float*>(d_blob), y3x2, y3x2_cs, out2, out2_cs, y3x1, y3x1_cs, out1, out1_cs, y3x0, y3x0_cs,
+                                             out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, stop_after,
+                                             static_cast<hipStream_t>(stream)));
+        return BSR_OK;
+      });
+}
+
+}  // namespace
+
+int bsr_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,
+                         const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0, int out0_cs,
+                         const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads, void* scratch, void* stream) {
+  return lower_trunk_grad("bsr_lower_trunk_grad", device, d_blob, blob_bytes, y3x2, y3x2_cs, out2, out2_cs, y3x1, y3x1_cs, out1, out1_cs, y3x0, y3x0_cs,
+                          out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, bsr::kLtLaunches, stream);
+}
+
+int bsr_debug_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,
+                               const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0,
+                               int out0_cs, const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads,
+                               void* scratch, int stop_after, void* stream) {
+  return lower_trunk_grad("bsr_debug_lower_trunk_grad", device, d_blob, blob_bytes, y3x2, y3x2_cs, out2, out2_cs, y3x1, y3x1_cs, out1, out1_cs, y3x0,
+                          y3x0_cs, out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, stop_after, stream);
+}
+
 size_t bsr_heads_grad_blob_bytes(void) { return (size_t)bsr::kHgBlobFloats * sizeof(float); }
 
 size_t bsr_heads_grad_scratch_bytes(int B, int H, int W) { return bsr::hg_size_ok(B, H, W) ? bsr::hg_plan(B, H, W).total : 0; }
@@ -2543,6 +2598,28 @@ int bsr_last_block(bsr_handle* h, int block, const float** y3x, int* y3x_cs, con
 
 int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]) {
   return last_block("bsr_last_block5", h, 5, y3x, y3x_cs, xin, out, x_cs, shape4);
+}
+
+int bsr_last_lower_trunk(bsr_handle* h, const float* tensors7[7], int strides7[7], int shape4[4]) {
+  if (h == nullptr || tensors7 == nullptr || strides7 == nullptr || shape4 == nullptr) return fail(BSR_ERR_ARG, "bsr_last_lower_trunk: null argument");
+  if (h->var.rgb) return fail(BSR_ERR_STATE, "bsr_last_lower_trunk: the lower trunk's backward takes the GSC width 257 only, not an RGB handle's 513");
+  if (h->var.tsm) return fail(BSR_ERR_STATE, "bsr_last_lower_trunk: the lower trunk's backward takes the GSC width 257 only, not a TSM handle's 291");
+  if (h->dtype != BSR_DTYPE_F32)
+    return fail(BSR_ERR_STATE, "bsr_last_lower_trunk: the blocks' tensors are kept for the backward in BSR_DTYPE_F32 handles only, not in the 16-bit modes");
+  if (!h->ran) return fail(BSR_ERR_STATE, "bsr_last_lower_trunk: no forward has run on this handle");
+  // make_plan gives xa, every y3[i] and every r[i] a slot of its own.  forward_impl's down3 and uv_resize8 alone write xa, both ahead of
+  // res_block(0); res_block(i) alone writes y3[i] and r[i]; up1 and bmask_xhole only read r[2]: nothing after block 0 touches xa, and
+  // nothing after block i its y3[i] and r[i]
+  for (int k = 0; k < 3; ++k) {
+    tensors7[2 * k] = h->ws + h->plan.y3[2 - k];
+    strides7[2 * k] = h->var.cs_y3x;
+    tensors7[2 * k + 1] = h->ws + h->plan.r[2 - k];
+    strides7[2 * k + 1] = h->var.cs_r;
+  }
+  tensors7[6] = h->ws + h->plan.xa;
+  strides7[6] = h->var.cs_a;
+  shape4[0] = h->B; shape4[1] = h->H / 8; shape4[2] = h->W / 8; shape4[3] = 257;
+  return BSR_OK;
 }
 
 }  // extern "C"

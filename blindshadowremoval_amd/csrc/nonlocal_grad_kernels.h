@@ -7,7 +7,7 @@
 // N = B T rows (T = h w tokens per image, a multiple of 128).  Twelve launches on the caller's stream, one after the other: no host
 // synchronisation, no second stream, no floating-point atomic; every word a launch reads was written by the caller or by an earlier
 // launch of the same call, and every sum runs in a fixed order, so a call repeats its bits.  All matrix work is v_mfma_f32_16x16x4_f32.
-//    1  nl_entry_kernel      gz = LeakyReluGrad(d_out, out) where d_out is loaded -> d_skip (all 261 channels) and dz (the first 257, row
+//    1  nl_entry_kernel<X>   gz = LeakyReluGrad(d_out, out) where d_out is loaded -> d_skip (all X = 261 channels) and dz (the first 257, row
 //                            stride 272, the pad 0); y3 = y3x - pad(xin) -> X (stride 272, pad 0); per 64 rows the column sums of dz in
 //                            float64 in row order.
 //    2  nl_gemm_kernel<0>    proj = [theta | phi | g] = X Wqkv + b            (K = 272, N = 384): the forward composes them away
@@ -104,8 +104,12 @@ struct NlEntryArgs {
   int y3x_cs, xin_cs, out_cs;
 };
 
-// grid (N / 64)
+// grid (N / 64).  X: the width of the block's input and so of the skip — 261 (blocks 3..5), 257 (blocks 1, 2: nothing beyond the block's own
+// channels) or 99 (block 0: the skip reaches the first 99 channels only, out = lrelu(z + pad_257(xin))).  d_out and out are read
+// max(X, 257) wide, xin for c < X alone, d_skip is written X wide.
+template <int X>
 __global__ __launch_bounds__(256) void nl_entry_kernel(const NlEntryArgs a) {
+  constexpr int G = X > kNlC ? X : kNlC;    // d_out's dense width
   const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * 64;
   for (int c = tid; c < kNlCp; c += 256) {
@@ -114,9 +118,12 @@ __global__ __launch_bounds__(256) void nl_entry_kernel(const NlEntryArgs a) {
       const size_t row = row0 + i;
       float g = 0.f, x = 0.f;
       if (c < kNlC) {
-        g = clr_leaky_grad(a.d_out[row * kNlX + c], a.out[row * a.out_cs + c]);
-        x = a.y3x[row * a.y3x_cs + c] - a.xin[row * a.xin_cs + c];
-        a.d_skip[row * kNlX + c] = g;
+        g = clr_leaky_grad(a.d_out[row * G + c], a.out[row * a.out_cs + c]);
+        x = a.y3x[row * a.y3x_cs + c];
+        if (X >= kNlC || c < X) {
+          x -= a.xin[row * a.xin_cs + c];
+          a.d_skip[row * X + c] = g;
+        }
       }
       a.dz[row * kNlCp + c] = g;
       a.X[row * kNlCp + c] = x;
@@ -124,11 +131,13 @@ __global__ __launch_bounds__(256) void nl_entry_kernel(const NlEntryArgs a) {
     }
     a.szpart[(size_t)blockIdx.x * kNlCp + c] = s;
   }
-  constexpr int E = kNlX - kNlC;            // the skip's own channels 257..260
-  for (int i = tid; i < 64 * E; i += 256) {
-    const size_t row = row0 + i / E;
-    const int c = kNlC + i % E;
-    a.d_skip[row * kNlX + c] = clr_leaky_grad(a.d_out[row * kNlX + c], a.out[row * a.out_cs + c]);
+  if constexpr (X > kNlC) {
+    constexpr int E = X - kNlC;             // the skip's own channels 257..260
+    for (int i = tid; i < 64 * E; i += 256) {
+      const size_t row = row0 + i / E;
+      const int c = kNlC + i % E;
+      a.d_skip[row * X + c] = clr_leaky_grad(a.d_out[row * X + c], a.out[row * a.out_cs + c]);
+    }
   }
 }
 
@@ -545,7 +554,9 @@ inline hipError_t launch_nl_att(K kernel, PerDeviceOnce& once, const NlAttArgs& 
 }
 
 // The first `stop_after` of the twelve launches above (kNlLaunches: all of them; fewer are for the tests' stage-by-stage comparison).
-// h, w: the 1/8-resolution grid's, so every tensor is [B,h,w,.]: d_out and d_skip dense 261 wide, d_y3 dense 257 wide.
+// h, w: the 1/8-resolution grid's, so every tensor is [B,h,w,.]: d_out dense max(X, 257) wide, d_skip dense X wide, d_y3 dense 257 wide.
+// X: the width of the block's input (nl_entry_kernel); nothing else of the chain, its blob or its scratch carries it.
+template <int X = kNlX>
 inline hipError_t launch_nonlocal_grad(const float* blob, const float* y3x, int y3x_cs, const float* xin, int xin_cs, const float* out, int out_cs,
                                        const float* d_out, int B, int h, int w, float* d_y3, float* d_skip, float* grads, void* scratch, int stop_after,
                                        hipStream_t stream) {
@@ -553,7 +564,7 @@ inline hipError_t launch_nonlocal_grad(const float* blob, const float* y3x, int 
   unsigned char* base = static_cast<unsigned char*>(scratch);
   auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   auto d = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
-  float *X = f(pl.map[0]), *dz = f(pl.map[1]), *proj = f(pl.map[2]), *A = f(pl.map[3]), *L = f(pl.map[4]), *dA = f(pl.map[5]), *D = f(pl.map[6]);
+  float *y3 = f(pl.map[0]), *dz = f(pl.map[1]), *proj = f(pl.map[2]), *A = f(pl.map[3]), *L = f(pl.map[4]), *dA = f(pl.map[5]), *D = f(pl.map[6]);
   float *dproj = f(pl.map[7]), *part1 = f(pl.part1), *part2 = f(pl.part2);
   double *Wgd = d(pl.map[8]), *Sz = d(pl.map[9]), *szpart = d(pl.szpart), *bpart = d(pl.bpart);
   const int N = pl.N;
@@ -561,14 +572,14 @@ inline hipError_t launch_nonlocal_grad(const float* blob, const float* y3x, int 
   int done = 0;
   if (stop_after <= done++) return hipSuccess;
   {
-    NlEntryArgs a{y3x, xin, out, d_out, d_skip, X, dz, szpart, y3x_cs, xin_cs, out_cs};
-    hipLaunchKernelGGL(nl_entry_kernel, dim3(N / 64), dim3(256), 0, stream, a);
+    NlEntryArgs a{y3x, xin, out, d_out, d_skip, y3, dz, szpart, y3x_cs, xin_cs, out_cs};
+    hipLaunchKernelGGL(nl_entry_kernel<X>, dim3(N / 64), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (stop_after <= done++) return hipSuccess;
   {
     NlGemmArgs a{};
-    a.a = X; a.a_cs = kNlCp; a.K = kNlCp; a.w = blob + nl_blob_off(0); a.w_cs = kNlQ; a.bias = blob + nl_blob_off(1);
+    a.a = y3; a.a_cs = kNlCp; a.K = kNlCp; a.w = blob + nl_blob_off(0); a.w_cs = kNlQ; a.bias = blob + nl_blob_off(1);
     a.out = proj; a.out_cs = kNlQ; a.n_store = kNlQ;
     hipLaunchKernelGGL(nl_gemm_kernel<0>, dim3(N / 64, 3), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -599,7 +610,7 @@ inline hipError_t launch_nonlocal_grad(const float* blob, const float* y3x, int 
   }
   if (stop_after <= done++) return hipSuccess;
   {
-    NlTnArgs a{X, dproj, part1, kNlCp, kNlCp, kNlQ, kNlQ, kNlTnMp, N / 128, pl.P};
+    NlTnArgs a{y3, dproj, part1, kNlCp, kNlCp, kNlQ, kNlQ, kNlTnMp, N / 128, pl.P};
     hipLaunchKernelGGL(nl_tn_kernel, dim3(pl.P, kNlTnMp / 64, 3), dim3(256), 0, stream, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }

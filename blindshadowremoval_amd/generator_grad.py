@@ -28,7 +28,8 @@ import numpy as np
 
 from .discriminator import conv2d_same_dgrad, leaky_grad
 from .weights import (BN_EPS, LRELU_ALPHA, RES_CH, generator_bottleneck_trainable_names, generator_colour_trunk_trainable_names, generator_decoder_trainable_names,
-                      generator_grey_decoder_trainable_names, generator_heads_trainable_names, generator_nonlocal_trainable_names, generator_tail_trainable_names)
+                      generator_grey_decoder_trainable_names, generator_heads_trainable_names, generator_lower_trunk_trainable_names,
+                      generator_nonlocal_trainable_names, generator_tail_trainable_names)
 
 TAIL_LAYERS = ("clr_conv1", "clr_conv2", "clr_conv3")
 TAIL_NORM_NAMES = ("d_f", "d_gs") + tuple(generator_tail_trainable_names())
@@ -397,8 +398,9 @@ def nonlocal_bn_vectors(weights: Dict[str, np.ndarray], block: int = 5, dtype=np
 
 
 def nonlocal_forward(weights: Dict[str, np.ndarray], y3, xin, block: int = 5, dtype=np.float64) -> Dict[str, np.ndarray]:
-    """y3 [B,h,w,257] (bnorm3's output), xin [B,h,w,C] (the block's input, C >= 257) -> dict(theta, phi, g, A [B,T,128], c [B,T,257],
-    z [B,h,w,257], out [B,h,w,C]) in `dtype`, T = h w tokens per image, X = y3 as [B,T,257]:
+    """y3 [B,h,w,257] (bnorm3's output), xin [B,h,w,C] (the block's input) -> dict(theta, phi, g, A [B,T,128], c [B,T,257],
+    z [B,h,w,257], out [B,h,w,max(C, 257)]) in `dtype`, T = h w tokens per image, X = y3 as [B,T,257].  A skip narrower than the block
+    (res_stack/0: C = 99) reaches the first C channels: out = lrelu_0.3(z + pad_257(xin)).
       theta = X Wt + bt, phi = X Wp + bp, g = X Wg + bg;  S = theta phi^T, P = softmax_rows(S) per image with the row maximum subtracted;
       A = P g;  c = A Ww + bw;  z = X + ((c - mean) rstd gamma + beta);  out = lrelu_0.3(pad_C(z) + xin)."""
     T = dtype
@@ -418,8 +420,12 @@ def nonlocal_forward(weights: Dict[str, np.ndarray], y3, xin, block: int = 5, dt
     bw, _, mean, rstd, gamma, beta = nonlocal_bn_vectors(weights, block, T)
     c = A @ np.asarray(weights[st + "w/kernel"], T)[0, 0] + bw
     z = (X + ((c - mean) * rstd * gamma + beta)).reshape(B, h, w, n)
-    s = xin.copy()
-    s[..., :n] += z
+    if C >= n:
+        s = xin.copy()
+        s[..., :n] += z
+    else:
+        s = z.copy()
+        s[..., :C] += xin
     out = dict(proj)
     out.update({"S": S, "P": P, "A": A, "c": c, "z": z, "pre": s, "out": _lrelu(s)})
     return out
@@ -427,9 +433,9 @@ def nonlocal_forward(weights: Dict[str, np.ndarray], y3, xin, block: int = 5, dt
 
 def nonlocal_grad(weights: Dict[str, np.ndarray], y3, xin, d_out, block: int = 5, acts: Optional[Dict[str, np.ndarray]] = None,
                   dtype=np.float64) -> Dict[str, np.ndarray]:
-    """The gradient d_out [B,h,w,C] at res_stack/<block>'s output -> dict(the ten variables of
+    """The gradient d_out [B,h,w,max(C, 257)] at res_stack/<block>'s output -> dict(the ten variables of
     weights.generator_nonlocal_trainable_names(block) in their own shapes, `d_y3` [B,h,w,257] at bnorm3's output, `d_skip` [B,h,w,C] the
-    gradient the skip carries to the block's input, the stage maps `gz` [B,h,w,C], `dA`, `d_theta`, `d_phi`, `d_g` [B,T,128], `D` [B,T],
+    gradient the skip carries to the block's input (gz[..., :C]: all of gz for C >= 257), the stage maps `gz` [B,h,w,max(C, 257)], `dA`, `d_theta`, `d_phi`, `d_g` [B,T,128], `D` [B,T],
     and `out`, `A` as used), float64 from the float32 variables (`dtype` float32 runs the same arithmetic in float32: the error model of
     the device's hard-softmax bound).  In this order:
       gz = leaky_grad(d_out, out) (an activation of exactly +-0 takes the slope);  d_skip = gz;  dz = gz[..., :257];  Sz = sum dz
@@ -451,7 +457,7 @@ def nonlocal_grad(weights: Dict[str, np.ndarray], y3, xin, d_out, block: int = 5
     Wt, Wp, Wg, Ww = (np.asarray(weights[st + k + "/kernel"], T)[0, 0] for k in ("theta", "phi", "g", "w"))
     bw, inv, mean, rstd, _, _ = nonlocal_bn_vectors(weights, block, T)
     gz = leaky_grad(np.asarray(d_out, T), out_a).astype(T)
-    res: Dict[str, np.ndarray] = {"out": out_a, "A": A, "gz": gz, "d_skip": gz.copy()}
+    res: Dict[str, np.ndarray] = {"out": out_a, "A": A, "gz": gz, "d_skip": gz[..., :np.shape(xin)[3]].copy()}
     dz = gz[..., :n].reshape(B, h * w, n)
     Sz = dz.sum(axis=(0, 1))
     Wgd = np.tensordot(A, dz, axes=([0, 1], [0, 1]))
@@ -826,3 +832,77 @@ def colour_trunk_example_inputs(h: int, w: int, B: int, seed: int = 0, weights: 
         return x, bmask, uv, d_xin5, d_x
     fw = trunk_forward(weights, x, bmask, uv)
     return (x, bmask, uv, d_xin5, d_x) + tuple(fw[k].astype(np.float32) for k in ("xh", "y3_3", "res3", "y3_4", "res4"))
+
+
+# ---- res_stack/2, res_stack/1 and res_stack/0: from the complete gradient at res_stack/2's output to the gradient at the trunk's input
+LOWER_TRUNK_BLOCKS = (2, 1, 0)           # in the backward's order
+LOWER_TRUNK_NORM_NAMES = ("d_x0",) + tuple(generator_lower_trunk_trainable_names())
+LOWER_TRUNK_DATA = ("d_y3_2", "d_skip_2", "d_xin2", "d_y3_1", "d_skip_1", "d_xin1", "d_y3_0", "d_skip_0")
+X0_CH = 99                               # x0 = cat[down3's output 96 | the resized uv 3]
+
+
+def lower_trunk_forward(weights: Dict[str, np.ndarray], x0, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """x0 [B,h,w,99] = cat[down3's output 96 | the resized uv 3] -> dict(per block b = 0, 1, 2 `y3_<b>` [B,h,w,257] (bnorm3's output),
+    `res<b>` [B,h,w,257] (the block's output), the bottleneck's `a1_<b>`, `a2_<b>` [B,h,w,128] and `pre_<b>` (relu3's input)) in `dtype`:
+    bottleneck_forward and nonlocal_forward of block 0 on x0, whose skip reaches the first 99 output channels, of block 1 on res0 and of
+    block 2 on res1 (model.py Generator.call: for i in range(n_res // 2))."""
+    T = dtype
+    out: Dict[str, np.ndarray] = {}
+    xin = np.asarray(x0, T)
+    for b in (0, 1, 2):
+        bf = bottleneck_forward(weights, xin, b, T)
+        nf = nonlocal_forward(weights, bf["y3"], xin, b, T)
+        out.update({"y3_%d" % b: bf["y3"], "res%d" % b: nf["out"], "a1_%d" % b: bf["a1"], "a2_%d" % b: bf["a2"], "pre_%d" % b: nf["pre"]})
+        xin = nf["out"]
+    return out
+
+
+def lower_trunk_grad(weights: Dict[str, np.ndarray], x0, y3_0, res0, y3_1, res1, y3_2, res2, d_res2,
+                     acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """The complete gradient d_res2 [B,h,w,257] at res_stack/2's output (colour_trunk_grad's d_res2) -> dict(`d_x0` [B,h,w,99] the
+    gradient at x0 — channels 0..95 at down3's output; 96..98 belong to the resized uv, an input, and reach nothing — the 66 variables of
+    weights.generator_lower_trunk_trainable_names() under their own blocks' names, the intermediate data gradients `d_xin2`, `d_xin1`
+    [B,h,w,257], `d_y3_<b>` [B,h,w,257] and `d_skip_<b>` ([B,h,w,257]; block 0's [B,h,w,99]) per block, and `a1_<b>`, `a2_<b>` as used),
+    float64 from the float32 variables.  The statements above chained, for block 2 on (y3_2, res1, res2), block 1 on (y3_1, res0, res1)
+    and block 0 on (y3_0, x0, res0):
+      nonlocal_grad(y3, xin, d_out, block=b, acts={"out": out_b}) -> d_y3, d_skip;  bottleneck_grad(xin, d_y3, d_skip, block=b) -> d_xin
+    with each block's d_xin as the next block's d_out.  `acts` carries `a1_<b>`, `a2_<b>` (for example the device's): the bottlenecks'
+    masks and kernel-gradient inputs are read from them."""
+    res: Dict[str, np.ndarray] = {}
+    d_out = d_res2
+    for b, y3, xin, out in ((2, y3_2, res1, res2), (1, y3_1, res0, res1), (0, y3_0, x0, res0)):
+        n = nonlocal_grad(weights, y3, xin, d_out, block=b, acts={"out": out})
+        a = None if acts is None else {"a1": acts["a1_%d" % b], "a2": acts["a2_%d" % b]}
+        t = bottleneck_grad(weights, xin, n["d_y3"], n["d_skip"], block=b, acts=a)
+        res.update((name, n[name]) for name in generator_nonlocal_trainable_names(b))
+        res.update((name, t[name]) for name in generator_bottleneck_trainable_names(b))
+        res.update({"d_y3_%d" % b: n["d_y3"], "d_skip_%d" % b: n["d_skip"], "a1_%d" % b: t["a1"], "a2_%d" % b: t["a2"],
+                    ("d_xin%d" % b) if b else "d_x0": t["d_xin"]})
+        d_out = t["d_xin"]
+    return res
+
+
+def lower_trunk_objective_f64(weights: Dict[str, np.ndarray], x0, d_res2, masks: Optional[list] = None, dtype=np.float64):
+    """<d_res2, res2> in `dtype` with no float32 rounding anywhere: the scalar whose gradient with respect to x0 and the 66 variables
+    lower_trunk_grad states.  A list given as `masks` receives the nine LeakyReLU masks (z > 0) of blocks 0, 1 and 2: a1, a2 and relu3's."""
+    fw = lower_trunk_forward(weights, x0, dtype)
+    if masks is not None:
+        masks += [fw[k % b] > 0 for b in (0, 1, 2) for k in ("a1_%d", "a2_%d", "pre_%d")]
+    return (np.asarray(d_res2, dtype) * fw["res2"]).sum()
+
+
+lower_trunk_norms = functools.partial(grad_norms, names=LOWER_TRUNK_NORM_NAMES)   # of `d_x0` and each of the 66 variable gradients
+
+
+def lower_trunk_example_inputs(h: int, w: int, B: int, seed: int = 0, weights: Optional[Dict[str, np.ndarray]] = None):
+    """Seeded (x0 [B,h,w,99]: 96 channels like a LeakyReLU output and 3 uniform like uv; d_res2 [B,h,w,257]) float32 at a coarse grid;
+    with `weights`, followed by (y3_0, res0, y3_1, res1, y3_2, res2): lower_trunk_forward's on x0 in float64, rounded to float32."""
+    rng = np.random.default_rng(7000 + seed)
+    x = rng.standard_normal((B, h, w, X0_CH - 3)).astype(np.float32)
+    x = np.where(x >= 0, x, np.float32(LRELU_ALPHA) * x).astype(np.float32)
+    x0 = np.concatenate([x, rng.uniform(0.0, 1.0, (B, h, w, 3)).astype(np.float32)], axis=3)
+    d_res2 = (rng.standard_normal((B, h, w, RES_CH)) / (B * h * w * RES_CH)).astype(np.float32)
+    if weights is None:
+        return x0, d_res2
+    fw = lower_trunk_forward(weights, x0)
+    return (x0, d_res2) + tuple(fw[k].astype(np.float32) for k in ("y3_0", "res0", "y3_1", "res1", "y3_2", "res2"))

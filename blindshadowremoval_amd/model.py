@@ -272,6 +272,16 @@ class Generator:
         (y3, xh, o3), (y3_cs, xh_cs, o3_cs), _ = self.last_block(3)
         return (y4, o4, y3, o3, xh), (y4_cs, o4_cs, y3_cs, o3_cs, xh_cs), shape
 
+    def last_lower_trunk(self) -> Tuple[Tuple[int, ...], Tuple[int, ...], Tuple[int, int, int, int]]:
+        """((y3x2, out2, y3x1, out1, y3x0, out0, x0) device addresses, their floats between pixels, (B, H/8, W/8, 257)) of what the last
+        forward kept of res_stack/2, /1 and /0 in the handle's workspace (bsr_last_lower_trunk): block 2's input is out1, block 1's is
+        out0, block 0's is x0 = cat[down3's output 96 | the resized uv 3].  No copy; valid until the next forward on this generator.
+        Under last_block5's conditions."""
+        self._require_weights()
+        ptrs, strides, shape = (ctypes.c_void_p * 7)(), (ctypes.c_int * 7)(), (ctypes.c_int * 4)()
+        _lib.check(self._lib.bsr_last_lower_trunk(self._handle, ctypes.byref(ptrs), ctypes.byref(strides), ctypes.byref(shape)), "bsr_last_lower_trunk")
+        return tuple(int(p or 0) for p in ptrs), tuple(int(s) for s in strides), (shape[0], shape[1], shape[2], shape[3])
+
     def last_y(self) -> Tuple[int, int, Tuple[int, int, int, int]]:
         """(y's device address, its floats between pixels, (B, H, W, 64)) of the last forward's y, up3's output and the grey heads' input,
         in the handle's workspace (bsr_last_y): no copy; valid until the next forward on this generator.  Under last_f's conditions."""

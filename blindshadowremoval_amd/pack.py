@@ -961,38 +961,53 @@ def unpack_nonlocal_grad(blob: bytes) -> Dict[str, np.ndarray]:
 # ---- the generator's bottleneck backward (csrc/bottleneck_grad_kernels.h): a blob of its own, no header, float32 ----
 BOTTLENECK_TSM_TEXT = "the bottleneck's device chain takes the GSC width only (TSM's 877 is covered by generator_grad.bottleneck_grad)"
 BOTTLENECK_BLOCK_TEXT = "block must be 3, 4 or 5 (the colour branch's blocks share their shapes), got %r"
+BOTTLENECK_WIDTH = 261       # conv1's input width in blocks 3..5
+LOWER_TRUNK_WIDTHS = {0: 99, 1: 257, 2: 257}          # conv1's input width in the blocks below the hole
+LOWER_TRUNK_TEXT = ("the lower trunk's device chain takes the GSC widths only: res_stack/%d/conv1/kernel must be [1,1,%d,128], got %s (TSM's blocks "
+                    "0..2 are 291 wide, the RGB baseline's 513)")
 
 
-def bottleneck_grad_layout():
-    """([(name, offset in floats, shape)], floats) of the bottleneck's gradient blob, d = 128, taps in row-major order t = 3 a + b:
-      w1f   [272][128]     the BN-folded FORWARD image of conv1: w1f[c][k] = W1[c][k] inv1[k] (rows 261..271 zero)
+def _pad_to(n: int, step: int) -> int:
+    return (n + step - 1) // step * step
+
+
+def bottleneck_grad_layout(width: int = BOTTLENECK_WIDTH):
+    """([(name, offset in floats, shape)], floats) of the bottleneck's gradient blob, d = 128, taps in row-major order t = 3 a + b, for a
+    block whose input is `width` channels wide (261; 257 and 99 for the blocks below the hole), xp = width rounded up to 16, w1t's
+    columns = width rounded up to 128:
+      w1f   [xp][128]      the BN-folded FORWARD image of conv1: w1f[c][k] = W1[c][k] inv1[k] (rows width.. zero; [272][128] at 261)
       b1f   [128]          (b1 - mean1) inv1 + beta1
       w2f   [9][128][128]  the folded forward image of conv2: w2f[t][c][o] = K2[a][b][c][o] inv2[o]
       b2f   [128]          (b2 - mean2) inv2 + beta2
       w3t   [272][128]     conv3 for the data gradient: w3t[n][k] = inv3[n] W3[k][n] (rows 257..271 zero)
       w2t   [9][128][128]  conv2 for the data gradient, taps turned by 180 degrees, channel roles swapped:
                            w2t[t][o][c] = inv2[o] K2[2 - a][2 - b][c][o]
-      w1t   [128][384]     conv1 for the data gradient: w1t[k][c] = inv1[k] W1[c][k] (columns 261.. zero)
-      k1    [261][128], k2 [9][128][128], k3 [128][257]   the three kernels in the variables' own order (d gamma is formed from them)
+      w1t   [128][..]      conv1 for the data gradient: w1t[k][c] = inv1[k] W1[c][k] (columns width.. zero; [128][384] at 261)
+      k1    [width][128], k2 [9][128][128], k3 [128][257]   the three kernels in the variables' own order (d gamma is formed from them)
       vecs1 [4][128], vecs2 [4][128], vecs3 [4][257]      per layer: bias, inv, moving_mean, rstd
     inv, rstd and every folded image are formed in float64 and rounded once."""
     out, off = [], 0
-    for name, shape in (("w1f", (NONLOCAL_CP, 128)), ("b1f", (128,)), ("w2f", (9, 128, 128)), ("b2f", (128,)), ("w3t", (NONLOCAL_CP, 128)),
-                        ("w2t", (9, 128, 128)), ("w1t", (128, 384)), ("k1", (261, 128)), ("k2", (9, 128, 128)), ("k3", (128, 257)),
+    for name, shape in (("w1f", (_pad_to(width, 16), 128)), ("b1f", (128,)), ("w2f", (9, 128, 128)), ("b2f", (128,)), ("w3t", (NONLOCAL_CP, 128)),
+                        ("w2t", (9, 128, 128)), ("w1t", (128, _pad_to(width, 128))), ("k1", (width, 128)), ("k2", (9, 128, 128)), ("k3", (128, 257)),
                         ("vecs1", (4, 128)), ("vecs2", (4, 128)), ("vecs3", (4, 257))):
         out.append((name, off, shape))
         off += int(np.prod(shape))
     return out, off
 
 
-def bottleneck_grad_record(weights: Dict[str, np.ndarray], block: int = 5) -> Dict[str, np.ndarray]:
-    """name -> float32 array of bottleneck_grad_layout's shapes.  ValueError for shapes other than the GSC generator's."""
-    from .weights import BN_EPS
+def bottleneck_grad_record(weights: Dict[str, np.ndarray], block: int = 5, width: int = BOTTLENECK_WIDTH) -> Dict[str, np.ndarray]:
+    """name -> float32 array of bottleneck_grad_layout's shapes.  ValueError for shapes other than the GSC generator's, and for a block
+    outside 3..5 (lower_trunk_bottleneck_record is the blocks below the hole's)."""
     if block not in (3, 4, 5):
         raise ValueError(BOTTLENECK_BLOCK_TEXT % (block,))
+    return _bottleneck_record(weights, block, width)
+
+
+def _bottleneck_record(weights: Dict[str, np.ndarray], block: int, width: int) -> Dict[str, np.ndarray]:
+    from .weights import BN_EPS
     st = "res_stack/%d/" % block
     k = {}
-    for j, shape in ((1, (1, 1, 261, 128)), (2, (3, 3, 128, 128)), (3, (1, 1, 128, 257))):
+    for j, shape in ((1, (1, 1, width, 128)), (2, (3, 3, 128, 128)), (3, (1, 1, 128, 257))):
         k[j] = np.asarray(weights[st + "conv%d/kernel" % j], np.float64)
         if k[j].shape != shape:
             raise ValueError("%sconv%d/kernel must be %s, got %s" % (st, j, list(shape), k[j].shape))
@@ -1005,12 +1020,12 @@ def bottleneck_grad_record(weights: Dict[str, np.ndarray], block: int = 5) -> Di
         vec[j] = (bias, gamma * rstd, mean, rstd, beta)
     inv1, inv2, inv3 = vec[1][1], vec[2][1], vec[3][1]
     w1, w2, w3 = k[1][0, 0], k[2].reshape(9, 128, 128), k[3][0, 0]
-    w1f = np.zeros((NONLOCAL_CP, 128), np.float64)
-    w1f[:261] = w1 * inv1[None, :]
+    w1f = np.zeros((_pad_to(width, 16), 128), np.float64)
+    w1f[:width] = w1 * inv1[None, :]
     w3t = np.zeros((NONLOCAL_CP, 128), np.float64)
     w3t[:257] = (w3 * inv3[None, :]).T
-    w1t = np.zeros((128, 384), np.float64)
-    w1t[:, :261] = (w1 * inv1[None, :]).T
+    w1t = np.zeros((128, _pad_to(width, 128)), np.float64)
+    w1t[:, :width] = (w1 * inv1[None, :]).T
     w2f = w2 * inv2[None, None, :]
     rec = {"w1f": w1f, "b1f": (vec[1][0] - vec[1][2]) * inv1 + vec[1][4], "w2f": w2f, "b2f": (vec[2][0] - vec[2][2]) * inv2 + vec[2][4],
            "w3t": w3t, "w2t": np.transpose(w2f[::-1], (0, 2, 1)), "w1t": w1t, "k1": w1, "k2": w2, "k3": w3}
@@ -1026,8 +1041,11 @@ def pack_bottleneck_grad(weights: Dict[str, np.ndarray], block: int = 5) -> byte
         raise ValueError(BOTTLENECK_BLOCK_TEXT % (block,))
     if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, 261, 128):
         raise ValueError(BOTTLENECK_TSM_TEXT)
-    layout, total = bottleneck_grad_layout()
-    rec = bottleneck_grad_record(weights, block)
+    return _join_record(bottleneck_grad_layout(), bottleneck_grad_record(weights, block))
+
+
+def _join_record(layout_total, rec: Dict[str, np.ndarray]) -> bytes:
+    layout, total = layout_total
     blob = np.zeros(total, np.float32)
     for name, off, shape in layout:
         assert rec[name].shape == tuple(shape), name
@@ -1035,9 +1053,10 @@ def pack_bottleneck_grad(weights: Dict[str, np.ndarray], block: int = 5) -> byte
     return blob.tobytes()
 
 
-def unpack_bottleneck_grad(blob: bytes) -> Dict[str, np.ndarray]:
-    """The inverse of pack_bottleneck_grad: bottleneck_grad_record's dict."""
-    layout, total = bottleneck_grad_layout()
+def unpack_bottleneck_grad(blob: bytes, width: int = BOTTLENECK_WIDTH) -> Dict[str, np.ndarray]:
+    """The inverse of pack_bottleneck_grad (and, at a block's `width`, of one bottleneck part of pack_lower_trunk_grad):
+    bottleneck_grad_record's dict."""
+    layout, total = bottleneck_grad_layout(width)
     arr = np.frombuffer(blob, np.float32)
     if arr.size != total:
         raise ValueError("a bottleneck gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
@@ -1049,6 +1068,52 @@ def pack_colour_trunk_grad(weights: Dict[str, np.ndarray]) -> bytes:
     """The generator's variables (res_stack/4's and res_stack/3's are read) -> the blob bsr_colour_trunk_grad takes: pack_nonlocal_grad and
     pack_bottleneck_grad of block 4, then of block 3, in the order of the chain's launches.  ValueError (NONLOCAL_TSM_TEXT) for TSM weights."""
     return b"".join(pack(weights, block) for block in (4, 3) for pack in (pack_nonlocal_grad, pack_bottleneck_grad))
+
+
+# ---- the backward of res_stack/2, /1 and /0 (csrc/lower_trunk_grad_kernels.h): six blobs end to end, the bottlenecks' at their own widths ----
+def lower_trunk_bottleneck_record(weights: Dict[str, np.ndarray], block: int) -> Dict[str, np.ndarray]:
+    """bottleneck_grad_record for block 0, 1 or 2, at the block's own input width (LOWER_TRUNK_WIDTHS).  ValueError (LOWER_TRUNK_TEXT)
+    for TSM and RGB weights."""
+    width = LOWER_TRUNK_WIDTHS[block]
+    shape = tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block]))
+    if shape != (1, 1, width, 128):
+        raise ValueError(LOWER_TRUNK_TEXT % (block, width, shape))
+    return _bottleneck_record(weights, block, width)
+
+
+def lower_trunk_grad_parts():
+    """[(kind, block, floats)] of pack_lower_trunk_grad's six parts in the order of the chain's launches: ("nl", 2), ("bn", 2), ("nl", 1),
+    ("bn", 1), ("nl", 0), ("bn", 0).  Every part is a multiple of four floats."""
+    return [(kind, b, nonlocal_grad_layout()[1] if kind == "nl" else bottleneck_grad_layout(LOWER_TRUNK_WIDTHS[b])[1])
+            for b in (2, 1, 0) for kind in ("nl", "bn")]
+
+
+def pack_lower_trunk_grad(weights: Dict[str, np.ndarray]) -> bytes:
+    """The generator's variables (res_stack/0's, /1's and /2's are read) -> the blob bsr_lower_trunk_grad takes: per block 2, 1, 0 the
+    non-local blob (nonlocal_grad_layout: it does not carry the input's width) and the bottleneck blob at the block's width (257, 257, 99).
+    ValueError (LOWER_TRUNK_TEXT) for TSM and RGB weights, whose blocks 0..2 are 291 and 513 wide."""
+    parts = []
+    for b in (2, 1, 0):
+        bn = lower_trunk_bottleneck_record(weights, b)      # the width check comes first
+        parts.append(_join_record(nonlocal_grad_layout(), nonlocal_grad_record(weights, b)))
+        parts.append(_join_record(bottleneck_grad_layout(LOWER_TRUNK_WIDTHS[b]), bn))
+    return b"".join(parts)
+
+
+def unpack_lower_trunk_grad(blob: bytes) -> Dict[str, np.ndarray]:
+    """The inverse of pack_lower_trunk_grad: "nl<b>.<name>" -> nonlocal_grad_record's arrays and "bn<b>.<name>" -> bottleneck_grad_record's
+    at block b's width, b = 0, 1, 2."""
+    parts = lower_trunk_grad_parts()
+    total = sum(n for _, _, n in parts)
+    if len(blob) != 4 * total:
+        raise ValueError("a lower trunk gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
+    out, at = {}, 0
+    for kind, b, n in parts:
+        part = blob[4 * at:4 * (at + n)]
+        rec = unpack_nonlocal_grad(part) if kind == "nl" else unpack_bottleneck_grad(part, LOWER_TRUNK_WIDTHS[b])
+        out.update(("%s%d.%s" % (kind, b, name), a) for name, a in rec.items())
+        at += n
+    return out
 
 
 # ---- the generator's grey heads' backward (csrc/heads_grad_kernels.h): a blob of its own, no header, float32 ----

@@ -163,6 +163,13 @@ def generator_colour_trunk_trainable_names() -> List[str]:
     return [n for n in generator_variable_shapes() if n.startswith(("res_stack/3/", "res_stack/4/")) and not n.rsplit("/", 1)[1].startswith("moving_")]
 
 
+def generator_lower_trunk_trainable_names() -> List[str]:
+    """The 66 trainable variables of res_stack/0, res_stack/1 and res_stack/2, the blocks below the hole, block 0 first: per block the
+    twelve of generator_bottleneck_trainable_names, then the ten of generator_nonlocal_trainable_names (block 0's conv1 is 99 -> 128, the
+    others' 257 -> 128); moving_mean and moving_variance take no gradient."""
+    return [n for b in (0, 1, 2) for names in (generator_bottleneck_trainable_names, generator_nonlocal_trainable_names) for n in names(b)]
+
+
 def generator_heads_trainable_names(variant: str = "gsc") -> List[str]:
     """The four trainable variables of the generator's grey heads in generator_variable_shapes' order, 6 274 floats: the kernel
     [7,7,64,1] and bias of conv2 ('tconv3', the mask head) and of conv3 ('tconv4', the con head).  GSC and TSM share them; the RGB

@@ -132,6 +132,13 @@ int bsr_last_block5(bsr_handle* h, const float** y3x, int* y3x_cs, const float**
  * every block's y3x and output, and xh, a slot of its own, on the fused-attention route and on the separate-launch route, so nothing
  * after the block overwrites them.  The rules and error codes of bsr_last_block5; any other block gives BSR_ERR_ARG.  Added under ABI 8. */
 int bsr_last_block(bsr_handle* h, int block, const float** y3x, int* y3x_cs, const float** xin, const float** out, int* x_cs, int shape4[4]);
+/* What the last forward kept of res_stack/2, /1 and /0, the blocks below the hole, in place: tensors7 = y3x and the output of block 2,
+ * of block 1, of block 0, then xa = cat[down3's output 96 | the resized uv 3], block 0's input; strides7 their floats between pixels
+ * (288, 264, 288, 264, 288, 264, 120 on a GSC handle); shape4 = [B,H/8,W/8,257].  Block 2's input is block 1's output and block 1's is
+ * block 0's.  Every one lies in a slot of its own that nothing after its block overwrites; xa's lanes past channel 98 and the outputs'
+ * past 256 are the forward's padding.  The rules and error codes of bsr_last_block5.  bsr_last_block keeps refusing blocks other than
+ * 3, 4 and 5: their tensors are 261 wide, these 257.  Added under ABI 8. */
+int bsr_last_lower_trunk(bsr_handle* h, const float* tensors7[7], int strides7[7], int shape4[4]);
 
 /* Per-kernel-class device time (ms) of the last forward run with timing enabled; classes are indexed
  * 0: conv3x3 (+stride-2), 1: transposed 3x3 (all but class 6), 2: conv1x1, 3: attention, 4: conv7 (stem + heads), 5: glue,
@@ -484,6 +491,40 @@ int bsr_debug_colour_trunk_grad(int device, const void* d_blob, size_t blob_byte
  * d_xin3[..., :257] (1 - xh[..., 257]) + d_x with d_xin3 dense [B,h,w,261], d_x dense [B,h,w,257] or null, d_res2 dense [B,h,w,257], the
  * three 16-byte aligned, and xh_cs >= 258 floats between xh's pixels.  The size rule and error codes of bsr_colour_trunk_grad. */
 int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_xin3, const float* d_x, int B, int h, int w, float* d_res2, void* stream);
+
+/* The backward of the generator between res_stack/2's output and the trunk's input (training=False, fp32, GSC width; the reference's
+ * model.py Generator.call: x = cat[down3 96 | uv 3], then res_stack/0, /1, /2): the three blocks both branches share.  d_blob:
+ * bsr_lower_trunk_grad_blob_bytes() bytes of pack.pack_lower_trunk_grad, six blobs end to end in the order of the launches (block 2's
+ * non-local and bottleneck blobs, block 1's, block 0's; the bottleneck blobs at the widths 257, 257 and 99 of the blocks' inputs), each a
+ * multiple of 16 bytes, 16-byte aligned.  Inputs as bsr_last_lower_trunk hands them out (or dense tensors): y3x<b>, out<b> of blocks 2,
+ * 1, 0 with at least 257 floats between pixels and x0 = cat[down3's output | uv] with x0_cs >= 99; channels of x0 past 98 are never
+ * read.  d_res2 dense [B,h,w,257] = d loss / d (res_stack/2's output) (bsr_colour_trunk_grad's d_res2), never written.  Outputs: d_x0
+ * dense [B,h,w,99], the gradient at x0 (channels 0..95 at down3's output; 96..98 belong to uv, an input); and grads,
+ * bsr_lower_trunk_grad_floats() = 1022354 float32: the 66 variables of weights.generator_lower_trunk_trainable_names() in that order
+ * (block 0's twelve bottleneck variables, its ten non-local ones, then block 1's, then block 2's), variable `index` (0..65) at float
+ * offset bsr_lower_trunk_grad_var_offset(index); SIZE_MAX out of range.  72 launches on `stream`, one after the other
+ * (csrc/lower_trunk_grad_kernels.h): bsr_nonlocal_grad's twelve and bsr_bottleneck_grad's twelve per block at the block's input width
+ * (block 0: K = 112 for conv1, two row tiles for its kernel gradient, one column tile for its data gradient); no host synchronisation,
+ * no floating-point atomics: a call repeats its bits.  scratch: bsr_lower_trunk_grad_scratch_bytes(B, h, w) bytes, 256-byte aligned;
+ * every word read is written earlier in the same call; each of the six sub-chains has a region of its own.
+ * bsr_lower_trunk_grad_offset(B, h, w, map) is the byte offset of map 0..9 bsr_nonlocal_grad_offset's maps of block 2, 10..17
+ * bsr_bottleneck_grad_offset's of block 2, 18..35 the same of block 1, 36..53 of block 0 (its xp [N][112], its Wg [99 x 128 | ..]),
+ * 54 d_y3 [N][257], 55 d_skip [N][257], 56 d_xin [N][257] of block 2, 57..59 of block 1, 60 d_y3 [N][257] and 61 d_skip [N][99] of
+ * block 0; SIZE_MAX out of range.  A bad argument gives BSR_ERR_ARG with a message and nothing launched.  bsr_debug_lower_trunk_grad
+ * stops after `stop_after` (0..72) of the launches, one running count across the sub-chains.  ADDITIONS under ABI 8:
+ * bsr_abi_version() stays 8. */
+size_t bsr_lower_trunk_grad_blob_bytes(void);
+size_t bsr_lower_trunk_grad_scratch_bytes(int B, int h, int w);
+size_t bsr_lower_trunk_grad_floats(void);
+size_t bsr_lower_trunk_grad_var_offset(int index);
+size_t bsr_lower_trunk_grad_offset(int B, int h, int w, int map);
+int bsr_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,
+                         const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0, int out0_cs,
+                         const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads, void* scratch, void* stream);
+int bsr_debug_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,
+                               const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0,
+                               int out0_cs, const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads,
+                               void* scratch, int stop_after, void* stream);
 
 /* The backward of the generator's grey heads (training=False, fp32; the reference's model.py:246-250): conv2 (7x7, 64 -> 1, tanh) gives
  * mask, conv3 (7x7, 64 -> 1) gives con, gs = gray(inputs) (1 + mask) + con.  d_blob: bsr_heads_grad_blob_bytes() bytes of
