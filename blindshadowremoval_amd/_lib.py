@@ -52,6 +52,8 @@ SIGNATURES = {
     "bsr_debug_wino_filter": (c_i, [c_v, c_v]),
     "bsr_debug_wino_convt": (c_i, [c_v, c_v, c_v, c_v, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_v]),
     "bsr_debug_wino_convt_filter": (c_i, [c_v, c_v, c_i]),
+    "bsr_debug_wino_clr": (c_i, [c_v, c_v, c_i, c_v, c_v, c_v, c_v, c_v, c_v, c_v, c_v, c_i, c_i, c_i, c_i, c_v]),
+    "bsr_debug_wino_clr_filter": (c_i, [c_v, c_v, c_v]),
     "bsr_debug_keys_compose": (c_i, [c_v, c_v, c_v, c_v]),
     "bsr_debug_values_compose": (c_i, [c_v, c_v, c_v, c_v, c_v, c_v]),
     "bsr_prep_rows": (c_i, [c_i, c_v, c_sz, c_sz, c_sz, c_i, c_i, c_v, c_v, c_v]),

@@ -35,6 +35,7 @@
 #include "sfw_kernels.h"
 #include "wino_conv2.h"
 #include "wino_convt.h"
+#include "wino_clr.h"
 #include "wild_crop_kernels.h"
 #include "wild_paste_kernels.h"
 #include "shadow_synth_kernels.h"
@@ -237,6 +238,7 @@ struct bsr_handle {
   float* d_blob = nullptr;
   float* d_wino = nullptr;       // fp32 GSC / TSM handles: the Winograd weight streams of res0..5.conv2 (wino_conv2.h), derived from the blob's direct images at bsr_create
   float* d_winot = nullptr;      // fp32 GSC handles: the 25-position weight streams of up2, up3 and clr_up3 (wino_convt.h), derived from the blob's direct images at bsr_create
+  float* d_wclr = nullptr;       // fp32 GSC / TSM handles: clr_conv1's Winograd image U (wino_clr.h), derived from the blob's direct images ('clr_conv1', 'clr_conv1.gs') at bsr_create
   float* d_keys = nullptr;       // fp32 GSC / TSM handles: the res0..5.c3q images with theta composed onto phi, N = [y3 | q' | g] (keys_compose), derived from the blob's at bsr_create
   float* d_values = nullptr;     // fp32 GSC / TSM handles: per block the `w` image with g composed onto it, the c3q image of N = [y3 | q'] and the g image the att<i> probe
                                  // applies (values_compose), derived from the blob's at bsr_create
@@ -272,6 +274,8 @@ struct bsr_handle {
                                  // (A/B measurements, the bit-identity test of the two shapes in a whole forward)
   bool wino_convt = true;        // env BSR_WINO_CONVT=0: the fp32 GSC up2 / up3 / clr_up3 on the direct implicit-GEMM kernel instead of the 25-product form of wino_convt.h
                                  // (A/B measurements, the two-forms test)
+  bool wino_clr = true;          // env BSR_WINO_CLR=0: the fp32 colour tail (clr_conv1 + clr_conv2 + clr_conv3 + dif) on the direct conv_n16_kernel instead of the Winograd
+                                 // F(2x2, 3x3) form of wino_clr.h (A/B measurements, the two-forms test)
   bool keys_conv2 = true;        // env BSR_KEYS_CONV2=0: the fp32 attention with phi projected by res*.c3q (N = 672, conv2's output in a buffer of its own) instead of conv2's
                                  // output as the keys (A/B measurements, the two-forms test)
   bool values_conv2 = true;      // env BSR_VALUES_CONV2=0 (read only while keys_conv2 is on): g projected by res*.c3q (N = 544) and the attention on [q' | t2 | g] rows instead
@@ -340,6 +344,34 @@ void wino_convt_filter_transform(const float* direct, float* out, int cin) {
           double acc = 0.0;
           for (int b = 0; b < 3; ++b) acc += t[x][b] * G[y][b];
           out[(((((size_t)(k / 16) * 25 + 5 * x + y) * 2 + n / 32) * 2 + g) * 64 + 32 * hh + n % 32) * 4 + j] = (float)acc;
+        }
+    }
+}
+
+// The Winograd F(2x2, 3x3) filter transform U = G g G^T of clr_conv1 (wino_clr.h), in float64, rounded once: the layer's direct image
+// [2 chunks][9 taps (a, b)][16 cout][32 + 4 channels] and the gs channel's [16 cout][16 taps, 9 used] -> [16 positions 4 xi + nu][4 K groups g]
+// [64 lanes 16 q + r][4 j] = channel 16 g + 4 q + j, cout r, then [16 positions][16 cout] of the gs channel.
+// blindshadowremoval_amd/pack.py: pack_wino_clr states the same in numpy.
+constexpr size_t kWinoClrFloats = bsr::WinoClrCfg::W_FLOATS;
+void wino_clr_filter_transform(const float* direct, const float* w_gs, float* out) {
+  static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+  for (int k = 0; k < 65; ++k)      // k = 64: the gs channel
+    for (int n = 0; n < 16; ++n) {
+      double t[4][3];
+      for (int x = 0; x < 4; ++x)
+        for (int b = 0; b < 3; ++b) {
+          double acc = 0.0;
+          for (int a = 0; a < 3; ++a)
+            acc += G[x][a] * (double)(k < 64 ? direct[((size_t)((k / 32) * 9 + a * 3 + b) * 16 + n) * 36 + k % 32] : w_gs[n * 16 + a * 3 + b]);
+          t[x][b] = acc;
+        }
+      for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) {
+          double acc = 0.0;
+          for (int b = 0; b < 3; ++b) acc += t[x][b] * G[y][b];
+          const int pos = 4 * x + y;
+          if (k < 64) out[((size_t)(pos * 4 + k / 16) * 64 + 16 * ((k % 16) / 4) + n) * 4 + k % 4] = (float)acc;
+          else out[bsr::WinoClrCfg::U_FLOATS + pos * 16 + n] = (float)acc;
         }
     }
 }
@@ -730,6 +762,18 @@ struct Launcher {
     a.gs = gs; a.w_gs = h->clr_gs_w; a.tail_w = h->tail_w; a.inputs = inputs; a.con_rgb = con_rgb; a.dif = dif; a.packed = packed;
     a.range_flag = h->range_flag;
     if (H % (4 * RW) != 0 || W % 32 != 0) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': image is not a multiple of its tile"); return; }
+    // the fp32 colour tail in Winograd F(2x2, 3x3) form (wino_clr.h), at every batch and image size; BSR_WINO_CLR=0 keeps the direct kernel.
+    // Same timing class and name as the direct kernel's launch.  The 16-bit modes and the heads keep conv_n16_kernel.
+    if constexpr (KH == 3 && KW == 3 && GS && TAIL && RW == 2) {
+      if (h->dtype == BSR_DTYPE_F32 && h->wino_clr && h->d_wclr != nullptr) {
+        if (const char* why = bsr::wino_clr_refusal(h->B, H, W, in_cs)) { rc = fail(BSR_ERR_ARG, std::string("layer '") + name + "': " + why); return; }
+        a.w = h->d_wclr;
+        begin(cls, name);
+        check(bsr::launch_wino_clr(a, h->B, s), name);
+        end();
+        return;
+      }
+    }
     begin(cls, name);
     with_dtype(h->dtype, [&](auto prec, auto half) { check(bsr::launch_conv_n16<KH, KW, GS, TAIL, RW, prec.value, half.value>(a, h->B, s), name); });
     end();
@@ -820,7 +864,7 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
   h->dtype = dtype;
   h->att_pv1 = dtype == BSR_DTYPE_F16;
   const struct { const char* env; bool* on; } switches[] = {{"BSR_FUSE_HEADS", &h->fuse_heads}, {"BSR_FUSE_ATTW", &h->fuse_attw}, {"BSR_CONV3_F16", &h->conv3_f16},
-                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}, {"BSR_WINO_PAIRS", &h->wino_pairs}, {"BSR_WINO_CONVT", &h->wino_convt},
+                                                            {"BSR_CONV1_GEMM", &h->conv1_gemm}, {"BSR_WINO_CONV2", &h->wino_conv2}, {"BSR_WINO_PAIRS", &h->wino_pairs}, {"BSR_WINO_CONVT", &h->wino_convt}, {"BSR_WINO_CLR", &h->wino_clr},
                                                             {"BSR_KEYS_CONV2", &h->keys_conv2}, {"BSR_VALUES_CONV2", &h->values_conv2}};
   for (const auto& sw : switches)
     if (const char* e_ = getenv(sw.env)) *sw.on = atoi(e_) != 0;
@@ -915,6 +959,16 @@ int bsr_create(bsr_handle** out, int device, const void* packed_weights, size_t 
       if (e == hipSuccess) e = hipMemcpy(h->d_winot, ut.data(), ut.size() * sizeof(float), hipMemcpyHostToDevice);
       if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: transposed-layer Winograd weights: ") + hipGetErrorString(e)); }
     }
+    {   // clr_conv1's Winograd image, once per handle (kept whatever BSR_WINO_CLR says: 65 KB)
+      LayerW l;
+      if (find_layer(h, "clr_conv1", 2, 9, 36, 16, &l) != BSR_OK || l.n_pad != 16) { bsr_destroy(h); return fail(BSR_ERR_BLOB, "bsr_create: layer 'clr_conv1' is not a [2][9][16][36] image"); }
+      std::vector<float> uc(kWinoClrFloats);
+      auto host_of = [&](const float* dev) { return reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(dev) - reinterpret_cast<const uint8_t*>(h->d_blob))); };
+      wino_clr_filter_transform(host_of(l.w), host_of(h->clr_gs_w), uc.data());
+      e = hipMalloc(reinterpret_cast<void**>(&h->d_wclr), uc.size() * sizeof(float));
+      if (e == hipSuccess) e = hipMemcpy(h->d_wclr, uc.data(), uc.size() * sizeof(float), hipMemcpyHostToDevice);
+      if (e != hipSuccess) { bsr_destroy(h); return fail(BSR_ERR_HIP, std::string("bsr_create: colour-tail Winograd weights: ") + hipGetErrorString(e)); }
+    }
     // the res0..5.c3q images for conv2's output as the attention keys, once per handle (kept whatever BSR_KEYS_CONV2 says: 2 MB)
     std::vector<float> q(6 * kKeysFloats);
     auto host = [&](const float* dev) { return reinterpret_cast<const float*>(blob + (reinterpret_cast<const uint8_t*>(dev) - reinterpret_cast<const uint8_t*>(h->d_blob))); };
@@ -960,6 +1014,7 @@ void bsr_destroy(bsr_handle* h) {
   if (h->d_blob) hipFree(h->d_blob);
   if (h->d_wino) hipFree(h->d_wino);
   if (h->d_winot) hipFree(h->d_winot);
+  if (h->d_wclr) hipFree(h->d_wclr);
   if (h->d_keys) hipFree(h->d_keys);
   if (h->d_values) hipFree(h->d_values);
   if (h->att_scratch) hipFree(h->att_scratch);
@@ -2372,6 +2427,42 @@ int bsr_debug_wino_convt_filter(const float* direct, float* out, int cin) {
   if (direct == nullptr || out == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt_filter: null argument");
   if (cin <= 0 || cin % 16 != 0) return fail(BSR_ERR_ARG, "bsr_debug_wino_convt_filter: Cin must be a positive multiple of 16");
   wino_convt_filter_transform(direct, out, cin);
+  return BSR_OK;
+}
+
+int bsr_debug_wino_clr_filter(const float* direct, const float* w_gs, float* out) {
+  if (direct == nullptr || w_gs == nullptr || out == nullptr) return fail(BSR_ERR_ARG, "bsr_debug_wino_clr_filter: null argument");
+  wino_clr_filter_transform(direct, w_gs, out);
+  return BSR_OK;
+}
+
+int bsr_debug_wino_clr(const float* gs, const float* f, int in_cs, const float* inputs, const float* w_direct, const float* w_gs, const float* bias,
+                       const float* tail_w, float* con_rgb, float* dif, float* packed, int B, int H, int W, int wino, void* stream) {
+  if (gs == nullptr || f == nullptr || inputs == nullptr || w_direct == nullptr || w_gs == nullptr || bias == nullptr || tail_w == nullptr)
+    return fail(BSR_ERR_ARG, "bsr_debug_wino_clr: null argument");
+  if (packed == nullptr && (con_rgb == nullptr || dif == nullptr)) return fail(BSR_ERR_ARG, "bsr_debug_wino_clr: neither packed nor con_rgb | dif given");
+  if (const char* why = bsr::wino_clr_refusal(B, H, W, in_cs)) return fail(BSR_ERR_ARG, std::string("bsr_debug_wino_clr: ") + why);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one device image of the weights (HOST pointers): direct [2][9][16][36] | gs [16][16] | bias [16] | tail [337 -> 340] | U
+  constexpr size_t kDirect = 2 * 9 * 16 * 36, kGs = kDirect, kBias = kGs + 256, kTail = kBias + 16, kU = kTail + 340;
+  std::vector<float> img(kU + kWinoClrFloats, 0.f);
+  memcpy(img.data(), w_direct, kDirect * sizeof(float));
+  memcpy(img.data() + kGs, w_gs, 256 * sizeof(float));
+  memcpy(img.data() + kBias, bias, 16 * sizeof(float));
+  memcpy(img.data() + kTail, tail_w, 337 * sizeof(float));
+  wino_clr_filter_transform(w_direct, w_gs, img.data() + kU);
+  float* d = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), img.size() * sizeof(float)));
+  hipError_t e = hipMemcpy(d, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    bsr::ConvN16Args a{};
+    a.in = f; a.in_cs = in_cs; a.H = H; a.W = W; a.w = wino ? d + kU : d; a.bias = d + kBias; a.act = 1; a.pad_t = 1; a.pad_l = 1;
+    a.gs = gs; a.w_gs = d + kGs; a.tail_w = d + kTail; a.inputs = inputs; a.con_rgb = con_rgb; a.dif = dif; a.packed = packed;
+    e = wino ? bsr::launch_wino_clr(a, B, s) : bsr::launch_conv_n16<3, 3, true, true, 2>(a, B, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(d);
+  HIP_TRY(e);
   return BSR_OK;
 }
 

@@ -261,6 +261,22 @@ def pack_wino_convt(kernel_tkn: np.ndarray, bias: np.ndarray):
     return arr, bias.astype(np.float32)
 
 
+def pack_wino_clr(kernel_tkn: np.ndarray, gs_tn: np.ndarray) -> np.ndarray:
+    """clr_conv1 (folded; kernel_tkn [9, 64, 16] = the f channels, gs_tn [9, 16] = the gs channel) as the weight image of csrc/wino_clr.h:
+    [16 positions 4 xi + nu][4 K groups g][64 lanes 16 q + r][4 j] = U[position, channel 16 g + 4 q + j, cout r] in A-fragment order, then
+    [16 positions][16 cout] of the gs channel; 16640 float32, flat.
+
+    Like pack_wino's, the image is not a blob entry: bsr_create derives it, once per fp32 handle, from the float32 weights of the blob's
+    direct images ('clr_conv1', 'clr_conv1.gs') with this very arithmetic (bsr_api.hip: wino_clr_filter_transform, float64, rounded once).
+    This function is its statement; tests/test_wino_clr_cpu.py holds the library's transform to it."""
+    taps, k, n = kernel_tkn.shape
+    assert (taps, k, n) == (9, 64, 16) and gs_tn.shape == (9, 16)
+    u = wino_filter_transform(kernel_tkn.astype(np.float32))                                         # [16, 64, 16]
+    u = u.reshape(16, 4, 4, 4, 16).transpose(0, 1, 2, 4, 3)                                          # [pos, g, q, j, r] -> [pos, g, q, r, j]
+    ugs = wino_filter_transform(gs_tn.astype(np.float32).reshape(9, 1, 16))                          # [16, 1, 16]
+    return np.concatenate([np.ascontiguousarray(u).reshape(-1), ugs.reshape(-1)])
+
+
 KEYS_N = 288 + 256        # [y3 288 | q' 128 | g 128]
 KEYS_N_PAD = KEYS_N + 64  # + two zero tiles of slack (gemm_nloop group reads, NI = 3)
 

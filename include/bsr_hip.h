@@ -751,6 +751,19 @@ int bsr_debug_wino_convt(const float* x, const float* w_direct, const float* bia
 /* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to the direct images of up2, up3 and clr_up3 of
  * an fp32 GSC blob.  direct = the layer's [ceil(cin / 32)][9][64][36] image, out = [cin / 16][25][2][2][64][4] floats (HOST pointers). */
 int bsr_debug_wino_convt_filter(const float* direct, float* out, int cin);
+/* Test hook (additive): the fp32 colour tail alone — clr_conv1 (3x3 over cat[gs, f], 65 -> 16, + LeakyReLU_0.3) with clr_conv2, clr_conv3 and
+ * the grayscale difference fused behind it — in Winograd F(2x2, 3x3) form (wino != 0: csrc/wino_clr.h) or in direct form (wino == 0:
+ * conv_n16_kernel<3, 3, true, true, 2>).  gs [B,H,W,1], f [B,H,W,in_cs] (channels 0..63 read), inputs [B,H,W,3] and the outputs are device
+ * pointers.  packed == NULL: con_rgb [B,H,W,3] and dif [B,H,W,1] are written; else packed [B,H,W,4] = con_rgb | dif and they are not.
+ * The weights are HOST pointers as in the blob: w_direct = 'clr_conv1' [2][9][16][36], w_gs = 'clr_conv1.gs' [16][16], bias [16],
+ * tail_w = 'tail.w' [337]; the entry transforms them as bsr_create does, launches and waits.  H % 8 == 0, W % 32 == 0, in_cs >= 64 and
+ * a multiple of 4; anything else is refused before any launch. */
+int bsr_debug_wino_clr(const float* gs, const float* f, int in_cs, const float* inputs, const float* w_direct, const float* w_gs, const float* bias,
+                       const float* tail_w, float* con_rgb, float* dif, float* packed, int B, int H, int W, int wino, void* stream);
+/* Test hook (additive, host only, no GPU call): the filter transform bsr_create applies to clr_conv1 of an fp32 GSC / TSM blob.
+ * direct = 'clr_conv1' [2][9][16][36], w_gs = 'clr_conv1.gs' [16][16], out = [16][4][64][4] + [16][16] floats (HOST pointers;
+ * blindshadowremoval_amd.pack.pack_wino_clr). */
+int bsr_debug_wino_clr_filter(const float* direct, const float* w_gs, float* out);
 /* Test hook (additive, host only, no GPU call): the image bsr_create derives from each res<i>.c3q of an fp32 GSC / TSM blob for the
  * attention that takes conv2's output as its keys (env BSR_KEYS_CONV2, default on): N = [y3 288 | q' 128 | g 128 | 64 zero] with
  * q' = theta composed onto phi's weights in float64 (blindshadowremoval_amd.pack.compose_keys_c3q).  c3q_w = the layer's [4][1][768][36]
