@@ -1,26 +1,17 @@
 """The device binding of the backward of res_stack/4, res_stack/3 and the hole: bsr_colour_trunk_grad (csrc/colour_trunk_grad_kernels.h),
-held to generator_grad.py's host statement (colour_trunk_grad).  A post_gpu.GradStage like bottleneck_grad_gpu.BottleneckGrad: here are
-the stage's declaration, its public calls and what the chain leaves in the scratch."""
+held to generator_grad.py's host statement (colour_trunk_grad).  A block_chain_gpu.BlockChainStage: here are its declaration, its public
+calls and the hole's."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
-from . import _lib, bottleneck_grad_gpu, nonlocal_grad_gpu
+from .block_chain_gpu import BlockChainStage
 from .pack import pack_colour_trunk_grad
-from .post_gpu import DENSE, OPTIONAL, STRIDED, GradStage
+from .post_gpu import DENSE, OPTIONAL, STRIDED
 from .weights import generator_colour_trunk_trainable_names
 
-BLOCKS = (4, 3)                # in the chain's order
-# the chain's launches in order and what each writes: the two existing chains per block, their names prefixed, and the hole
-LAUNCHES = tuple(("%s%d.%s" % (tag, b, name), "block %d: %s" % (b, what)) for b in BLOCKS
-                 for tag, chain in (("nl", nonlocal_grad_gpu.LAUNCHES), ("bn", bottleneck_grad_gpu.LAUNCHES))
-                 for name, what in chain) + (("hole", "d_res2"),)
-N_NL_MAPS, N_BN_MAPS = 10, 8   # bsr_nonlocal_grad_offset's and bsr_bottleneck_grad_offset's maps: a block's take 18 of bsr_colour_trunk_grad_offset's
-# the intermediate data gradients: name -> (bsr_colour_trunk_grad_offset's map, channels)
-DATA = {"d_y3_4": (36, 257), "d_skip_4": (37, 261), "d_xin4": (38, 261), "d_y3_3": (39, 257), "d_skip_3": (40, 261), "d_xin3": (41, 261)}
-KEPT = tuple("a%d_%d" % (j, b) for b in BLOCKS for j in (1, 2)) + tuple(DATA)
 C_IN, C_Y = 261, 257
 SIZE_TEXT = "the colour trunk takes B >= 1 grids with h a multiple of 4 and w a multiple of 32, got B=%d h=%d w=%d"
 NO_WEIGHTS_TEXT = "the colour trunk has no weights: call load_weights or restore first"
@@ -36,7 +27,7 @@ def _aligned(**tensors) -> None:
             raise ValueError(ALIGN_TEXT % (name, t.data_ptr()))
 
 
-class ColourTrunk(GradStage):
+class ColourTrunk(BlockChainStage):
     """`ColourTrunk(device).colour_trunk_grad(y3x4, out4, y3x3, out3, xh, d_xin, d_x)` — the gradients of the generator's res_stack/4,
     res_stack/3 and the hole x_hole = x (1 - bmask) (training=False; GSC width) on `device`, after `load_weights(dict)` (the generator's
     variables; ValueError for TSM weights) or `restore(ckpt_dir)`: `d_res2`, the complete gradient at res_stack/2's output — the colour
@@ -44,36 +35,16 @@ class ColourTrunk(GradStage):
     weights.generator_colour_trunk_trainable_names().  `backward(generator, d_xin, d_x)` reads y3x4, out4, y3x3, out3, xh in place from
     the generator's workspace."""
     SYMBOL = "bsr_colour_trunk_grad"
+    BLOCKS, TAIL = (4, 3), ("hole", "d_res2")          # in the chain's order; the hole reads block 3's d_xin
     PACK, NAMES = staticmethod(pack_colour_trunk_grad), staticmethod(generator_colour_trunk_trainable_names)
     INPUTS = (("y3x4", C_Y, 1, STRIDED), ("out4", C_IN, 1, STRIDED), ("y3x3", C_Y, 1, STRIDED), ("out3", C_IN, 1, STRIDED), ("xh", C_IN, 1, STRIDED),
               ("d_xin", C_IN, 1, DENSE), ("d_x", C_Y, 1, OPTIONAL))
     LEAD = "d_xin"
     OUTPUTS = (("d_res2", C_Y, 1),)
-    KEPT = KEPT
     MULTIPLES = (4, 32)
     DIMS = IMAGE_DIMS = "h,w"
     LIKE_TEXT, SIZE_TEXT, NO_WEIGHTS_TEXT, WHAT = "for this d_xin", SIZE_TEXT, NO_WEIGHTS_TEXT, "the colour trunk"
-    LAUNCHES = LAUNCHES
     LAST = "last_colour_trunk"
-
-    def maps(self, b: int, h: int, w: int) -> Dict[str, torch.Tensor]:
-        """Copies of what the last call of these sizes left in the scratch: per block b = 4, 3 NonLocalGrad.maps' under `nl<b>.<name>` and
-        BottleneckGrad.maps' under `bn<b>.<name>` (each sub-chain has a region of its own), the bottlenecks' `a1_<b>`, `a2_<b>` again
-        under the names the host statement gives them, and the intermediate data gradients `d_y3_<b>` [B,h,w,257], `d_skip_<b>`, `d_xin4`,
-        `d_xin3` [B,h,w,261]."""
-        lib = _lib.load()
-        self.scratch3(b, h, w)
-        out = {}
-        for k, block in enumerate(BLOCKS):
-            first = k * (N_NL_MAPS + N_BN_MAPS)
-            nl = nonlocal_grad_gpu.read_maps(self.view, lambda i: int(lib.bsr_colour_trunk_grad_offset(b, h, w, first + i)), b, h * w)
-            bn = bottleneck_grad_gpu.read_maps(self.view, lambda i: int(lib.bsr_colour_trunk_grad_offset(b, h, w, first + N_NL_MAPS + i)), b, h, w)
-            out.update(("nl%d.%s" % (block, name), t) for name, t in nl.items())
-            out.update(("bn%d.%s" % (block, name), t) for name, t in bn.items())
-            out["a1_%d" % block], out["a2_%d" % block] = bn["a1"], bn["a2"]
-        for name, (index, c) in DATA.items():
-            out[name] = self.view(int(lib.bsr_colour_trunk_grad_offset(b, h, w, index)), (b, h, w, c)).clone()
-        return out
 
     def colour_trunk_grad(self, y3x4: torch.Tensor, out4: torch.Tensor, y3x3: torch.Tensor, out3: torch.Tensor, xh: torch.Tensor, d_xin: torch.Tensor,
                           d_x: Optional[torch.Tensor] = None, keep: bool = False):
@@ -119,3 +90,6 @@ class ColourTrunk(GradStage):
     def stages(self, y3x4, out4, y3x3, out3, xh, d_xin, d_x, n):
         """The chain stopped after `n` of its launches (`LAUNCHES`) -> `maps`, `d_res2` and the flat gradient buffer under ""."""
         return super().stages(y3x4, out4, y3x3, out3, xh, d_xin, d_x, n)
+
+
+BLOCKS, LAUNCHES, DATA, KEPT = ColourTrunk.BLOCKS, ColourTrunk.LAUNCHES, ColourTrunk.DATA, ColourTrunk.KEPT

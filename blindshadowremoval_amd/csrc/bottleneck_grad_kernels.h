@@ -4,7 +4,7 @@
 // output) and d_skip (or none) it writes d_xin and the twelve variable gradients.  blindshadowremoval_amd/generator_grad.py is the host
 // statement (bottleneck_grad); pack.pack_bottleneck_grad writes the blob.
 //
-// The chain is a template on X, the width of the block's input: 261 for blocks 3..5, and for lower_trunk_grad_kernels.h 257 (blocks 1, 2)
+// The chain is a template on X, the width of the block's input: 261 for blocks 3..5, and for block_chain_grad.h 257 (blocks 1, 2)
 // and 99 (block 0, conv1 99 -> 128).  Where the text below says 261, 272 and 384 it speaks of X, of X rounded up to 16 and of X rounded
 // up to 128; the kernels that carry X in their index arithmetic are instantiated per width, the others take it as K, n_store, strides
 // and grids.

@@ -49,7 +49,6 @@
 #include "nonlocal_grad_kernels.h"
 #include "bottleneck_grad_kernels.h"
 #include "colour_trunk_grad_kernels.h"
-#include "lower_trunk_grad_kernels.h"
 #include "heads_grad_kernels.h"
 #include "vgg_kernels.h"
 #include "vgg_grad_kernels.h"
@@ -1948,18 +1947,31 @@ int bsr_debug_bottleneck_grad(int device, const void* d_blob, size_t blob_bytes,
                          stream);
 }
 
-size_t bsr_colour_trunk_grad_blob_bytes(void) { return bsr::ct_blob_off(4) * sizeof(float); }
+namespace {
 
-size_t bsr_colour_trunk_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::ct_plan(B, h, w).total : 0; }
+// the size queries of a chain of blocks (block_chain_grad.h), as the bsr_<stage>_grad_* queries below answer them
+size_t chain_blob_bytes(const bsr::BlockChain& c) { return bsr::chain_blob_off(c, 2 * c.n) * sizeof(float); }
 
-size_t bsr_colour_trunk_grad_floats(void) { return bsr::ct_var_offset(bsr::kCtVars); }
+size_t chain_scratch_bytes(const bsr::BlockChain& c, int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::chain_plan(c, B, h, w).total : 0; }
 
-size_t bsr_colour_trunk_grad_var_offset(int index) { return index < 0 || index >= bsr::kCtVars ? SIZE_MAX : bsr::ct_var_offset(index); }
+size_t chain_var_offset_checked(const bsr::BlockChain& c, int index) { return index < 0 || index >= c.vars() ? SIZE_MAX : bsr::chain_var_offset(c, index); }
 
-size_t bsr_colour_trunk_grad_offset(int B, int h, int w, int map) {
-  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kCtMaps) return SIZE_MAX;
-  return bsr::ct_plan(B, h, w).map[map];
+size_t chain_offset_checked(const bsr::BlockChain& c, int B, int h, int w, int map) {
+  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= c.maps()) return SIZE_MAX;
+  return bsr::chain_plan(c, B, h, w).map[map];
 }
+
+}  // namespace
+
+size_t bsr_colour_trunk_grad_blob_bytes(void) { return chain_blob_bytes(bsr::kColourChain); }
+
+size_t bsr_colour_trunk_grad_scratch_bytes(int B, int h, int w) { return chain_scratch_bytes(bsr::kColourChain, B, h, w); }
+
+size_t bsr_colour_trunk_grad_floats(void) { return bsr::chain_var_offset(bsr::kColourChain, bsr::kColourChain.vars()); }
+
+size_t bsr_colour_trunk_grad_var_offset(int index) { return chain_var_offset_checked(bsr::kColourChain, index); }
+
+size_t bsr_colour_trunk_grad_offset(int B, int h, int w, int map) { return chain_offset_checked(bsr::kColourChain, B, h, w, map); }
 
 namespace {
 
@@ -1976,7 +1988,7 @@ int colour_trunk_grad(const char* name, int device, const void* d_blob, size_t b
         "y3x4_cs and y3x3_cs must be at least 257, out4_cs, out3_cs and xh_cs at least 261"}},
       {{16, "d_blob, d_x and d_res2", {d_blob, d_x, d_res2}},
        {4, "y3x4, out4, y3x3, out3, xh, d_xin and grads", {y3x4, out4, y3x3, out3, xh, d_xin, grads}}},
-      scratch, stop_after, bsr::kCtLaunches, device, [&] {
+      scratch, stop_after, bsr::kColourChain.launches(), device, [&] {
         HIP_TRY(bsr::launch_colour_trunk_grad(static_cast<const float*>(d_blob), y3x4, y3x4_cs, out4, out4_cs, y3x3, y3x3_cs, out3, out3_cs, xh, xh_cs, d_xin,
                                               d_x, B, h, w, d_res2, grads, scratch, stop_after, static_cast<hipStream_t>(stream)));
         return BSR_OK;
@@ -1989,7 +2001,7 @@ int bsr_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, con
                           const float* y3x3, int y3x3_cs, const float* out3, int out3_cs, const float* xh, int xh_cs, const float* d_xin, const float* d_x,
                           int B, int h, int w, float* d_res2, float* grads, void* scratch, void* stream) {
   return colour_trunk_grad("bsr_colour_trunk_grad", device, d_blob, blob_bytes, y3x4, y3x4_cs, out4, out4_cs, y3x3, y3x3_cs, out3, out3_cs, xh, xh_cs, d_xin,
-                           d_x, B, h, w, d_res2, grads, scratch, bsr::kCtLaunches, stream);
+                           d_x, B, h, w, d_res2, grads, scratch, bsr::kColourChain.launches(), stream);
 }
 
 int bsr_debug_colour_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x4, int y3x4_cs, const float* out4, int out4_cs,
@@ -2011,18 +2023,15 @@ int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_x
       });
 }
 
-size_t bsr_lower_trunk_grad_blob_bytes(void) { return bsr::lt_blob_off(2 * bsr::kLtBlocks) * sizeof(float); }
+size_t bsr_lower_trunk_grad_blob_bytes(void) { return chain_blob_bytes(bsr::kLowerChain); }
 
-size_t bsr_lower_trunk_grad_scratch_bytes(int B, int h, int w) { return bsr::nl_size_ok(B, h, w) ? bsr::lt_plan(B, h, w).total : 0; }
+size_t bsr_lower_trunk_grad_scratch_bytes(int B, int h, int w) { return chain_scratch_bytes(bsr::kLowerChain, B, h, w); }
 
-size_t bsr_lower_trunk_grad_floats(void) { return bsr::lt_var_offset(bsr::kLtVars); }
+size_t bsr_lower_trunk_grad_floats(void) { return bsr::chain_var_offset(bsr::kLowerChain, bsr::kLowerChain.vars()); }
 
-size_t bsr_lower_trunk_grad_var_offset(int index) { return index < 0 || index >= bsr::kLtVars ? SIZE_MAX : bsr::lt_var_offset(index); }
+size_t bsr_lower_trunk_grad_var_offset(int index) { return chain_var_offset_checked(bsr::kLowerChain, index); }
 
-size_t bsr_lower_trunk_grad_offset(int B, int h, int w, int map) {
-  if (!bsr::nl_size_ok(B, h, w) || map < 0 || map >= bsr::kLtMaps) return SIZE_MAX;
-  return bsr::lt_plan(B, h, w).map[map];
-}
+size_t bsr_lower_trunk_grad_offset(int B, int h, int w, int map) { return chain_offset_checked(bsr::kLowerChain, B, h, w, map); }
 
 namespace {
 
@@ -2040,10 +2049,14 @@ int lower_trunk_grad(const char* name, int device, const void* d_blob, size_t bl
         "y3x2_cs, y3x1_cs, y3x0_cs, out2_cs, out1_cs and out0_cs must be at least 257, x0_cs at least 99"}},
       {{16, "d_blob", {d_blob}},
        {4, "y3x2, out2, y3x1, out1, y3x0, out0, x0, d_res2, d_x0 and grads", {y3x2, out2, y3x1, out1, y3x0, out0, x0, d_res2, d_x0, grads}}},
-      scratch, stop_after, bsr::kLtLaunches, device, [&] {
-        HIP_TRY(bsr::launch_lower_trunk_grad(static_cast<const float*>(d_blob), y3x2, y3x2_cs, out2, out2_cs, y3x1, y3x1_cs, out1, out1_cs, y3x0, y3x0_cs,
-                                             out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, stop_after,
-                                             static_cast<hipStream_t>(stream)));
+      scratch, stop_after, bsr::kLowerChain.launches(), device, [&] {
+        // block 2's input is out1, block 1's is out0, block 0's is x0
+        const bsr::ChainBlockIn in[3] = {{y3x2, out1, out2, y3x2_cs, out1_cs, out2_cs}, {y3x1, out0, out1, y3x1_cs, out0_cs, out1_cs},
+                                         {y3x0, x0, out0, y3x0_cs, x0_cs, out0_cs}};
+        float* d_last = d_x0;
+        int left = stop_after;
+        HIP_TRY(bsr::launch_block_chain(bsr::kLowerChain, static_cast<const float*>(d_blob), in, d_res2, B, h, w, &d_last, grads, scratch, left,
+                                        static_cast<hipStream_t>(stream)));
         return BSR_OK;
       });
 }
@@ -2054,7 +2067,7 @@ int bsr_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, cons
                          const float* y3x1, int y3x1_cs, const float* out1, int out1_cs, const float* y3x0, int y3x0_cs, const float* out0, int out0_cs,
                          const float* x0, int x0_cs, const float* d_res2, int B, int h, int w, float* d_x0, float* grads, void* scratch, void* stream) {
   return lower_trunk_grad("bsr_lower_trunk_grad", device, d_blob, blob_bytes, y3x2, y3x2_cs, out2, out2_cs, y3x1, y3x1_cs, out1, out1_cs, y3x0, y3x0_cs,
-                          out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, bsr::kLtLaunches, stream);
+                          out0, out0_cs, x0, x0_cs, d_res2, B, h, w, d_x0, grads, scratch, bsr::kLowerChain.launches(), stream);
 }
 
 int bsr_debug_lower_trunk_grad(int device, const void* d_blob, size_t blob_bytes, const float* y3x2, int y3x2_cs, const float* out2, int out2_cs,

@@ -740,6 +740,35 @@ def heads_example_inputs(H: int, W: int, B: int, seed: int = 0):
     return inputs, y, d_gs
 
 
+# ---- a chain of residual blocks: what the two trunk stages below share
+def blocks_forward(weights: Dict[str, np.ndarray], xin, blocks, dtype=np.float64) -> Dict[str, np.ndarray]:
+    """bottleneck_forward and nonlocal_forward of each of `blocks` in the forward's order, the first on `xin`, each next one on the
+    output before -> dict(per block b `y3_<b>`, `res<b>`, `a1_<b>`, `a2_<b>`, `pre_<b>`) in `dtype`."""
+    out: Dict[str, np.ndarray] = {}
+    for b in blocks:
+        bf = bottleneck_forward(weights, xin, b, dtype)
+        nf = nonlocal_forward(weights, bf["y3"], xin, b, dtype)
+        out.update({"y3_%d" % b: bf["y3"], "res%d" % b: nf["out"], "a1_%d" % b: bf["a1"], "a2_%d" % b: bf["a2"], "pre_%d" % b: nf["pre"]})
+        xin = nf["out"]
+    return out
+
+
+def blocks_grad(weights: Dict[str, np.ndarray], rows, d_out, acts: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """`rows` of (block, y3, xin, out) in the backward's order, d_out the gradient at the first row's output -> dict(per block b its 22
+    variables, `d_y3_<b>`, `d_skip_<b>`, `d_xin<b>` and `a1_<b>`, `a2_<b>` as used): nonlocal_grad, then bottleneck_grad, each block's
+    d_xin the next row's d_out.  `acts` carries `a1_<b>`, `a2_<b>`."""
+    res: Dict[str, np.ndarray] = {}
+    for b, y3, xin, out in rows:
+        n = nonlocal_grad(weights, y3, xin, d_out, block=b, acts={"out": out})
+        a = None if acts is None else {"a1": acts["a1_%d" % b], "a2": acts["a2_%d" % b]}
+        t = bottleneck_grad(weights, xin, n["d_y3"], n["d_skip"], block=b, acts=a)
+        res.update((name, n[name]) for name in generator_nonlocal_trainable_names(b))
+        res.update((name, t[name]) for name in generator_bottleneck_trainable_names(b))
+        res.update({"d_y3_%d" % b: n["d_y3"], "d_skip_%d" % b: n["d_skip"], "d_xin%d" % b: t["d_xin"], "a1_%d" % b: t["a1"], "a2_%d" % b: t["a2"]})
+        d_out = t["d_xin"]
+    return res
+
+
 # ---- res_stack/4, res_stack/3 and the hole: from the gradient at res_stack/5's input to the complete gradient at res_stack/2's output
 COLOUR_TRUNK_BLOCKS = (4, 3)             # in the backward's order
 COLOUR_TRUNK_NORM_NAMES = ("d_res2",) + tuple(generator_colour_trunk_trainable_names())
@@ -768,12 +797,7 @@ def trunk_forward(weights: Dict[str, np.ndarray], x, bmask, uv, dtype=np.float64
     T = dtype
     x, bmask, uv = np.asarray(x, T), np.asarray(bmask, T), np.asarray(uv, T)
     out = {"xh": np.concatenate([x * (T(1) - bmask), bmask, uv], axis=3)}
-    xin = out["xh"]
-    for b in (3, 4):
-        bf = bottleneck_forward(weights, xin, b, T)
-        nf = nonlocal_forward(weights, bf["y3"], xin, b, T)
-        out.update({"y3_%d" % b: bf["y3"], "res%d" % b: nf["out"], "a1_%d" % b: bf["a1"], "a2_%d" % b: bf["a2"], "pre_%d" % b: nf["pre"]})
-        xin = nf["out"]
+    out.update(blocks_forward(weights, out["xh"], (3, 4), T))
     return out
 
 
@@ -787,17 +811,8 @@ def colour_trunk_grad(weights: Dict[str, np.ndarray], xh, y3_3, res3, y3_4, res4
       nonlocal_grad(y3, xin, d_out, block=b, acts={"out": out_b}) -> d_y3, d_skip;  bottleneck_grad(xin, d_y3, d_skip, block=b) -> d_xin
     with block 4's d_xin as block 3's d_out, and hole_grad(xh, d_xin3, d_x) at the end.  `acts` carries `a1_<b>`, `a2_<b>` (for example the
     device's): the bottlenecks' masks and kernel-gradient inputs are read from them."""
-    res: Dict[str, np.ndarray] = {}
-    d_out = d_xin5
-    for b, y3, xin, out in ((4, y3_4, res3, res4), (3, y3_3, xh, res3)):
-        n = nonlocal_grad(weights, y3, xin, d_out, block=b, acts={"out": out})
-        a = None if acts is None else {"a1": acts["a1_%d" % b], "a2": acts["a2_%d" % b]}
-        t = bottleneck_grad(weights, xin, n["d_y3"], n["d_skip"], block=b, acts=a)
-        res.update((name, n[name]) for name in generator_nonlocal_trainable_names(b))
-        res.update((name, t[name]) for name in generator_bottleneck_trainable_names(b))
-        res.update({"d_y3_%d" % b: n["d_y3"], "d_skip_%d" % b: n["d_skip"], "d_xin%d" % b: t["d_xin"], "a1_%d" % b: t["a1"], "a2_%d" % b: t["a2"]})
-        d_out = t["d_xin"]
-    res["d_res2"] = hole_grad(xh, d_out, d_x)
+    res = blocks_grad(weights, ((4, y3_4, res3, res4), (3, y3_3, xh, res3)), d_xin5, acts)
+    res["d_res2"] = hole_grad(xh, res["d_xin3"], d_x)
     return res
 
 
@@ -846,15 +861,7 @@ def lower_trunk_forward(weights: Dict[str, np.ndarray], x0, dtype=np.float64) ->
     `res<b>` [B,h,w,257] (the block's output), the bottleneck's `a1_<b>`, `a2_<b>` [B,h,w,128] and `pre_<b>` (relu3's input)) in `dtype`:
     bottleneck_forward and nonlocal_forward of block 0 on x0, whose skip reaches the first 99 output channels, of block 1 on res0 and of
     block 2 on res1 (model.py Generator.call: for i in range(n_res // 2))."""
-    T = dtype
-    out: Dict[str, np.ndarray] = {}
-    xin = np.asarray(x0, T)
-    for b in (0, 1, 2):
-        bf = bottleneck_forward(weights, xin, b, T)
-        nf = nonlocal_forward(weights, bf["y3"], xin, b, T)
-        out.update({"y3_%d" % b: bf["y3"], "res%d" % b: nf["out"], "a1_%d" % b: bf["a1"], "a2_%d" % b: bf["a2"], "pre_%d" % b: nf["pre"]})
-        xin = nf["out"]
-    return out
+    return blocks_forward(weights, np.asarray(x0, dtype), (0, 1, 2), dtype)
 
 
 def lower_trunk_grad(weights: Dict[str, np.ndarray], x0, y3_0, res0, y3_1, res1, y3_2, res2, d_res2,
@@ -868,17 +875,8 @@ def lower_trunk_grad(weights: Dict[str, np.ndarray], x0, y3_0, res0, y3_1, res1,
       nonlocal_grad(y3, xin, d_out, block=b, acts={"out": out_b}) -> d_y3, d_skip;  bottleneck_grad(xin, d_y3, d_skip, block=b) -> d_xin
     with each block's d_xin as the next block's d_out.  `acts` carries `a1_<b>`, `a2_<b>` (for example the device's): the bottlenecks'
     masks and kernel-gradient inputs are read from them."""
-    res: Dict[str, np.ndarray] = {}
-    d_out = d_res2
-    for b, y3, xin, out in ((2, y3_2, res1, res2), (1, y3_1, res0, res1), (0, y3_0, x0, res0)):
-        n = nonlocal_grad(weights, y3, xin, d_out, block=b, acts={"out": out})
-        a = None if acts is None else {"a1": acts["a1_%d" % b], "a2": acts["a2_%d" % b]}
-        t = bottleneck_grad(weights, xin, n["d_y3"], n["d_skip"], block=b, acts=a)
-        res.update((name, n[name]) for name in generator_nonlocal_trainable_names(b))
-        res.update((name, t[name]) for name in generator_bottleneck_trainable_names(b))
-        res.update({"d_y3_%d" % b: n["d_y3"], "d_skip_%d" % b: n["d_skip"], "a1_%d" % b: t["a1"], "a2_%d" % b: t["a2"],
-                    ("d_xin%d" % b) if b else "d_x0": t["d_xin"]})
-        d_out = t["d_xin"]
+    res = blocks_grad(weights, ((2, y3_2, res1, res2), (1, y3_1, res0, res1), (0, y3_0, x0, res0)), d_res2, acts)
+    res["d_x0"] = res.pop("d_xin0")              # the last block's d_xin is the stage's output
     return res
 
 

@@ -954,15 +954,9 @@ def nonlocal_grad_record(weights: Dict[str, np.ndarray], block: int = 5) -> Dict
 def pack_nonlocal_grad(weights: Dict[str, np.ndarray], block: int = 5) -> bytes:
     """The generator's variables (res_stack/<block>/non_local's 12 are read) -> the blob bsr_nonlocal_grad takes (nonlocal_grad_layout).
     ValueError for TSM weights: the chain's skip is 261 wide."""
-    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, 261, 128):
+    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, BOTTLENECK_WIDTH, 128):
         raise ValueError(NONLOCAL_TSM_TEXT)
-    layout, total = nonlocal_grad_layout()
-    rec = nonlocal_grad_record(weights, block)
-    blob = np.zeros(total, np.float32)
-    for name, off, shape in layout:
-        assert rec[name].shape == tuple(shape), name
-        blob[off:off + rec[name].size] = rec[name].reshape(-1)
-    return blob.tobytes()
+    return _join_record(nonlocal_grad_layout(), nonlocal_grad_record(weights, block))
 
 
 def unpack_nonlocal_grad(blob: bytes) -> Dict[str, np.ndarray]:
@@ -977,8 +971,8 @@ def unpack_nonlocal_grad(blob: bytes) -> Dict[str, np.ndarray]:
 # ---- the generator's bottleneck backward (csrc/bottleneck_grad_kernels.h): a blob of its own, no header, float32 ----
 BOTTLENECK_TSM_TEXT = "the bottleneck's device chain takes the GSC width only (TSM's 877 is covered by generator_grad.bottleneck_grad)"
 BOTTLENECK_BLOCK_TEXT = "block must be 3, 4 or 5 (the colour branch's blocks share their shapes), got %r"
-BOTTLENECK_WIDTH = 261       # conv1's input width in blocks 3..5
-LOWER_TRUNK_WIDTHS = {0: 99, 1: 257, 2: 257}          # conv1's input width in the blocks below the hole
+BLOCK_WIDTHS = {0: 99, 1: 257, 2: 257, 3: 261, 4: 261, 5: 261}      # conv1's input width per block of res_stack: the one table
+BOTTLENECK_WIDTH, LOWER_TRUNK_WIDTHS = BLOCK_WIDTHS[5], {b: BLOCK_WIDTHS[b] for b in (0, 1, 2)}     # blocks 3..5; the blocks below the hole
 LOWER_TRUNK_TEXT = ("the lower trunk's device chain takes the GSC widths only: res_stack/%d/conv1/kernel must be [1,1,%d,128], got %s (TSM's blocks "
                     "0..2 are 291 wide, the RGB baseline's 513)")
 
@@ -1055,7 +1049,7 @@ def pack_bottleneck_grad(weights: Dict[str, np.ndarray], block: int = 5) -> byte
     takes (bottleneck_grad_layout).  ValueError for TSM weights: the chain's input is 261 wide."""
     if block not in (3, 4, 5):
         raise ValueError(BOTTLENECK_BLOCK_TEXT % (block,))
-    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, 261, 128):
+    if tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block])) != (1, 1, BOTTLENECK_WIDTH, 128):
         raise ValueError(BOTTLENECK_TSM_TEXT)
     return _join_record(bottleneck_grad_layout(), bottleneck_grad_record(weights, block))
 
@@ -1079,57 +1073,72 @@ def unpack_bottleneck_grad(blob: bytes, width: int = BOTTLENECK_WIDTH) -> Dict[s
     return {name: arr[off:off + int(np.prod(shape))].reshape(shape).copy() for name, off, shape in layout}
 
 
-# ---- the backward of res_stack/4, /3 and the hole (csrc/colour_trunk_grad_kernels.h): the four blobs above end to end ----
+# ---- a chain of blocks' backward (csrc/block_chain_grad.h): per block as launched the non-local blob, then the bottleneck's at its width ----
+def block_chain_width(weights: Dict[str, np.ndarray], block: int) -> int:
+    """BLOCK_WIDTHS[block] if conv1's kernel has it; else ValueError: NONLOCAL_TSM_TEXT for blocks 3..5, LOWER_TRUNK_TEXT below."""
+    width = BLOCK_WIDTHS[block]
+    shape = tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block]))
+    if shape != (1, 1, width, 128):
+        raise ValueError(NONLOCAL_TSM_TEXT if block >= 3 else LOWER_TRUNK_TEXT % (block, width, shape))
+    return width
+
+
+def block_chain_parts(blocks):
+    """[(kind, block, floats)] of pack_block_chain's parts: ("nl", b), ("bn", b) per block.  Every part is a multiple of four floats."""
+    return [(kind, b, nonlocal_grad_layout()[1] if kind == "nl" else bottleneck_grad_layout(BLOCK_WIDTHS[b])[1]) for b in blocks for kind in ("nl", "bn")]
+
+
+def pack_block_chain(weights: Dict[str, np.ndarray], blocks) -> bytes:
+    """The generator's variables (those of `blocks` are read) -> block_chain_parts' blobs end to end.  A block's width check comes first."""
+    parts = []
+    for b in blocks:
+        width = block_chain_width(weights, b)
+        parts.append(_join_record(nonlocal_grad_layout(), nonlocal_grad_record(weights, b)))
+        parts.append(_join_record(bottleneck_grad_layout(width), _bottleneck_record(weights, b, width)))
+    return b"".join(parts)
+
+
+def unpack_block_chain(blob: bytes, blocks, what: str) -> Dict[str, np.ndarray]:
+    """The inverse of pack_block_chain: "nl<b>.<name>" -> nonlocal_grad_record's arrays, "bn<b>.<name>" -> bottleneck_grad_record's."""
+    parts = block_chain_parts(blocks)
+    total = sum(n for _, _, n in parts)
+    if len(blob) != 4 * total:
+        raise ValueError("a %s gradient blob holds %d bytes, got %d" % (what, total * 4, len(blob)))
+    out, at = {}, 0
+    for kind, b, n in parts:
+        part = blob[4 * at:4 * (at + n)]
+        rec = unpack_nonlocal_grad(part) if kind == "nl" else unpack_bottleneck_grad(part, BLOCK_WIDTHS[b])
+        out.update(("%s%d.%s" % (kind, b, name), a) for name, a in rec.items())
+        at += n
+    return out
+
+
 def pack_colour_trunk_grad(weights: Dict[str, np.ndarray]) -> bytes:
     """The generator's variables (res_stack/4's and res_stack/3's are read) -> the blob bsr_colour_trunk_grad takes: pack_nonlocal_grad and
     pack_bottleneck_grad of block 4, then of block 3, in the order of the chain's launches.  ValueError (NONLOCAL_TSM_TEXT) for TSM weights."""
-    return b"".join(pack(weights, block) for block in (4, 3) for pack in (pack_nonlocal_grad, pack_bottleneck_grad))
+    return pack_block_chain(weights, (4, 3))
 
 
-# ---- the backward of res_stack/2, /1 and /0 (csrc/lower_trunk_grad_kernels.h): six blobs end to end, the bottlenecks' at their own widths ----
 def lower_trunk_bottleneck_record(weights: Dict[str, np.ndarray], block: int) -> Dict[str, np.ndarray]:
-    """bottleneck_grad_record for block 0, 1 or 2, at the block's own input width (LOWER_TRUNK_WIDTHS).  ValueError (LOWER_TRUNK_TEXT)
-    for TSM and RGB weights."""
-    width = LOWER_TRUNK_WIDTHS[block]
-    shape = tuple(np.shape(weights["res_stack/%d/conv1/kernel" % block]))
-    if shape != (1, 1, width, 128):
-        raise ValueError(LOWER_TRUNK_TEXT % (block, width, shape))
-    return _bottleneck_record(weights, block, width)
+    """bottleneck_grad_record for block 0, 1 or 2 at its own input width.  ValueError (LOWER_TRUNK_TEXT) for TSM and RGB weights."""
+    return _bottleneck_record(weights, block, block_chain_width(weights, block))
 
 
 def lower_trunk_grad_parts():
-    """[(kind, block, floats)] of pack_lower_trunk_grad's six parts in the order of the chain's launches: ("nl", 2), ("bn", 2), ("nl", 1),
-    ("bn", 1), ("nl", 0), ("bn", 0).  Every part is a multiple of four floats."""
-    return [(kind, b, nonlocal_grad_layout()[1] if kind == "nl" else bottleneck_grad_layout(LOWER_TRUNK_WIDTHS[b])[1])
-            for b in (2, 1, 0) for kind in ("nl", "bn")]
+    """block_chain_parts of pack_lower_trunk_grad's six: ("nl", 2), ("bn", 2), ("nl", 1), ("bn", 1), ("nl", 0), ("bn", 0)."""
+    return block_chain_parts((2, 1, 0))
 
 
 def pack_lower_trunk_grad(weights: Dict[str, np.ndarray]) -> bytes:
     """The generator's variables (res_stack/0's, /1's and /2's are read) -> the blob bsr_lower_trunk_grad takes: per block 2, 1, 0 the
     non-local blob (nonlocal_grad_layout: it does not carry the input's width) and the bottleneck blob at the block's width (257, 257, 99).
     ValueError (LOWER_TRUNK_TEXT) for TSM and RGB weights, whose blocks 0..2 are 291 and 513 wide."""
-    parts = []
-    for b in (2, 1, 0):
-        bn = lower_trunk_bottleneck_record(weights, b)      # the width check comes first
-        parts.append(_join_record(nonlocal_grad_layout(), nonlocal_grad_record(weights, b)))
-        parts.append(_join_record(bottleneck_grad_layout(LOWER_TRUNK_WIDTHS[b]), bn))
-    return b"".join(parts)
+    return pack_block_chain(weights, (2, 1, 0))
 
 
 def unpack_lower_trunk_grad(blob: bytes) -> Dict[str, np.ndarray]:
-    """The inverse of pack_lower_trunk_grad: "nl<b>.<name>" -> nonlocal_grad_record's arrays and "bn<b>.<name>" -> bottleneck_grad_record's
-    at block b's width, b = 0, 1, 2."""
-    parts = lower_trunk_grad_parts()
-    total = sum(n for _, _, n in parts)
-    if len(blob) != 4 * total:
-        raise ValueError("a lower trunk gradient blob holds %d bytes, got %d" % (total * 4, len(blob)))
-    out, at = {}, 0
-    for kind, b, n in parts:
-        part = blob[4 * at:4 * (at + n)]
-        rec = unpack_nonlocal_grad(part) if kind == "nl" else unpack_bottleneck_grad(part, LOWER_TRUNK_WIDTHS[b])
-        out.update(("%s%d.%s" % (kind, b, name), a) for name, a in rec.items())
-        at += n
-    return out
+    """The inverse of pack_lower_trunk_grad: unpack_block_chain's dict for b = 0, 1, 2."""
+    return unpack_block_chain(blob, (2, 1, 0), "lower trunk")
 
 
 # ---- the generator's grey heads' backward (csrc/heads_grad_kernels.h): a blob of its own, no header, float32 ----

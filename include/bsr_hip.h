@@ -503,7 +503,7 @@ int bsr_debug_hole_grad(int device, const float* xh, int xh_cs, const float* d_x
  * bsr_lower_trunk_grad_floats() = 1022354 float32: the 66 variables of weights.generator_lower_trunk_trainable_names() in that order
  * (block 0's twelve bottleneck variables, its ten non-local ones, then block 1's, then block 2's), variable `index` (0..65) at float
  * offset bsr_lower_trunk_grad_var_offset(index); SIZE_MAX out of range.  72 launches on `stream`, one after the other
- * (csrc/lower_trunk_grad_kernels.h): bsr_nonlocal_grad's twelve and bsr_bottleneck_grad's twelve per block at the block's input width
+ * (csrc/block_chain_grad.h): bsr_nonlocal_grad's twelve and bsr_bottleneck_grad's twelve per block at the block's input width
  * (block 0: K = 112 for conv1, two row tiles for its kernel gradient, one column tile for its data gradient); no host synchronisation,
  * no floating-point atomics: a call repeats its bits.  scratch: bsr_lower_trunk_grad_scratch_bytes(B, h, w) bytes, 256-byte aligned;
  * every word read is written earlier in the same call; each of the six sub-chains has a region of its own.

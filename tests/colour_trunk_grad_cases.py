@@ -7,8 +7,10 @@ arithmetic's type); `d_x` may be None.  Grids are (h, w, B) on the 1/8 grid."""
 import numpy as np
 
 from blindshadowremoval_amd import generator_grad as host
-from blindshadowremoval_amd.weights import (BN_EPS, LRELU_ALPHA, generator_bottleneck_trainable_names, generator_colour_trunk_trainable_names,
-                                            generator_nonlocal_trainable_names, init_weights)
+from blindshadowremoval_amd.weights import generator_bottleneck_trainable_names, generator_colour_trunk_trainable_names, generator_nonlocal_trainable_names
+
+import block_chain_cases as chain
+from block_chain_cases import autograd_block
 
 f32 = np.float32
 NAMES = tuple(generator_colour_trunk_trainable_names())
@@ -26,20 +28,17 @@ GPU_SIZES = ((4, 32, 1), (8, 32, 2), (12, 32, 3), (4, 64, 1))
 # measured on an MI355X over GPU_SIZES (tools/colour_trunk_bench.py --parity, profiles/colour_trunk_grad_bench.json)
 E2E_MEASURED = 4.08e-6        # res_stack/3/non_local/theta/bias at (12, 32, 3); 3.03e-6, 3.38e-6, 3.4e-6 at (4, 32, 1), (8, 32, 2), (4, 64, 1)
 E2E_BOUND = min(4 * E2E_MEASURED, 1e-3)
+# block_chain_cases.device_digest of the device's keep=True result on device_results' inputs at two of GPU_SIZES, recorded on an MI355X from
+# commit 7a2e835 ("Run the fp32 colour tail's clr_conv1 in Winograd form, V in registers"), the last before the two trunk stages shared one
+# statement of the chain: a call repeats its bits, so a mismatch means that what runs has changed
+PARENT_DEVICE_DIGESTS = {(4, 32, 1): "f87bd706c5f8971e", (12, 32, 3): "09c619f87a1fdad8"}
 # the same of `d_res2` and the 44 variables at the end of both branches chained on one forward at (32, 256), B = 2: the five table stages,
 # GreyDecoder and ColourTrunk against the host statements chained on the device's own activations
 CHAINED_MEASURED = 2.39e-6    # res_stack/3/non_local/phi/kernel; d_res2 9.1e-7
 CHAINED_BOUND = min(4 * CHAINED_MEASURED, 1e-3)
 
-_weights = {}
 _cases = {}
-
-
-def ct_weights(seed=3, variant="gsc"):
-    """init_weights(seed): non-trivial BN statistics.  Cached: treat as read-only."""
-    if (seed, variant) not in _weights:
-        _weights[(seed, variant)] = init_weights(seed, variant=variant)
-    return _weights[(seed, variant)]
+ct_weights = chain.weights          # init_weights(3) by default, cached: treat as read-only
 
 
 def check_inputs(fw, bmask):
@@ -82,64 +81,22 @@ def device_inputs(wt, x, bmask, uv):
 
 
 def worst_scaled_diff(got, ref, names=OUTPUTS):
-    """The largest of max |got[v] - ref[v]| / max |ref[v]| over `names` (an output whose reference is all 0 must be all 0), and the name
-    it occurred at.  A block's d phi/bias is identically zero in exact arithmetic (the rows of dS sum to 0), so it is held as an absolute
-    bound on the scale of max |d theta/bias| of that block, as nonlocal_grad_cases does."""
-    worst, at = 0.0, ""
-    for name in names:
-        a, b = np.asarray(got[name], np.float64), np.asarray(ref[name], np.float64)
-        assert a.shape == b.shape, (name, a.shape, b.shape)
-        scale = np.abs(b).max()
-        if name.endswith("non_local/phi/bias"):
-            scale = np.abs(np.asarray(ref[name.replace("phi/bias", "theta/bias")], np.float64)).max()
-        d = float(np.abs(a - b).max() / scale) if scale > 0 else (0.0 if not a.any() else np.inf)
-        if d > worst:
-            worst, at = d, name
-    return worst, at
+    """block_chain_cases.worst_scaled_diff, over the 45 outputs unless `names` says otherwise."""
+    return chain.worst_scaled_diff(got, ref, names)
 
 
-# ---- torch autograd in float64, written from the reference's semantics (model.py:23-61, 81-113, 256-262): per block conv2d with padding
-# 1, inference BN, leaky_relu 0.3, the non-local block, the zero-padded skip; the hole with bmask and uv constants.  The 44 variables and x
-# are leaves
+# ---- torch autograd in float64: block_chain_cases.autograd_block per block; the hole with bmask and uv constants (model.py:256-262).  The
+# 44 variables and x are leaves
 def autograd_grads(weights, x, bmask, uv, d_xin, d_x=None):
     """d (<d_xin, res4> + <d_x, x>) / d each of the 44 variables and x by torch autograd in float64 from the float32 variables: name ->
     float64 array in the variable's shape, `d_res2` [B,h,w,257]."""
     import torch
-    import torch.nn.functional as F
     t64 = lambda a: torch.from_numpy(np.array(a, np.float64))                        # noqa: E731
     leaves = {n: t64(weights[n]).requires_grad_(True) for n in NAMES}
     xt = t64(x).requires_grad_(True)
-
-    def bn(c, stem):
-        mean, var = (t64(weights[stem + p]) for p in ("moving_mean", "moving_variance"))
-        return (c - mean) / torch.sqrt(var + BN_EPS) * leaves[stem + "gamma"] + leaves[stem + "beta"]
-
-    def block(t, b):
-        st = "res_stack/%d/" % b
-        B, h, w, C = t.shape
-
-        def conv(u, j, pad):
-            k = leaves[st + "conv%d/kernel" % j].permute(3, 2, 0, 1)                 # HWIO -> OIHW
-            c = F.conv2d(u.permute(0, 3, 1, 2), k, leaves[st + "conv%d/bias" % j], padding=pad).permute(0, 2, 3, 1)
-            return bn(c, st + "bnorm%d/" % j)
-
-        y = F.leaky_relu(conv(t, 1, 0), LRELU_ALPHA)
-        y = F.leaky_relu(conv(y, 2, 1), LRELU_ALPHA)
-        y = conv(y, 3, 0)
-        nl = st + "non_local/"
-        proj = lambda u, name: torch.matmul(u, leaves[nl + name + "/kernel"][0, 0]) + leaves[nl + name + "/bias"]   # noqa: E731
-        g_x = proj(y, "g").reshape(B, h * w, -1)
-        phi_x = proj(y, "phi").reshape(B, h * w, -1).transpose(1, 2)
-        theta_x = proj(y, "theta").reshape(B, h * w, -1)
-        f = torch.softmax(torch.matmul(theta_x, phi_x), -1)
-        w_y = bn(proj(torch.matmul(f, g_x).reshape(B, h, w, -1), "w"), nl + "bnorm/")
-        z = y + w_y
-        z = torch.cat([z, torch.zeros(B, h, w, C - z.shape[3], dtype=torch.float64)], dim=3)
-        return F.leaky_relu(t + z, LRELU_ALPHA)
-
     hole = t64(bmask)
     xh = torch.cat([xt * (1 - hole), hole, t64(uv)], dim=3)
-    obj = (block(block(xh, 3), 4) * t64(d_xin)).sum()
+    obj = (autograd_block(autograd_block(xh, 3, leaves, weights), 4, leaves, weights) * t64(d_xin)).sum()
     if d_x is not None:
         obj = obj + (xt * t64(d_x)).sum()
     obj.backward()

@@ -8,9 +8,12 @@ import hashlib
 
 import numpy as np
 
-from blindshadowremoval_amd import generator_grad as host
+from blindshadowremoval_amd import generator_grad as host, pack
 from blindshadowremoval_amd.weights import (BN_EPS, LRELU_ALPHA, generator_bottleneck_trainable_names, generator_lower_trunk_trainable_names,
                                             generator_nonlocal_trainable_names, init_weights)
+
+import block_chain_cases as chain
+from block_chain_cases import autograd_block, to_dev, to_host      # noqa: F401
 
 f32 = np.float32
 NAMES = tuple(generator_lower_trunk_trainable_names())
@@ -30,20 +33,17 @@ GPU_SIZES = ((4, 32, 1), (8, 32, 2), (12, 32, 3), (4, 64, 1))
 # measured on an MI355X over GPU_SIZES (tools/lower_trunk_bench.py --parity, profiles/lower_trunk_grad_bench.json)
 E2E_MEASURED = 6.41e-6        # res_stack/0/bnorm2/gamma at (12, 32, 3); 5.03e-6, 5.57e-6, 4.28e-6 at (4, 32, 1), (8, 32, 2), (4, 64, 1)
 E2E_BOUND = min(4 * E2E_MEASURED, 1e-3)
+# block_chain_cases.device_digest of the device's keep=True result on device_results' inputs at two of GPU_SIZES, recorded on an MI355X from
+# commit 7a2e835 ("Run the fp32 colour tail's clr_conv1 in Winograd form, V in registers"), the last before the two trunk stages shared one
+# statement of the chain: a call repeats its bits, so a mismatch means that what runs has changed
+PARENT_DEVICE_DIGESTS = {(4, 32, 1): "5788f23824252ae4", (12, 32, 3): "a2d8d2c71151d0d3"}
 # the same of `d_x0` and the 66 variables at the end of the whole backward chained on one forward at (32, 256), B = 2: the five table
 # stages, GreyDecoder, ColourTrunk and LowerTrunk against the eight host statements chained on the device's own activations
 CHAINED_MEASURED = 4.76e-6    # res_stack/2/non_local/phi/kernel; d_x0 1.21e-6
 CHAINED_BOUND = min(4 * CHAINED_MEASURED, 1e-3)
 
-_weights = {}
 _cases = {}
-
-
-def lt_weights(seed=WEIGHTS_SEED, variant="gsc"):
-    """init_weights(seed): non-trivial BN statistics.  Cached: treat as read-only."""
-    if (seed, variant) not in _weights:
-        _weights[(seed, variant)] = init_weights(seed, variant=variant)
-    return _weights[(seed, variant)]
+lt_weights = chain.weights          # init_weights(3) by default, which is WEIGHTS_SEED; cached: treat as read-only
 
 
 def check_inputs(fw):
@@ -95,60 +95,11 @@ def device_inputs(wt, x0):
 
 
 def worst_scaled_diff(got, ref, names=OUTPUTS):
-    """The largest of max |got[v] - ref[v]| / max |ref[v]| over `names` (an output whose reference is all 0 must be all 0), and the name
-    it occurred at.  A block's d phi/bias is identically zero in exact arithmetic (the rows of dS sum to 0), so it is held as an absolute
-    bound on the scale of max |d theta/bias| of that block, as nonlocal_grad_cases does."""
-    worst, at = 0.0, ""
-    for name in names:
-        a, b = np.asarray(got[name], np.float64), np.asarray(ref[name], np.float64)
-        assert a.shape == b.shape, (name, a.shape, b.shape)
-        scale = np.abs(b).max()
-        if name.endswith("non_local/phi/bias"):
-            scale = np.abs(np.asarray(ref[name.replace("phi/bias", "theta/bias")], np.float64)).max()
-        d = float(np.abs(a - b).max() / scale) if scale > 0 else (0.0 if not a.any() else np.inf)
-        if d > worst:
-            worst, at = d, name
-    return worst, at
+    """block_chain_cases.worst_scaled_diff, over the 67 outputs unless `names` says otherwise."""
+    return chain.worst_scaled_diff(got, ref, names)
 
 
-# ---- torch autograd in float64, written from the reference's semantics (model.py:23-61, 81-113 and Generator.call): per block conv2d
-# with padding 1, inference BN, leaky_relu 0.3, the non-local block, and the skip zero-padded to the wider of the two.  The variables
-# and the input are leaves
-def autograd_block(t, b, leaves, weights):
-    """res_stack/<b> on t [B,h,w,C] in torch float64: `leaves` name -> tensor for the block's trainable variables."""
-    import torch
-    import torch.nn.functional as F
-    t64 = lambda a: torch.from_numpy(np.array(a, np.float64))                        # noqa: E731
-    st = "res_stack/%d/" % b
-    B, h, w, C = t.shape
-
-    def bn(c, stem):
-        mean, var = (t64(weights[stem + p]) for p in ("moving_mean", "moving_variance"))
-        return (c - mean) / torch.sqrt(var + BN_EPS) * leaves[stem + "gamma"] + leaves[stem + "beta"]
-
-    def conv(u, j, pad):
-        k = leaves[st + "conv%d/kernel" % j].permute(3, 2, 0, 1)                     # HWIO -> OIHW
-        c = F.conv2d(u.permute(0, 3, 1, 2), k, leaves[st + "conv%d/bias" % j], padding=pad).permute(0, 2, 3, 1)
-        return bn(c, st + "bnorm%d/" % j)
-
-    y = F.leaky_relu(conv(t, 1, 0), LRELU_ALPHA)
-    y = F.leaky_relu(conv(y, 2, 1), LRELU_ALPHA)
-    y = conv(y, 3, 0)
-    nl = st + "non_local/"
-    proj = lambda u, name: torch.matmul(u, leaves[nl + name + "/kernel"][0, 0]) + leaves[nl + name + "/bias"]   # noqa: E731
-    g_x = proj(y, "g").reshape(B, h * w, -1)
-    phi_x = proj(y, "phi").reshape(B, h * w, -1).transpose(1, 2)
-    theta_x = proj(y, "theta").reshape(B, h * w, -1)
-    f = torch.softmax(torch.matmul(theta_x, phi_x), -1)
-    z = y + bn(proj(torch.matmul(f, g_x).reshape(B, h, w, -1), "w"), nl + "bnorm/")
-    n = z.shape[3]
-    if C < n:                                                                        # model.py:105-113: the narrower of the two is padded
-        t = torch.cat([t, torch.zeros(B, h, w, n - C, dtype=torch.float64)], dim=3)
-    elif C > n:
-        z = torch.cat([z, torch.zeros(B, h, w, C - n, dtype=torch.float64)], dim=3)
-    return F.leaky_relu(t + z, LRELU_ALPHA)
-
-
+# ---- torch autograd in float64: block_chain_cases.autograd_block per block.  The variables and the input are leaves
 def autograd_grads(weights, x0, d_res2):
     """d <d_res2, res2> / d each of the 66 variables and x0 by torch autograd in float64 from the float32 variables: name -> float64
     array in the variable's shape, `d_x0` [B,h,w,99]."""
@@ -190,7 +141,8 @@ def autograd_nonlocal(weights, y3, xin, d_out, block):
 # colour_trunk_grad_cases.case(4, 32, 1), computed from the parent commit
 def statement_hashes():
     """name -> the first 16 hex digits of SHA-256 over the float64 bytes of every array nonlocal_forward, nonlocal_grad, bottleneck_grad
-    (block 5, C = 261) and colour_trunk_grad return on colour_trunk_grad_cases.case(4, 32, 1), keys in sorted order."""
+    (block 5, C = 261) and colour_trunk_grad return on colour_trunk_grad_cases.case(4, 32, 1), keys in sorted order; the same of
+    lower_trunk_forward and lower_trunk_grad on case(4, 32, 1); and of the bytes of the two trunk stages' blobs."""
     import colour_trunk_grad_cases as ct
 
     def digest(d):
@@ -208,12 +160,23 @@ def statement_hashes():
     out["nonlocal_grad"] = digest(n)
     out["bottleneck_grad"] = digest(host.bottleneck_grad(wt, fw["res3"], n["d_y3"], n["d_skip"], block=4))
     out["colour_trunk_grad"] = digest(host.colour_trunk_grad(wt, fw["xh"], fw["y3_3"], fw["res3"], fw["y3_4"], fw["res4"], d_xin, d_x))
+    # what the two trunk stages stated before they shared blocks_forward, blocks_grad and pack_block_chain: lower_trunk_forward and
+    # lower_trunk_grad on case(4, 32, 1), and the two blobs of init_weights(3)
+    wt, x0, d_res2 = case(4, 32, 1)
+    fw = host.lower_trunk_forward(wt, x0)
+    out["lower_trunk_forward"] = digest(fw)
+    out["lower_trunk_grad"] = digest(host.lower_trunk_grad(wt, x0, *(fw[k] for k in FORWARD_KEYS), d_res2))
+    for pack_blob in (pack.pack_colour_trunk_grad, pack.pack_lower_trunk_grad):
+        out[pack_blob.__name__] = hashlib.sha256(pack_blob(lt_weights(3))).hexdigest()[:16]
     return out
 
 
-# statement_hashes() of the commit before this stage ("Backpropagate through res_stack/4, /3 and the hole to res_stack/2")
+# statement_hashes() of the commit before this stage ("Backpropagate through res_stack/4, /3 and the hole to res_stack/2"); the last four
+# of the commit before the two trunk stages shared one statement (7a2e835, "Run the fp32 colour tail's clr_conv1 in Winograd form, V in
+# registers")
 PARENT_HASHES = {"trunk_forward": "8c4ed034f8f80d1c", "nonlocal_forward": "97da193570627956", "nonlocal_grad": "b4128aacb455776f",
-                 "bottleneck_grad": "1e2d9561be137e4a", "colour_trunk_grad": "67b35df3a6dcdb65"}
+                 "bottleneck_grad": "1e2d9561be137e4a", "colour_trunk_grad": "67b35df3a6dcdb65", "lower_trunk_forward": "aef8a25568988b03",
+                 "lower_trunk_grad": "fc38bec6559da48c", "pack_colour_trunk_grad": "9b219beb4fe1502a", "pack_lower_trunk_grad": "595933d59e055770"}
 
 
 # ---- constructed cases
@@ -286,16 +249,6 @@ CONSTRUCTED = (check_zero_d_res2, check_the_blocks_take_their_own_weights, check
 
 # ---- on the device: what test_lower_trunk_grad_gpu.py and tools/lower_trunk_bench.py share
 PROBES = ("y3x2", "res2", "y3x1", "res1", "y3x0", "res0", "x0")      # Generator.probe's names of LowerTrunk's strided inputs, in their order
-
-
-def to_dev(*arrays):
-    import torch
-    dev = torch.device("cuda", 0)
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
-
-
-def to_host(res):
-    return {k: v.cpu().numpy() for k, v in res.items()}
 
 
 def probe_copies(probes):

@@ -17,26 +17,18 @@ import numpy as np
 import pytest
 
 from blindshadowremoval_amd import generator_grad as host
-from blindshadowremoval_amd.weights import generator_bottleneck_trainable_names, generator_nonlocal_trainable_names
 
+import block_chain_cases as chain
 import colour_trunk_grad_cases as cases
+from block_chain_cases import scaled_error, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 f32 = np.float32
 SIZES = cases.GPU_SIZES
 OUT_KEYS = ("", "d_res2")
-# the launch (1..49) that writes each map, from the two chains' own tables (test_nonlocal_grad_gpu.py, test_bottleneck_grad_gpu.py)
-NL_FIRST = {"y3": 1, "dz": 1, "theta": 2, "phi": 2, "g": 2, "m": 3, "r": 3, "A": 3, "dA": 4, "D": 4, "d_phi": 5, "d_g": 5, "d_theta": 6, "Wgd": 11, "Sz": 12}
-BN_FIRST = {"xp": 1, "dyp": 1, "a1": 2, "a2": 3, "gz2": 4, "gz1": 5, "Wg1": 11, "Wg2": 11, "Wg3": 11, "S1": 12, "S2": 12, "S3": 12}
-FIRST = {}
-for _k, _b in enumerate(cases.BLOCKS):
-    FIRST.update(("nl%d.%s" % (_b, n), 24 * _k + at) for n, at in NL_FIRST.items())
-    FIRST.update(("bn%d.%s" % (_b, n), 24 * _k + 12 + at) for n, at in BN_FIRST.items())
-    FIRST.update({"d_skip_%d" % _b: 24 * _k + 1, "d_y3_%d" % _b: 24 * _k + 10, "d_xin%d" % _b: 24 * _k + 21})
-    FIRST.update((n, 24 * _k + (11 if n.endswith("/kernel") else 12)) for n in generator_nonlocal_trainable_names(_b))
-    FIRST.update((n, 24 * _k + 12 + (11 if n.endswith("/kernel") else 12)) for n in generator_bottleneck_trainable_names(_b))
-FIRST["d_res2"] = 49
+FIRST = chain.first_table(cases.BLOCKS, "d_res2", tail=True)      # the launch (1..49) that first writes each map and output
+assert FIRST["d_res2"] == 49
 
 
 @pytest.fixture(scope="module")
@@ -45,15 +37,6 @@ def runner():
     r = ColourTrunk(0)
     r.load_weights(cases.ct_weights())
     return r
-
-
-def to_dev(*arrays):
-    dev = torch.device("cuda", 0)
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
-
-
-def to_host(res):
-    return {k: v.cpu().numpy() for k, v in res.items()}
 
 
 def device_run(runner, wt, x, bmask, uv, d_xin, d_x):
@@ -65,11 +48,6 @@ def device_run(runner, wt, x, bmask, uv, d_xin, d_x):
     out = to_host(res)
     out.update({"res4": arrays[1], "res3": arrays[3], "xh": arrays[4], "y3_4": y3_4, "y3_3": y3_3, "dtype": f32})
     return out
-
-
-def scaled_error(got, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(got, np.float64) - ref).max() / np.abs(ref).max())
 
 
 @pytest.fixture(scope="module")
@@ -96,31 +74,12 @@ def test_constructed_case(runner, check):
 def test_every_stop_leaves_what_the_complete_call_leaves(runner, device_results, h, w, B):
     """stages(..., n) for n = 1..49: what launches 1..n write is the complete call's, byte for byte, and the outputs of the launches
     that did not run are zero.  So every launch of the complete call ran on the inputs the per-launch statements below read."""
-    from blindshadowremoval_amd import ColourTrunk
     _, arrays, _, _, _ = device_results[(h, w, B)]
-    t = to_dev(*arrays)
-    whole = runner.stages(*t, 49)
-    whole.update(ColourTrunk.split_grads(whole[""]))
-    assert set(FIRST) <= set(whole) and len(runner.LAUNCHES) == 49
-    for stop in range(1, 50):
-        runner._scratch.zero_()                # what a stop leaves was written by this call, not by the one before
-        got = runner.stages(*t, stop)
-        got.update(ColourTrunk.split_grads(got[""]))
-        for name, at in FIRST.items():
-            if stop >= at:
-                assert torch.equal(got[name], whole[name]), (stop, name)
-            elif "/" in name or name == "d_res2":
-                assert not bool(got[name].any()), (stop, name)
-    with pytest.raises(ValueError, match="stop_after"):
-        runner.stages(*t, 50)
+    assert len(runner.LAUNCHES) == 49
+    chain.check_every_stop(runner, arrays, FIRST, "d_res2")
 
 
-def _as_block5(wt, res, b):
-    """Block b's variables, and its gradients out of `res`, under res_stack/5's names: what the single-block tests read."""
-    import bottleneck_grad_cases
-    moved = bottleneck_grad_cases.with_block5(wt, b)
-    src = "res_stack/%d/" % b
-    return moved, {"res_stack/5/" + n[len(src):]: v for n, v in res.items() if n.startswith(src)}
+_as_block5 = chain.as_block5
 
 
 @pytest.mark.parametrize("h,w,B", SIZES)
@@ -189,25 +148,22 @@ def test_the_hole_kernel_alone(runner, h, w, B):
             assert not got[hole].any() if grey is None else got[hole].tobytes() == d_x[hole].tobytes()
 
 
+def test_the_device_keeps_the_bits_of_the_commit_before_the_shared_chain(device_results):
+    """The flat gradient buffer, d_res2 and every kept entry at (4, 32, 1) and (12, 32, 3) hash to what the parent commit left on the MI355X
+    (cases.PARENT_DEVICE_DIGESTS).  No further launch."""
+    from blindshadowremoval_amd import ColourTrunk
+    for size, want in cases.PARENT_DEVICE_DIGESTS.items():
+        assert chain.device_digest(device_results[size][3], "d_res2", ColourTrunk.KEPT) == want, size
+
+
 def flat_bytes(res):
-    return [res[k].cpu().numpy().tobytes() for k in OUT_KEYS]
+    return chain.flat_bytes(res, OUT_KEYS)
 
 
 def test_a_repeated_call_and_two_sizes_on_one_scratch(runner, device_results):
     wt, arrays3, _, res3, _ = device_results[(12, 32, 3)]
     _, arrays1, _, res1, _ = device_results[(4, 32, 1)]
-    t3, t1 = to_dev(*arrays3), to_dev(*arrays1)
-    first3 = flat_bytes(runner.colour_trunk_grad(*t3))
-    first1 = flat_bytes(runner.colour_trunk_grad(*t1))          # B = 3 then B = 1 on the larger call's scratch
-    assert first3 == [res3[k].tobytes() for k in OUT_KEYS] and first1 == [res1[k].tobytes() for k in OUT_KEYS]
-    assert flat_bytes(runner.colour_trunk_grad(*t3)) == first3
-    assert flat_bytes(runner.colour_trunk_grad(*t1)) == first1
-    assert flat_bytes(runner.colour_trunk_grad(*t1, keep=True)) == first1   # keeping the maps changes no output
-    for t, a in zip(t1, arrays1):
-        assert t.cpu().numpy().tobytes() == a.tobytes()                     # no input is ever written
-    fresh = type(runner)(0)
-    fresh.load_weights(wt)
-    assert flat_bytes(fresh.colour_trunk_grad(*t1)) == first1   # a scratch of its own size gives the same bytes
+    chain.check_a_repeated_call_and_two_sizes_on_one_scratch(runner, "colour_trunk_grad", wt, (arrays3, res3), (arrays1, res1), OUT_KEYS)
 
 
 def test_no_d_x_is_a_zero_d_x(runner, device_results):
@@ -224,22 +180,7 @@ def test_no_d_x_is_a_zero_d_x(runner, device_results):
 def test_the_chain_is_captured_into_a_graph_and_replays_the_same_bytes(runner, device_results):
     """Stream capture refuses a host synchronisation and work on another stream that is not joined: a call that is captured, replayed
     and gives the eager call's bytes has neither.  The chain is a line of launches: the captured graph has no branches."""
-    _, arrays, _, _, _ = device_results[(4, 32, 1)]
-    t = to_dev(*arrays)
-    eager = flat_bytes(runner.colour_trunk_grad(*t))
-    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        runner.colour_trunk_grad(*t)
-        torch.cuda.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            res = runner.colour_trunk_grad(*t)
-    torch.cuda.current_stream().wait_stream(side)
-    for k in OUT_KEYS:
-        res[k].zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    assert flat_bytes(res) == eager
+    chain.check_graph_capture(runner, "colour_trunk_grad", device_results[(4, 32, 1)][1], OUT_KEYS)
 
 
 def test_argument_errors_raise_before_any_launch(runner, device_results):

@@ -125,7 +125,8 @@ def test_the_bottleneck_statements_take_the_lower_blocks_widths():
 
 def test_the_statements_of_the_colour_branch_keep_their_bytes():
     """nonlocal_forward, nonlocal_grad, bottleneck_grad and colour_trunk_grad at C = 261 on colour_trunk_grad_cases.case(4, 32, 1): the
-    hashes of the commit before the skip could be narrower than the block."""
+    hashes of the commit before the skip could be narrower than the block.  And lower_trunk_forward, lower_trunk_grad and the two
+    trunk blobs: the hashes of the commit before the two stages shared one statement of the chain."""
     assert cases.statement_hashes() == cases.PARENT_HASHES
 
 

@@ -1,4 +1,4 @@
-"""Time of the backward of res_stack/2, res_stack/1 and res_stack/0 on the device (bsr_lower_trunk_grad, csrc/lower_trunk_grad_kernels.h),
+"""Time of the backward of res_stack/2, res_stack/1 and res_stack/0 on the device (bsr_lower_trunk_grad, csrc/block_chain_grad.h),
 one JSON line, also written to --out (profiles/lower_trunk_grad_bench.json).
 
 B items of S x S: the generator's forward on random images (weights from init_weights(1)) supplies the seven tensors, d_res2 comes from
